@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the adsbdec "-f" demodulation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode stream|shard]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode stream|shard] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -234,6 +234,36 @@ def timed_steps(step, steps, fence, sync=None):
     dt = time.perf_counter() - t0
     fence()
     return dt, raw
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, frames, stats=None):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one .npy per field.  Frame i is row i
+    of every frames_* array (in the library's order); frames_bytes holds the 14 bytes of a frame, zero-padded behind
+    frames_len.  Integer fields are stored as float64 (exact below 2^53).  Above 64 MB in all, a fixed seeded sample of
+    the frames is written, in their order, and frames_index says which."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(frames)
+    row_bytes = 8 * 5 + 4 * 14
+    idx = np.arange(n)
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    sel = [frames[i] for i in idx]
+    raw = np.zeros((len(sel), 14), np.float32)
+    for r, f in enumerate(sel):
+        raw[r, :len(f["frame"])] = np.frombuffer(f["frame"], np.uint8)
+    arrays = {"frames_index": idx.astype(np.float64),
+              "frames_g": np.array([f["g"] for f in sel], np.float64),
+              "frames_ts": np.array([f["ts"] for f in sel], np.float64),
+              "frames_pw": np.array([f["pw"] for f in sel], np.float64),
+              "frames_len": np.array([len(f["frame"]) for f in sel], np.float64),
+              "frames_bytes": raw}
+    if stats is not None:   # valid.c's Try/Ok table: rows try / ok, columns DF 11 / 17 / 18
+        arrays["stats_try_ok"] = np.array([[stats[k][d] for d in (11, 17, 18)] for k in ("try", "ok")], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def bind_near_gpu(torch, device):
@@ -638,7 +668,12 @@ def main():
     #                                                                                the timed region; the job must end non-zero, not hang
     ap.add_argument("--one-device-test", action="store_true",
                     help="plumbing test only: every rank uses GPU 0 and gloo (numbers are meaningless)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's frames, and the Try/Ok table "
+                         "with --stats) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and args.mode != "shard":
@@ -768,6 +803,8 @@ def main():
 
     value = world * n * args.steps / dt / 1e6  # Msamples/s, whole job
     frames = capi._frames_to_dicts(raw[0], raw[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frames, dec.stats() if args.stats else None)
     p1 = dec.profile()
     roofline, roofline_valu = roofline_objects(p0, p1, args.steps, profile_tag(args), clock, dt / args.steps * 1e3)
 
@@ -1054,6 +1091,8 @@ def run_shard(args, torch, capi, rank, world, fence):
     value = total * args.steps / dt / 1e6
     frames = capi._frames_to_dicts(raw[0], raw[1])
     stats_table = md.stats() if args.stats else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frames, stats_table)
 
     cpu, parity = None, None
     if not args.no_cpu_baseline:

@@ -9,6 +9,9 @@ this module; the product (adsbdec_amd/) never does.
 from __future__ import annotations
 
 import ctypes as C
+import gzip
+import hashlib
+import json
 import os
 import subprocess
 import tempfile
@@ -20,6 +23,9 @@ LIB_PATH = os.path.join(HERE, "liboracle.so")
 REF_ADSBDEC = os.path.join(HERE, "_ref", "ref_adsbdec")
 REF_ADSBDEC_NATIVE = os.path.join(HERE, "_ref", "ref_adsbdec_native")
 REF_POWER = os.path.join(HERE, "_ref", "ref_power")
+# answers of the real chain on the captures the CPU tests feed it, recorded where oracle/_ref could be built
+# (oracle/make_ref_recordings.py): where it cannot, ref_decode / ref_demod / ref_power_digest replay them
+REF_RECORDINGS = os.path.join(os.path.dirname(HERE), "tests", "golden", "ref_recordings.json.gz")
 # captures handed to the reference binaries go through files; /dev/shm keeps them in memory
 _TMP = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else "/tmp"
 
@@ -180,7 +186,69 @@ def avr_lines(frames, outformat: int = 0) -> bytes:
 # valid.c:30-31)
 # --------------------------------------------------------------------------
 def ref_available() -> bool:
+    """The compiled reference chain is here and can be run."""
     return os.path.exists(REF_ADSBDEC) and os.path.exists(REF_POWER)
+
+
+def ref_answers_available() -> bool:
+    """ref_decode / ref_demod / ref_power_digest can answer: live, or from the recordings."""
+    return ref_available() or os.path.exists(REF_RECORDINGS)
+
+
+_recorded = None
+_recording = os.environ.get("ORACLE_REF_RECORD")   # set by oracle/make_ref_recordings.py only
+
+
+def _key(what: str, data: np.ndarray, **opts) -> str:
+    h = hashlib.sha256(f"{what}|{data.dtype.str}|{data.size}|{sorted(opts.items())}".encode())
+    h.update(np.ascontiguousarray(data).tobytes())
+    return h.hexdigest()
+
+
+def _encode(answer):
+    frames, stats = answer
+    return {"frames": [[f["ts"], f["pw"], f["frame"].hex(), f["avr"].decode(), f["mlat"].decode(), f["beast"].hex()] for f in frames],
+            "try": [stats["try"][d] for d in (11, 17, 18)], "ok": [stats["ok"][d] for d in (11, 17, 18)]}
+
+
+def _decode(rec):
+    frames = [dict(ts=ts, pw=pw, frame=bytes.fromhex(fr), avr=avr.encode(), mlat=mlat.encode(), beast=bytes.fromhex(beast))
+              for ts, pw, fr, avr, mlat, beast in rec["frames"]]
+    return frames, {"try": dict(zip((11, 17, 18), rec["try"])), "ok": dict(zip((11, 17, 18), rec["ok"]))}
+
+
+def _record(key: str, value) -> None:
+    with open(_recording, "a") as f:
+        f.write(json.dumps([key, value]) + "\n")
+
+
+def _replay(key: str):
+    global _recorded
+    if _recorded is None:
+        with gzip.open(REF_RECORDINGS, "rt") as f:
+            _recorded = json.load(f)
+    if key not in _recorded:
+        raise KeyError(f"no recorded answer of the reference chain for this call ({key[:16]}): oracle/_ref is not built here, "
+                       "and tests/golden/ref_recordings.json.gz was recorded for other inputs (oracle/make_ref_recordings.py)")
+    return _recorded[key]
+
+
+def ref_power_digest(x, chunk: int | None = None, m: int | None = None) -> tuple[int, str]:
+    """(number of power samples, sha256 of the first m of them) that ref_power gives: live, or recorded."""
+    x = _as_u16(x)
+    key = _key("power", x, chunk=chunk, m=m)
+    if not ref_available():
+        return tuple(_replay(key))
+    a = ref_power(x, chunk)
+    answer = (int(a.size), power_digest(a, m))
+    if _recording:
+        _record(key, answer)
+    return answer
+
+
+def power_digest(a: np.ndarray, m: int | None = None) -> str:
+    assert a.dtype == np.float32
+    return hashlib.sha256(np.ascontiguousarray(a[:m]).view(np.uint32).tobytes()).hexdigest()
 
 
 def _parse_ref_output(p):
@@ -213,9 +281,15 @@ def ref_decode(x, df18: bool = False, chunk: int | None = None, native: bool = F
     if path is not None:
         return _parse_ref_output(subprocess.run([exe] + opts + [path], capture_output=True, check=True))
     x = _as_u16(x)
+    key = _key("decode", x, df18=bool(df18), chunk=chunk, native=native)
+    if not ref_available():
+        return _decode(_replay(key))
     with tempfile.NamedTemporaryFile(suffix=".u16", dir=_TMP) as tf:
         x.tofile(tf.name)
-        return _parse_ref_output(subprocess.run([exe] + opts + [tf.name], capture_output=True, check=True))
+        answer = _parse_ref_output(subprocess.run([exe] + opts + [tf.name], capture_output=True, check=True))
+    if _recording:
+        _record(key, _encode(answer))
+    return answer
 
 
 def ref_power(x, chunk: int | None = None) -> np.ndarray:
@@ -235,7 +309,13 @@ def ref_demod(a: np.ndarray, df18: bool = False):
     `a` (synthetic power fuzz of getdf/getabyte; the carry loop around deqframe is
     the harness's restatement of air.c:94-99 in this mode -- pinning uses ref_decode)."""
     assert a.dtype == np.float32
+    key = _key("demod", a, df18=bool(df18))
+    if not ref_available():
+        return _decode(_replay(key))
     with tempfile.NamedTemporaryFile(suffix=".f32", dir=_TMP) as tf:
         a.tofile(tf.name)
         cmd = [REF_ADSBDEC] + (["-a"] if df18 else []) + ["-p", tf.name]
-        return _parse_ref_output(subprocess.run(cmd, capture_output=True, check=True))
+        answer = _parse_ref_output(subprocess.run(cmd, capture_output=True, check=True))
+    if _recording:
+        _record(key, _encode(answer))
+    return answer

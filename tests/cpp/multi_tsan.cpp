@@ -73,6 +73,33 @@ std::atomic<int> g_gang_streams{0}, g_gang_shards{0}; // decodes whose frames we
 thread_local std::string g_err;
 thread_local std::mt19937 g_rng{std::random_device{}()};
 
+// May this process place memory on `node`?  (/proc/self/status, Mems_allowed_list: "0", "0-1", "0,2-3")
+inline bool memory_node_allowed(int node)
+{
+    FILE *f = fopen("/proc/self/status", "r");
+    if (!f)
+        return node == 0;
+    char line[4096];
+    bool yes = false;
+    while (fgets(line, sizeof line, f))
+        if (!strncmp(line, "Mems_allowed_list:", 18)) {
+            for (char *p = line + 18; *p;) {
+                char *e;
+                const long a = strtol(p, &e, 10);
+                if (e == p) {
+                    p++;
+                    continue;
+                }
+                const long b = (*e == '-') ? strtol(e + 1, &e, 10) : a;
+                yes |= a <= node && node <= b;
+                p = e;
+            }
+            break;
+        }
+    fclose(f);
+    return yes;
+}
+
 inline void jitter()
 {
     if (g_rng() % 3 == 0)
@@ -534,9 +561,13 @@ int main(int argc, char **argv)
             const int src = (round + rep) % 3;
             uint16_t *placed = nullptr;
             if (src == 0 && rep == 0) {
-                // the capture in an array laid out shard by shard on the nodes of the devices that pull it (numa.cpp); this
-                // machine has one node, the made-up map two: mbind for node 1 is refused or not, the pages live on node 0
-                // either way, and the placement query must say so -- workers on even devices local, on odd devices remote
+                // the capture in an array laid out shard by shard on the nodes of the devices that pull it (numa.cpp).  Where
+                // this process may not place memory on node 1 (one node), mbind for it is refused or not, the pages live on
+                // node 0 either way, and the placement query must say so -- workers on even devices local, on odd devices
+                // remote.  Where it may (a two-node host), the pages go where the made-up map says, node boundaries rounded
+                // to huge pages (a slice's halo may lie on its neighbour's node): the node that holds most of a slice must
+                // agree with the share of it on the device's node
+                const bool two_nodes = fake::memory_node_allowed(0) && fake::memory_node_allowed(1);
                 placed = adsb_multi_host_alloc(m, x.size());
                 if (!placed) {
                     fprintf(stderr, "adsb_multi_host_alloc failed: %s\n", adsb_multi_last_error(m));
@@ -552,7 +583,10 @@ int main(int argc, char **argv)
                         fprintf(stderr, "worker %d: placement of the wrong device\n", i);
                         return 1;
                     }
-                    if (pl.slice_node >= 0 && (pl.slice_node != 0 || pl.local_fraction != (pl.device_node == 0 ? 1.0 : 0.0))) {
+                    const bool ok_pl = two_nodes ? (pl.slice_node == 0 || pl.slice_node == 1) &&
+                                                       (pl.slice_node == pl.device_node ? pl.local_fraction >= 0.5 : pl.local_fraction <= 0.5)
+                                                 : pl.slice_node == 0 && pl.local_fraction == (pl.device_node == 0 ? 1.0 : 0.0);
+                    if (pl.slice_node >= 0 && !ok_pl) {
                         fprintf(stderr, "worker %d (device %d, node %d): slice on node %d, local fraction %.2f\n", i, pl.device, pl.device_node,
                                 pl.slice_node, pl.local_fraction);
                         return 1;

@@ -4,6 +4,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -123,3 +124,30 @@ def test_main_workloads_name_their_evidence_sets():
     roof, valu = bench.roofline_objects(p0, p1, 100, "_dense10", clock=(2.3, 9), step_ms=0.21)
     assert "profiles/r6_dense10_pmc.json" in roof["traffic_source"] and abs(roof["frac"] - 4 * 134216525 / 0.175e-3 / 1e9 / 8000) < 1e-3
     assert valu["valu_wave_instructions"] > 70e6     # a full channel's tiles issue more than the sparse capture's 65 M
+
+
+def test_dump_outputs_writes_every_frame_field_as_float(tmp_path, monkeypatch):
+    frames = [dict(g=7, ts=8, pw=900, frame=bytes(range(1, 8))), dict(g=2 ** 40, ts=2 ** 40 + 1, pw=2 ** 31, frame=bytes(range(14)))]
+    stats = {"try": {11: 5, 17: 3, 18: 0}, "ok": {11: 1, 17: 2, 18: 0}}
+    bench.dump_outputs(str(tmp_path / "out"), frames, stats)
+    got = {p[:-4]: np.load(tmp_path / "out" / p) for p in os.listdir(tmp_path / "out")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["frames_g"].tolist() == [7, 2 ** 40] and got["frames_ts"].tolist() == [8, 2 ** 40 + 1]
+    assert got["frames_pw"].tolist() == [900, 2 ** 31] and got["frames_len"].tolist() == [7, 14]
+    assert got["frames_bytes"][0].tolist() == list(range(1, 8)) + [0] * 7 and got["frames_bytes"][1].tolist() == list(range(14))
+    assert got["stats_try_ok"].tolist() == [[5, 3, 0], [1, 2, 0]]
+    # above the size limit: the same seeded sample every time, in stream order, and named by frames_index
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 96 * 10)
+    many = [dict(g=i, ts=i, pw=i, frame=b"\x01\x02") for i in range(100)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), many)
+    ia, ib = np.load(tmp_path / "a" / "frames_index.npy"), np.load(tmp_path / "b" / "frames_index.npy")
+    assert ia.size == 10 and np.array_equal(ia, ib) and np.all(np.diff(ia) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "frames_g.npy"), ia)
+    assert not os.path.exists(tmp_path / "a" / "stats_try_ok.npy")
+
+
+def test_steps_below_one_are_refused(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit, match="--steps must be at least 1"):
+        bench.main()

@@ -262,7 +262,8 @@ def test_resolver_input_paths_agree(tmp_path):
     built = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-pthread", src, "-o", str(tsan)],
                            capture_output=True, text=True)
     if built.returncode == 0:
-        out = subprocess.run([str(tsan), "40"], capture_output=True, text=True)
+        from test_sanitizers import NO_ASLR   # (TSan's address layout, see there)
+        out = subprocess.run(NO_ASLR + [str(tsan), "40"], capture_output=True, text=True)
         assert out.returncode == 0 and out.stdout.startswith("ok") and "ThreadSanitizer" not in out.stderr, out.stdout + out.stderr
 
 

@@ -2,7 +2,7 @@
 
  - CRC table and known answers (crc.h)
  - the restatement against the REAL reference deqframe/valid/formatpkt in oracle/_ref
-   (skipped on machines without it) on synthetic POWER buffers that fuzz getdf
+   (its recorded answers where it is not built) on synthetic POWER buffers that fuzz getdf
  - the restatement against the committed golden fixtures (minted through the real
    chain, oracle/make_golden.py)
  - known-answer / property tests of the front end (air.c:54-92)
@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, golden_cases, golden_records, load_golden, records
+from oracle import oracle as O
 
 TAPS = np.array([0.012627, 0.025254, 0.037881, 0.050508, 0.063135, 0.075761, 0.088388,
                  0.088388, 0.075761, 0.063135, 0.050508, 0.037881, 0.025254, 0.012627]).astype(np.float32)
@@ -52,8 +53,8 @@ def test_oracle_reproduces_golden(oracle, name):
         assert oracle.formatpkt(f["frame"], f["ts"], f["pw"], 2) == bytes.fromhex(g["beast"])
 
 
-needs_ref = pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref", "ref_adsbdec")),
-                               reason="oracle/_ref not built (needs /root/reference)")
+needs_ref = pytest.mark.skipif(not O.ref_answers_available(),
+                               reason="neither oracle/_ref nor its recorded answers (tests/golden/ref_recordings.json.gz) are here")
 
 
 @needs_ref

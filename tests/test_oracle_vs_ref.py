@@ -17,8 +17,10 @@ over > 2000 seeded captures: all seven FIR phases, full-range noise, codes beyon
 (SURVEY Q10), ragged tails (len % 4 != 0), frames planted across the
 call horizons so that the carry base turns odd, with and without -a.
 
-They are skipped where oracle/_ref is absent (it is built only where
-/root/reference exists and travels to the GPU box with the snapshot).
+Where oracle/_ref is absent (it is built only where the reference sources are at hand),
+the chain's answers on these very captures come from tests/golden/ref_recordings.json.gz,
+recorded through it by oracle/make_ref_recordings.py; power samples are compared by
+sha256 of their bits.
 """
 import numpy as np
 import pytest
@@ -26,7 +28,7 @@ import pytest
 from tools import gen_signal as G
 from oracle import oracle as O
 
-pytestmark = pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built (needs /root/reference)")
+pytestmark = pytest.mark.skipif(not O.ref_answers_available(), reason="neither oracle/_ref nor its recorded answers are here")
 
 FIRST_CALL = 2 * 40980          # input samples at which aidx first reaches APBUFFSZ (air.c:94)
 N_GROUPS, PER_GROUP = 16, 130   # 2080 captures
@@ -81,10 +83,9 @@ def test_restatement_equals_real_chain_fuzz(oracle, group):
         assert key(of) == key(rf), f"seed {seed}: frames differ ({len(of)} vs {len(rf)})"
         assert ostats == rstats, f"seed {seed}: Try/Ok differ"
         if seed % 4 == 0:
-            a, b = oracle.power(x), oracle.ref_power(x)
+            a = oracle.power(x)
             m = x.size // 4 * 2     # a ragged tail's last pair is stale-buffer arithmetic in the reference
-            assert a.size == b.size and np.array_equal(a[:m].view(np.uint32), b[:m].view(np.uint32)), \
-                f"seed {seed}: power samples differ"
+            assert oracle.ref_power_digest(x, m=m) == (a.size, oracle.power_digest(a, m)), f"seed {seed}: power samples differ"
         for f, r in zip(of[:8], rf[:8]):
             assert oracle.formatpkt(f["frame"], f["ts"], f["pw"], 0) == r["avr"]
             assert oracle.formatpkt(f["frame"], f["ts"], f["pw"], 1) == r["mlat"]
@@ -101,8 +102,7 @@ def test_power_bit_exact_all_phases_and_full_range(oracle):
         x = rng.integers(0, hi, n, dtype=np.uint16)
         want = oracle.power(x)
         for chunk in (None, 4, 28, 4096, 65536 + 4):
-            got = oracle.ref_power(x, chunk)
-            assert np.array_equal(want.view(np.uint32), got.view(np.uint32)), (hi, n, chunk)
+            assert oracle.ref_power_digest(x, chunk) == (want.size, oracle.power_digest(want)), (hi, n, chunk)
     # the 7 summation orders really differ (otherwise the test above proves less than it says)
     x = rng.integers(0, 4096, 28 * 50, dtype=np.uint16)
     a = oracle.power(x)
@@ -142,7 +142,7 @@ def test_native_flags_vs_strict(oracle):
     here is made for.  Frames and Try/Ok must agree on this capture; pw may differ by
     one unit on a few frames when the host fuses."""
     import os
-    if not os.path.exists(O.REF_ADSBDEC_NATIVE):
+    if O.ref_available() and not os.path.exists(O.REF_ADSBDEC_NATIVE):
         pytest.skip("native build absent")
     x, _ = G.dense_capture(1 << 21, seed=31, sigma=60.0, n_frames=800, amp=(100, 1800))
     try:

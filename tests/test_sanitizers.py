@@ -9,6 +9,8 @@ Two harnesses (tests/cpp/), each built twice with g++:
 What the reference has in these places is one mutex + condition variable (output.c:159-202); this replaces it with
 lock-free polling and a pool of workers, so it gets a race detector behind it."""
 import os
+import platform
+import shutil
 import subprocess
 
 import pytest
@@ -16,6 +18,10 @@ import pytest
 from conftest import ROOT
 
 CPP = os.path.join(ROOT, "tests", "cpp")
+# ThreadSanitizer wants a PIE program where the kernel's default randomisation puts it; a host with wider mmap randomisation
+# maps it elsewhere and TSan stops at start-up ("unexpected memory mapping"): the sanitized programs run with it off (setarch -R,
+# a personality flag of that one child)
+NO_ASLR = ["setarch", platform.machine(), "-R"] if shutil.which("setarch") else []
 SAN = {"tsan": ["-fsanitize=thread"], "asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
 
 
@@ -30,7 +36,7 @@ def _build(tmp_path, src, san):
 def _run(exe, rounds, timeout=600):
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1", ASAN_OPTIONS="detect_leaks=1",
                UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, str(rounds)], capture_output=True, text=True, timeout=timeout, env=env)
+    p = subprocess.run(NO_ASLR + [exe, str(rounds)], capture_output=True, text=True, timeout=timeout, env=env)
     assert p.returncode == 0 and p.stdout.startswith("ok:"), (p.stdout[-500:], p.stderr[-4000:])
     assert "ThreadSanitizer" not in p.stderr and "AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
     return p.stdout
