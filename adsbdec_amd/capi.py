@@ -118,6 +118,12 @@ SYMBOLS = {
     "adsb_push_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_push_device_final": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_decode_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Frame))]),
+    "adsb_push_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_push_packed_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_push_device_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_push_device_packed_final": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_decode_device_packed": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Frame))]),
+    "adsb_unpack_packed12": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adsb_finish": (C.c_int, [C.c_void_p]),
     "adsb_host_alloc": (C.c_void_p, [C.c_size_t]),
     "adsb_host_free": (None, [C.c_void_p]),
@@ -361,6 +367,67 @@ class Decoder:
         if k < 0:
             self._check(-1, "adsb_decode_device")
         return self._out, k
+
+    # ---- Airspy packed 12-bit input (include/adsbdec_amd.h): n always counts SAMPLES (a multiple of 8), 1.5 bytes each
+    @staticmethod
+    def _packed_arg(buf):
+        if isinstance(buf, tuple):
+            return buf
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"] and buf.size % 12 == 0
+        return buf.ctypes.data, buf.size // 12 * 8
+
+    def push_packed(self, buf):
+        """adsb_push_packed: buf = packed bytes (uint8 ndarray) or (ptr, n_samples)."""
+        ptr, n = self._packed_arg(buf)
+        self._check(self._L.adsb_push_packed(self._h, ptr, n), "adsb_push_packed")
+
+    def push_packed_async(self, buf):
+        """adsb_push_packed_async: buf stays borrowed until the next push/finish/sync returns."""
+        ptr, n = self._packed_arg(buf)
+        self._check(self._L.adsb_push_packed_async(self._h, ptr, n), "adsb_push_packed_async")
+
+    def push_device_packed(self, ptr: int, n: int):
+        self._check(self._L.adsb_push_device_packed(self._h, ptr, n), "adsb_push_device_packed")
+
+    def push_device_packed_final(self, ptr: int, n: int):
+        self._check(self._L.adsb_push_device_packed_final(self._h, ptr, n), "adsb_push_device_packed_final")
+
+    def decode_device_packed_raw(self, ptr: int, n: int):
+        """adsb_decode_device_packed -> (Frame pointer, count), as decode_device_raw."""
+        k = self._L.adsb_decode_device_packed(self._h, ptr, n, self._out_ref)
+        if k < 0:
+            self._check(-1, "adsb_decode_device_packed")
+        return self._out, k
+
+    def decode_packed(self, buf: np.ndarray, chunk: int | None = None, mode: str = "sync"):
+        """decode() for packed bytes: chunk counts samples (a multiple of 8); the same three modes."""
+        assert buf.dtype == np.uint8 and buf.size % 12 == 0
+        assert chunk is None or chunk % 8 == 0
+        self.reset()
+        step = (chunk if chunk else buf.size // 12 * 8) // 8 * 12   # bytes per push
+        pieces = [buf[i:i + step] for i in range(0, buf.size, max(step, 12))]
+        out = []
+        if mode == "sync":
+            for p in pieces:
+                self.push_packed(p)
+            self.finish()
+            return self.drain()
+        nbuf = 2 if mode == "async" else 1
+        if mode not in ("async", "overlap"):
+            raise ValueError(mode)
+        with PinnedBuffers(nbuf, max(1, step // 2)) as bufs:
+            for k, p in enumerate(pieces):
+                b = bufs[k % nbuf].view(np.uint8)[: p.size]
+                b[:] = p                    # async: the push from this buffer was two calls ago; overlap: the copy is over
+                if mode == "async":
+                    self.push_packed_async(b)
+                else:
+                    self._check(self._L.adsb_push_packed(self._h, b.ctypes.data, b.size // 12 * 8), "adsb_push_packed")
+                    b[:] = 0xFF             # the buffer is the caller's again
+                out += self.drain()
+            self.finish()
+            out += self.drain()
+        return out
 
     def finish(self):
         self._check(self._L.adsb_finish(self._h), "adsb_finish")

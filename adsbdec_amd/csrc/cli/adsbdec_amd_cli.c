@@ -12,6 +12,9 @@
  *                   frames (the reference's -e flag is parsed but does nothing and exits
  *                   with the usage text, main.c:40,60,85-87; that behaviour is kept for -e)
  *     -d k          EXTENSION: decode on GPU k of the node (default: the first one)
+ *     -p            EXTENSION: the file holds Airspy packed 12-bit samples (adsbdec_amd.h: the format; -p as in
+ *                   airspy_rx), unpacked on the GPU.  A trailing partial group (file size % 12 != 0) is not decoded and
+ *                   stderr says how many bytes were ignored.  Not with -G (the multi-GPU driver reads uint16 files only).
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -54,6 +57,8 @@
  * host-to-device copy of one buffer with the scan of the previous one. */
 #define BUF_SAMPLES (16u * 1024u * 1024u)
 #define RING_MAX_BYTES (1024ull * 1024ull * 1024ull)
+/* bytes per ring buffer: BUF_SAMPLES samples, as uint16 (32 MiB) or packed 12-bit with -p (24 MiB: whole 12-byte groups) */
+static size_t buf_bytes = (size_t)BUF_SAMPLES * 2;
 
 typedef struct {
     uint16_t *buf;
@@ -74,7 +79,7 @@ typedef struct {
 static void *reader_main(void *arg)
 {
     ring *r = (ring *)arg;
-    const size_t cap = (size_t)BUF_SAMPLES * 2;
+    const size_t cap = buf_bytes;
     for (int k = 0;; k++) {
         ring_slot *s = &r->slot[k % r->nbuf];
         pthread_mutex_lock(&r->mu);
@@ -131,14 +136,14 @@ static void *locker_main(void *arg)
         const size_t bytes = s->bytes;
         if (r->use_register && !s->registered && s->buf && bytes >= 2) {
             const double t0 = now_ms();
-            s->registered = adsb_host_register(s->buf, (size_t)BUF_SAMPLES * 2) == 0;
+            s->registered = adsb_host_register(s->buf, buf_bytes) == 0;
             r->t_reg += now_ms() - t0;
         }
         pthread_mutex_lock(&r->mu);
         s->ready = 1;
         pthread_cond_broadcast(&r->cv);
         pthread_mutex_unlock(&r->mu);
-        if (bytes < (size_t)BUF_SAMPLES * 2)
+        if (bytes < buf_bytes)
             return NULL;
     }
 }
@@ -146,7 +151,7 @@ static void *locker_main(void *arg)
 static void usage(void)
 {
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
-    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n\n");
+    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
     printf("\t-b : output binary beast format\n");
@@ -154,6 +159,7 @@ static void usage(void)
     printf("\t-l addr[:port] : listen to addr:port (default port 30002) and send ouput to the peer that connects\n");
     printf("\t-x : (extension) repair 1-bit CRC errors in DF17/18 frames\n");
     printf("\t-d k : (extension) use GPU k\n");
+    printf("\t-p : (extension) the file holds Airspy packed 12-bit samples (8 samples in 12 bytes), unpacked on the GPU; not with -G\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-f : input from filename (raw 16 bits real: uint16 carrying the 12-bit ADC code centred on 2048;\n");
@@ -371,11 +377,11 @@ int main(int argc, char **argv)
     const char *filename = NULL;
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
-    int outformat = 0, df18 = 0, fix1 = 0, c;
+    int outformat = 0, df18 = 0, fix1 = 0, packed = 0, c;
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxd:G:s:l:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpd:G:s:l:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -424,6 +430,9 @@ int main(int argc, char **argv)
         case 'x':
             fix1 = 1;
             break;
+        case 'p':
+            packed = 1;
+            break;
         default:
             usage();
             return 1;
@@ -434,6 +443,12 @@ int main(int argc, char **argv)
         usage();
         return 1;
     }
+    if (packed && ndev) {
+        fprintf(stderr, "-p (packed 12-bit input) is not supported with -G: the multi-GPU driver reads uint16 files only\n");
+        return 1;
+    }
+    if (packed)
+        buf_bytes = (size_t)BUF_SAMPLES / 8 * 12;
     install_signals();
     sink_init(&out_sink, outmode, rawaddr);
     out_sink.stop = &stop_requested;
@@ -492,7 +507,7 @@ int main(int argc, char **argv)
             ring_max = (unsigned long long)atoll(getenv("ADSB_CLI_RING_MB")) << 20;
         if (size > ring_max || size == 0)
             size = ring_max; /* pipes and large files: a bounded ring, the reader waits for free buffers */
-        rg.nbuf = (int)(size / ((unsigned long long)BUF_SAMPLES * 2)) + 2;
+        rg.nbuf = (int)(size / buf_bytes) + 2;
         if (rg.nbuf < 3)
             rg.nbuf = 3;
         rg.slot = (ring_slot *)calloc((size_t)rg.nbuf, sizeof *rg.slot);
@@ -559,10 +574,18 @@ int main(int argc, char **argv)
                 break;
             }
             const size_t bytes = s->bytes;
-            if (bytes >= 2) {
-                /* a trailing odd byte is dropped, like decodeiq(iqbuff, n / 2) (air.c:239) */
+            /* a trailing odd byte is dropped, like decodeiq(iqbuff, n / 2) (air.c:239); packed: a trailing partial group (only the
+             * last buffer can have one: a full buffer is whole groups) */
+            const size_t n_samples = packed ? bytes / 12 * 8 : bytes / 2;
+            if (packed && bytes % 12)
+                fprintf(stderr, "%zu trailing bytes ignored (not a whole 12-byte group of packed samples)\n", bytes % 12);
+            if (n_samples) {
                 const double t_p0 = now_ms();
-                const int prc = s->registered ? adsb_push_async(dec, s->buf, bytes / 2) : adsb_push(dec, s->buf, bytes / 2);
+                int prc;
+                if (packed)
+                    prc = s->registered ? adsb_push_packed_async(dec, s->buf, n_samples) : adsb_push_packed(dec, s->buf, n_samples);
+                else
+                    prc = s->registered ? adsb_push_async(dec, s->buf, n_samples) : adsb_push(dec, s->buf, n_samples);
                 t_push += now_ms() - t_p0;
                 n_push++;
                 if (timing > 1)
@@ -588,7 +611,7 @@ int main(int argc, char **argv)
                 pthread_mutex_unlock(&rg.mu);
             }
             prev = k % rg.nbuf;
-            if (bytes < (size_t)BUF_SAMPLES * 2)
+            if (bytes < buf_bytes)
                 break; /* that was the last buffer */
             if (stop_requested) {
                 stopped = 1;

@@ -22,6 +22,11 @@
 // A buffer pushed with adsb_push_device() at a stream position that is a multiple
 // of 8 samples and a 16-byte aligned address is scanned IN PLACE: only the ~4 KiB
 // seam with the previous push and the ~5 KiB tail go through the staging buffer.
+// Packed 12-bit input (adsb_push_packed*, adsb_push_device_packed*) is unpacked by a kernel of its own
+// (unpack12.hip) into exactly the samples those two paths would have been given as uint16:
+//   land[2]    host pushes: the packed bytes of a piece land here (one buffer per copy stream, 1.5 B x
+//              stage_cap), and the unpack writes stage[cur] + stage_fill on the stream of that copy
+//   unpacked   device pushes: 2 B x n of scratch, scanned in place like a uint16 push
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,6 +53,7 @@
 #include "../../include/adsbdec_amd_diag.h"
 #include "config_abi.hpp"
 #include "handoff.hpp"
+#include "packed12.h"
 #include "resolver.hpp"
 #include "scan_kernel.h"
 #include "stitch.hpp"
@@ -238,6 +244,11 @@ struct adsb_decoder {
     hipEvent_t ev_tail = nullptr; // behind a staging compaction's tail copy (process_stage): the copy streams wait for it
     hipEvent_t ev_wait = nullptr; // wait_stream's marker (created at its first use)
     uint64_t piece = 0;        // pieces pushed asynchronously so far
+    // packed 12-bit ingress: landing buffers of host pushes (allocated at the first one), the device pushes' scratch
+    uint8_t *land[kCopyStreams] = {nullptr, nullptr};
+    uint16_t *unpacked = nullptr;
+    size_t unpacked_cap = 0;        // samples
+    hipEvent_t ev_unpack = nullptr; // behind a device push's unpack: the second scan stream waits for it
 
     // Shard-stream mode (adsb_shard_begin .. adsb_shard_end): the stream starts at sample shard_first instead of 0, ends
     // behind offset shard_g_end instead of at the end-of-file horizon, and the resolver runs in chain mode.
@@ -1436,14 +1447,20 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight = false)
 // that the tail copy (it writes [0, left)) does not touch, that scan k-1 does not read (it
 // reads the other buffer, or this one below `left`), and whose previous reader, scan k-2,
 // was collected while piece k-1 was pushed.
-int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind kind, bool async = false)
+// packed (adsb_push_packed*): src holds n / 8 groups of packed 12-bit samples (n % 8 == 0, stage_fill % 8 == 0).  The
+// copy lands them in land[] and the unpack kernel writes the samples where the copy would have, on the copy's stream,
+// before the copy's event: to everything that orders against the copies it is part of the copy.
+int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind kind, bool async = false, bool packed = false)
 {
-    const uint16_t *p = static_cast<const uint16_t *>(src);
+    const char *p = static_cast<const char *>(src);
     while (n) {
-        const uint64_t room = d->stage_cap - kStageSlack - d->stage_fill;
+        uint64_t room = d->stage_cap - kStageSlack - d->stage_fill;
+        if (packed)
+            room = round_down(room, adsb::kPackedGroupSamples);
         if (room == 0)
             return d->fail("staging buffer exhausted (stage_samples too small)");
         const size_t take = (size_t)std::min<uint64_t>(room, n);
+        const size_t bytes = packed ? take / adsb::kPackedGroupSamples * adsb::kPackedGroupBytes : take * sizeof(uint16_t);
         if (async) {
             d->piece++;
             const int cs = (int)(d->piece % adsb_decoder::kCopyStreams);
@@ -1453,19 +1470,31 @@ int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind kind, bo
             // the piece before it, which ends in that line.
             if (d->piece > 1 && (d->stage_fill * sizeof(uint16_t)) % 128 != 0 && d->dbg_async != 2)
                 HIP_TRY(d, hipStreamWaitEvent(cstream, d->ev_copy[cs ^ 1], 0));
-            HIP_TRY(d, hipMemcpyAsync(d->stage[d->cur] + d->stage_fill, p, take * sizeof(uint16_t), kind, cstream));
+            if (packed) {
+                HIP_TRY(d, hipMemcpyAsync(d->land[cs], p, bytes, kind, cstream));
+                HIP_TRY(d, adsb::launch_unpack12(d->stage[d->cur] + d->stage_fill, d->land[cs], take / adsb::kPackedGroupSamples, cstream));
+            } else {
+                HIP_TRY(d, hipMemcpyAsync(d->stage[d->cur] + d->stage_fill, p, bytes, kind, cstream));
+            }
             HIP_TRY(d, hipEventRecord(d->ev_copy[cs], cstream));
             if (d->dbg_async != 2)
                 HIP_TRY(d, hipStreamWaitEvent(d->stream, d->ev_copy[cs], 0));
             if (d->dbg_async == 1)
                 WAIT_STREAM(d, cstream, "a copy stream");
         } else {
-            HIP_TRY(d, hipMemcpyAsync(d->stage[d->cur] + d->stage_fill, p, take * sizeof(uint16_t), kind, d->stream));
+            // (packed: land[0] -- an earlier asynchronous piece that used it is ordered in front by its event, and an earlier
+            // synchronous push was complete when it returned)
+            if (packed) {
+                HIP_TRY(d, hipMemcpyAsync(d->land[0], p, bytes, kind, d->stream));
+                HIP_TRY(d, adsb::launch_unpack12(d->stage[d->cur] + d->stage_fill, d->land[0], take / adsb::kPackedGroupSamples, d->stream));
+            } else {
+                HIP_TRY(d, hipMemcpyAsync(d->stage[d->cur] + d->stage_fill, p, bytes, kind, d->stream));
+            }
             d->copy_unconfirmed = true;
         }
         d->stage_fill += take;
         d->n_samples += take;
-        p += take;
+        p += bytes;
         n -= take;
         if (process_stage(d, false, async))
             return -1;
@@ -1475,6 +1504,64 @@ int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind kind, bo
             // scan leaves only its copy to wait for (already complete in every other case).
             WAIT_EVENT(d, d->ev_copy[(d->piece - 1) % adsb_decoder::kCopyStreams], "the host-to-device copy of the previous piece");
         }
+    }
+    return 0;
+}
+
+// The rules every packed push checks before it changes anything: whole groups, at stream position `at` (a multiple of 8).
+int packed_refusal(adsb_decoder *d, const char *what, size_t n, uint64_t at)
+{
+    if (n % adsb::kPackedGroupSamples != 0)
+        return d->fail("%s: n = %zu is not a multiple of 8 (packed 12-bit input comes in whole 8-sample groups)", what, n);
+    if (at % adsb::kPackedGroupSamples != 0)
+        return d->fail("%s at stream position %llu: packed input must start at a multiple of 8 samples", what,
+                       (unsigned long long)at);
+    return 0;
+}
+
+// The landing buffers of packed host pushes, one per copy stream: a handle that never sees packed input has none.
+int ensure_landing(adsb_decoder *d)
+{
+    const size_t bytes = d->stage_cap / adsb::kPackedGroupSamples * adsb::kPackedGroupBytes;
+    for (int i = 0; i < adsb_decoder::kCopyStreams; i++) {
+        if (d->land[i])
+            continue;
+        if (hipMalloc(&d->land[i], bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            d->land[i] = nullptr;
+            return d->fail("packed input: cannot allocate a landing buffer of %zu bytes on the device", bytes);
+        }
+    }
+    return 0;
+}
+
+int push_packed_host(adsb_decoder *d, const void *packed, size_t n, bool async, const char *what)
+{
+    if (!d)
+        return -1;
+    if (d->finished)
+        return d->fail("%s after adsb_finish", what);
+    if (packed_refusal(d, what, n, d->n_samples) || stream_too_long(d, n))
+        return -1;
+    if (n == 0)
+        return 0;
+    if (!packed)
+        return d->fail("%s: NULL samples", what);
+    HIP_TRY(d, hipSetDevice(d->device));
+    if (ensure_landing(d))
+        return -1;
+    if (async)
+        return push_copy(d, packed, n, hipMemcpyHostToDevice, true, true);
+    if (d->cfg.push_overlap) { // as adsb_push: return once the copy (here: copy + unpack) of this piece has completed
+        if (push_copy(d, packed, n, hipMemcpyHostToDevice, true, true))
+            return -1;
+        return wait_last_copy(d);
+    }
+    if (push_copy(d, packed, n, hipMemcpyHostToDevice, false, true))
+        return -1;
+    if (d->copy_unconfirmed) {
+        WAIT_STREAM(d, d->stream, "the scan stream");
+        d->copy_unconfirmed = false;
     }
     return 0;
 }
@@ -1727,6 +1814,10 @@ void adsb_destroy(adsb_decoder *d)
         if (d->copy_stream[i]) (void)hipStreamDestroy(d->copy_stream[i]);
     }
     if (d->ev_tail) (void)hipEventDestroy(d->ev_tail);
+    if (d->ev_unpack) (void)hipEventDestroy(d->ev_unpack);
+    for (uint8_t *l : d->land)
+        if (l) (void)hipFree(l);
+    if (d->unpacked) (void)hipFree(d->unpacked);
     if (d->ev_wait) (void)hipEventDestroy(d->ev_wait);
     for (int i = 0; i < 2; i++)
         if (d->stage[i])
@@ -1877,6 +1968,16 @@ int adsb_push_async(adsb_decoder *d, const uint16_t *samples, size_t n)
         return d->fail("adsb_push_async: NULL samples");
     HIP_TRY(d, hipSetDevice(d->device));
     return push_copy(d, samples, n, hipMemcpyHostToDevice, true);
+}
+
+int adsb_push_packed(adsb_decoder *d, const void *packed, size_t n)
+{
+    return push_packed_host(d, packed, n, false, "adsb_push_packed");
+}
+
+int adsb_push_packed_async(adsb_decoder *d, const void *packed, size_t n)
+{
+    return push_packed_host(d, packed, n, true, "adsb_push_packed_async");
 }
 
 int adsb_sync(adsb_decoder *d)
@@ -2083,6 +2184,53 @@ int push_device_impl(adsb_decoder *d, const void *device_samples, size_t n, bool
     return 0;
 }
 
+// adsb_push_device_packed*: unpack into the handle's scratch (grown to 2 B x n on demand), then push that in place.
+// The checks come first: a refused push leaves the handle as it was.
+int packed_device_refusal(adsb_decoder *d, const void *device_packed, size_t n, uint64_t at, const char *what)
+{
+    if (packed_refusal(d, what, n, at))
+        return -1;
+    if ((uintptr_t)device_packed % 4 != 0)
+        return d->fail("%s: device pointer %p is not 4-byte aligned", what, device_packed);
+    if (n && !device_packed)
+        return d->fail("%s: NULL samples", what);
+    return 0;
+}
+
+int push_device_packed_impl(adsb_decoder *d, const void *device_packed, size_t n, bool final, const char *what)
+{
+    if (d->finished)
+        return d->fail("%s after adsb_finish", what);
+    if (final && d->shard_on)
+        return d->fail("a shard stream ends with adsb_shard_end");
+    if (packed_device_refusal(d, device_packed, n, d->n_samples, what) || stream_too_long(d, n))
+        return -1;
+    if (n == 0)
+        return final ? push_device_impl(d, nullptr, 0, true) : 0;
+    HIP_TRY(d, hipSetDevice(d->device));
+    if (n > d->unpacked_cap) { // (every earlier push into the scratch has completed: push_device_impl returns behind its reads)
+        if (d->unpacked)
+            (void)hipFree(d->unpacked);
+        d->unpacked = nullptr;
+        d->unpacked_cap = 0;
+        if (hipMalloc(&d->unpacked, n * sizeof(uint16_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            d->unpacked = nullptr;
+            return d->fail("%s: cannot allocate %zu bytes of device scratch for the unpacked samples (2 bytes per sample)", what,
+                           n * sizeof(uint16_t));
+        }
+        d->unpacked_cap = n;
+    }
+    HIP_TRY(d, adsb::launch_unpack12(d->unpacked, device_packed, n / adsb::kPackedGroupSamples, d->stream));
+    if (d->stream2) { // the in-place launches alternate onto the second scan stream, which nothing else orders behind the unpack
+        if (!d->ev_unpack)
+            HIP_TRY(d, hipEventCreateWithFlags(&d->ev_unpack, hipEventDisableTiming));
+        HIP_TRY(d, hipEventRecord(d->ev_unpack, d->stream));
+        HIP_TRY(d, hipStreamWaitEvent(d->stream2, d->ev_unpack, 0));
+    }
+    return push_device_impl(d, d->unpacked, n, final);
+}
+
 } // namespace
 
 extern "C" {
@@ -2106,6 +2254,53 @@ long adsb_decode_device(adsb_decoder *d, const void *device_samples, size_t n, c
     if (adsb_reset(d) != 0 || push_device_impl(d, device_samples, n, true) != 0)
         return -1;
     return (long)d->res.take(frames);
+}
+
+int adsb_push_device_packed(adsb_decoder *d, const void *device_packed, size_t n)
+{
+    if (!d)
+        return -1;
+    return push_device_packed_impl(d, device_packed, n, false, "adsb_push_device_packed");
+}
+
+int adsb_push_device_packed_final(adsb_decoder *d, const void *device_packed, size_t n)
+{
+    if (!d)
+        return -1;
+    return push_device_packed_impl(d, device_packed, n, true, "adsb_push_device_packed_final");
+}
+
+long adsb_decode_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_frame **frames)
+{
+    if (!d || !frames)
+        return -1;
+    // refused before the reset, at the position the reset will set: a refused call leaves the handle as it was
+    if (packed_device_refusal(d, device_packed, n, 0, "adsb_decode_device_packed"))
+        return -1;
+    if (adsb_reset(d) != 0 || push_device_packed_impl(d, device_packed, n, true, "adsb_decode_device_packed") != 0)
+        return -1;
+    return (long)d->res.take(frames);
+}
+
+int adsb_unpack_packed12(void *dst_u16, const void *src, size_t n, void *stream)
+{
+    char why[160] = "";
+    if (n % adsb::kPackedGroupSamples != 0)
+        snprintf(why, sizeof why, "adsb_unpack_packed12: n = %zu is not a multiple of 8", n);
+    else if (n && (!dst_u16 || !src))
+        snprintf(why, sizeof why, "adsb_unpack_packed12: NULL buffer");
+    else if ((uintptr_t)dst_u16 % 16 != 0 || (uintptr_t)src % 4 != 0)
+        snprintf(why, sizeof why, "adsb_unpack_packed12: dst must be 16-byte and src 4-byte aligned (%p, %p)", dst_u16, src);
+    else if (n) {
+        const hipError_t e = adsb::launch_unpack12(static_cast<uint16_t *>(dst_u16), src, n / adsb::kPackedGroupSamples,
+                                                   static_cast<hipStream_t>(stream));
+        if (e != hipSuccess)
+            snprintf(why, sizeof why, "adsb_unpack_packed12: launch failed: %s", hipGetErrorString(e));
+    }
+    if (!why[0])
+        return 0;
+    g_create_error = why;
+    return -1;
 }
 
 int adsb_finish(adsb_decoder *d)

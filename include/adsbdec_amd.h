@@ -20,28 +20,22 @@
  */
 #ifndef ADSBDEC_AMD_H
 #define ADSBDEC_AMD_H
-
 #include <stddef.h>
 #include <stdint.h>
-
 #ifdef __cplusplus
 extern "C" {
 #endif
-
 /* Bumped when an entry point or struct member changes meaning or place; within one version adsb_config and adsb_profile grow
  * at their END only (adsb_create reads cfg->struct_size bytes, adsb_get_profile passes the caller's size).
  * 5 (round 6): adsb_config carries `abi` (adsb_create / adsb_multi_create refuse any other value by name: a binary built against
  *    ABI <= 4 must be rebuilt); the debug_* test knobs left it for adsb_debug_config (adsbdec_amd_diag.h); adsb_profile grew. */
 #define ADSB_ABI_VERSION 5
-
 /* Constants of the path (adsbdec.h:1-3, air.c:32,47). */
 #define ADSB_PULSEW 5
 #define ADSB_DECOFFSET 1200
 #define ADSB_APBUFFSZ 40980
 #define ADSB_WINDOW 1196 /* power samples one long-frame evaluation touches: a[g .. g+1195] */
-
 typedef struct adsb_decoder adsb_decoder; /* one stream == the statics of air.c / demod.c / valid.c */
-
 /* Record leaving the path == the arguments of netout() (valid.c:26, output.c:159) == blk_t (output.c:45-52), plus the
  * global power-sample index of the preamble. */
 typedef struct adsb_frame {
@@ -52,14 +46,12 @@ typedef struct adsb_frame {
     uint8_t frame[14]; /* demod.c:110-123                                         */
     uint8_t reserved;  /* bit 0: repaired by the 1-bit extension (cfg.fix_1bit)   */
 } adsb_frame;
-
 /* valid.c:30-31,84-100: Try/Ok per DF, in the order 11, 17, 18. */
 typedef struct adsb_stats {
     uint64_t try_[3];
     uint64_t ok[3];
     uint64_t fixed; /* frames accepted after a 1-bit repair (extension; 0 by default) */
 } adsb_stats;
-
 typedef struct adsb_config {
     uint32_t struct_size;   /* sizeof(adsb_config) as the CALLER knows it                                         */
     uint32_t abi;           /* ADSB_ABI_VERSION of the caller's header; anything else is refused                  */
@@ -91,7 +83,6 @@ typedef struct adsb_config {
                                second copy engine: 7-9 ms each) beside its other work: for a one-shot process      */
     const void *debug;      /* NULL, or an adsb_debug_config (adsbdec_amd_diag.h: test knobs); copied by adsb_create */
 } adsb_config;
-
 /* Counters accumulate over the life of the handle (adsb_reset keeps them: take differences). */
 typedef struct adsb_profile {
     uint64_t launches;     /* scan-kernel launches since adsb_create                                  */
@@ -113,11 +104,9 @@ typedef struct adsb_profile {
     uint32_t gang_launches;        /* launches whose frames went through the gang                                  */
     uint64_t gang_batches;         /* batches of tiles handed to the gang to be decided ahead of the caller        */
 } adsb_profile;
-
 /* Defaults; the struct's size is the CALLER's: adsb_config_default(&cfg) = adsb_config_init(&cfg, sizeof cfg), which sets cfg.abi. */
 void adsb_config_init(adsb_config *cfg, size_t struct_size);
 #define adsb_config_default(cfg) adsb_config_init((cfg), sizeof(adsb_config))
-
 /* The stream state that air.c:33-34,49-50 / demod.c:86 / valid.c:30-31 keep in statics.  NULL on failure
  * (adsb_last_error(NULL) has the reason).  adsb_reset: the same handle, a fresh stream (ring, ts, stats). */
 adsb_decoder *adsb_create(const adsb_config *cfg);
@@ -139,6 +128,22 @@ int adsb_push_device_final(adsb_decoder *d, const void *device_samples, size_t n
 /* The whole of `adsbdec -f` for ONE capture resident in HBM: adsb_reset + adsb_push_device_final + adsb_take.
  * Returns the number of frames (*frames as adsb_take), or -1. */
 long adsb_decode_device(adsb_decoder *d, const void *device_samples, size_t n, const adsb_frame **frames);
+/* Airspy packed 12-bit input (air.c:120,128,150-151,173-177: the reference asks libairspy for packing, then turns it off).  A group
+ * is 8 samples s0..s7 (12-bit codes, air.c:64) in three little-endian 32-bit words w0 w1 w2; read as ONE 96-bit big-endian number
+ * w0:w1:w2 it is s0 s1 .. s7, 12 bits each, most significant first (written from this definition, not checked against libairspy):
+ *   s0 = w0 >> 20,  s1 = (w0 >> 8) & 0xfff,  s2 = (w0 & 0xff) << 4 | w1 >> 28,  s3 = (w1 >> 16) & 0xfff,  s4 = (w1 >> 4) & 0xfff,
+ *   s5 = (w1 & 0xf) << 8 | w2 >> 24,  s6 = (w2 >> 12) & 0xfff,  s7 = w2 & 0xfff.
+ * n counts SAMPLES: n % 8 == 0, ADSB_PACKED12_BYTES(n) bytes are read, at a stream position that is a multiple of 8 (uint16 and
+ * packed pushes mix at such positions); device pointers 4-byte aligned.  Otherwise -1 and the handle is unchanged.  Frames, ts,
+ * Try/Ok, counters and contracts: those of the uint16 calls.  Extra device memory: host pushes, two landing buffers of 1.5 B x
+ * stage_samples (at the first one); device pushes, a scratch of 2 B x n kept by the handle (grown on demand, freed by adsb_destroy)
+ * into which the input is unpacked and then scanned in place. */
+#define ADSB_PACKED12_BYTES(n) ((n) / 8 * 12)
+int adsb_push_packed(adsb_decoder *d, const void *packed, size_t n);
+int adsb_push_packed_async(adsb_decoder *d, const void *packed, size_t n);
+int adsb_push_device_packed(adsb_decoder *d, const void *device_packed, size_t n);
+int adsb_push_device_packed_final(adsb_decoder *d, const void *device_packed, size_t n);
+long adsb_decode_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_frame **frames);
 /* End of input (fileInput's EOF, air.c:241-244): the remaining offsets, and the end-of-file horizon. */
 int adsb_finish(adsb_decoder *d);
 /* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.
@@ -195,13 +200,11 @@ typedef struct adsb_multi_info { /* of the last adsb_multi_decode_* call */
     int32_t helper_threads; /* reader / gang threads the workers' handles own after the call (sum of
                                adsb_profile.host_threads_running; per worker: adsb_multi_worker_profile)             */
 } adsb_multi_info;
-
 /* n_devices workers; devices[i] = HIP ordinal of worker i (NULL: 0 .. n_devices-1; an ordinal may repeat: plumbing tests
  * on a one-GPU box).  cfg as for adsb_create (device and stream are ignored).  NULL on failure (adsb_multi_last_error(NULL)). */
 adsb_multi *adsb_multi_create(const adsb_config *cfg, int n_devices, const int *devices);
 void adsb_multi_destroy(adsb_multi *m);
 int adsb_multi_devices(const adsb_multi *m);
-
 /* configs[4]: ONE capture, time-sharded over as many devices as it is worth (>= 128 Ki offsets per shard); each worker
  * feeds its halo'd slice in 32 MiB pieces (copy of a piece under the scan of the one before), resolves its shard while
  * its kernels run; the calling thread stitches and the workers gather.  Returns the number of frames, in the reference's
@@ -217,14 +220,12 @@ long adsb_multi_decode_device(adsb_multi *m, uint64_t total_samples, const void 
 int adsb_multi_plan(const adsb_multi *m, uint64_t total_samples, uint64_t *g_begin, uint64_t *g_end,
                     uint64_t *first_sample, uint64_t *n_samples);
 int adsb_multi_get_stats(const adsb_multi *m, adsb_stats *out); /* the stream's Try/Ok table (cfg.collect_stats) */
-
 /* configs[3]: n_streams INDEPENDENT captures, stream s on worker s mod adsb_multi_devices(m), each with its own ts and
  * statistics -- N times what `adsbdec -f` does (main.c:60-89), side by side.  0 / -1; results per stream afterwards. */
 int adsb_multi_decode_streams_host(adsb_multi *m, int n_streams, const uint16_t *const *samples, const size_t *n);
 int adsb_multi_decode_streams_file(adsb_multi *m, int n_streams, const char *const *paths);
 long adsb_multi_stream_frames(const adsb_multi *m, int stream, const adsb_frame **frames);
 int adsb_multi_stream_stats(const adsb_multi *m, int stream, adsb_stats *out);
-
 int adsb_multi_get_info(const adsb_multi *m, adsb_multi_info *out);
 /* A page-locked array for ONE capture that adsb_multi_decode_host will decode, every shard's part on the NUMA node of the
  * device that pulls it (free with adsb_host_free); adsb_multi_worker_placement says whether that held for the last decode. */
@@ -241,9 +242,7 @@ int adsb_multi_worker_profile_sized(const adsb_multi *m, int worker, adsb_profil
 #define adsb_multi_worker_profile(m, worker, out) adsb_multi_worker_profile_sized((m), (worker), (out), sizeof(adsb_profile))
 /* Last error text of m, or of the last failed adsb_multi_create() when m == NULL; names the device and worker. */
 const char *adsb_multi_last_error(const adsb_multi *m);
-
 int adsb_abi_version(void);
-
 #ifdef __cplusplus
 }
 #endif

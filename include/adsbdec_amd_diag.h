@@ -252,6 +252,12 @@ uint16_t *adsb_host_alloc_sharded(uint64_t total_samples, int n_shards, const ui
 int adsb_host_placement(const void *p, size_t bytes, int want_node, int *major_node, double *fraction_on_want);
 int adsb_host_release_mapped(void *p); /* adsb_host_free's first look (1: p was a mapping of the two calls above and is gone) */
 
+/* ---- the unpack of Airspy packed 12-bit input on its own (adsbdec_amd.h: the format; air.c:128,150-151) ------------------------
+ * n samples (n % 8 == 0) = ADSB_PACKED12_BYTES(n) bytes of device memory at src (4-byte aligned) -> n uint16 samples at dst_u16
+ * (16-byte aligned), enqueued on `stream` (a hipStream_t; NULL: the null stream): the caller synchronizes.  The kernel the packed
+ * pushes run.  0, or -1 with the reason in adsb_last_error(NULL). */
+int adsb_unpack_packed12(void *dst_u16, const void *src, size_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
