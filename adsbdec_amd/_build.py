@@ -60,7 +60,10 @@ def _recorded_deps(obj: str) -> list[str] | None:
 
 def _stale(obj: str, src: str) -> bool:
     deps = _recorded_deps(obj)
-    return deps is None or _newer(obj, [src] + deps)
+    # An object compiled in another copy of the tree (a checkout moved or copied together with its lib/) records that copy's
+    # files: their times say nothing about this tree's sources, so it is rebuilt.  (-MMD leaves system headers out: every
+    # file a compile here reads lies under ROOT.)
+    return deps is None or any(not d.startswith(ROOT + os.sep) for d in deps) or _newer(obj, [src] + deps)
 
 
 def _run(cmd: list[str]) -> None:

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import candidate_model
 from conftest import records
 
 pytestmark = pytest.mark.gpu
@@ -248,15 +249,23 @@ def test_shard_stream_primitives_equal_the_one_call_scan(capi, captures, torch_c
             hc1, hc2 = [ckey(c1[i]) for i in range(h1.n_head)], [ckey(cp[i]) for i in range(h2.n_head)]
             if every is None:
                 d3 = capi.Decoder(df18=True, all_candidates=True)
-                cs, nc, _ = d3.scan_shard(t.data_ptr(), 0, total, 0, max(0, total // 2 - 1195), cand_cap=1 << 18)
-                every = {ckey(cs[i]) for i in range(nc)}
+                cs, nc, _ = d3.scan_shard(t.data_ptr(), 0, total, 0, 2 * ((total + 3) // 4) - 1195, cand_cap=1 << 18)
+                every = [ckey(cs[i]) for i in range(nc)]   # every offset of the capture, ascending
                 d3.close()
             for hc in (hc1, hc2):
-                assert hc == sorted(hc) and all(p["g_begin"] <= c[0] < h1.head_end for c in hc) and set(hc) <= every
+                assert hc == sorted(hc) and all(p["g_begin"] <= c[0] < h1.head_end for c in hc) and set(hc) <= set(every)
                 accepted = {(int(f1[i].g), int(f1[i].pw), int(f1[i].len), bytes(f1[i].frame)[: f1[i].len].ljust(14, b"\0")) for i in range(h1.n_frames)
                             if f1[i].g < h1.head_end}
                 assert {(c[0], c[1], c[2], c[3][: c[2]].ljust(14, b"\0")) for c in hc} >= accepted
             assert abs(h1.n_head - h2.n_head) <= max(8, h1.n_head // 8)
+            # ... and the candidates they differ in are reachable from no entry the stitcher can re-enter the shard at: the two
+            # head lists and the exhaustive one, cut at head_end, give the same greedy chain from every offset of
+            # [g_begin, g_begin + 1200) (tests/candidate_model.py)
+            model = lambda cl: [(c[0], c[1], c[3][: c[2]]) for c in cl if c[0] < h1.head_end]
+            m1, m2, me = model(hc1), model(hc2), model(c for c in every if c[0] >= p["g_begin"])
+            entries = range(p["g_begin"], min(p["g_begin"] + candidate_model.ENTRY_REACH, h1.head_end))
+            for u, v in ((me, m1), (me, m2), (m1, m2)):
+                assert not candidate_model.equivalent_from(u, v, entries, h1.head_end), (mode, p["g_begin"])
             assert list(b1[: h1.n_bases]) == list(b2[: h2.n_bases])
             # a shard stream refuses what belongs to an ordinary stream, and the other way round
             assert L.adsb_push(d2._h, x.ctypes.data, 8) != 0

@@ -522,3 +522,23 @@ def test_build_follows_the_headers_the_compiler_read(tmp_path):
         assert not _build._stale(os.path.join(_build.LIBDIR, "numa.cpp.o"), os.path.join(_build.CSRC, "numa.cpp"))   # (does not include it)
     finally:
         os.utime(gang, (st.st_atime, st.st_mtime))
+
+
+def test_build_rebuilds_objects_compiled_in_another_copy_of_the_tree(tmp_path):
+    """An object whose depfile names files of ANOTHER copy of the tree (a checkout copied or moved together with its lib/,
+    the old copy still in place) is stale: those files' times say nothing about this tree's headers, and an edit here would
+    otherwise leave the object -- and a depfile that does not name this tree's headers -- as it was."""
+    from adsbdec_amd import _build
+    src = os.path.join(_build.CSRC, "host_abi.cpp")
+    here = [src, os.path.join(_build.CSRC, "gang.hpp")]
+    other = tmp_path / "old_copy" / "adsbdec_amd" / "csrc"
+    other.mkdir(parents=True)
+    (other / "gang.hpp").write_text("// the old copy's header\n")
+    obj = tmp_path / "host_abi.cpp.o"
+    obj.write_bytes(b"")
+    future = max(os.path.getmtime(p) for p in here + [str(other / "gang.hpp")]) + 60
+    os.utime(obj, (future, future))                      # newer than every file it names: only WHERE they lie can make it stale
+    (tmp_path / "host_abi.cpp.o.d").write_text(f"{obj}: \\\n " + " \\\n ".join(here) + "\n")
+    assert not _build._stale(str(obj), src)
+    (tmp_path / "host_abi.cpp.o.d").write_text(f"{obj}: \\\n {src} \\\n {other / 'gang.hpp'}\n")
+    assert _build._stale(str(obj), src)
