@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the adsbdec "-f" demodulation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode stream|shard] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode stream|shard] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -30,6 +30,14 @@ the JSON line as `preroll_ms`): the GPU's clock governor needs ~20 ms of load to
 and a service decoding captures back to back lives in that steady state.
 `value_cold` is the same step timed right after an idle period, without pre-roll.
 
+A plain run does only what the headline figure needs: it sets up, pre-rolls, warms up,
+times the K steps, writes --dump-outputs and prints the line.  --full adds, after the timed
+steps, everything else the benchmark measures or checks: the repeat of every capture of
+the rotation, the CPU baseline and the parity gates (on every rank; in shard mode against
+the single-handle decode and the CPU path), and the legs that take runs of their own
+(value_cold, value_1000_steps, with_stats, dense, the host-fed and C host program
+figures).  In a plain run those keys are null.
+
 Rank 0 prints ONE JSON line.  `value` is whole-job Msamples/s, inputs resident in HBM.
 `roofline` prices the scan kernel against HBM (algorithmic traffic = 2 B per input sample
 = 4 B per preamble offset; kernel time = latest tile end - earliest tile start on the
@@ -38,8 +46,8 @@ rocprofv3); `roofline_valu` prices it against what actually binds it, VALU issue
 (DESIGN.md 4).  `cpu_baseline` is the REAL reference chain (oracle/_ref/ref_adsbdec:
 air.c decodeiq + demod.c + valid.c compiled from the reference, 1 thread) timed on this
 host on the same capture when that binary travelled with the snapshot (kind
-"reference"), else the oracle's C restatement (kind "port"); either way the run is gated:
-every frame the GPU path returned must equal the CPU result.  `e2e_host_fed` is the
+"reference"), else the oracle's C restatement (kind "port"); either way a --full run is
+gated: every frame the GPU path returned must equal the CPU result.  `e2e_host_fed` is the
 PCIe-inclusive rate from page-locked host memory (never `value`).
 """
 from __future__ import annotations
@@ -638,7 +646,7 @@ def host_fed_rates(torch, capi, x_dev, df18):
     return out
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -656,8 +664,8 @@ def main():
     ap.add_argument("--gate-storm", action="store_true",
                     help="the adversarial capture as the main workload: nothing but frame starts, every tile overflows its survivor queue, -a")
     ap.add_argument("--stats", action="store_true", help="also reproduce valid.c's Try counters (collect_stats=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cold / dense / host-fed legs (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity gates")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the cold / dense / host-fed legs (profiling runs)")
     ap.add_argument("--shard-source", choices=["device", "host", "file"], default="device",
                     help="shard mode: the slices are resident in their devices' HBM (default), or one capture in page-locked host "
                          "memory / in a tmpfs file is fed to the devices by the library's workers (PCIe-inclusive)")
@@ -671,7 +679,15 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0's frames, and the Try/Ok table "
                          "with --stats) as DIR/<name>.npy")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline figure: the CPU baseline and the parity "
+                         "gates, and the legs that take runs of their own (cold, 1000 steps, host-fed, C host program, with the "
+                         "Try/Ok table, dense captures); --no-cpu-baseline / --no-extras trim it")
+    return ap
+
+
+def main():
+    args = make_parser().parse_args()
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
 
@@ -753,12 +769,15 @@ def main():
         return dec.decode_device_raw(p, m)  # adsb_decode_device == adsb_reset + adsb_push_device_final + adsb_take, one call;
         #                                     the frames stay where the library queued them and are converted after timing
 
+    if not args.no_extras:
+        step(0)                       # loads the code object, allocates the slot buffers (outside the pre-roll's wall time)
+        torch.cuda.synchronize()
+        time.sleep(0.5)               # let the clocks fall back: the pre-roll starts from idle (as it does behind the cold
+        #                               figure), not straight behind the capture generation
+
     # ---- cold figure: the first steps after an idle period, no pre-roll (a one-shot `adsbdec -f` user lives here)
     value_cold = None
-    if not args.no_extras:
-        step(0)                       # loads the code object, allocates the slot buffers
-        torch.cuda.synchronize()
-        time.sleep(0.5)               # let the clocks fall back
+    if args.full and not args.no_extras:
         cold_steps = 3
         pk0 = dec.profile()
         with ClockSampler(local_rank) as cold_clock:
@@ -811,7 +830,7 @@ def main():
     # ---- the same step 1000 more times (the driver's default is 20 steps = 3 ms of measurement; box-to-box the kernel
     # spreads by 7 %): a sturdier sample of the same quantity, every rank, same fences
     steady = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         q0 = dec.profile()
         with ClockSampler(local_rank) as sampler2:
             dt2, _ = timed_steps(step, 1000, fence, torch.cuda.synchronize)
@@ -823,19 +842,21 @@ def main():
                   "what": "the timed region repeated with 1000 steps right behind the K steps of `value` (same captures in rotation, "
                           "same fences): 0.15 s of measurement instead of 3 ms"}
 
+    # ---- everything below, up to the JSON line, runs with --full only: a plain run stops at the headline figure
     # every capture of the rotation, decoded once more and kept for the gate
     per_capture = []
-    for j in range(len(ptrs)):
-        pj = step(j)
-        per_capture.append(capi._frames_to_dicts(pj[0], pj[1]))
-    if frames_key(per_capture[last]) != frames_key(frames):
-        raise SystemExit("PARITY FAILURE: the last timed step and a repeat of the same capture differ")
+    if args.full:
+        for j in range(len(ptrs)):
+            pj = step(j)
+            per_capture.append(capi._frames_to_dicts(pj[0], pj[1]))
+        if frames_key(per_capture[last]) != frames_key(frames):
+            raise SystemExit("PARITY FAILURE: the last timed step and a repeat of the same capture differ")
 
     # ---- correctness gate on EVERY rank (each decodes its own stream: demod.c:86,99,125-141 and air.c:94-99 are
     # sequential rules that nothing else would check at N > 1) + the CPU baseline, timed on rank 0 only ----
     cpu = None
     parity = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         if world > 1:        # one rank (re)builds the checker's shared object, the others load it afterwards
             if rank == 0:
@@ -864,7 +885,7 @@ def main():
     multi = None
     sharded = None
     cli = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         e2e = host_fed_rates(torch, capi, xs[0], df18)
         multi = multi_stream_host_fed(torch, capi, xs[0], df18)
         dsx = capi.Decoder(df18=df18, device=local_rank, collect_stats=True)
@@ -977,7 +998,7 @@ def main():
             "value": round(value, 1), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "preroll_ms": args.preroll_ms, "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": workload, "samples_per_gpu": n, "frames_decoded_rank0": len(frames),
                        "parity_vs_cpu": parity, "ranks_gated": world if parity else 0, "cpu_binding_rank0": cpu_binding},
             "roofline": roofline, "roofline_valu": roofline_valu, "cpu_baseline": cpu,
@@ -1095,7 +1116,7 @@ def run_shard(args, torch, capi, rank, world, fence):
         dump_outputs(args.dump_outputs, frames, stats_table)
 
     cpu, parity = None, None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         if source == "device":
             whole = capture(0, total)
             x_host = None
@@ -1121,7 +1142,7 @@ def run_shard(args, torch, capi, rank, world, fence):
         "metric": "Msamples/s demodulated (20MSPS uint16 real), whole job",
         "value": round(value, 1), "unit": "Msamples/s", "n_gpus": n_dev, "steps": args.steps,
         "warmup": args.warmup, "preroll_ms": args.preroll_ms, "ms_per_step": round(dt / args.steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
         "config": {"workload": ("BASELINE configs[4] x configs[2] (112-bit frames packed back to back, ~10 % of the offsets pass the preamble "
                                 "test: every worker's handle runs its reader thread and gang of four): " if dense10 else "BASELINE configs[4]: ")
                                + f"ONE stream of {total} uint16 samples time-sharded over {len(plan)} "

@@ -147,6 +147,13 @@ def test_dump_outputs_writes_every_frame_field_as_float(tmp_path, monkeypatch):
     assert not os.path.exists(tmp_path / "a" / "stats_try_ok.npy")
 
 
+def test_full_is_opt_in():
+    """A plain run stops at the headline figure; the gates, the CPU baseline and the legs of their own need --full."""
+    ap = bench.make_parser()
+    assert ap.parse_args([]).full is False
+    assert ap.parse_args(["--full", "--no-extras"]).full is True
+
+
 def test_steps_below_one_are_refused(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
     with pytest.raises(SystemExit, match="--steps must be at least 1"):

@@ -369,7 +369,7 @@ def test_cli_several_captures_one_per_handle(capi, oracle, tmp_path):
 
 def test_bench_shard_mode_runs_the_c_driver(tmp_path):
     """`python bench.py --mode shard --gpus K --one-device-test`: ONE process, K handles on this GPU through adsb_multi_*
-    (device-resident slices, and a page-locked host capture), gated against the single-handle decode of the same stream."""
+    (device-resident slices, and a page-locked host capture), gated (--full) against the single-handle decode of the same stream."""
     import json
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -377,7 +377,7 @@ def test_bench_shard_mode_runs_the_c_driver(tmp_path):
     for extra in (["--gpus", "3"], ["--gpus", "8", "--stats"], ["--gpus", "2", "--shard-source", "host", "--stats"],
                   ["--gpus", "2", "--shard-source", "file"]):
         p = subprocess.run([sys.executable, "bench.py", "--mode", "shard", "--one-device-test", "--samples", str(64 << 20), "--steps", "3",
-                            "--warmup", "1", "--preroll-ms", "0"] + extra, cwd=root, capture_output=True, timeout=900, env=env)
+                            "--warmup", "1", "--preroll-ms", "0", "--full"] + extra, cwd=root, capture_output=True, timeout=900, env=env)
         assert p.returncode == 0, p.stderr.decode()[-3000:]
         lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
         assert len(lines) == 1

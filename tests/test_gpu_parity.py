@@ -913,11 +913,32 @@ def test_two_rank_independent_streams_are_gated_on_every_rank():
     """BASELINE configs[3] plumbing: `python bench.py --gpus 2` (stream mode), two ranks on this one GPU, each
     with its own stream and handle; EVERY rank compares its frames with the oracle after the timed region."""
     line = _bench_line(["--gpus", "2", "--one-device-test", "--samples", str(16 << 20), "--steps", "3", "--warmup", "1",
-                        "--preroll-ms", "0", "--no-extras"])
+                        "--preroll-ms", "0", "--no-extras", "--full"])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak"
     assert line["config"]["parity_vs_cpu"] is True and line["config"]["ranks_gated"] == 2
     assert line["config"]["frames_decoded_rank0"] > 500
     assert line["cpu_baseline"]["value"] > 0
+
+
+def test_plain_run_stops_at_the_headline_figure(capi, oracle, torch_cuda, tmp_path):
+    """`python bench.py` without --full: the timed steps, --dump-outputs and the line -- no gate, no CPU baseline, no leg of
+    its own -- and the dumped frames are those of the last timed step's capture (checked here against the oracle)."""
+    from tools.gen_signal import make_workload
+    n = 16 << 20
+    line = _bench_line(["--samples", str(n), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert line["full"] is False and line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "Msamples/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["roofline"]["launch_ms"] > 0
+    assert line["cpu_baseline"] is None and line["config"]["parity_vs_cpu"] is None and line["config"]["ranks_gated"] == 0
+    for key in ("value_cold", "value_1000_steps", "with_stats", "dense", "e2e_host_fed", "multi_stream_host_fed",
+                "e2e_host_fed_sharded", "cli_whole_process"):
+        assert line[key] is None, key
+    # step 1 of the rotation (seed 1 + 1000) was the last timed one
+    x, _ = make_workload(torch_cuda, n - n % 28, seed=1001)
+    want, _ = oracle.decode(x.cpu().numpy().view(np.uint16), df18=False)
+    for key in ("g", "ts", "pw"):
+        assert np.load(tmp_path / "out" / f"frames_{key}.npy").tolist() == [f[key] for f in want], key
+    assert line["config"]["frames_decoded_rank0"] == len(want) > 500
 
 
 # ------------------------------------------------------------------ size-independent properties
@@ -932,7 +953,7 @@ def test_eight_ranks_on_one_device(capi):
     if n_dev < 8:
         pytest.skip(f"needs 8 GPUs (one rank per device), found {n_dev}")
     line = _bench_line(["--gpus", "8", "--samples", str(8 << 20), "--steps", "3", "--warmup", "1",
-                        "--preroll-ms", "0", "--no-extras"], timeout=1200)
+                        "--preroll-ms", "0", "--no-extras", "--full"], timeout=1200)
     assert line["n_gpus"] == 8 and line["scaling"] == "weak"
     assert line["config"]["parity_vs_cpu"] is True and line["config"]["ranks_gated"] == 8
     assert line["cpu_baseline"]["value"] > 0
