@@ -405,6 +405,18 @@ bool stream_too_long(adsb_decoder *d, size_t n)
     return true;
 }
 
+// The same limit for the shard primitives, which take stream positions instead of counting pushes: a window
+// [first_sample, first_sample + n) and a stream length total_samples must both stay below 2^32 samples.
+bool shard_too_long(adsb_decoder *d, const char *what, uint64_t first_sample, uint64_t n, uint64_t total_samples)
+{
+    const uint64_t lim = 1ull << 32;
+    if (first_sample < lim && n < lim - first_sample && total_samples < lim)
+        return false;
+    d->fail("%s: %s reaches 2^32 samples: the reference's sample counter wraps there (air.c:34) and no parity is defined beyond",
+            what, total_samples < lim ? "window" : "stream");
+    return true;
+}
+
 int slot_reserve_device_tries(adsb_decoder *d, ScanSlot &s, size_t want_list, size_t want_tiles)
 {
     if (want_list > s.d_try_cap || want_tiles > s.d_try_tiles) {
@@ -2381,6 +2393,8 @@ int adsb_scan_shard(adsb_decoder *d, const void *device_samples, uint64_t first_
 {
     if (!d || !device_samples || !n_cands || !n_tries)
         return -1;
+    if (shard_too_long(d, "adsb_scan_shard", first_sample, n, 0))
+        return -1;
     if (first_sample % 8 || (uintptr_t)device_samples % 16)
         return d->fail("adsb_scan_shard: buffer must start at a multiple of 8 samples, 16-byte aligned");
     if (g_begin % 28)
@@ -2422,6 +2436,8 @@ int adsb_scan_shard_host(adsb_decoder *d, const uint16_t *host_samples, uint64_t
                          size_t *n_tries)
 {
     if (!d || !host_samples || !n_cands || !n_tries)
+        return -1;
+    if (shard_too_long(d, "adsb_scan_shard_host", first_sample, n, 0))
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     if (n > d->win_cap) {
@@ -2498,6 +2514,8 @@ int scan_shard_resolved_core(adsb_decoder *d, const void *device_samples, uint64
     *fp = nullptr;
     if (d->n_samples != 0 || d->res.pending() != 0) // (it runs this handle's own resolver: a stream in progress would be lost)
         return d->fail("adsb_scan_shard_resolved: the handle holds a stream (adsb_reset it, or use a handle of its own)");
+    if (shard_too_long(d, "adsb_scan_shard_resolved", first_sample, n, total_samples))
+        return -1;
     if (first_sample % 8 || (uintptr_t)device_samples % 16)
         return d->fail("adsb_scan_shard_resolved: buffer must start at a multiple of 8 samples, 16-byte aligned");
     if (g_begin % 28)
@@ -2589,6 +2607,8 @@ int adsb_shard_begin(adsb_decoder *d, uint64_t first_sample, uint64_t g_begin, u
                      uint64_t *bases, size_t bases_cap)
 {
     if (!d)
+        return -1;
+    if (shard_too_long(d, "adsb_shard_begin", first_sample, 0, total_samples))
         return -1;
     if (first_sample % 8)
         return d->fail("adsb_shard_begin: first_sample must be a multiple of 8 samples");

@@ -97,7 +97,10 @@ long adsb_resolver_advance_stream(adsb_resolver *r, const void *stream, size_t g
  * return its CRC-valid candidates / tries (sorted). No stream state is touched:
  * this is the per-shard call of the multi-GPU path. Returns counts through
  * n_cands/n_tries; -1 on error, -2 if a capacity was too small (counts are set
- * to what is needed). */
+ * to what is needed).
+ * The 2^32 limit of a stream holds here too: this call, adsb_scan_shard_host,
+ * adsb_scan_shard_resolved* and adsb_shard_begin fail (with a message naming
+ * 2^32) when first_sample + n or total_samples reaches 2^32 samples. */
 int adsb_scan_shard(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n,
                     uint64_t g_begin, uint64_t g_end, adsb_candidate *cands, size_t cand_cap,
                     size_t *n_cands, uint64_t *tries, size_t try_cap, size_t *n_tries);

@@ -292,6 +292,25 @@ def ref_decode(x, df18: bool = False, chunk: int | None = None, native: bool = F
     return answer
 
 
+def ref_decode_pieces(pieces, df18: bool = False):
+    """ref_decode of the concatenation of `pieces` (uint16 arrays), written to the chain through a pipe: its read loop is
+    fread on the path it is given (fileInput's shape), so a stream of any length needs no file of that size."""
+    opts = ["-a"] if df18 else []
+    with tempfile.TemporaryFile() as out, tempfile.TemporaryFile() as err:
+        p = subprocess.Popen([REF_ADSBDEC] + opts + ["/dev/stdin"], stdin=subprocess.PIPE, stdout=out, stderr=err)
+        try:
+            for x in pieces:
+                p.stdin.write(memoryview(_as_u16(x)).cast("B"))
+        finally:
+            p.stdin.close()
+        rc = p.wait()
+        out.seek(0)
+        err.seek(0)
+        res = subprocess.CompletedProcess(p.args, rc, out.read(), err.read())
+    res.check_returncode()
+    return _parse_ref_output(res)
+
+
 def ref_power(x, chunk: int | None = None) -> np.ndarray:
     """Power samples produced by the REAL decodeiq (air.c:54-92) for capture x: one
     per 2 input samples, 2*ceil(n/4) of them (a ragged tail's last pair is computed

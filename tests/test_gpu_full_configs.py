@@ -287,15 +287,38 @@ def test_config2_dense_traffic_through_the_multi_gpu_driver(capi, oracle, torch_
         md.close()
 
 
+def _frames_equal_the_oracle_offset_by_offset(oracle, t, frames, df18, chunk=1 << 27):
+    """Each frame's pw and bytes against the oracle's evaluation of its offset g (oracle.eval_offset) on power samples of a
+    local window copied from the device: from the multiple of 28 samples at or below 2 g - 12 (the stream's FIR phase, and
+    the 14 taps behind power sample g) to the frame's whole window.  The copies go in pieces of `chunk` samples."""
+    n = t.numel()
+    k = 0
+    for c0 in range(0, n, chunk):
+        host = None
+        while k < len(frames):
+            g = frames[k]["g"]
+            s0, s1 = max(0, (2 * g - 12) // 28 * 28), 2 * (g + 1196)
+            if s0 >= c0 + chunk:
+                break
+            if host is None:
+                host = _host(t[c0: min(n, c0 + chunk + 2 * 1196 + 28)])
+            a = oracle.power(np.ascontiguousarray(host[s0 - c0: s1 - c0]))
+            ok, fr, pw = oracle.eval_offset(a, g - s0 // 2, df18)
+            assert ok >= 2 and (fr, pw) == (bytes(frames[k]["frame"]), frames[k]["pw"]), frames[k]
+            k += 1
+    assert k == len(frames)
+
+
 @pytest.mark.gpu_big          # opt-in (--gpu-big): 8 GiB of HBM, 215 k frames synthesised on the host, minutes of wall time
 @pytest.mark.limit(1500)
-def test_a_stream_just_below_the_sample_counter_limit(capi, torch_cuda):
+def test_a_stream_just_below_the_sample_counter_limit(capi, oracle, torch_cuda):
     """The longest stream there is: 2^32 - 4 samples (3.6 minutes of signal, 8 GiB resident in HBM; the reference's sample
     counter wraps at 2^32, air.c:34, and the library refuses a stream that would reach it).  No CPU oracle at this size: the
     size-independent properties instead -- ts is the checksum of the whole greedy replay (demod.c:86,99,128,134), every decoded
     frame is one that was sent, in order -- and two independent paths through the library against each other, frame for frame
     and Try/Ok table for table: one handle decoding the stream in one pass (32 launches), and the multi-GPU driver with eight
-    handles on this device (eight shards, each resolved on its own, seams and horizon stitched)."""
+    handles on this device (eight shards, each resolved on its own, seams and horizon stitched).  And every frame's pw and
+    bytes, above sample 2^31 too, against the oracle's evaluation of its offset on the samples around it."""
     from adsbdec_amd import sharding
     from tools.gen_signal import make_workload
     n = ((1 << 32) - 1) // 28 * 28
@@ -311,6 +334,8 @@ def test_a_stream_just_below_the_sample_counter_limit(capi, torch_cuda):
         assert got[-1]["g"] > (n // 2) - 40_980 - 1200 - 30_000          # frames right up to the end-of-file horizon
         sent = iter(fr for _, fr in truth)
         assert all(any(f["frame"] == s for s in sent) for f in got)
+        assert sum(f["g"] >= 1 << 30 for f in got) > 0.4 * len(got)
+        _frames_equal_the_oracle_offset_by_offset(oracle, t, got, False)
         md = sharding.MultiDecoder(8, [0] * 8, df18=False, collect_stats=True)
         try:
             plan = md.plan(n)
