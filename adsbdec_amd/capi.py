@@ -109,6 +109,9 @@ SYMBOLS = {
     "adsb_create": (C.c_void_p, [C.c_void_p]),
     "adsb_destroy": (None, [C.c_void_p]),
     "adsb_reset": (C.c_int, [C.c_void_p]),
+    "adsb_set_long_stream": (C.c_int, [C.c_void_p, C.c_int]),
+    "adsb_get_wraps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "adsb_multi_set_long_streams": (C.c_int, [C.c_void_p, C.c_int]),
     "adsb_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_push_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_sync": (C.c_int, [C.c_void_p]),
@@ -306,7 +309,7 @@ def make_config(df18: bool = False, device: int = -1, collect_stats: bool = Fals
 class Decoder:
     """One stream (== the statics of air.c / demod.c / valid.c).  Keywords: make_config."""
 
-    def __init__(self, **cfg_kw):
+    def __init__(self, long_stream: bool = False, **cfg_kw):
         L = load()
         cfg = make_config(**cfg_kw)
         self._L = L
@@ -314,6 +317,8 @@ class Decoder:
         self._h = L.adsb_create(C.byref(cfg))
         if not self._h:
             raise AdsbError("adsb_create failed: " + (L.adsb_last_error(None) or b"").decode())
+        if long_stream:
+            self.set_long_stream(True)
         self._out = C.POINTER(Frame)()          # decode_device_raw's result pointer and its reference, made once
         self._out_ref = C.byref(self._out)
         self._decode_device = L.adsb_decode_device
@@ -335,6 +340,16 @@ class Decoder:
 
     def reset(self):
         self._check(self._L.adsb_reset(self._h), "adsb_reset")
+
+    def set_long_stream(self, on: bool = True):
+        """adsb_set_long_stream: streams of 2^32 samples and more (fresh or reset handle, before the first push)."""
+        self._check(self._L.adsb_set_long_stream(self._h, int(bool(on))), "adsb_set_long_stream")
+
+    def wraps(self):
+        """(wraps of the reference's sample counter in the current stream, offsets that went through the seam kernel)."""
+        w, s = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.adsb_get_wraps(self._h, C.byref(w), C.byref(s)), "adsb_get_wraps")
+        return int(w.value), int(s.value)
 
     def push(self, x: np.ndarray):
         x = np.ascontiguousarray(x)

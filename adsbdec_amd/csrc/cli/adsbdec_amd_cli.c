@@ -164,6 +164,8 @@ static void usage(void)
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-f : input from filename (raw 16 bits real: uint16 carrying the 12-bit ADC code centred on 2048;\n");
     printf("\t     bit-identical to adsbdec for codes 0..4095, see adsbdec_amd.h for the wider domain)\n");
+    printf("\t     a file of any length: 2^32 samples (8 GiB) and more are decoded through the wraps of adsbdec's 32-bit\n");
+    printf("\t     sample counter, as adsbdec itself does; one file sharded over several GPUs (-G) stays below 2^32 samples\n");
 }
 
 static sink out_sink; /* stdout unless -s / -l */
@@ -341,6 +343,7 @@ static int run_multi(const adsb_config *cfg, int *devs, int ndev, char **files, 
                 print_stats(&st);
         }
     } else {
+        adsb_multi_set_long_streams(m, 1); /* one capture per device: ordinary handles, files of any length */
         if (adsb_multi_decode_streams_file(m, nfiles, (const char *const *)files) != 0) {
             fprintf(stderr, "adsb_multi_decode_streams_file() failed: %s\n", adsb_multi_last_error(m));
             rc = 255;
@@ -542,6 +545,10 @@ int main(int argc, char **argv)
     if (!dec) {
         fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
         return 255; /* runOutput() == -1 -> exit status 255 (main.c:101-105) */
+    }
+    if (adsb_set_long_stream(dec, 1) != 0) { /* always: the reference reads a file of any length (its counter wraps, air.c:34) */
+        fprintf(stderr, "adsb_set_long_stream() failed: %s\n", adsb_last_error(dec));
+        return 255;
     }
     const double t_init = now_ms();
 

@@ -19,6 +19,7 @@
 //   cands      "loose" list, kCandWords dwords per record, appended with one atomic: records
 //              that could not go through the stream; collected after completion
 //   tries      try words of per-shard scans, which hand the list back to the caller
+//   seam_out   long streams (adsb_set_long_stream): the records and try words of a seam launch (seam_kernel.h), waited for
 // A buffer pushed with adsb_push_device() at a stream position that is a multiple
 // of 8 samples and a 16-byte aligned address is scanned IN PLACE: only the ~4 KiB
 // seam with the previous push and the ~5 KiB tail go through the staging buffer.
@@ -56,6 +57,7 @@
 #include "packed12.h"
 #include "resolver.hpp"
 #include "scan_kernel.h"
+#include "seam_kernel.h"
 #include "stitch.hpp"
 
 namespace {
@@ -116,6 +118,8 @@ struct ScanSlot {
     bool prof_pending[2] = {false, false}; // kernel time of a collected launch not read yet
     hipEvent_t ev_count = nullptr; // statistics runs: the count pass over d_tries (count stream) has ended;
     bool count_pending = false;    // the slot's next scan waits for it before it overwrites the list
+    uint64_t epoch_base = 0; // long streams: first power sample P of the epoch the launch lies in.  `args` stays in stream
+                             // coordinates for everything the host does; the KERNEL is given them minus P (slot_launch)
 };
 
 constexpr int kSlots = 4;
@@ -159,6 +163,12 @@ struct adsb_decoder {
     uint64_t n_samples = 0; // samples accepted
     uint64_t g_scanned = 0; // every offset below has been submitted to the device
     bool finished = false;
+    // Long streams (adsb_set_long_stream): no refusal at 2^32 samples; launches are cut at every wrap of the reference's
+    // sample counter and the offsets around it go through the seam kernel (scan_submit, seam_kernel.h)
+    bool long_stream = false;
+    uint64_t seam_offsets = 0;     // offsets of the current stream that went through the seam kernel
+    uint32_t *seam_out = nullptr;  // pinned: adsb::kSeamOutWords (the seam kernel's records and try words)
+    ScanSlot seam_slot;            // what count_tries_pass needs of a slot (its try list, two events), for a seam launch
 
     // staging
     uint16_t *stage[2] = {nullptr, nullptr};
@@ -372,7 +382,13 @@ uint64_t scannable_end(const adsb_decoder *d, uint64_t n_samples, bool final)
     if (d->shard_on)
         m = n_samples / 2; // every complete pair
     uint64_t g_end = m >= ADSB_WINDOW ? m - ADSB_WINDOW + 1 : 0;
-    if (!final)
+    if (!final && d->long_stream) {
+        // run boundaries are those of the EPOCH (a scan launch is given epoch-relative indices, and 2^31 mod 28 = 16); a scan
+        // may stop anywhere among the seam offsets of a wrap, which need no alignment -- only the staging tail's (4 offsets)
+        const uint64_t P = round_down(g_end, adsb::kEpoch), r = g_end - P;
+        const bool in_seam = (P && r < (uint64_t)adsb::kSeamBehind) || r >= adsb::kEpoch - adsb::kSeamWindow;
+        g_end = in_seam ? round_down(g_end, 4) : P + round_down(r, 28);
+    } else if (!final)
         g_end = round_down(g_end, 28);
     if (d->shard_on && g_end > d->shard_g_end)
         g_end = d->shard_g_end;
@@ -395,13 +411,13 @@ int wait_last_copy(adsb_decoder *d)
 }
 
 // The reference's ring index `fidx` is a uint32_t that counts input samples (air.c:34): at 2^32 samples it
-// wraps, 2^32 mod 14 = 4, and the ring phase jumps.  No parity is defined beyond that point, so a
-// stream is refused there instead of being decoded differently from the reference.
+// wraps, 2^32 mod 14 = 4, and the ring phase jumps.  By default a stream is refused there; a handle with
+// adsb_set_long_stream follows the reference through the wrap (scan_submit, seam_kernel.hip; DESIGN.md "Input domain").
 bool stream_too_long(adsb_decoder *d, size_t n)
 {
-    if (d->n_samples + (uint64_t)n < (1ull << 32))
+    if (d->long_stream || d->n_samples + (uint64_t)n < (1ull << 32))
         return false;
-    d->fail("stream would reach 2^32 samples: the reference's sample counter wraps there (air.c:34) and no parity is defined beyond");
+    d->fail("stream would reach 2^32 samples: the reference's sample counter wraps there (air.c:34); adsb_set_long_stream decodes beyond");
     return true;
 }
 
@@ -556,7 +572,21 @@ int slot_launch(adsb_decoder *d, ScanSlot &s)
     // d_counters are zero here: cleared at creation, and the report kernel behind every scan leaves them so
     s.args.profile = d->cfg.profile ? 1 : 0;
     s.args.report = s.hc();
-    HIP_TRY(d, adsb::launch_scan(s.args, stats, ls));
+    if (s.epoch_base) {
+        // the kernel sees a fresh stream whose sample 0 is input sample w * 2^32: r mod 7, the run boundaries and the typed-load
+        // alignment are the epoch's (P is a multiple of 4 pairs); pairs of the epoch before read as silence, and no offset of
+        // this launch reads them (the first launch of an epoch starts at r = 28)
+        adsb::ScanArgs ka = s.args;
+        const int64_t P = (int64_t)s.epoch_base;
+        ka.g_begin -= s.epoch_base;
+        ka.g_end -= s.epoch_base;
+        ka.pbuf0 -= P;
+        ka.p_lo = std::max<int64_t>(ka.p_lo - P, 0);
+        ka.p_hi -= P;
+        HIP_TRY(d, adsb::launch_scan(ka, stats, ls));
+    } else {
+        HIP_TRY(d, adsb::launch_scan(s.args, stats, ls));
+    }
     HIP_TRY(d, hipEventRecord(s.ev_ready[s.ev_cur], ls));
     if (stats && count_flush(d)) // the previous pass's calls are made now, while this scan runs
         return -1;
@@ -1306,6 +1336,73 @@ int scan_drain(adsb_decoder *d)
     return 0;
 }
 
+// Offsets [g_begin, g_end) among the seam offsets of the wrap at power sample P (seam_kernel.h): one small launch, waited for.
+// Every launch before it is collected first, so its records reach the sink in offset order between those of the launches on
+// either side, and its tries are counted by a pass of their own between theirs.  Once per 2^32 samples: the wait costs
+// nothing that matters.
+int seam_scan(adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, uint64_t buf_n, uint64_t P, uint64_t g_begin, uint64_t g_end)
+{
+    const bool stats = d->cfg.collect_stats != 0;
+    if (!d->seam_out)
+        return d->fail("internal: seam scan on a handle without adsb_set_long_stream");
+    const bool ff = d->final_follows;
+    d->final_follows = false; // (the launches in front are not the stream's last)
+    const int rc = scan_drain(d);
+    d->final_follows = ff;
+    if (rc)
+        return -1;
+    ScanSlot &s = d->seam_slot;
+    if (stats) { // the count pass over the previous seam launch's tries reads seam_out
+        if (d->pending.valid && d->pending.slot == &s && count_flush(d))
+            return -1;
+        if (s.count_pending) {
+            HIP_TRY(d, hipStreamWaitEvent(d->stream, s.ev_count, 0));
+            s.count_pending = false;
+        }
+    }
+    adsb::SeamArgs a{};
+    a.x = reinterpret_cast<const uint32_t *>(buf);
+    a.pbuf0 = (int64_t)(buf_first / 2);
+    a.p_lo = a.pbuf0;
+    a.p_hi = a.pbuf0 + (int64_t)(buf_n / 2);
+    a.boundary = P;
+    a.g_begin = g_begin;
+    a.g_end = g_end;
+    a.df18 = d->cfg.df18 ? 1 : 0;
+    a.synd = d->d_synd;
+    a.fix_tab = d->cfg.fix_1bit ? d->d_fix : nullptr;
+    a.fix_mul = d->fix_mul;
+    a.want_tries = stats ? 1 : 0;
+    a.out = d->seam_out;
+    HIP_TRY(d, adsb::launch_seam(a, d->stream));
+    HIP_TRY(d, hipEventRecord(s.ev_ready[0], d->stream));
+    WAIT_EVENT(d, s.ev_ready[0], "a seam launch");
+    const size_t nc = d->seam_out[0], nt = d->seam_out[1];
+    if (nc > (size_t)adsb::kSeamMaxOffsets || nt > (size_t)adsb::kSeamMaxOffsets)
+        return d->fail("internal: a seam launch reported %zu records and %zu tries for %llu offsets", nc, nt, (unsigned long long)(g_end - g_begin));
+    s.args = adsb::ScanArgs{};
+    s.args.g_begin = g_begin; // the base of the records' and the try words' relative offsets
+    s.args.g_end = g_end;
+    s.ev_cur = 0;
+    s.try_regions = false;
+    const uint32_t *recs = d->seam_out + adsb::kSeamOutHeader;
+    sort_order(d, recs, nc);
+    const bool host_tries = stats && d->sink.cands;
+    uint32_t *tries = d->seam_out + adsb::kSeamOutHeader + (size_t)adsb::kCandWords * adsb::kSeamMaxOffsets;
+    if (host_tries && nt)
+        sort_tries(d, tries, nt);
+    deliver(d, s, recs, d->order.data(), nc, adsb::kCandWords, 0, tries, host_tries ? nt : 0, g_end);
+    if (stats && !host_tries && nt) {
+        s.d_tries = tries; // (pinned host memory: the count kernel reads it where it lies)
+        if (count_tries_pass(d, &s, (uint32_t)nt, g_begin, false))
+            return -1;
+    }
+    d->seam_offsets += g_end - g_begin;
+    d->prof.launches++;
+    d->prof.offsets += g_end - g_begin;
+    return 0;
+}
+
 // Submit offsets [g_begin, g_end) of a device buffer holding stream samples
 // [buf_first, buf_first + buf_n) (buf_first % 8 == 0, buf 16-byte aligned) as a
 // pipeline of chunked launches: while the device scans chunk k+1 the host sorts
@@ -1315,8 +1412,26 @@ int scan_submit(adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, uint64
 {
     const bool stats = d->cfg.collect_stats != 0;
     while (g_begin < g_end) {
+        uint64_t g_limit = g_end, epoch_base = 0;
+        if (d->long_stream) {
+            // A launch lies in ONE epoch.  The offsets [P - 1196, P + 28) around a wrap at P read a power sample that follows
+            // neither epoch's formula (P - 1 .. P + 5): they go through the seam kernel, in their turn.
+            const uint64_t P = round_down(g_begin, adsb::kEpoch), Pn = P + adsb::kEpoch;
+            const uint64_t wrap = (P && g_begin < adsb::seam_end(P)) ? P : g_begin >= adsb::seam_first(Pn) ? Pn : 0;
+            if (wrap) {
+                const uint64_t g_stop = std::min(g_end, adsb::seam_end(wrap));
+                if (seam_scan(d, buf, buf_first, buf_n, wrap, g_begin, g_stop))
+                    return -1;
+                g_begin = g_stop;
+                continue;
+            }
+            g_limit = std::min(g_end, adsb::seam_first(Pn));
+            epoch_base = P;
+            if ((g_begin - P) % 28 != 0)
+                return d->fail("internal: a scan launch at offset %llu does not start on a run boundary of its epoch", (unsigned long long)g_begin);
+        }
         // streamed launches: everything but a per-shard scan that hands the try list back
-        const uint64_t g_stop = std::min(g_end, g_begin + chunk_offsets(!d->no_streaming && !(stats && d->sink.cands)));
+        const uint64_t g_stop = std::min(g_limit, g_begin + chunk_offsets(!d->no_streaming && !(stats && d->sink.cands)));
         const uint64_t n_off = g_stop - g_begin;
         if (d->slot_count == kSlots && slot_collect(d))
             return -1;
@@ -1351,6 +1466,7 @@ int scan_submit(adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, uint64
                                                                                                   : adsb::kClistCap;
         a.fix_tab = d->cfg.fix_1bit ? d->d_fix : nullptr;
         a.fix_mul = d->fix_mul;
+        s.epoch_base = epoch_base;
         if (slot_launch(d, s))
             return -1;
         s.piece = d->piece;
@@ -1845,6 +1961,9 @@ void adsb_destroy(adsb_decoder *d)
         if (d->ev_frames[b]) (void)hipEventDestroy(d->ev_frames[b]);
     }
     if (d->d_try_acc) (void)hipFree(d->d_try_acc);
+    if (d->seam_out) (void)hipHostFree(d->seam_out);
+    if (d->seam_slot.ev_ready[0]) (void)hipEventDestroy(d->seam_slot.ev_ready[0]);
+    if (d->seam_slot.ev_count) (void)hipEventDestroy(d->seam_slot.ev_count);
     for (ScanSlot &sl : d->slots) {
         if (sl.d_counters) (void)hipFree(sl.d_counters);
         if (sl.h_counters) (void)hipHostFree(sl.h_counters);
@@ -1906,6 +2025,7 @@ int adsb_reset(adsb_decoder *d)
     d->sink = ScanSink{};
     d->n_samples = 0;
     d->g_scanned = 0;
+    d->seam_offsets = 0;
     d->finished = false;
     d->stage_first = 0;
     d->stage_fill = 0;
@@ -1931,6 +2051,34 @@ int adsb_reset(adsb_decoder *d)
         d->slot_head = 0;
     d->slot_count = 0;
     d->err.clear();
+    return 0;
+}
+
+// Follow the reference through the wraps of its sample counter instead of refusing a stream at 2^32 samples.
+int adsb_set_long_stream(adsb_decoder *d, int on)
+{
+    if (!d)
+        return -1;
+    if (d->n_samples || d->finished || d->slot_count || d->stage_fill || d->shard_on)
+        return d->fail("adsb_set_long_stream: only on a fresh or reset handle, before the first push");
+    if (on && !d->seam_out) {
+        HIP_TRY(d, hipSetDevice(d->device));
+        HIP_TRY(d, hipHostMalloc(&d->seam_out, adsb::kSeamOutWords * sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(d, hipEventCreateWithFlags(&d->seam_slot.ev_ready[0], hipEventDisableTiming));
+        HIP_TRY(d, hipEventCreateWithFlags(&d->seam_slot.ev_count, hipEventDisableTiming));
+    }
+    d->long_stream = on != 0;
+    return 0;
+}
+
+int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets)
+{
+    if (!d)
+        return -1;
+    if (wraps)
+        *wraps = d->n_samples >> 32; // (the counter has wrapped once the stream holds 2^32 samples)
+    if (seam_offsets)
+        *seam_offsets = d->seam_offsets;
     return 0;
 }
 

@@ -99,7 +99,7 @@ struct Job {
     // Stream: streams [stream_lo, stream_lo + stream_step, ...) of the caller's arrays, results into `results`
     const Source *streams = nullptr;
     const uint64_t *stream_n = nullptr;
-    int n_streams = 0, stream_lo = 0, stream_step = 1;
+    int n_streams = 0, stream_lo = 0, stream_step = 1, long_streams = 0;
     StreamResult *results = nullptr;
     // Gather: this worker's final frames (`n_new` accepted by the seam repair, then `keep` speculative ones from `drop`
     // on, ts - ts_sub) into dst
@@ -171,6 +171,10 @@ inline double worker_limit_s(const adsb_config &cfg)
 
 } // namespace
 
+// The one call of this file that a decoder backend may lack: the sanitizer harness links multi.cpp against a table look-up in
+// place of decoder.hip (tests/cpp/multi_tsan.cpp), which has no long streams.  In the library the symbol is always there.
+extern "C" int adsb_set_long_stream(adsb_decoder *d, int on) __attribute__((weak));
+
 struct adsb_multi {
     adsb_config cfg{};
     adsb_debug_config dbg{};
@@ -184,6 +188,7 @@ struct adsb_multi {
     double create_ms = 0;
     uint64_t piece_samples = kPieceSamples;
     bool broken = false; // a worker stopped answering (gave_up): every later call fails at once
+    bool long_streams = false; // adsb_multi_set_long_streams: the stream calls' captures may reach 2^32 samples and beyond
 
     long gave_up(const Worker &w)
     {
@@ -508,6 +513,8 @@ void run_streams(Worker &w, const Job &j, uint64_t piece)
         long nf = -1;
         if (adsb_reset(w.dec)) {
             w.fail_dec("adsb_reset");
+        } else if (adsb_set_long_stream ? adsb_set_long_stream(w.dec, j.long_streams) : j.long_streams) { // (sticky on the handle: set either way)
+            w.fail_dec("adsb_set_long_stream");
         } else if (feed(w, j.streams[s], 0, j.stream_n[s], piece) == 0) {
             if (adsb_finish(w.dec))
                 w.fail_dec("adsb_finish");
@@ -866,6 +873,7 @@ int decode_streams_impl(adsb_multi *m, const std::vector<Source> &src, const std
         j.stream_lo = i;
         j.stream_step = nw;
         j.results = m->streams.data();
+        j.long_streams = m->long_streams ? 1 : 0;
         post(*m->w[i], j);
     }
     for (int i = 0; i < used; i++) {
@@ -1088,6 +1096,14 @@ long adsb_multi_decode_device(adsb_multi *m, uint64_t total_samples, const void 
         if (!slices[i])
             return m->fail("adsb_multi_decode_device: slice %d is NULL", i);
     return decode_sharded(m, Source{}, slices, n_slices, total_samples, frames);
+}
+
+int adsb_multi_set_long_streams(adsb_multi *m, int on)
+{
+    if (!m)
+        return -1;
+    m->long_streams = on != 0; // (the workers' handles are told at their next stream job, behind its adsb_reset)
+    return 0;
 }
 
 int adsb_multi_decode_streams_host(adsb_multi *m, int n_streams, const uint16_t *const *samples, const size_t *n)

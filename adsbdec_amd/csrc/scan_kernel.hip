@@ -66,6 +66,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "power_ordered.h" // taps, power_ordered<>, columns_to_bytes: shared with seam_kernel.hip
 #include "scan_kernel.h"
 #include "slicer_bits.h"
 #include "scan_stamps.h" // ADSB_STAMP / ADSB_COUNT: nothing in the shipped build (a measurement build's per-phase tile clocks)
@@ -75,17 +76,6 @@ namespace adsb {
 static_assert(5 * lds_bytes(7) <= 160 * 1024, "five workgroups of a K = 7 tile share a CU's LDS");
 
 namespace {
-
-// air.c:36-45. Each tap is (float)<double literal>, as in the reference's
-// `static const float dsfilter[] = { 0.012627, ... }`.
-template <int K>
-__device__ __forceinline__ constexpr float tap()
-{
-    constexpr double lit[14] = {0.012627, 0.025254, 0.037881, 0.050508, 0.063135,
-                                0.075761, 0.088388, 0.088388, 0.075761, 0.063135,
-                                0.050508, 0.037881, 0.025254, 0.012627};
-    return (float)lit[K];
-}
 
 // The FIR of one run: 28 outputs, each the sum of seven (I, Q) products in the reference's order.
 //
@@ -114,7 +104,6 @@ __device__ __forceinline__ constexpr float tap()
 //      the same step (J mod 7 = p: step p; (J + 6) mod 7 = p - 1: age 6 comes at step p): ONE product M = h0 (I, Q) serves
 //      both, each through one fused multiply-add by (2, 1) or (1, 2).  The first step of an output has no addition
 //      (p = 0 / p = 6): nothing to share there.  Outputs J and J + 6 have to be advanced together for this: the plan below.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // kc[0..3] = 2048 (T[12-2b], T[13-2b]) in vector registers, kc[4..7] = (T[12-2b], T[13-2b]) in scalar ones, b = 0..3
 struct FirConsts {
@@ -234,26 +223,6 @@ __device__ __forceinline__ void power_run(const f32x2 (&vv)[34], float *a, const
     }
 }
 
-// Same arithmetic for power samples at RUN-TIME indices (rare path: pw of a
-// CRC-valid candidate needs a[g], a[g+10], a[g+35], a[g+45]).  Rounds exactly like
-// power_sample<>: same products, same order (one static order per phase p = m mod
-// 7), first product not added to zero.  All loads are issued before any use: the
-// whole workgroup waits for this path at the next barrier.
-template <int P>
-__device__ __forceinline__ float power_ordered(const f32x2 (&pr)[7])
-{
-    // pr[a] = (T[12-2a], T[13-2a]) * (I, Q) of the pair of age a; order p, p-1, .., 0, 6, .., p+1
-    f32x2 s = pr[P];
-#pragma unroll
-    for (int a = P - 1; a >= 0; a--)
-        s = s + pr[a];
-#pragma unroll
-    for (int a = 6; a > P; a--)
-        s = s + pr[a];
-    const f32x2 sq = s * s;
-    return sq.x + sq.y;
-}
-
 // The 28 pairs behind the four power samples of demod.c:102-105 at offset g (0, +10, +35, +45; seven pairs each): the
 // loads on their own, so that a caller can issue them early and do other work while they are in flight.
 __device__ __forceinline__ void pw_load(const uint32_t *__restrict__ x, int64_t pbuf0, int64_t p_lo, int64_t p_hi, int64_t g,
@@ -282,7 +251,8 @@ __device__ __forceinline__ void pw_load(const uint32_t *__restrict__ x, int64_t 
 __device__ __forceinline__ uint32_t pw_compute(const uint32_t (&raw)[4][7], int64_t g)
 {
     const int off[4] = {0, 10, 35, 45};
-    // power indices stay below 2^31 (streams of < 2^32 samples): 32-bit arithmetic for phase and parity
+    // power indices stay below 2^31 (a launch's indices are relative to its 2^32-sample epoch: decoder.hip slot_launch): 32-bit
+    // arithmetic for phase and parity
     const uint32_t g32 = (uint32_t)g, g7 = g32 % 7u;
     float pw_s[4];
 #pragma unroll
@@ -301,16 +271,7 @@ __device__ __forceinline__ uint32_t pw_compute(const uint32_t (&raw)[4][7], int6
             const f32x2 v = (((m - a) & 1) == 0) ? (f - mid) : (mid - f); // fs/4 sign of the pair
             pr[a] = taps[a] * v;
         }
-        float r;
-        switch (p) {
-        case 0: r = power_ordered<0>(pr); break;
-        case 1: r = power_ordered<1>(pr); break;
-        case 2: r = power_ordered<2>(pr); break;
-        case 3: r = power_ordered<3>(pr); break;
-        case 4: r = power_ordered<4>(pr); break;
-        case 5: r = power_ordered<5>(pr); break;
-        default: r = power_ordered<6>(pr); break;
-        }
+        const float r = power_by_phase(pr, p);
         pw_s[k] = r;
     }
     const int p1 = __float2int_rz(pw_s[0] + pw_s[1]);
@@ -323,28 +284,6 @@ __device__ __noinline__ uint32_t pw_at(const uint32_t *__restrict__ x, int64_t p
     uint32_t raw[4][7];
     pw_load(x, pbuf0, p_lo, p_hi, g, raw);
     return pw_compute(raw, g);
-}
-
-// The slicer gathers the frame as 14 column bytes (frame bit k = 14 b + c is bit b
-// of column c; four columns per word).  Rebuild the 14 frame bytes in order (bit k
-// is bit 7 - k%8 of byte k/8), packed little-endian into wds[0..3], with the
-// length in byte 14.  A static 112-bit transpose: 2 operations per bit.
-__device__ __forceinline__ void columns_to_bytes(const uint32_t (&cw)[4], bool is_short, uint32_t (&wds)[4])
-{
-    wds[0] = wds[1] = wds[2] = wds[3] = 0;
-#pragma unroll
-    for (int k = 0; k < 112; k++) {
-        const int b = k / 14, c = k % 14;
-        const uint32_t bit = (cw[c >> 2] >> (8 * (c & 3) + b)) & 1u;
-        const int n = k >> 3;
-        wds[n >> 2] |= bit << (8 * (n & 3) + 7 - (k & 7));
-    }
-    if (is_short) { // DF11: 56 bits = 7 bytes
-        wds[1] &= 0x00FFFFFFu;
-        wds[2] = 0;
-        wds[3] = 0;
-    }
-    wds[3] |= (is_short ? 7u : 14u) << 16;
 }
 
 // One 16-byte granule of the hand-off stream, written THROUGH to host memory (sc0 sc1).

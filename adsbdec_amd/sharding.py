@@ -124,6 +124,11 @@ class MultiDecoder:
         return {k: getattr(p, k) for k, _ in capi.Profile._fields_}
 
     # -- configs[3]: independent captures, one stream each
+    def set_long_streams(self, on: bool = True):
+        """adsb_multi_set_long_streams: the captures of the two stream calls may hold 2^32 samples and more."""
+        if self._L.adsb_multi_set_long_streams(self._h, int(bool(on))) != 0:
+            raise self._err("adsb_multi_set_long_streams")
+
     def decode_streams_host(self, xs):
         """xs: uint16 ndarrays, or (address, n) pairs."""
         pairs = [(x.ctypes.data, x.size) if not isinstance(x, tuple) else x for x in xs]

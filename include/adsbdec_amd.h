@@ -2,22 +2,19 @@
  * adsbdec_amd.h -- C-ABI of libadsbdec_amd.so: the MI355X (gfx950) drop-in for the offline "-f" demodulation path
  * of TLeconte/adsbdec.  This header is everything a drop-in host and a multi-GPU host call; the primitives underneath
  * (resolver handle, hand-off walker, shard scans, stitcher) and the test knobs are in adsbdec_amd_diag.h.
- *
  * The reference has no plugin/FFI interface: its whole interface is one prototype (adsbdec.h:5) plus extern C functions
  * with file-scope state.  Each entry point names the reference seam it stands behind (file:line under
  * /root/reference); INTEGRATION.md shows the change a maintainer makes in air.c / output.c to bind them.
- *
  * Conventions follow the reference: int 0 / -1 with a message from adsb_last_error() (the reference prints to stderr,
  * air.c:113-118); one producer thread per handle (decodeiq is not re-entrant: air.c:33-34,49-50, demod.c:86); plain
  * pointers and sizes, no C++/torch types.  The HIP path is the only implementation: there is no CPU fallback, and
  * adsb_create() fails loudly when no gfx950 device is usable.
- *
  * Input domain.  uint16 samples carrying the Airspy's 12-bit ADC code centred on 2048 (air.c:64).  Results are
  * bit-identical to the reference for every code in [0, 4095] and beyond, up to |x-2048| <= ~23 000 (the preamble sums
  * still fit an int); larger codes make the reference's `int p1 = float + float` (demod.c:102-105) overflow -- undefined
  * behaviour that wraps with gcc -- while this library compares un-wrapped values: accepted, no parity claimed.
- * Streams are limited to < 2^32 samples (the reference's `fidx` wraps there): a push that would reach it fails.
- */
+ * Streams end below 2^32 samples (the reference's `fidx` wraps there, SURVEY Q13: a push that would reach it fails) unless
+ * adsb_set_long_stream is on: then any length, decoded as the reference does through every wrap (DESIGN.md "Input domain"). */
 #ifndef ADSBDEC_AMD_H
 #define ADSBDEC_AMD_H
 #include <stddef.h>
@@ -144,6 +141,10 @@ int adsb_push_packed_async(adsb_decoder *d, const void *packed, size_t n);
 int adsb_push_device_packed(adsb_decoder *d, const void *device_packed, size_t n);
 int adsb_push_device_packed_final(adsb_decoder *d, const void *device_packed, size_t n);
 long adsb_decode_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_frame **frames);
+/* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps at
+ * every 2^32 samples, bit for bit.  Only on a fresh or reset handle before the first push (else -1); sticky across adsb_reset.
+ * The shard calls keep their 2^32 limit.  adsb_get_wraps: wraps so far, and offsets that went through the seam kernel. */
+int adsb_set_long_stream(adsb_decoder *d, int on);   int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
 /* End of input (fileInput's EOF, air.c:241-244): the remaining offsets, and the end-of-file horizon. */
 int adsb_finish(adsb_decoder *d);
 /* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.
@@ -182,8 +183,7 @@ int adsb_plan_shards(uint64_t total_samples, int n_shards, uint64_t *g_begin, ui
                      uint64_t *first_sample, uint64_t *n_samples);
 /* ---- ONE process, several GPUs (csrc/multi.cpp): the host of BASELINE configs[3] / configs[4] ---------------------
  * A worker thread and a decoder handle per device; no collective on the data path.  Stands where
- * fileInput's loop (air.c:217-246) hands its buffers to decodeiq and the frames come back in ascending order for
- * netout (output.c:159-182). */
+ * fileInput's loop (air.c:217-246) hands its buffers to decodeiq and the frames come back in ascending order for netout (output.c:159-182). */
 typedef struct adsb_multi adsb_multi;
 typedef struct adsb_multi_info { /* of the last adsb_multi_decode_* call */
     int32_t shards;         /* shards the capture was cut into (streams decoded side by side, for the stream calls)  */
@@ -222,6 +222,7 @@ int adsb_multi_plan(const adsb_multi *m, uint64_t total_samples, uint64_t *g_beg
 int adsb_multi_get_stats(const adsb_multi *m, adsb_stats *out); /* the stream's Try/Ok table (cfg.collect_stats) */
 /* configs[3]: n_streams INDEPENDENT captures, stream s on worker s mod adsb_multi_devices(m), each with its own ts and
  * statistics -- N times what `adsbdec -f` does (main.c:60-89), side by side.  0 / -1; results per stream afterwards. */
+int adsb_multi_set_long_streams(adsb_multi *m, int on); /* adsb_set_long_stream for the workers of the two stream calls below */
 int adsb_multi_decode_streams_host(adsb_multi *m, int n_streams, const uint16_t *const *samples, const size_t *n);
 int adsb_multi_decode_streams_file(adsb_multi *m, int n_streams, const char *const *paths);
 long adsb_multi_stream_frames(const adsb_multi *m, int stream, const adsb_frame **frames);
