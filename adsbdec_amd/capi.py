@@ -54,6 +54,17 @@ class ShardFix(C.Structure):
                 ("ts_sub", C.c_int64)]
 
 
+class BatchSegment(C.Structure):
+    """adsb_batch_segment (include/adsbdec_amd_diag.h): a capture's offsets [o_begin, o_end) at the virtual offsets from base on."""
+    _fields_ = [("capture", C.c_uint64), ("o_begin", C.c_uint64), ("o_end", C.c_uint64), ("base", C.c_uint64),
+                ("launch", C.c_uint32), ("first_tile", C.c_uint32), ("tiles", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class BatchLaunch(C.Structure):
+    _fields_ = [("g_begin", C.c_uint64), ("g_end", C.c_uint64), ("seg_first", C.c_uint32), ("seg_end", C.c_uint32),
+                ("tiles", C.c_uint32), ("passes", C.c_int32)]
+
+
 class Config(C.Structure):
     """adsb_config, ABI 5 (include/adsbdec_amd.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("abi", C.c_uint32), ("df18", C.c_int32), ("device", C.c_int32),
@@ -121,6 +132,15 @@ SYMBOLS = {
     "adsb_push_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_push_device_final": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_decode_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Frame))]),
+    "adsb_decode_batch_device": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                            C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_decode_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                          C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_batch_layout": (C.c_long, [C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(BatchSegment), C.c_size_t,
+                                     C.POINTER(BatchLaunch), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "adsb_batch_resolve": (C.c_long, [C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Candidate), C.c_size_t,
+                                      C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(Frame), C.c_size_t, C.POINTER(C.c_uint64),
+                                      C.POINTER(Stats)]),
     "adsb_push_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_push_packed_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_push_device_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -383,6 +403,43 @@ class Decoder:
             self._check(-1, "adsb_decode_device")
         return self._out, k
 
+    # ---- a batch of independent captures in as few launches as they fit (adsb_decode_batch_*)
+    def decode_batch_device_raw(self, ptrs, ns):
+        """adsb_decode_batch_device -> (Frame pointer, first: ctypes array of len(ns) + 1 indices, Stats array): capture i's
+        frames are pointer[first[i] : first[i + 1]], valid until the next call of this decoder."""
+        k = len(ns)
+        p = (C.c_void_p * max(1, k))(*[int(v) if v else None for v in ptrs])
+        n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        total = self._L.adsb_decode_batch_device(self._h, k, p, n, self._out_ref, first, st)
+        if total < 0:
+            self._check(-1, "adsb_decode_batch_device")
+        return self._out, first, st
+
+    def _batch_result(self, out, first, st, k, stats):
+        frames = [_frames_to_dicts(out[int(first[i]):int(first[i + 1])], int(first[i + 1] - first[i])) for i in range(k)]
+        return (frames, [_stats_to_dict(st[i], self._fix) for i in range(k)]) if stats else frames
+
+    def decode_batch_device(self, ptrs, ns, stats: bool = False):
+        """Captures resident in HBM (16-byte aligned pointers) -> a list of per-capture frame lists, each what decode_device
+        gives for that capture alone; stats=True: (that, the per-capture Try/Ok tables)."""
+        out, first, st = self.decode_batch_device_raw(ptrs, ns)
+        return self._batch_result(out, first, st, len(ns), stats)
+
+    def decode_batch(self, arrays, stats: bool = False):
+        """The same for uint16 arrays in host memory (adsb_decode_batch_host copies them to scratch of the handle's)."""
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        assert all(a.dtype == np.uint16 for a in arrays)
+        k = len(arrays)
+        p = (C.c_void_p * max(1, k))(*[a.ctypes.data if a.size else None for a in arrays])
+        n = (C.c_size_t * max(1, k))(*[a.size for a in arrays])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        if self._L.adsb_decode_batch_host(self._h, k, p, n, self._out_ref, first, st) < 0:
+            self._check(-1, "adsb_decode_batch_host")
+        return self._batch_result(self._out, first, st, k, stats)
+
     # ---- Airspy packed 12-bit input (include/adsbdec_amd.h): n always counts SAMPLES (a multiple of 8), 1.5 bytes each
     @staticmethod
     def _packed_arg(buf):
@@ -632,6 +689,44 @@ class Resolver:
         st = Stats()
         self._L.adsb_resolver_stats(self._h, C.byref(st))
         return _stats_to_dict(st)
+
+
+def batch_layout(ns, cus: int = 0, passes: int = 0):
+    """adsb_batch_layout -> (segments, launches) as lists of dicts, or None when the batch is refused (a capture of 2^32 samples)."""
+    L = load()
+    k = len(ns)
+    n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
+    nl = C.c_size_t(0)
+    ns_ = L.adsb_batch_layout(k, n, cus, passes, None, 0, None, 0, C.byref(nl))
+    if ns_ < 0:
+        return None
+    segs, launches = (BatchSegment * max(1, ns_))(), (BatchLaunch * max(1, nl.value))()
+    if L.adsb_batch_layout(k, n, cus, passes, segs, ns_, launches, nl.value, C.byref(nl)) != ns_:
+        raise AdsbError("adsb_batch_layout failed")
+    as_dict = lambda o: {f: int(getattr(o, f)) for f, _ in o._fields_ if f != "pad"}
+    return [as_dict(segs[i]) for i in range(ns_)], [as_dict(launches[i]) for i in range(nl.value)]
+
+
+def batch_resolve(ns, cands, tries, cus: int = 0, passes: int = 0):
+    """adsb_batch_resolve: cands = list of (virtual g, pw, frame bytes) ascending, tries = uint64 (g << 2 | code) ascending ->
+    (per-capture frame lists, per-capture Try/Ok tables)."""
+    L = load()
+    k = len(ns)
+    n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
+    arr = (Candidate * max(1, len(cands)))()
+    for i, (g, pw, fr) in enumerate(cands):
+        arr[i].g, arr[i].pw, arr[i].len = g, pw, len(fr)
+        for j, b in enumerate(fr):
+            arr[i].frame[j] = b
+    t = np.ascontiguousarray(tries, dtype=np.uint64)
+    first, st = (C.c_uint64 * (k + 1))(), (Stats * max(1, k))()
+    cap = len(cands) + 1
+    out = (Frame * cap)()
+    total = L.adsb_batch_resolve(k, n, cus, passes, arr, len(cands), t.ctypes.data_as(C.POINTER(C.c_uint64)), t.size, out, cap, first, st)
+    if total < 0 or total > cap:
+        raise AdsbError("adsb_batch_resolve failed")
+    return ([_frames_to_dicts(out[int(first[i]):int(first[i + 1])], int(first[i + 1] - first[i])) for i in range(k)],
+            [_stats_to_dict(st[i]) for i in range(k)])
 
 
 def plan_shards(total_samples: int, n_shards: int):

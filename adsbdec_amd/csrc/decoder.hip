@@ -28,6 +28,9 @@
 //   land[2]    host pushes: the packed bytes of a piece land here (one buffer per copy stream, 1.5 B x
 //              stage_cap), and the unpack writes stage[cur] + stage_fill on the stream of that copy
 //   unpacked   device pushes: 2 B x n of scratch, scanned in place like a uint16 push
+// A batch of captures (adsb_decode_batch_*, batch.hpp) is scanned in place too, by launches of scan_batch_kernel:
+//   batch_tab  a launch's segment table and its tile -> segment words (scan_kernel.h BatchSeg), uploaded from batch_tab_h
+//   batch_in   adsb_decode_batch_host: the captures, each at a 128-byte boundary
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,6 +55,7 @@
 #include <sched.h>
 
 #include "../../include/adsbdec_amd_diag.h"
+#include "batch.hpp"
 #include "config_abi.hpp"
 #include "handoff.hpp"
 #include "packed12.h"
@@ -266,6 +270,21 @@ struct adsb_decoder {
     uint64_t shard_g_begin = 0, shard_g_end = 0;
     size_t shard_bases_cap = 0;
     std::vector<adsb_candidate> shard_hv;
+    // A batch of independent captures (adsb_decode_batch_*, batch.hpp): a resolver of its own, reset per capture, and the
+    // frames of the whole batch, handed out in place; the handle's stream (res, the staging buffers) stays reset beside it
+    adsb::Resolver batch_res;
+    std::vector<adsb_frame> batch_frames;
+    std::vector<adsb_batch_segment> batch_segs;
+    std::vector<adsb_batch_launch> batch_launches;
+    std::vector<adsb_candidate> batch_cands, batch_cbuf; // the batch's sorted records in virtual offsets; one capture's
+    std::vector<uint64_t> batch_tries, batch_tbuf;
+    std::vector<adsb_stats> batch_per;
+    void *batch_tab = nullptr, *batch_tab_h = nullptr; // device / pinned host
+    size_t batch_tab_cap = 0;                          // bytes
+    uint16_t *batch_in = nullptr;
+    size_t batch_in_cap = 0;    // bytes
+    bool batch_stats_on = false; // the last call was a batch: adsb_get_stats answers batch_stats, the sum over its captures
+    adsb_stats batch_stats{};
     uint16_t *win_buf = nullptr; // adsb_scan_shard_host: device copy of the caller's window
     size_t win_cap = 0; // head candidates (handed out in place by adsb_shard_end)
 
@@ -1953,6 +1972,9 @@ void adsb_destroy(adsb_decoder *d)
     if (d->d_synd) (void)hipFree(d->d_synd);
     if (d->d_fix) (void)hipFree(d->d_fix);
     if (d->win_buf) (void)hipFree(d->win_buf);
+    if (d->batch_tab) (void)hipFree(d->batch_tab);
+    if (d->batch_tab_h) (void)hipHostFree(d->batch_tab_h);
+    if (d->batch_in) (void)hipFree(d->batch_in);
     for (int i = 0; i < 2; i++)
         if (d->d_carry[i]) (void)hipFree(d->d_carry[i]);
     if (d->d_frames) (void)hipFree(d->d_frames);
@@ -2032,6 +2054,8 @@ int adsb_reset(adsb_decoder *d)
     d->cur = 0;
     d->res.reset();
     d->res.log_accepted(d->cfg.collect_stats != 0);
+    d->batch_frames.clear(); // (what a batch call handed out is gone with the next reset, like adsb_take's frames)
+    d->batch_stats_on = false;
     if (d->acc_dirty) { // behind any count pass still queued -- or still to be enqueued (count_flush)
         if (d->pending.valid) {
             d->pending.clear_after = true;
@@ -2506,6 +2530,10 @@ int adsb_get_stats(const adsb_decoder *d, adsb_stats *out)
     if (!d || !out)
         return -1;
     adsb_decoder *m = const_cast<adsb_decoder *>(d); // the try counters live on the device until asked for
+    if (d->batch_stats_on) { // a batch counts on the host, per capture: the sum
+        *out = d->batch_stats;
+        return 0;
+    }
     if (m->cfg.collect_stats && (hipSetDevice(m->device) != hipSuccess || read_tries(m)))
         return -1;
     *out = m->res.stats();
@@ -2532,6 +2560,327 @@ int adsb_get_profile_sized(const adsb_decoder *d, adsb_profile *out, size_t size
 const char *adsb_last_error(const adsb_decoder *d)
 {
     return d ? d->err.c_str() : g_cpu_refusal ? g_cpu_refusal : g_create_error.c_str();
+}
+
+} // extern "C"
+
+// ---- a batch of independent captures in as few launches as they fit (batch.hpp) ---------------------------------------------
+namespace {
+
+static_assert(adsb::kBatchRun == adsb::kRun && adsb::batch_tile_offsets(2) == (uint64_t)adsb::tile_offsets(2) &&
+                  adsb::batch_tile_offsets(adsb::kMaxPasses) == (uint64_t)adsb::tile_offsets(adsb::kMaxPasses) &&
+                  adsb::kBatchMaxLaunchOffsets == adsb::kMaxLaunchOffsets,
+              "batch.hpp restates the tile geometry of scan_kernel.h");
+
+int batch_passes_cap(uint64_t n_offsets, void *cus) { return adsb::choose_passes(n_offsets, *static_cast<int *>(cus)); }
+
+inline int batch_forced_passes(int passes) { return (passes >= 2 && passes <= adsb::kMaxPasses) ? passes : 0; }
+
+// The refusals of adsb_decode_batch_*, before anything of the handle changes.
+int batch_refusal(adsb_decoder *d, const char *what, size_t n_captures, const void *const *p, const size_t *n, bool device)
+{
+    if (n_captures && (!p || !n))
+        return d->fail("%s: NULL capture arrays", what);
+    for (size_t i = 0; i < n_captures; i++) {
+        if ((uint64_t)n[i] >= (1ull << 32))
+            return d->fail("%s: capture %zu has %zu samples: 2^32 or more, where the reference's sample counter wraps (air.c:34); "
+                           "a batch has no long-stream mode", what, i, n[i]);
+        if (n[i] && !p[i])
+            return d->fail("%s: capture %zu: NULL samples", what, i);
+        if (device && (uintptr_t)p[i] % 16 != 0)
+            return d->fail("%s: capture %zu: device pointer %p is not 16-byte aligned", what, i, p[i]);
+    }
+    return 0;
+}
+
+// One launch of the batch: table up, scan, wait, regrow and repeat on overflow (as slot_collect does), then the sorted
+// records and tries behind d->batch_cands / batch_tries, in virtual offsets.
+int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void *const *p, const size_t *n)
+{
+    using clk = std::chrono::steady_clock;
+    if (L.tiles == 0)
+        return 0;
+    const bool stats = d->cfg.collect_stats != 0;
+    ScanSlot &s = d->slots[d->slot_head];
+    uint64_t offsets = 0;
+    uint32_t n_tab = 0; // segments with tiles
+    for (uint32_t k = L.seg_first; k < L.seg_end; k++) {
+        offsets += d->batch_segs[k].o_end - d->batch_segs[k].o_begin;
+        n_tab += d->batch_segs[k].tiles != 0;
+    }
+    // test knobs: start from buffers that are too small, so that the relaunch path runs.  As in scan_submit they bite on a
+    // slot whose buffers are still smaller than the knob only -- a fresh handle: slot_reserve never shrinks what a slot has.
+    const size_t cand_want = d->dbg.cand_cap > 0 ? (size_t)d->dbg.cand_cap : (size_t)(offsets / 128 + 32768);
+    const size_t try_want = d->dbg.try_cap > 0 ? (size_t)d->dbg.try_cap : (size_t)(offsets / 32 + 65536);
+    if (slot_reserve(d, s, std::max(s.cand_cap, cand_want), stats ? std::max(s.try_cap, try_want) : s.try_cap))
+        return -1;
+    // the table: the segments that have tiles, then a word per tile
+    const size_t tab_bytes = (size_t)n_tab * sizeof(adsb::BatchSeg) + (size_t)L.tiles * sizeof(uint32_t);
+    if (tab_bytes > d->batch_tab_cap) {
+        if (d->batch_tab)
+            HIP_TRY(d, hipFree(d->batch_tab));
+        if (d->batch_tab_h)
+            HIP_TRY(d, hipHostFree(d->batch_tab_h));
+        d->batch_tab = d->batch_tab_h = nullptr;
+        d->batch_tab_cap = 0;
+        const size_t cap = tab_bytes + tab_bytes / 4 + 4096;
+        HIP_TRY(d, hipMalloc(&d->batch_tab, cap));
+        HIP_TRY(d, hipHostMalloc(&d->batch_tab_h, cap, hipHostMallocDefault));
+        d->batch_tab_cap = cap;
+    }
+    adsb::BatchSeg *seg_h = static_cast<adsb::BatchSeg *>(d->batch_tab_h);
+    uint32_t *tile_h = reinterpret_cast<uint32_t *>(seg_h + n_tab);
+    uint32_t row = 0;
+    for (uint32_t k = L.seg_first; k < L.seg_end; k++) {
+        const adsb_batch_segment &sg = d->batch_segs[k];
+        if (sg.tiles == 0)
+            continue;
+        // in the launch's coordinates the capture's pair 0 is pair `origin`: the buffer holds pairs from there on, and nothing
+        // below it exists (a stream's start: silence, air.c:33)
+        const int64_t origin = (int64_t)(sg.base - L.g_begin) - (int64_t)sg.o_begin;
+        adsb::BatchSeg &b = seg_h[row];
+        b.x = (uint64_t)(uintptr_t)p[sg.capture];
+        b.pbuf0 = origin;
+        b.p_lo = origin;
+        b.p_hi = origin + (int64_t)(n[sg.capture] / 2);
+        b.g_begin = sg.base - L.g_begin;
+        b.g_end = b.g_begin + (sg.o_end - sg.o_begin);
+        b.first_tile = sg.first_tile;
+        b.pad = 0;
+        for (uint32_t t = 0; t < sg.tiles; t++)
+            tile_h[sg.first_tile + t] = row;
+        row++;
+    }
+    hipStream_t ls = d->stream;
+    HIP_TRY(d, hipMemcpyAsync(d->batch_tab, d->batch_tab_h, tab_bytes, hipMemcpyHostToDevice, ls));
+    const adsb::BatchSeg *seg_d = static_cast<const adsb::BatchSeg *>(d->batch_tab);
+    const uint32_t *tile_d = reinterpret_cast<const uint32_t *>(seg_d + n_tab);
+
+    adsb::ScanArgs &a = s.args;
+    a = adsb::ScanArgs{};
+    a.g_begin = 0; // the launch's own coordinates: g_rel = virtual offset - L.g_begin
+    a.g_end = L.g_end - L.g_begin;
+    a.df18 = d->cfg.df18 ? 1 : 0;
+    a.passes = L.passes;
+    a.big_tiles = 0;
+    a.synd = d->d_synd;
+    a.queue_cap = (d->dbg.queue_cap >= 256 && d->dbg.queue_cap <= adsb::kQueueCap) ? d->dbg.queue_cap : adsb::kQueueCap;
+    a.all_candidates = d->cfg.all_candidates ? 1 : 0;
+    a.clist_cap = (d->dbg.clist_cap >= 1 && d->dbg.clist_cap <= adsb::kClistCap) ? d->dbg.clist_cap : adsb::kClistCap;
+    a.fix_tab = d->cfg.fix_1bit ? d->d_fix : nullptr;
+    a.fix_mul = d->fix_mul;
+    a.counters = s.d_counters; // zero: cleared at creation, and the report kernel behind every scan leaves them so
+    a.profile = d->cfg.profile ? 1 : 0;
+    s.streaming = false;
+    s.tries_on_device = s.try_regions = false;
+    s.epoch_base = 0;
+    s.ntiles = L.tiles;
+    if (d->pending.valid && d->pending.slot == &s && count_flush(d)) // (slot_launch: what may still use the slot's past)
+        return -1;
+    if (s.count_pending) {
+        HIP_TRY(d, hipStreamWaitEvent(ls, s.ev_count, 0));
+        s.count_pending = false;
+    }
+    const auto t_wait = clk::now();
+    for (int attempt = 0;; attempt++) {
+        s.ev_cur ^= 1;
+        if (slot_settle_profile(d, s, s.ev_cur))
+            return -1;
+        s.ev_offsets[s.ev_cur] = offsets;
+        if (s.launch_stream && s.launch_stream != ls)
+            HIP_TRY(d, hipStreamWaitEvent(ls, s.ev_ready[s.ev_cur ^ 1], 0));
+        s.launch_stream = ls;
+        a.gen = ++d->launch_gen * 0x9E3779B9u + 0x7F4A7C15u;
+        a.cands = s.cands;
+        a.cand_cap = (uint32_t)std::min<size_t>(s.cand_cap, 0xFFFFFFFFu);
+        a.tries = s.tries;
+        a.try_cap = (uint32_t)std::min<size_t>(s.try_cap, 0xFFFFFFFFu);
+        a.report = s.hc();
+        s.busy = true; // (a failure from here on leaves a launch in flight: adsb_reset waits for it)
+        HIP_TRY(d, adsb::launch_scan_batch(a, seg_d, tile_d, L.tiles, stats, ls));
+        HIP_TRY(d, hipEventRecord(s.ev_ready[s.ev_cur], ls));
+        WAIT_EVENT(d, s.ev_ready[s.ev_cur], "a batch scan launch");
+        s.busy = false;
+        s.prof_pending[s.ev_cur] = d->cfg.profile != 0;
+        if (slot_settle_profile(d, s, s.ev_cur))
+            return -1;
+        d->prof.launches++;
+        d->prof.offsets += offsets;
+        d->prof.last_offsets = offsets;
+        const size_t nc = s.hc()[0], nt = s.hc()[1];
+        if (nc <= s.cand_cap && nt <= s.try_cap)
+            break;
+        // the counters keep counting past the capacities: one repeat with exact sizes suffices (slot_collect)
+        if (attempt >= 2)
+            return d->fail("record buffers overflowed repeatedly (%zu candidates, %zu tries)", nc, nt);
+        d->prof.relaunches++;
+        if (slot_reserve(d, s, std::max(s.cand_cap, nc + nc / 8 + 64), std::max(s.try_cap, nt + nt / 8 + 64)))
+            return -1;
+    }
+    const auto t_host = clk::now();
+    d->prof.wait_ms += std::chrono::duration<double, std::milli>(t_host - t_wait).count();
+    const size_t nc = s.hc()[0], nt = s.hc()[1];
+    sort_order(d, s.cands, nc);
+    if (nt)
+        sort_tries(d, s.tries, nt);
+    d->prof.candidates += nc;
+    d->prof.tries += nt;
+    const size_t at = d->batch_cands.size();
+    d->batch_cands.resize(at + nc);
+    for (size_t i = 0; i < nc; i++) {
+        const uint32_t *r = s.cands + (size_t)d->order[i] * adsb::kCandWords;
+        adsb_candidate &c = d->batch_cands[at + i];
+        std::memset(&c, 0, sizeof c);
+        c.g = L.g_begin + r[0];
+        c.pw = r[1];
+        std::memcpy(c.frame, &r[2], 14);
+        c.len = (uint8_t)((r[5] >> 16) & 0xFF);
+        c.reserved = (uint8_t)((r[5] >> 24) & 1u);
+    }
+    const size_t tat = d->batch_tries.size();
+    d->batch_tries.resize(tat + nt);
+    for (size_t i = 0; i < nt; i++)
+        d->batch_tries[tat + i] = (((uint64_t)(s.tries[i] >> 2) + L.g_begin) << 2) | (s.tries[i] & 3u);
+    d->prof.host_ms += std::chrono::duration<double, std::milli>(clk::now() - t_host).count();
+    return 0;
+}
+
+long decode_batch(adsb_decoder *d, size_t n_captures, const void *const *p, const size_t *n, const adsb_frame **frames,
+                  uint64_t *first, adsb_stats *stats)
+{
+    using clk = std::chrono::steady_clock;
+    size_t bad = 0;
+    // A batch is whole streams, ended: like adsb_decode_device it leaves the handle finished, whether it succeeds or not,
+    // so a push without adsb_reset is refused and never meets batch_stats or the batch's frames.
+    d->finished = true;
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &d->n_cus, batch_forced_passes(d->dbg.passes), d->batch_segs,
+                            d->batch_launches, &bad))
+        return d->fail("internal: capture %zu is too long for a batch", bad); // (batch_refusal has looked)
+    d->batch_cands.clear();
+    d->batch_tries.clear();
+    for (const adsb_batch_launch &L : d->batch_launches)
+        if (batch_launch_collect(d, L, p, n))
+            return -1;
+    const auto t_host = clk::now();
+    d->batch_per.resize(n_captures); // every capture's table: the caller's `stats`, and the sum adsb_get_stats answers
+    const bool ok = adsb::batch_resolve(d->batch_res, n_captures, n, d->batch_segs.data(), d->batch_segs.size(), d->batch_cands.data(),
+                                        d->batch_cands.size(), d->batch_tries.data(), d->batch_tries.size(), d->batch_frames, first,
+                                        d->batch_per.data(), d->batch_cbuf, d->batch_tbuf);
+    if (!ok) {
+        d->batch_frames.clear();
+        return d->fail("internal: a record of a batch launch lies in no capture's offsets");
+    }
+    std::memset(&d->batch_stats, 0, sizeof d->batch_stats);
+    for (size_t i = 0; i < n_captures; i++) {
+        const adsb_stats &st = d->batch_per[i];
+        for (int k = 0; k < 3; k++) {
+            d->batch_stats.try_[k] += st.try_[k];
+            d->batch_stats.ok[k] += st.ok[k];
+        }
+        d->batch_stats.fixed += st.fixed;
+        if (stats)
+            stats[i] = st;
+    }
+    d->batch_stats_on = true;
+    d->prof.host_ms += std::chrono::duration<double, std::milli>(clk::now() - t_host).count();
+    *frames = d->batch_frames.empty() ? nullptr : d->batch_frames.data();
+    return (long)d->batch_frames.size();
+}
+
+} // namespace
+
+extern "C" {
+
+long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
+                              const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal(d, "adsb_decode_batch_device", n_captures, device_samples, n, true))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    return decode_batch(d, n_captures, device_samples, n, frames, first, stats);
+}
+
+long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n,
+                            const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal(d, "adsb_decode_batch_host", n_captures, reinterpret_cast<const void *const *>(samples), n, false))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    // every capture at a 128-byte boundary of one scratch array of the handle's
+    std::vector<size_t> off(n_captures);
+    size_t bytes = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        off[i] = bytes;
+        bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+    }
+    if (bytes > d->batch_in_cap) {
+        if (d->batch_in)
+            HIP_TRY(d, hipFree(d->batch_in));
+        d->batch_in = nullptr;
+        d->batch_in_cap = 0;
+        if (hipMalloc(&d->batch_in, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            d->batch_in = nullptr;
+            return d->fail("adsb_decode_batch_host: cannot allocate %zu bytes of device scratch for the captures", bytes);
+        }
+        d->batch_in_cap = bytes;
+    }
+    std::vector<const void *> at(n_captures);
+    for (size_t i = 0; i < n_captures; i++) {
+        char *dst = reinterpret_cast<char *>(d->batch_in) + off[i];
+        at[i] = dst;
+        if (n[i])
+            HIP_TRY(d, hipMemcpyAsync(dst, samples[i], n[i] * sizeof(uint16_t), hipMemcpyHostToDevice,
+                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
+    }
+    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the scan needs no event)
+        WAIT_STREAM(d, cs, "a copy stream");
+    return decode_batch(d, n_captures, at.data(), n, frames, first, stats);
+}
+
+long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, adsb_batch_segment *segs, size_t seg_cap,
+                       adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
+{
+    if ((n_captures && !n) || (seg_cap && !segs) || (launch_cap && !launches) || !n_launches)
+        return -1;
+    std::vector<adsb_batch_segment> sv;
+    std::vector<adsb_batch_launch> lv;
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), sv, lv, nullptr))
+        return -1;
+    if (!sv.empty() && seg_cap)
+        std::memcpy(segs, sv.data(), std::min(seg_cap, sv.size()) * sizeof sv[0]);
+    if (!lv.empty() && launch_cap)
+        std::memcpy(launches, lv.data(), std::min(launch_cap, lv.size()) * sizeof lv[0]);
+    *n_launches = lv.size();
+    return (long)sv.size();
+}
+
+long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes, const adsb_candidate *cands, size_t n_cands,
+                        const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first, adsb_stats *stats)
+{
+    if ((n_captures && !n) || (n_cands && !cands) || (n_tries && !tries) || (frame_cap && !frames) || !first)
+        return -1;
+    std::vector<adsb_batch_segment> sv;
+    std::vector<adsb_batch_launch> lv;
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), sv, lv, nullptr))
+        return -1;
+    adsb::Resolver r;
+    std::vector<adsb_frame> out;
+    std::vector<adsb_candidate> cbuf;
+    std::vector<uint64_t> tbuf;
+    if (!adsb::batch_resolve(r, n_captures, n, sv.data(), sv.size(), cands, n_cands, tries, n_tries, out, first, stats, cbuf, tbuf))
+        return -1;
+    if (!out.empty() && out.size() <= frame_cap)
+        std::memcpy(frames, out.data(), out.size() * sizeof out[0]);
+    return (long)out.size();
 }
 
 // ---- stateless per-shard scan (multi-GPU path) -----------------

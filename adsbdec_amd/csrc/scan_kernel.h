@@ -176,6 +176,26 @@ uint32_t make_fix_table(uint32_t *tab /* kFixSlots */);
 int choose_passes(uint64_t n_offsets, int cus, bool dense = false);
 
 hipError_t launch_scan(const ScanArgs &args, bool stats, hipStream_t stream);
+
+// A launch whose tiles belong to different captures (scan_batch_kernel.hip; the layout: batch.hpp).  A SEGMENT is a range of
+// offsets of one capture: the members of ScanArgs that describe the samples and the offsets, in the launch's own ("virtual")
+// coordinates, plus the launch's first tile of it.  Tile t of the launch is tile t - first_tile of segment tile_seg[t]: its
+// first offset is g_begin + 28 tile_first_run(t - first_tile, 0, K), it reads the segment's samples and stops at the segment's
+// g_end -- no tile straddles two segments, none covers the space between them.  Everything else is the launch's ScanArgs
+// (x, pbuf0, p_lo, p_hi, g_end unused; g_begin: what the records' and try words' g_rel count from; big_tiles = 0,
+// hand = null, try_counts = null: the records go to the loose list, the tries to the launch-wide list).
+struct BatchSeg {
+    uint64_t x; // the device address ScanArgs::x would hold (a number: the kernel says which address space it is in) ...
+    int64_t pbuf0;
+    int64_t p_lo, p_hi;
+    uint64_t g_begin, g_end;
+    uint32_t first_tile, pad;
+};
+// segs and tile_seg (n_tiles words) are device memory
+hipError_t launch_scan_batch(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
+                             hipStream_t stream);
+// the report kernel of launch_scan on its own (scan_kernel.hip)
+hipError_t launch_report(const ScanArgs &args, hipStream_t stream);
 // Device-to-device copy of n uint16 samples by the library's own kernel (the staging tail: see scan_kernel.hip).
 hipError_t launch_copy_samples(uint16_t *dst, const uint16_t *src, size_t n, hipStream_t stream);
 

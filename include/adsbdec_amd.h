@@ -1,14 +1,13 @@
 /*
- * adsbdec_amd.h -- C-ABI of libadsbdec_amd.so: the MI355X (gfx950) drop-in for the offline "-f" demodulation path
- * of TLeconte/adsbdec.  This header is everything a drop-in host and a multi-GPU host call; the primitives underneath
- * (resolver handle, hand-off walker, shard scans, stitcher) and the test knobs are in adsbdec_amd_diag.h.
- * The reference has no plugin/FFI interface: its whole interface is one prototype (adsbdec.h:5) plus extern C functions
- * with file-scope state.  Each entry point names the reference seam it stands behind (file:line under
- * /root/reference); INTEGRATION.md shows the change a maintainer makes in air.c / output.c to bind them.
- * Conventions follow the reference: int 0 / -1 with a message from adsb_last_error() (the reference prints to stderr,
- * air.c:113-118); one producer thread per handle (decodeiq is not re-entrant: air.c:33-34,49-50, demod.c:86); plain
- * pointers and sizes, no C++/torch types.  The HIP path is the only implementation: there is no CPU fallback, and
- * adsb_create() fails loudly when no gfx950 device is usable.
+ * adsbdec_amd.h -- C-ABI of libadsbdec_amd.so: the MI355X (gfx950) drop-in for the offline "-f" demodulation path of
+ * TLeconte/adsbdec.  This header is everything a drop-in host and a multi-GPU host call; the primitives underneath (resolver
+ * handle, hand-off walker, shard scans, stitcher) and the test knobs are in adsbdec_amd_diag.h.  The reference has no plugin/FFI
+ * interface: its whole interface is one prototype (adsbdec.h:5) plus extern C functions with file-scope state.
+ * Each entry point names the reference seam it stands behind (file:line under /root/reference); INTEGRATION.md shows the change a
+ * maintainer makes in air.c / output.c to bind them.  Conventions follow the reference: int 0 / -1 with a message from
+ * adsb_last_error() (the reference prints to stderr, air.c:113-118); one producer thread per handle (decodeiq is not re-entrant:
+ * air.c:33-34,49-50, demod.c:86); plain pointers and sizes, no C++/torch types.  The HIP path is the only implementation: there
+ * is no CPU fallback, and adsb_create() fails loudly when no gfx950 device is usable.
  * Input domain.  uint16 samples carrying the Airspy's 12-bit ADC code centred on 2048 (air.c:64).  Results are
  * bit-identical to the reference for every code in [0, 4095] and beyond, up to |x-2048| <= ~23 000 (the preamble sums
  * still fit an int); larger codes make the reference's `int p1 = float + float` (demod.c:102-105) overflow -- undefined
@@ -62,13 +61,11 @@ typedef struct adsb_config {
                                scan can provably never visit (same frames, ~4x fewer records)                     */
     int32_t fix_1bit;       /* EXTENSION, not in the reference (its -e does nothing): repair DF17/18 frames
                                whose CRC residual is the syndrome of one bit in [5,112).  Off by default.         */
-    int32_t push_overlap;   /* 1: adsb_push() returns once `samples` is COPIED to the device and leaves the scan in
-                               flight; the frames of a call become drainable during the NEXT push / finish / sync
-                               (same frames, same order).  0 (default): drainable when the call returns.          */
+    int32_t push_overlap;   /* 1: adsb_push() returns once `samples` is COPIED to the device, the scan in flight; a call's frames become
+                               drainable during the NEXT push / finish / sync (same frames, same order).  0 (default): when the call returns */
     int32_t host_threads;   /* Threads that consume the device's hand-off stream (decodeiq, air.c:54, never started one).
-                               1: the calling thread alone, ALWAYS -- the library never starts a thread.
-                               2: + a thread of the handle's own that reads the stream of large launches; N >= 3
-                               (<= 17): + N - 2 more that decide batches of tiles ahead and write the frames.
+                               1: the calling thread alone, ALWAYS -- the library never starts a thread.  2: + a thread of the handle's own
+                               that reads large launches' stream; N >= 3 (<= 17): + N - 2 that decide batches of tiles ahead and write frames.
                                0 (default): 1, until a launch hands over a record per 2 048 offsets (a channel near its capacity);
                                launches that follow such a one run with 6 (5 threads that poll during a launch and
                                0.4 ms beyond, then sleep; 2 where the process has < 12 CPUs): the step takes 1.2 x its
@@ -80,7 +77,7 @@ typedef struct adsb_config {
                                second copy engine: 7-9 ms each) beside its other work: for a one-shot process      */
     const void *debug;      /* NULL, or an adsb_debug_config (adsbdec_amd_diag.h: test knobs); copied by adsb_create */
 } adsb_config;
-/* Counters accumulate over the life of the handle (adsb_reset keeps them: take differences). */
+/* Counters accumulate over the life of the handle (adsb_reset keeps them: take differences); the last three members came with ABI 5. */
 typedef struct adsb_profile {
     uint64_t launches;     /* scan-kernel launches since adsb_create                                  */
     uint64_t relaunches;   /* launches repeated after a record-buffer overflow                        */
@@ -95,7 +92,6 @@ typedef struct adsb_profile {
     uint64_t big_offsets;  /* offsets per launch of the largest launch size seen                      */
     uint64_t big_launches; /* launches of that size                                                   */
     double big_ms;         /* sum of their durations on the device clock (profile=1)                  */
-    /* ---- ABI 5 ---- */
     uint32_t host_threads_running; /* threads of the handle's own that exist NOW: reader (0/1) + gang helpers; 0 under
                                       ordinary traffic and always with cfg.host_threads = 1                        */
     uint32_t gang_launches;        /* launches whose frames went through the gang                                  */
@@ -122,19 +118,25 @@ int adsb_sync(adsb_decoder *d);
  * multiple of 8 samples is scanned in place.  _final = push of the LAST piece + adsb_finish in one pass. */
 int adsb_push_device(adsb_decoder *d, const void *device_samples, size_t n);
 int adsb_push_device_final(adsb_decoder *d, const void *device_samples, size_t n);
-/* The whole of `adsbdec -f` for ONE capture resident in HBM: adsb_reset + adsb_push_device_final + adsb_take.
- * Returns the number of frames (*frames as adsb_take), or -1. */
+/* `adsbdec -f` for ONE capture in HBM: adsb_reset + adsb_push_device_final + adsb_take.  The number of frames (*frames as adsb_take) or -1. */
 long adsb_decode_device(adsb_decoder *d, const void *device_samples, size_t n, const adsb_frame **frames);
+/* n_captures INDEPENDENT captures in as few launches as they fit, each decoded exactly as adsb_decode_device(d, p[i], n[i]) would
+ * decode it alone (g and ts from 0).  Capture i's frames are (*frames)[first[i] .. first[i+1]) (first: n_captures + 1 entries), valid as
+ * adsb_take's; stats: NULL, or n_captures tables (try_ with cfg.collect_stats).  Leaves the handle as adsb_decode_device does: reset, then
+ * finished.  Returns all frames' number, or -1; refused with the handle unchanged: a _device pointer not 16-byte aligned, n[i] >= 2^32. */
+long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
+                              const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
+long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n,
+                            const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 /* Airspy packed 12-bit input (air.c:120,128,150-151,173-177: the reference asks libairspy for packing, then turns it off).  A group
  * is 8 samples s0..s7 (12-bit codes, air.c:64) in three little-endian 32-bit words w0 w1 w2; read as ONE 96-bit big-endian number
  * w0:w1:w2 it is s0 s1 .. s7, 12 bits each, most significant first (written from this definition, not checked against libairspy):
  *   s0 = w0 >> 20,  s1 = (w0 >> 8) & 0xfff,  s2 = (w0 & 0xff) << 4 | w1 >> 28,  s3 = (w1 >> 16) & 0xfff,  s4 = (w1 >> 4) & 0xfff,
  *   s5 = (w1 & 0xf) << 8 | w2 >> 24,  s6 = (w2 >> 12) & 0xfff,  s7 = w2 & 0xfff.
  * n counts SAMPLES: n % 8 == 0, ADSB_PACKED12_BYTES(n) bytes are read, at a stream position that is a multiple of 8 (uint16 and
- * packed pushes mix at such positions); device pointers 4-byte aligned.  Otherwise -1 and the handle is unchanged.  Frames, ts,
- * Try/Ok, counters and contracts: those of the uint16 calls.  Extra device memory: host pushes, two landing buffers of 1.5 B x
- * stage_samples (at the first one); device pushes, a scratch of 2 B x n kept by the handle (grown on demand, freed by adsb_destroy)
- * into which the input is unpacked and then scanned in place. */
+ * packed pushes mix at such positions); device pointers 4-byte aligned.  Otherwise -1 and the handle is unchanged.  Frames, ts, Try/Ok,
+ * counters and contracts: those of the uint16 calls.  Extra device memory: host pushes, two landing buffers of 1.5 B x stage_samples (at the
+ * first one); device pushes, a scratch of 2 B x n the handle keeps (grown on demand, freed by adsb_destroy): unpacked there, then scanned. */
 #define ADSB_PACKED12_BYTES(n) ((n) / 8 * 12)
 int adsb_push_packed(adsb_decoder *d, const void *packed, size_t n);
 int adsb_push_packed_async(adsb_decoder *d, const void *packed, size_t n);
@@ -147,17 +149,15 @@ long adsb_decode_device_packed(adsb_decoder *d, const void *device_packed, size_
 int adsb_set_long_stream(adsb_decoder *d, int on);   int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
 /* End of input (fileInput's EOF, air.c:241-244): the remaining offsets, and the end-of-file horizon. */
 int adsb_finish(adsb_decoder *d);
-/* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.
- * adsb_host_alloc_on binds the memory to the NUMA node of `device` (two-socket hosts; best effort).  adsb_host_register
- * page-locks memory the caller already owns.  0 / -1. */
+/* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.  adsb_host_alloc_on binds the
+ * memory to the NUMA node of `device` (best effort).  adsb_host_register page-locks memory the caller already owns.  0 / -1. */
 void *adsb_host_alloc(size_t bytes);
 void *adsb_host_alloc_on(size_t bytes, int device);
 void adsb_host_free(void *p);
 int adsb_host_register(void *p, size_t bytes);
 int adsb_host_unregister(void *p);
-/* Frame egress: the records the reference hands to netout() (output.c:159), in the same order.  adsb_drain copies
- * (returns the number, <= cap, or -1); adsb_take hands every pending frame out in place -- valid until the next call
- * that pushes into, finishes, resets or destroys the handle. */
+/* Frame egress: what the reference hands to netout() (output.c:159), in its order.  adsb_drain copies (returns the number, <= cap, or -1);
+ * adsb_take hands every pending frame out in place -- valid until the next call that pushes into, finishes, resets or destroys the handle. */
 long adsb_drain(adsb_decoder *d, adsb_frame *out, size_t cap);
 long adsb_take(adsb_decoder *d, const adsb_frame **frames);
 size_t adsb_pending(const adsb_decoder *d);

@@ -237,6 +237,38 @@ size_t adsb_resolver_walk_result(const adsb_resolver *r, int *final);
 long adsb_resolver_head(adsb_resolver *r, adsb_candidate *out, size_t cap);
 uint64_t adsb_resolver_skipped(const adsb_resolver *r);
 
+/* ---- a batch of independent captures (adsb_decode_batch_*; csrc/batch.hpp), without a device ---------------------------------
+ * The captures of a batch lie end to end in ONE space of "virtual" offsets, capture i's offset 0 at a base that is a multiple of
+ * 28 (so its arithmetic is that of a stream from 0: the FIR phase, the fs/4 sign and the run boundaries depend on the index mod
+ * 28 only), with at least ADSB_WINDOW + ADSB_DECOFFSET free offsets behind its last power sample.  A SEGMENT is a capture's
+ * offsets [o_begin, o_end) at the virtual offsets from `base` on -- all of them, but for a capture too long for one launch, which
+ * is cut into segments of whole tiles -- and takes `tiles` tiles of launch `launch` from first_tile on (no tile holds offsets of
+ * two segments; a capture without offsets -- shorter than a window, or than the reference's first deqframe call, air.c:94 -- has
+ * one empty segment).  A LAUNCH covers the virtual offsets [g_begin, g_end) (at most 2^30 - 28 x 8020: g_rel has 30 bits) with
+ * `tiles` tiles of `passes` passes. */
+typedef struct adsb_batch_segment {
+    uint64_t capture, o_begin, o_end, base;
+    uint32_t launch, first_tile, tiles, pad;
+} adsb_batch_segment;
+typedef struct adsb_batch_launch {
+    uint64_t g_begin, g_end;
+    uint32_t seg_first, seg_end, tiles; /* its segments: [seg_first, seg_end) */
+    int32_t passes;
+} adsb_batch_launch;
+/* The layout of n_captures captures of n[i] samples on a device of `cus` compute units (0: 256); passes > 0 forces the passes
+ * per tile (adsb_debug_config.passes).  Fills at most seg_cap / launch_cap entries; returns the number of segments (every capture
+ * has one or more, in capture order) and *n_launches, or -1 (a capture of 2^32 samples or more: a batch has no long-stream mode). */
+long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, adsb_batch_segment *segs, size_t seg_cap,
+                       adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches);
+/* What adsb_decode_batch_* does with the records of its launches: cands (ascending g) and tries (ascending (g << 2) | code) of the
+ * whole batch in the VIRTUAL offsets of that layout -> per capture the frames the reference decodes from it alone (g and ts from
+ * 0; demod.c:89,99,125-141, air.c:94-99 through adsb_resolver's code), capture i's at frames[first[i] .. first[i+1]) (first:
+ * n_captures + 1 entries), and its Try/Ok table (stats: NULL or n_captures entries).  Returns the number of frames (more than
+ * frame_cap: none was copied), or -1 (bad arguments, a record outside every segment). */
+long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes, const adsb_candidate *cands, size_t n_cands,
+                        const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first,
+                        adsb_stats *stats);
+
 /* ---- where a host-resident capture lives (csrc/numa.cpp) ---------------------------------------------------------------
  * Stands where the reference has `iqbuff = malloc(...)` (air.c:230).  A capture in host memory that eight devices pull at
  * once, each over its own link, should have every slice on the socket its device hangs off: a slice on the other socket
