@@ -147,6 +147,17 @@ SYMBOLS = {
     "adsb_push_device_packed_final": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_decode_device_packed": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Frame))]),
     "adsb_unpack_packed12": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adsb_decode_batch_device_packed": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                   C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_decode_batch_host_packed": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                 C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_multi_decode_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int,
+                                                C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_multi_decode_batch_files": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_int,
+                                                 C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_multi_batch_plan": (C.c_long, [C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_size_t),
+                                         C.POINTER(C.c_size_t), C.c_size_t]),
+    "adsb_multi_set_batch_bytes": (C.c_int, [C.c_void_p, C.c_uint64]),
     "adsb_finish": (C.c_int, [C.c_void_p]),
     "adsb_host_alloc": (C.c_void_p, [C.c_size_t]),
     "adsb_host_free": (None, [C.c_void_p]),
@@ -471,6 +482,38 @@ class Decoder:
             self._check(-1, "adsb_decode_device_packed")
         return self._out, k
 
+    # ---- a batch of packed captures (adsb_decode_batch_*_packed): one unpack launch, then the batch scan
+    def decode_batch_device_packed_raw(self, ptrs, ns):
+        """adsb_decode_batch_device_packed (ns count samples) -> what decode_batch_device_raw gives."""
+        k = len(ns)
+        p = (C.c_void_p * max(1, k))(*[int(v) if v else None for v in ptrs])
+        n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        total = self._L.adsb_decode_batch_device_packed(self._h, k, p, n, self._out_ref, first, st)
+        if total < 0:
+            self._check(-1, "adsb_decode_batch_device_packed")
+        return self._out, first, st
+
+    def decode_batch_device_packed(self, ptrs, ns, stats: bool = False):
+        """Packed captures resident in HBM (4-byte aligned pointers, ns in samples) -> what decode_batch_device gives for their
+        unpacked twins."""
+        out, first, st = self.decode_batch_device_packed_raw(ptrs, ns)
+        return self._batch_result(out, first, st, len(ns), stats)
+
+    def decode_batch_packed(self, bufs, stats: bool = False):
+        """The same for packed bytes (uint8 arrays of whole 12-byte groups) in host memory: adsb_decode_batch_host_packed."""
+        bufs = [np.ascontiguousarray(b) for b in bufs]
+        assert all(b.dtype == np.uint8 and b.size % 12 == 0 for b in bufs)
+        k = len(bufs)
+        p = (C.c_void_p * max(1, k))(*[b.ctypes.data if b.size else None for b in bufs])
+        n = (C.c_size_t * max(1, k))(*[b.size // 12 * 8 for b in bufs])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        if self._L.adsb_decode_batch_host_packed(self._h, k, p, n, self._out_ref, first, st) < 0:
+            self._check(-1, "adsb_decode_batch_host_packed")
+        return self._batch_result(self._out, first, st, k, stats)
+
     def decode_packed(self, buf: np.ndarray, chunk: int | None = None, mode: str = "sync"):
         """decode() for packed bytes: chunk counts samples (a multiple of 8); the same three modes."""
         assert buf.dtype == np.uint8 and buf.size % 12 == 0
@@ -705,6 +748,20 @@ def batch_layout(ns, cus: int = 0, passes: int = 0):
         raise AdsbError("adsb_batch_layout failed")
     as_dict = lambda o: {f: int(getattr(o, f)) for f, _ in o._fields_ if f != "pad"}
     return [as_dict(segs[i]) for i in range(ns_)], [as_dict(launches[i]) for i in range(nl.value)]
+
+
+def multi_batch_plan(ns, n_workers: int, batch_bytes: int = 0, packed: bool = False):
+    """adsb_multi_batch_plan -> (range: n_workers + 1 capture indices, subs: the sub-batches' starts and len(ns) behind them)."""
+    L = load()
+    k = len(ns)
+    n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
+    rng = (C.c_size_t * (n_workers + 1))()
+    cap = k + 1                                   # a sub-batch holds a capture at least
+    subs = (C.c_size_t * cap)()
+    nsub = L.adsb_multi_batch_plan(k, n, n_workers, batch_bytes, int(packed), rng, subs, cap)
+    if nsub < 0:
+        raise AdsbError("adsb_multi_batch_plan failed")
+    return [int(v) for v in rng], [int(subs[i]) for i in range(nsub + 1)]
 
 
 def batch_resolve(ns, cands, tries, cus: int = 0, passes: int = 0):

@@ -19,6 +19,12 @@
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
  *                   capture k's packets go to <file k>.avr / .mlat / .beast instead of stdout.
+ *     -B listfile   EXTENSION: a batch of captures, one path per line of listfile (empty lines are skipped; any number of
+ *                   them).  The runtime's start is paid once for all: the captures are decoded through the library's
+ *                   batch calls (adsb_multi_decode_batch_files), many short ones per launch, on the GPUs of -G or on the
+ *                   one of -d (default: the first one).  Capture k's packets go to <capture k>.avr / .mlat / .beast and
+ *                   stderr has, per capture, the line and the table several -f with -G print.  -p is allowed here (every
+ *                   capture is then a packed one; a trailing partial group is not decoded).  Not with -f, -s or -l.
  * The GPU runtime initialises every device it can see, which takes longer the more there are: before its first call
  * this program narrows ROCR_VISIBLE_DEVICES to the devices it is going to use (unless the variable is already set).
  *     -s addr[:port]  send the packets to a TCP peer instead of stdout (main.c:65-68; default port 30001)
@@ -151,7 +157,8 @@ static void *locker_main(void *arg)
 static void usage(void)
 {
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
-    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n\n");
+    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
+    printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
     printf("\t-b : output binary beast format\n");
@@ -162,6 +169,9 @@ static void usage(void)
     printf("\t-p : (extension) the file holds Airspy packed 12-bit samples (8 samples in 12 bytes), unpacked on the GPU; not with -G\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
+    printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
+    printf("\t     decoded many per launch on the GPU of -d or the GPUs of -G, packets of capture k written to\n");
+    printf("\t     <capture k>.avr | .mlat | .beast; -p allowed (all captures packed); not with -f, -s or -l\n");
     printf("\t-f : input from filename (raw 16 bits real: uint16 carrying the 12-bit ADC code centred on 2048;\n");
     printf("\t     bit-identical to adsbdec for codes 0..4095, see adsbdec_amd.h for the wider domain)\n");
     printf("\t     a file of any length: 2^32 samples (8 GiB) and more are decoded through the wraps of adsbdec's 32-bit\n");
@@ -375,16 +385,109 @@ static int run_multi(const adsb_config *cfg, int *devs, int ndev, char **files, 
     _exit(rc); /* (no teardown: see the end of main) */
 }
 
+/* -B: the paths of a list file, one per line, empty lines skipped.  NULL (with a message) when it cannot be read. */
+static char **read_list(const char *listfile, size_t *count)
+{
+    FILE *f = fopen(listfile, "r");
+    if (!f) {
+        fprintf(stderr, "%s: cannot read the list of captures: %s\n", listfile, strerror(errno));
+        return NULL;
+    }
+    char **paths = NULL, *line = NULL;
+    size_t n = 0, cap = 0, len = 0;
+    ssize_t got;
+    while ((got = getline(&line, &len, f)) >= 0) {
+        while (got > 0 && (line[got - 1] == '\n' || line[got - 1] == '\r'))
+            line[--got] = 0;
+        if (got == 0)
+            continue;
+        char **grown = paths;
+        if (n == cap && (grown = (char **)realloc(paths, (cap ? 2 * cap : 256) * sizeof *paths)) != NULL) {
+            cap = cap ? 2 * cap : 256;
+            paths = grown;
+        }
+        if (!grown || !(paths[n] = strdup(line))) {
+            fprintf(stderr, "%s: out of memory for the list of captures\n", listfile);
+            while (n > 0)
+                free(paths[--n]);
+            free(paths);
+            free(line);
+            fclose(f);
+            return NULL;
+        }
+        n++;
+    }
+    free(line);
+    fclose(f);
+    if (!paths) /* (an empty list: nothing to decode, and no error) */
+        paths = (char **)calloc(1, sizeof *paths);
+    *count = n;
+    return paths;
+}
+
+/* -B: every capture of the list through ONE start of the runtime and the library's batch calls; packets into <capture>.<format>. */
+static int run_batch_list(const adsb_config *cfg, int *devs, int ndev, char **paths, size_t n_captures, int packed, int outformat,
+                          int timing)
+{
+    static const char *ext[3] = {"avr", "mlat", "beast"};
+    const double t_start = now_ms();
+    adsb_multi *m = adsb_multi_create(cfg, ndev, devs);
+    if (!m) {
+        fprintf(stderr, "adsb_multi_create() failed: %s\n", adsb_multi_last_error(NULL));
+        return 255;
+    }
+    const double t_init = now_ms();
+    int rc = 0;
+    const adsb_frame *fr = NULL;
+    uint64_t *first = (uint64_t *)calloc(n_captures + 1, sizeof *first);
+    adsb_stats *st = (adsb_stats *)calloc(n_captures + 1, sizeof *st);
+    if (!first || !st) {
+        fprintf(stderr, "out of memory for the results of %zu captures\n", n_captures);
+        rc = 255;
+    } else if (adsb_multi_decode_batch_files(m, n_captures, (const char *const *)paths, packed, &fr, first, st) < 0) {
+        fprintf(stderr, "adsb_multi_decode_batch_files() failed: %s\n", adsb_multi_last_error(m));
+        rc = 255;
+    }
+    const double t_decoded = now_ms();
+    for (size_t k = 0; k < n_captures && rc == 0; k++) {
+        char path[4096];
+        if ((size_t)snprintf(path, sizeof path, "%s.%s", paths[k], ext[outformat]) >= sizeof path) {
+            fprintf(stderr, "%s: the name of its .%s file is longer than %zu bytes\n", paths[k], ext[outformat], sizeof path - 1);
+            rc = 1;
+            break;
+        }
+        const long n = (long)(first[k + 1] - first[k]);
+        FILE *out = fopen(path, "wb");
+        if (!out || write_frames_file(out, fr + first[k], n, outformat) != 0 || fclose(out) != 0) {
+            fprintf(stderr, "%s: cannot write\n", path);
+            rc = 1;
+            break;
+        }
+        fprintf(stderr, "== %s: %ld frames -> %s\n", paths[k], n, path);
+        print_stats(&st[k]);
+    }
+    if (timing) {
+        adsb_multi_info inf;
+        adsb_multi_get_info(m, &inf);
+        fprintf(stderr, "timing: runtime init %.1f ms, decode of %zu captures %.1f ms (%d workers, slowest %.1f ms), writing %.1f ms, total %.1f ms\n",
+                t_init - t_start, n_captures, t_decoded - t_init, inf.shards, inf.workers_ms, now_ms() - t_decoded, now_ms() - t_start);
+    }
+    fflush(stderr);
+    if (getenv("ADSB_CLI_CLEAN_EXIT"))
+        exit(rc);
+    _exit(rc); /* (no teardown: see the end of main) */
+}
+
 int main(int argc, char **argv)
 {
-    const char *filename = NULL;
+    const char *filename = NULL, *listfile = NULL;
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
     int outformat = 0, df18 = 0, fix1 = 0, packed = 0, c;
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpd:G:s:l:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpd:G:s:l:B:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -393,6 +496,9 @@ int main(int argc, char **argv)
                 return 1;
             }
             files[nfiles++] = optarg;
+            break;
+        case 'B':
+            listfile = optarg;
             break;
         case 'd': {
             char *end;
@@ -440,6 +546,28 @@ int main(int argc, char **argv)
             usage();
             return 1;
         }
+    }
+    if (listfile) { /* a batch: its own inputs and outputs -- no -f, no peer; -d and -G exclude each other here too */
+        if (filename || outmode != SINK_STDOUT || (ndev && device >= 0)) {
+            usage();
+            return 1;
+        }
+        size_t n_captures = 0;
+        char **paths = read_list(listfile, &n_captures);
+        if (!paths)
+            return 255;
+        install_signals();
+        if (ndev == 0) {
+            devs[0] = device >= 0 ? device : 0;
+            ndev = 1;
+        }
+        restrict_visible_devices(devs, ndev);
+        adsb_config bcfg;
+        adsb_config_default(&bcfg);
+        bcfg.df18 = df18;
+        bcfg.fix_1bit = fix1;
+        bcfg.collect_stats = 1; /* the reference always prints Try/Ok */
+        return run_batch_list(&bcfg, devs, ndev, paths, n_captures, packed, outformat, getenv("ADSB_CLI_TIMING") != NULL);
     }
     /* several captures need -G and go to files; -d and -G exclude each other */
     if (!filename || (nfiles > 1 && (ndev == 0 || outmode != SINK_STDOUT)) || (ndev && device >= 0)) {

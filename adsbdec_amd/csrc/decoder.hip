@@ -31,6 +31,10 @@
 // A batch of captures (adsb_decode_batch_*, batch.hpp) is scanned in place too, by launches of scan_batch_kernel:
 //   batch_tab  a launch's segment table and its tile -> segment words (scan_kernel.h BatchSeg), uploaded from batch_tab_h
 //   batch_in   adsb_decode_batch_host: the captures, each at a 128-byte boundary
+// and a batch of PACKED captures (adsb_decode_batch_*_packed) is unpacked first, by one launch of unpack12_batch.hip:
+//   batch_land     _host_packed: the packed bytes of the captures (1.5 B per sample), each at a 16-byte boundary
+//   batch_unpacked the unpacked captures (2 B per sample), each at a 128-byte boundary: what the batch scan then reads
+//   unpack_tab     that launch's table, a row per capture that has groups (packed12.h Unpack12Seg), uploaded from unpack_tab_h
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -283,6 +287,11 @@ struct adsb_decoder {
     size_t batch_tab_cap = 0;                          // bytes
     uint16_t *batch_in = nullptr;
     size_t batch_in_cap = 0;    // bytes
+    uint8_t *batch_land = nullptr;
+    uint16_t *batch_unpacked = nullptr;
+    size_t batch_land_cap = 0, batch_unpacked_cap = 0; // bytes
+    void *unpack_tab = nullptr, *unpack_tab_h = nullptr; // device / pinned host
+    size_t unpack_tab_cap = 0;                           // bytes
     bool batch_stats_on = false; // the last call was a batch: adsb_get_stats answers batch_stats, the sum over its captures
     adsb_stats batch_stats{};
     uint16_t *win_buf = nullptr; // adsb_scan_shard_host: device copy of the caller's window
@@ -1975,6 +1984,10 @@ void adsb_destroy(adsb_decoder *d)
     if (d->batch_tab) (void)hipFree(d->batch_tab);
     if (d->batch_tab_h) (void)hipHostFree(d->batch_tab_h);
     if (d->batch_in) (void)hipFree(d->batch_in);
+    if (d->batch_land) (void)hipFree(d->batch_land);
+    if (d->batch_unpacked) (void)hipFree(d->batch_unpacked);
+    if (d->unpack_tab) (void)hipFree(d->unpack_tab);
+    if (d->unpack_tab_h) (void)hipHostFree(d->unpack_tab_h);
     for (int i = 0; i < 2; i++)
         if (d->d_carry[i]) (void)hipFree(d->d_carry[i]);
     if (d->d_frames) (void)hipFree(d->d_frames);
@@ -2787,6 +2800,107 @@ long decode_batch(adsb_decoder *d, size_t n_captures, const void *const *p, cons
     return (long)d->batch_frames.size();
 }
 
+
+// The refusals of adsb_decode_batch_*_packed, before anything of the handle changes.
+int batch_packed_refusal(adsb_decoder *d, const char *what, size_t n_captures, const void *const *p, const size_t *n, bool device)
+{
+    if (n_captures && (!p || !n))
+        return d->fail("%s: NULL capture arrays", what);
+    for (size_t i = 0; i < n_captures; i++) {
+        if ((uint64_t)n[i] >= (1ull << 32))
+            return d->fail("%s: capture %zu has %zu samples: 2^32 or more, where the reference's sample counter wraps (air.c:34); "
+                           "a batch has no long-stream mode", what, i, n[i]);
+        if (n[i] % adsb::kPackedGroupSamples != 0)
+            return d->fail("%s: capture %zu: n = %zu is not a multiple of 8 (packed 12-bit input comes in whole 8-sample groups)", what,
+                           i, n[i]);
+        if (n[i] && !p[i])
+            return d->fail("%s: capture %zu: NULL samples", what, i);
+        if (device && (uintptr_t)p[i] % 4 != 0)
+            return d->fail("%s: capture %zu: device pointer %p is not 4-byte aligned", what, i, p[i]);
+    }
+    return 0;
+}
+
+// A device buffer of the handle's that only ever grows.
+template <class T> int batch_grow(adsb_decoder *d, const char *what, const char *of, T *&buf, size_t &cap, size_t bytes)
+{
+    if (bytes <= cap)
+        return 0;
+    if (buf)
+        HIP_TRY(d, hipFree(buf));
+    buf = nullptr;
+    cap = 0;
+    if (hipMalloc(&buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return d->fail("%s: cannot allocate %zu bytes of device scratch for %s", what, bytes, of);
+    }
+    cap = bytes;
+    return 0;
+}
+
+// The packed captures at src[] (device memory, 4-byte aligned) -> uint16 samples in batch_unpacked, capture i from at[i] on (a
+// 128-byte boundary), by ONE launch on the handle's stream: the batch scan that follows on that stream reads behind it.
+int batch_unpack(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n, std::vector<const void *> &at)
+{
+    at.assign(n_captures, nullptr);
+    size_t bytes = 0, rows = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+        rows += n[i] != 0;
+    }
+    if (batch_grow(d, what, "the unpacked samples (2 bytes per sample)", d->batch_unpacked, d->batch_unpacked_cap, bytes))
+        return -1;
+    const size_t tab_bytes = (rows + 1) * sizeof(adsb::Unpack12Seg);
+    if (tab_bytes > d->unpack_tab_cap) {
+        if (d->unpack_tab)
+            HIP_TRY(d, hipFree(d->unpack_tab));
+        if (d->unpack_tab_h)
+            HIP_TRY(d, hipHostFree(d->unpack_tab_h));
+        d->unpack_tab = d->unpack_tab_h = nullptr;
+        d->unpack_tab_cap = 0;
+        const size_t cap = tab_bytes + tab_bytes / 4 + 4096;
+        HIP_TRY(d, hipMalloc(&d->unpack_tab, cap));
+        HIP_TRY(d, hipHostMalloc(&d->unpack_tab_h, cap, hipHostMallocDefault));
+        d->unpack_tab_cap = cap;
+    }
+    adsb::Unpack12Seg *tab = static_cast<adsb::Unpack12Seg *>(d->unpack_tab_h);
+    size_t off = 0, row = 0;
+    uint64_t groups = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        at[i] = reinterpret_cast<const char *>(d->batch_unpacked) + off;
+        if (n[i]) {
+            tab[row].src = (uint64_t)(uintptr_t)src[i];
+            tab[row].dst16 = off / 16;
+            tab[row].g_first = groups;
+            row++;
+            groups += n[i] / adsb::kPackedGroupSamples;
+        }
+        off += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+    }
+    tab[row] = adsb::Unpack12Seg{0, 0, groups}; // behind the last row: where its groups end
+    if (groups == 0)
+        return 0;
+    HIP_TRY(d, hipMemcpyAsync(d->unpack_tab, d->unpack_tab_h, tab_bytes, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(d, adsb::launch_unpack12_batch(d->batch_unpacked, static_cast<const adsb::Unpack12Seg *>(d->unpack_tab), (uint32_t)row, groups,
+                                           d->stream));
+    return 0;
+}
+
+// unpack, decode; and the stream idle behind it whatever the result (a batch without an offset launches no scan that would have
+// been waited for: the table and the scratch are the next call's to rewrite)
+long decode_batch_packed(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n,
+                         const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    std::vector<const void *> at;
+    d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
+    if (batch_unpack(d, what, n_captures, src, n, at))
+        return -1;
+    const long k = decode_batch(d, n_captures, at.data(), n, frames, first, stats);
+    WAIT_STREAM(d, d->stream, "the scan stream");
+    return k;
+}
+
 } // namespace
 
 extern "C" {
@@ -2844,6 +2958,50 @@ long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *
     for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the scan needs no event)
         WAIT_STREAM(d, cs, "a copy stream");
     return decode_batch(d, n_captures, at.data(), n, frames, first, stats);
+}
+
+long adsb_decode_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n,
+                                     const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_packed_refusal(d, "adsb_decode_batch_device_packed", n_captures, device_packed, n, true))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    return decode_batch_packed(d, "adsb_decode_batch_device_packed", n_captures, device_packed, n, frames, first, stats);
+}
+
+long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const void *const *packed, const size_t *n,
+                                   const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    const char *what = "adsb_decode_batch_host_packed";
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_packed_refusal(d, what, n_captures, packed, n, false))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    // only the packed bytes cross the link: every capture's at a 16-byte boundary of one landing buffer of the handle's
+    size_t bytes = 0;
+    for (size_t i = 0; i < n_captures; i++)
+        bytes += (ADSB_PACKED12_BYTES(n[i]) + 15) & ~(size_t)15;
+    if (batch_grow(d, what, "the packed captures (1.5 bytes per sample)", d->batch_land, d->batch_land_cap, bytes))
+        return -1;
+    std::vector<const void *> land(n_captures);
+    size_t off = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        land[i] = d->batch_land + off;
+        if (n[i])
+            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, packed[i], ADSB_PACKED12_BYTES(n[i]), hipMemcpyHostToDevice,
+                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
+        off += (ADSB_PACKED12_BYTES(n[i]) + 15) & ~(size_t)15;
+    }
+    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the unpack needs no event)
+        WAIT_STREAM(d, cs, "a copy stream");
+    return decode_batch_packed(d, what, n_captures, land.data(), n, frames, first, stats);
 }
 
 long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, adsb_batch_segment *segs, size_t seg_cap,

@@ -13,6 +13,8 @@
 //           piece: the copy of piece k+1 overlaps the scan of piece k, the chain is resolved while the kernel runs),
 //           adsb_shard_end; with statistics also the two small windows of tries the stitcher needs (adsb_scan_shard_host)
 //   stream  an ordinary stream of its own (configs[3]: N captures on N devices)
+//   batch   a contiguous range of a batch of independent captures (adsb_multi_decode_batch_*), in sub-batches of bounded
+//           size: one adsb_decode_batch_host[_packed] each on the worker's handle
 // and the calling thread stitches (adsb_stitch_shards[_stats]) and gathers the frames.  A seam that cannot be decided from
 // the head candidates (-3) sends the whole capture through ONE handle as an ordinary stream: slower, same bytes.
 //
@@ -40,6 +42,7 @@
 #include <vector>
 
 #include "../../include/adsbdec_amd_diag.h"
+#include "batch.hpp"
 #include "config_abi.hpp"
 
 namespace {
@@ -52,9 +55,14 @@ thread_local std::string g_multi_create_error;
 constexpr uint64_t kPieceSamples = 16ull << 20;   // 32 MiB per host-to-device piece
 constexpr uint64_t kMinShardOffsets = 1ull << 17; // smaller shards are not worth a device (and statistics want the stream's
                                                   // last ADSB_TAIL_OFFSETS offsets and a head window inside ONE shard)
+// adsb_multi_decode_batch_*: the sample data of one sub-batch, at most (a longer capture is one of its own).  It bounds what a
+// worker holds per sub-batch: that much device scratch of its handle (packed: 7/3 of it, landing buffer + unpacked samples) and,
+// for files, as much page-locked host memory.  256 MiB is 64 Mi offsets and more -- a launch of milliseconds, against which
+// the call's fixed cost (tens of microseconds) is nothing -- and eight workers page-lock 2 GiB, not the archive.
+constexpr uint64_t kBatchBytes = 256ull << 20;
 constexpr uint64_t kHeadTryReach = 1200;          // a frame that starts inside the head window ends at most this far behind it
 
-enum class JobKind { None, Shard, Gather, Stream, Quit };
+enum class JobKind { None, Shard, Gather, Stream, Batch, Quit };
 
 inline void cpu_relax()
 {
@@ -89,8 +97,22 @@ struct StreamResult {
     double ms = 0;
 };
 
+struct BatchPart { // a worker's range of a batch, decoded: its captures' frames one behind the other
+    std::vector<adsb_frame> frames;
+    std::vector<uint64_t> count; // frames per capture of the range
+    std::vector<adsb_stats> stats;
+};
+
 struct Job {
     JobKind kind = JobKind::None;
+    // Batch: the sub-batches [sub_lo, sub_hi) of the plan (sub-batch k = captures [subs[k], subs[k + 1])); the captures lie in
+    // host memory (batch_mem) or are files the worker reads itself (batch_paths); batch_n: every capture's samples
+    const void *const *batch_mem = nullptr;
+    const char *const *batch_paths = nullptr;
+    const size_t *batch_n = nullptr, *subs = nullptr;
+    size_t sub_lo = 0, sub_hi = 0;
+    bool packed = false;
+    BatchPart *part = nullptr;
     Source src;
     uint64_t total = 0;                       // samples of the whole stream
     uint64_t first = 0, n = 0, g_begin = 0, g_end = 0; // Shard: the plan's entry
@@ -119,7 +141,7 @@ struct Worker {
     std::condition_variable cv;
     uint64_t posted = 0, done = 0; // jobs posted / finished (under mu)
     std::atomic<uint64_t> posted_a{0}, done_a{0}; // the same, for the spinning side of each hand-over
-    std::atomic<uint64_t> beat{0}; // signs of life inside a job (one per piece pushed, window scanned, stream ended): what the
+    std::atomic<uint64_t> beat{0}; // signs of life inside a job (one per piece pushed or read, window scanned, stream or sub-batch ended): what the
                                    // caller's deadline watches (wait_done)
     bool orphaned = false;         // (under mu) the driver gave this worker up: it cleans up after itself and ends
     // where the worker's slice of the last host-resident capture lives (adsb_multi_worker_placement); asked of the kernel
@@ -144,6 +166,8 @@ struct Worker {
     uint16_t *ring[kRing] = {};
     int ring_slots = 0;                      // of them allocated (a short slice needs fewer)
     uint64_t ring_samples = 0, piece = kPieceSamples;
+    char *batch_buf = nullptr; // page-locked: the files of one sub-batch, each capture at a 16-byte boundary
+    size_t batch_buf_bytes = 0;
 
     int fail(const char *fmt, ...)
     {
@@ -174,6 +198,11 @@ inline double worker_limit_s(const adsb_config &cfg)
 // The one call of this file that a decoder backend may lack: the sanitizer harness links multi.cpp against a table look-up in
 // place of decoder.hip (tests/cpp/multi_tsan.cpp), which has no long streams.  In the library the symbol is always there.
 extern "C" int adsb_set_long_stream(adsb_decoder *d, int on) __attribute__((weak));
+// ... and the two batch calls, which that backend has not either: a batch job then fails with a message.
+extern "C" long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n,
+                                       const adsb_frame **frames, uint64_t *first, adsb_stats *stats) __attribute__((weak));
+extern "C" long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const void *const *packed, const size_t *n,
+                                              const adsb_frame **frames, uint64_t *first, adsb_stats *stats) __attribute__((weak));
 
 struct adsb_multi {
     adsb_config cfg{};
@@ -182,6 +211,9 @@ struct adsb_multi {
     std::string err;
     std::vector<adsb_frame> out, new_frames;
     std::vector<StreamResult> streams;
+    std::vector<BatchPart> batch_parts; // adsb_multi_decode_batch_*: a part per worker; the plan and the lengths the jobs point at
+    std::vector<size_t> batch_n, batch_range, batch_subs;
+    uint64_t batch_bytes = kBatchBytes;
     adsb_stats stats{};
     bool have_stats = false;
     adsb_multi_info info{};
@@ -532,6 +564,89 @@ void run_streams(Worker &w, const Job &j, uint64_t piece)
     }
 }
 
+// A worker's range of a batch: every sub-batch is one batch call on the worker's handle.  Captures that are files are read here,
+// by the worker, into a page-locked buffer of its own that holds one sub-batch.
+void run_batch(Worker &w, const Job &j)
+{
+    BatchPart &out = *j.part;
+    out = BatchPart{};
+    if (j.packed ? !adsb_decode_batch_host_packed : !adsb_decode_batch_host) {
+        w.fail("device %d (worker %d): this decoder backend has no %s", w.device, w.index,
+               j.packed ? "adsb_decode_batch_host_packed" : "adsb_decode_batch_host");
+        return;
+    }
+    auto bytes_of = [&](size_t i) { return j.packed ? (size_t)ADSB_PACKED12_BYTES(j.batch_n[i]) : 2 * j.batch_n[i]; };
+    std::vector<const void *> ptrs;
+    std::vector<uint64_t> first;
+    for (size_t k = j.sub_lo; k < j.sub_hi; k++) {
+        const size_t a = j.subs[k], b = j.subs[k + 1], nb = b - a;
+        ptrs.assign(nb, nullptr);
+        if (j.batch_mem) {
+            for (size_t i = a; i < b; i++)
+                ptrs[i - a] = j.batch_mem[i];
+        } else {
+            size_t bytes = 0;
+            for (size_t i = a; i < b; i++)
+                bytes += (bytes_of(i) + 15) & ~(size_t)15;
+            if (bytes > w.batch_buf_bytes) {
+                if (w.batch_buf)
+                    adsb_host_free(w.batch_buf);
+                w.batch_buf_bytes = 0;
+                w.batch_buf = static_cast<char *>(adsb_host_alloc_on(bytes, w.device));
+                if (!w.batch_buf)
+                    w.batch_buf = static_cast<char *>(adsb_host_alloc(bytes));
+                if (!w.batch_buf) {
+                    w.fail("device %d (worker %d): cannot page-lock a %zu-byte read buffer", w.device, w.index, bytes);
+                    return;
+                }
+                w.batch_buf_bytes = bytes;
+            }
+            size_t off = 0;
+            for (size_t i = a; i < b; i++) {
+                const size_t len = bytes_of(i);
+                if (len) {
+                    // read in 32 MiB pieces with a sign of life after each (and so after every file): a slow filesystem under a
+                    // sub-batch of many files, or under one capture of gigabytes, is not taken for a wedged device
+                    constexpr uint64_t kReadSamples = 16ull << 20;
+                    const int fd = open(j.batch_paths[i], O_RDONLY);
+                    bool ok = fd >= 0;
+                    for (uint64_t at = 0; ok && at < len / 2; at += kReadSamples) {
+                        ok = read_samples(fd, reinterpret_cast<uint16_t *>(w.batch_buf + off) + at, at, std::min<uint64_t>(kReadSamples, len / 2 - at));
+                        w.beat.fetch_add(1, std::memory_order_relaxed);
+                    }
+                    if (fd >= 0)
+                        close(fd);
+                    if (!ok) {
+                        w.fail("capture %zu: %s: cannot be opened, or the read of its %zu bytes failed or fell short (device %d, worker %d)", i,
+                               j.batch_paths[i], len, w.device, w.index);
+                        return;
+                    }
+                    ptrs[i - a] = w.batch_buf + off;
+                }
+                off += (len + 15) & ~(size_t)15;
+            }
+        }
+        first.assign(nb + 1, 0);
+        const size_t st_at = out.stats.size();
+        out.stats.resize(st_at + nb);
+        adsb_stats none{};
+        const adsb_frame *fp = nullptr;
+        const long nf = j.packed ? adsb_decode_batch_host_packed(w.dec, nb, ptrs.data(), j.batch_n + a, &fp, first.data(), nb ? &out.stats[st_at] : &none)
+                                 : adsb_decode_batch_host(w.dec, nb, reinterpret_cast<const uint16_t *const *>(ptrs.data()), j.batch_n + a, &fp,
+                                                          first.data(), nb ? &out.stats[st_at] : &none);
+        if (nf < 0) {
+            const char *e = adsb_last_error(w.dec);
+            w.fail("device %d (worker %d): captures %zu .. %zu: %s", w.device, w.index, a, b, e ? e : "");
+            return;
+        }
+        if (nf > 0)
+            out.frames.insert(out.frames.end(), fp, fp + nf);
+        for (size_t i = 0; i < nb; i++)
+            out.count.push_back(first[i + 1] - first[i]);
+        w.beat.fetch_add(1, std::memory_order_relaxed);
+    }
+}
+
 // The worker consumes its handle's hand-off stream: memory the device writes, polled and resolved while the kernel runs
 // (DESIGN.md section 4).  From a core on the other socket that work was measured 3 x slower (1.90 against 0.61 ms of host
 // time per 1 Gi samples: profiles/r4_ab_runs.txt) and the worker, not the kernel, bounded the step.  So every worker
@@ -604,6 +719,8 @@ void worker_main(Worker *w, uint64_t piece)
             for (uint16_t *b : w->ring)
                 if (b)
                     adsb_host_free(b);
+            if (w->batch_buf)
+                adsb_host_free(w->batch_buf);
             delete w;
             return;
         }
@@ -621,6 +738,8 @@ void worker_main(Worker *w, uint64_t piece)
                 run_gather(*w, j);
             else if (j.kind == JobKind::Stream)
                 run_streams(*w, j, piece);
+            else if (j.kind == JobKind::Batch)
+                run_batch(*w, j);
         } catch (const std::exception &e) { // (bad_alloc of a result vector: the job fails, the thread lives)
             w->fail("device %d (worker %d): %s", w->device, w->index, e.what());
         }
@@ -636,6 +755,8 @@ void worker_main(Worker *w, uint64_t piece)
     for (uint16_t *b : w->ring)
         if (b)
             adsb_host_free(b);
+    if (w->batch_buf)
+        adsb_host_free(w->batch_buf);
 }
 
 void post(Worker &w, const Job &j)
@@ -910,6 +1031,133 @@ int decode_streams(adsb_multi *m, const std::vector<Source> &src, const std::vec
     }
 }
 
+// The plan of a batch (adsb_multi_batch_plan): a contiguous range of captures per worker, balanced by the offsets to scan, and
+// every range cut into sub-batches.  Capture i goes to worker floor(P_i x W / T), P_i the offsets of the captures in front of it
+// and T of all: monotonic, so the ranges are contiguous, and a worker's captures start inside ITS W-th of the offsets, so it gets
+// at most T / W plus its last capture's.  Without any offset (T = 0: every capture below the reference's first deqframe call)
+// the captures themselves are dealt out evenly.  range: n_workers + 1 entries; subs: the starts of all sub-batches in order, and
+// n_captures behind the last (a sub-batch never spans two ranges; an empty range has none).
+void batch_plan(size_t n_captures, const size_t *n, int n_workers, uint64_t batch_bytes, bool packed, std::vector<size_t> &range,
+                std::vector<size_t> &subs)
+{
+    const size_t W = (size_t)std::max(1, n_workers);
+    range.assign(W + 1, n_captures);
+    subs.clear();
+    unsigned __int128 total = 0;
+    for (size_t i = 0; i < n_captures; i++)
+        total += adsb::batch_offsets(n[i]);
+    unsigned __int128 before = 0;
+    size_t next = 0; // the first worker whose range has not begun
+    for (size_t i = 0; i < n_captures; i++) {
+        const size_t w = total ? (size_t)std::min<unsigned __int128>(W - 1, before * W / total) : i * W / n_captures;
+        for (; next <= w; next++)
+            range[next] = i;
+        before += adsb::batch_offsets(n[i]);
+    }
+    range[0] = 0;
+    for (size_t w = 0; w < W; w++) {
+        uint64_t bytes = 0;
+        for (size_t i = range[w]; i < range[w + 1]; i++) {
+            const uint64_t len = packed ? (uint64_t)n[i] / 8 * 12 : 2 * (uint64_t)n[i];
+            if (i == range[w] || bytes + len > batch_bytes) {
+                subs.push_back(i);
+                bytes = 0;
+            }
+            bytes += len;
+        }
+    }
+    subs.push_back(n_captures);
+}
+
+// The calling thread's side of adsb_multi_decode_batch_*: plan, a job per worker that has captures, then the parts one behind
+// the other in capture order.
+long decode_batch_impl(adsb_multi *m, size_t n_captures, const void *const *mem, const char *const *paths, const size_t *n, bool packed,
+                       const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    if (m->broken)
+        return m->fail("this adsb_multi handle is unusable: a worker stopped answering earlier (destroy it)");
+    m->err.clear();
+    m->have_stats = false;
+    m->info = adsb_multi_info{};
+    m->out.clear();
+    m->streams.clear(); // (no worker is inside a job here: a stream call's results end with the next call on m, as the header says)
+    *frames = nullptr;
+    const auto t0 = clk::now();
+    const size_t W = m->w.size();
+    batch_plan(n_captures, n, (int)W, m->batch_bytes, packed, m->batch_range, m->batch_subs);
+    m->batch_parts.assign(W, BatchPart{});
+    std::vector<bool> used(W, false);
+    size_t sub = 0;
+    for (size_t w = 0; w < W; w++) {
+        const size_t lo = sub;
+        while (sub + 1 < m->batch_subs.size() && m->batch_subs[sub] < m->batch_range[w + 1])
+            sub++;
+        if (sub == lo)
+            continue;
+        Job j;
+        j.kind = JobKind::Batch;
+        j.batch_mem = mem;
+        j.batch_paths = paths;
+        j.batch_n = n;
+        j.subs = m->batch_subs.data();
+        j.sub_lo = lo;
+        j.sub_hi = sub;
+        j.packed = packed;
+        j.part = &m->batch_parts[w];
+        used[w] = true;
+        m->info.shards++;
+        post(*m->w[w], j);
+    }
+    for (size_t w = 0; w < W; w++)
+        if (used[w]) {
+            if (!wait_done(*m->w[w]))
+                return m->gave_up(*m->w[w]);
+            m->info.workers_ms = std::max(m->info.workers_ms, m->w[w]->ms);
+        }
+    for (size_t w = 0; w < W; w++)
+        if (used[w] && m->w[w]->rc)
+            return m->fail("adsb_multi batch of %zu captures: %s", n_captures, m->w[w]->err.c_str());
+    const auto t_serial = clk::now();
+    size_t total = 0;
+    for (const BatchPart &p : m->batch_parts)
+        total += p.frames.size();
+    m->out.reserve(total);
+    m->stats = adsb_stats{};
+    size_t i = 0;
+    for (size_t w = 0; w < W; w++) {
+        const BatchPart &p = m->batch_parts[w];
+        m->out.insert(m->out.end(), p.frames.begin(), p.frames.end());
+        for (size_t k = 0; k < p.count.size(); k++, i++) {
+            first[i + 1] = (i ? first[i] : 0) + p.count[k];
+            for (int q = 0; q < 3; q++) {
+                m->stats.try_[q] += p.stats[k].try_[q];
+                m->stats.ok[q] += p.stats[k].ok[q];
+            }
+            m->stats.fixed += p.stats[k].fixed;
+            if (stats)
+                stats[i] = p.stats[k];
+        }
+    }
+    first[0] = 0;
+    if (i != n_captures || (n_captures ? first[n_captures] : 0) != m->out.size())
+        return m->fail("internal: the parts of a batch hold %zu captures of %zu", i, n_captures);
+    m->have_stats = true;
+    m->info.serial_us = 1e3 * ms_since(t_serial);
+    m->info.total_ms = ms_since(t0);
+    *frames = m->out.empty() ? nullptr : m->out.data();
+    return (long)m->out.size();
+}
+
+long decode_batch(adsb_multi *m, size_t n_captures, const void *const *mem, const char *const *paths, const size_t *n, bool packed,
+                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    try {
+        return decode_batch_impl(m, n_captures, mem, paths, n, packed, frames, first, stats);
+    } catch (const std::exception &e) {
+        return m->fail("adsb_multi decode of a batch: %s (out of memory?)", e.what());
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -1018,10 +1266,13 @@ void adsb_multi_destroy(adsb_multi *m)
             struct GivenUp {
                 std::vector<StreamResult> streams;
                 std::vector<adsb_frame> out, new_frames;
+                std::vector<BatchPart> batch_parts;
+                std::vector<size_t> batch_n, batch_range, batch_subs;
             };
             static std::mutex mu;
             static auto *given_up = new std::vector<std::unique_ptr<GivenUp>>();
-            std::unique_ptr<GivenUp> g(new GivenUp{std::move(m->streams), std::move(m->out), std::move(m->new_frames)});
+            std::unique_ptr<GivenUp> g(new GivenUp{std::move(m->streams), std::move(m->out), std::move(m->new_frames), std::move(m->batch_parts), std::move(m->batch_n),
+                                                   std::move(m->batch_range), std::move(m->batch_subs)});
             std::lock_guard<std::mutex> lk(mu);
             given_up->push_back(std::move(g));
         }
@@ -1155,6 +1406,80 @@ int adsb_multi_decode_streams_file(adsb_multi *m, int n_streams, const char *con
         if (s.fd >= 0)
             close(s.fd);
     return rc;
+}
+
+long adsb_multi_batch_plan(size_t n_captures, const size_t *n, int n_workers, uint64_t batch_bytes, int packed, size_t *range,
+                           size_t *subs, size_t sub_cap)
+{
+    if ((n_captures && !n) || n_workers <= 0 || !range || (sub_cap && !subs))
+        return -1;
+    try {
+        std::vector<size_t> r, s;
+        batch_plan(n_captures, n, n_workers, batch_bytes ? batch_bytes : kBatchBytes, packed != 0, r, s);
+        std::memcpy(range, r.data(), r.size() * sizeof r[0]);
+        if (sub_cap)
+            std::memcpy(subs, s.data(), std::min(sub_cap, s.size()) * sizeof s[0]);
+        return (long)s.size() - 1;
+    } catch (const std::exception &) {
+        return -1;
+    }
+}
+
+int adsb_multi_set_batch_bytes(adsb_multi *m, uint64_t batch_bytes)
+{
+    if (!m)
+        return -1;
+    m->batch_bytes = batch_bytes ? batch_bytes : kBatchBytes;
+    return 0;
+}
+
+long adsb_multi_decode_batch_host(adsb_multi *m, size_t n_captures, const void *const *samples, const size_t *n, int packed,
+                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    if (!m || !frames || !first)
+        return -1;
+    m->have_stats = false; // (a refused or failed call leaves no result of an earlier one behind)
+    if (n_captures && (!samples || !n))
+        return m->fail("adsb_multi_decode_batch_host: NULL capture arrays");
+    for (size_t i = 0; i < n_captures; i++) { // (what a worker's handle would refuse, before any worker starts)
+        if (n[i] && !samples[i])
+            return m->fail("adsb_multi_decode_batch_host: capture %zu: NULL samples", i);
+        if ((uint64_t)n[i] >= (1ull << 32))
+            return m->fail("adsb_multi_decode_batch_host: capture %zu has %zu samples: 2^32 or more; a batch has no long-stream mode", i, n[i]);
+        if (packed && n[i] % 8 != 0)
+            return m->fail("adsb_multi_decode_batch_host: capture %zu: n = %zu is not a multiple of 8 (packed 12-bit input comes in whole 8-sample groups)", i, n[i]);
+    }
+    return decode_batch(m, n_captures, samples, nullptr, n, packed != 0, frames, first, stats);
+}
+
+long adsb_multi_decode_batch_files(adsb_multi *m, size_t n_captures, const char *const *paths, int packed, const adsb_frame **frames,
+                                   uint64_t *first, adsb_stats *stats)
+{
+    if (!m || !frames || !first)
+        return -1;
+    m->have_stats = false;
+    if (n_captures && !paths)
+        return m->fail("adsb_multi_decode_batch_files: NULL paths");
+    try {
+        m->batch_n.assign(n_captures, 0);
+    } catch (const std::exception &e) {
+        return m->fail("adsb_multi_decode_batch_files: %s", e.what());
+    }
+    for (size_t i = 0; i < n_captures; i++) {
+        struct stat sb;
+        const int fd = paths[i] ? open(paths[i], O_RDONLY) : -1; // (opened, not only looked at: a file that cannot be read fails here)
+        const bool ok = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
+        if (fd >= 0)
+            close(fd);
+        if (!ok)
+            return m->fail("capture %zu: %s: not a readable regular file", i, paths[i] ? paths[i] : "(null)");
+        // uint16: a trailing odd byte is dropped (air.c:239); packed: whole 12-byte groups, the rest of the file is ignored
+        const uint64_t len = packed ? (uint64_t)sb.st_size / 12 * 8 : (uint64_t)sb.st_size / 2;
+        if (len >= (1ull << 32))
+            return m->fail("capture %zu: %s has %llu samples: 2^32 or more; a batch has no long-stream mode", i, paths[i], (unsigned long long)len);
+        m->batch_n[i] = (size_t)len;
+    }
+    return decode_batch(m, n_captures, nullptr, paths, m->batch_n.data(), packed != 0, frames, first, stats);
 }
 
 long adsb_multi_stream_frames(const adsb_multi *m, int stream, const adsb_frame **frames)

@@ -38,9 +38,35 @@ ADSB_HD inline void unpack12_group_pairs(uint32_t w0, uint32_t w1, uint32_t w2, 
         out[k] = (uint32_t)s[2 * k] | ((uint32_t)s[2 * k + 1] << 16);
 }
 
+// unpack12_batch.hip: the captures of a batch in one launch.  A row per capture that has groups, in capture order: its groups
+// are numbered g_first .. (the next row's g_first - 1), read from src (4-byte aligned) and written from dst + 8 * dst16 on (dst16
+// counts 16-byte units; dst itself 16-byte aligned).  Row n_rows, behind the last one, holds the number of all groups.
+struct Unpack12Seg {
+    uint64_t src;
+    uint64_t dst16;
+    uint64_t g_first;
+};
+constexpr unsigned kUnpack12Chunk = 256; // consecutive groups a block looks its rows up for at once (= its lanes)
+
+// The last row of tab[lo .. hi] whose first group is <= g (tab[lo].g_first <= g is the caller's): the kernel's look-up, for a
+// chunk's first and last group by the block and between those two rows by a lane (tests/cpp/unpack12_rows.cpp runs it on the CPU).
+ADSB_HD inline uint32_t unpack12_row(const Unpack12Seg *tab, uint32_t lo, uint32_t hi, uint64_t g)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (tab[mid].g_first <= g)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
 #ifdef __HIPCC__
 // unpack12.hip: `groups` groups at src (4-byte aligned) -> 8 * groups samples at dst (16-byte aligned), enqueued on `stream`
 hipError_t launch_unpack12(uint16_t *dst, const void *src, size_t groups, hipStream_t stream);
+
+hipError_t launch_unpack12_batch(uint16_t *dst, const Unpack12Seg *tab_device, uint32_t n_rows, uint64_t groups, hipStream_t stream);
 #endif
 
 } // namespace adsb

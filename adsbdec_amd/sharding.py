@@ -12,6 +12,7 @@ gather are C++ behind the C-ABI; this file only marshals arguments so that tests
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -154,3 +155,39 @@ class MultiDecoder:
         if self._L.adsb_multi_stream_stats(self._h, s, C.byref(st)) != 0:
             raise self._err("adsb_multi_stream_stats")
         return capi._stats_to_dict(st, self._fix)
+
+    # -- a batch of independent captures over the workers: contiguous ranges, balanced by the offsets to scan
+    def set_batch_bytes(self, batch_bytes: int = 0):
+        """adsb_multi_set_batch_bytes: the sample data of one sub-batch, at most (0: the default)."""
+        if self._L.adsb_multi_set_batch_bytes(self._h, batch_bytes) != 0:
+            raise self._err("adsb_multi_set_batch_bytes")
+
+    def _batch_result(self, p, first, st, k, stats):
+        frames = [capi._frames_to_dicts(p[int(first[i]):int(first[i + 1])], int(first[i + 1] - first[i])) for i in range(k)]
+        return (frames, [capi._stats_to_dict(st[i], self._fix) for i in range(k)]) if stats else frames
+
+    def decode_batch_host(self, arrays, packed: bool = False, stats: bool = False):
+        """adsb_multi_decode_batch_host: uint16 arrays, or with packed=True uint8 arrays of whole 12-byte groups -> a list of
+        per-capture frame lists, as Decoder.decode_batch; stats=True: (that, the per-capture Try/Ok tables)."""
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        assert all(a.dtype == (np.uint8 if packed else np.uint16) and (not packed or a.size % 12 == 0) for a in arrays)
+        k = len(arrays)
+        ptrs = (C.c_void_p * max(1, k))(*[a.ctypes.data if a.size else None for a in arrays])
+        lens = (C.c_size_t * max(1, k))(*[a.size // 12 * 8 if packed else a.size for a in arrays])
+        first = (C.c_uint64 * (k + 1))()
+        st = (capi.Stats * max(1, k))()
+        p = C.POINTER(capi.Frame)()
+        if self._L.adsb_multi_decode_batch_host(self._h, k, ptrs, lens, int(packed), C.byref(p), first, st) < 0:
+            raise self._err("adsb_multi_decode_batch_host")
+        return self._batch_result(p, first, st, k, stats)
+
+    def decode_batch_files(self, paths, packed: bool = False, stats: bool = False):
+        """adsb_multi_decode_batch_files: every worker reads the files of its range itself."""
+        k = len(paths)
+        arr = (C.c_char_p * max(1, k))(*[os.fsencode(q) for q in paths])
+        first = (C.c_uint64 * (k + 1))()
+        st = (capi.Stats * max(1, k))()
+        p = C.POINTER(capi.Frame)()
+        if self._L.adsb_multi_decode_batch_files(self._h, k, arr, int(packed), C.byref(p), first, st) < 0:
+            raise self._err("adsb_multi_decode_batch_files")
+        return self._batch_result(p, first, st, k, stats)

@@ -269,6 +269,19 @@ long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes,
                         const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first,
                         adsb_stats *stats);
 
+/* ---- a batch over the devices of adsb_multi (adsb_multi_decode_batch_*; csrc/multi.cpp), without a device ------------------------
+ * The plan, a pure function: n_captures captures of n[i] samples over n_workers workers.  Worker w gets the captures
+ * [range[w], range[w + 1]) (range: n_workers + 1 entries; contiguous, in order, possibly empty), balanced by the offsets the
+ * reference scans in each (batch.hpp batch_offsets -- scan work, not bytes): no worker gets more than the mean plus its last
+ * capture's.  A range is cut into sub-batches of at most batch_bytes of sample data (2 B per sample; packed != 0: 1.5 B; 0: the
+ * default, 256 MiB); a capture longer than that is a sub-batch of its own.  Sub-batch k is the captures [subs[k], subs[k + 1]):
+ * fills at most sub_cap entries of subs (the starts, then n_captures) and returns the number of sub-batches, or -1.
+ * adsb_multi_set_batch_bytes: that bound for m's later batch calls (0: the default).  It bounds what a worker holds at a time: as
+ * much device scratch (packed: 7/3 of it) and, for files, as much page-locked host memory. */
+long adsb_multi_batch_plan(size_t n_captures, const size_t *n, int n_workers, uint64_t batch_bytes, int packed, size_t *range,
+                           size_t *subs, size_t sub_cap);
+int adsb_multi_set_batch_bytes(adsb_multi *m, uint64_t batch_bytes);
+
 /* ---- where a host-resident capture lives (csrc/numa.cpp) ---------------------------------------------------------------
  * Stands where the reference has `iqbuff = malloc(...)` (air.c:230).  A capture in host memory that eight devices pull at
  * once, each over its own link, should have every slice on the socket its device hangs off: a slice on the other socket
