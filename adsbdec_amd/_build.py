@@ -20,7 +20,8 @@ LIB = os.path.join(LIBDIR, "libadsbdec_amd.so")
 CLI = os.path.join(LIBDIR, "adsbdec_amd_cli")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "seam_kernel.hip", "decoder.hip", "unpack12.hip", "unpack12_batch.hip"]
+HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "seam_kernel.hip", "decoder.hip", "decoder_lifecycle.hip",
+               "decoder_batch.hip", "decoder_shard.hip", "unpack12.hip", "unpack12_batch.hip"]
 C_SOURCES = ["format.c"]
 # host-only C++ (no HIP): the multi-GPU driver over the C-ABI, and the part of the C-ABI that needs no device
 CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]
@@ -32,7 +33,7 @@ CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]
 # -amdgpu-atomic-optimizer-strategy=None: the compiler otherwise turns the survivor queue's per-lane LDS
 # atomicAdd(qcount, n) into a scalar loop over the active lanes (readlane / writelane prefix sum, one iteration per
 # lane) -- a fine trade for contended global atomics, a bad one for an LDS counter: kernel -3.9 % without it.
-# -Xarch_host -mavx2: the HOST side of decoder.hip (the hand-off stream's check, the resolver's two loops, the frame writer) is
+# -Xarch_host -mavx2: the HOST side of decoder.hip and the units beside it (the hand-off stream's check, the resolver's two loops, the frame writer) is
 # what a call of the benchmark capture ends on; with 256-bit moves it is 2 % shorter (adsb_decode_device 0.1544 -> 0.1510 ms,
 # profiles/r6_ab_runs.txt section 15; BMI / POPCNT alone: nothing).  Every x86-64 host an MI355X ships in has AVX2; one that has
 # not is refused by adsb_create with a message (host_abi.cpp adsb_host_cpu_refusal, built without the flag).

@@ -1,6 +1,6 @@
 // batch.hpp -- a batch of INDEPENDENT captures in as few scan launches as they fit (adsb_decode_batch_*): where every capture
 // lies in a launch, and how a launch's records become every capture's frames.  Host-only code, no HIP in it: it is part of
-// the library through decoder.hip and is tested without a device through adsb_batch_layout / adsb_batch_resolve
+// the library through decoder_batch.hip and is tested without a device through adsb_batch_layout / adsb_batch_resolve
 // (include/adsbdec_amd_diag.h).
 //
 // Layout: virtual stream coordinates.  The captures of a batch are laid end to end in ONE space of power-sample indices, capture
@@ -32,7 +32,7 @@
 
 namespace adsb {
 
-// the tile geometry of scan_kernel.h, which needs HIP to be read (decoder.hip asserts that the two agree)
+// the tile geometry of scan_kernel.h, which needs HIP to be read (decoder_batch.hip asserts that the two agree)
 constexpr uint64_t kBatchRun = 28;
 constexpr uint64_t batch_tile_offsets(int k) { return kBatchRun * (uint64_t)(252 * k - 44); }
 constexpr uint64_t kBatchMaxLaunchOffsets = (1ull << 30) - batch_tile_offsets(32);

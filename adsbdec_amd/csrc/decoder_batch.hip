@@ -1,0 +1,403 @@
+// decoder_batch.hip -- a batch of independent captures in as few launches as they fit (adsb_decode_batch_*, batch.hpp): the
+// launches borrow a scan slot of the handle's (decoder_state.hpp) and are waited for one by one.
+#include "decoder_state.hpp"
+#include "packed12.h"
+
+using namespace adsb;
+
+namespace {
+
+static_assert(adsb::kBatchRun == adsb::kRun && adsb::batch_tile_offsets(2) == (uint64_t)adsb::tile_offsets(2) &&
+                  adsb::batch_tile_offsets(adsb::kMaxPasses) == (uint64_t)adsb::tile_offsets(adsb::kMaxPasses) &&
+                  adsb::kBatchMaxLaunchOffsets == adsb::kMaxLaunchOffsets,
+              "batch.hpp restates the tile geometry of scan_kernel.h");
+
+int batch_passes_cap(uint64_t n_offsets, void *cus) { return adsb::choose_passes(n_offsets, *static_cast<int *>(cus)); }
+
+inline int batch_forced_passes(int passes) { return (passes >= 2 && passes <= adsb::kMaxPasses) ? passes : 0; }
+
+// The refusals of adsb_decode_batch_*, before anything of the handle changes.  A device pointer must be aligned to `align`
+// bytes; packed captures come in whole 8-sample groups.
+int batch_refusal(adsb_decoder *d, const char *what, size_t n_captures, const void *const *p, const size_t *n, bool device,
+                  unsigned align, bool packed)
+{
+    if (n_captures && (!p || !n))
+        return d->fail("%s: NULL capture arrays", what);
+    for (size_t i = 0; i < n_captures; i++) {
+        if ((uint64_t)n[i] >= (1ull << 32))
+            return d->fail("%s: capture %zu has %zu samples: 2^32 or more, where the reference's sample counter wraps (air.c:34); "
+                           "a batch has no long-stream mode", what, i, n[i]);
+        if (packed && n[i] % adsb::kPackedGroupSamples != 0)
+            return d->fail("%s: capture %zu: n = %zu is not a multiple of 8 (packed 12-bit input comes in whole 8-sample groups)", what,
+                           i, n[i]);
+        if (n[i] && !p[i])
+            return d->fail("%s: capture %zu: NULL samples", what, i);
+        if (device && (uintptr_t)p[i] % align != 0)
+            return d->fail("%s: capture %zu: device pointer %p is not %u-byte aligned", what, i, p[i], align);
+    }
+    return 0;
+}
+
+// One launch of the batch: table up, scan, wait, regrow and repeat on overflow (as slot_collect does), then the sorted
+// records and tries behind d->batch_cands / batch_tries, in virtual offsets.
+int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void *const *p, const size_t *n)
+{
+    using clk = std::chrono::steady_clock;
+    if (L.tiles == 0)
+        return 0;
+    const bool stats = d->cfg.collect_stats != 0;
+    ScanSlot &s = d->slots[d->slot_head];
+    uint64_t offsets = 0;
+    uint32_t n_tab = 0; // segments with tiles
+    for (uint32_t k = L.seg_first; k < L.seg_end; k++) {
+        offsets += d->batch_segs[k].o_end - d->batch_segs[k].o_begin;
+        n_tab += d->batch_segs[k].tiles != 0;
+    }
+    size_t cand_want, try_want;
+    scan_record_room(d, offsets, &cand_want, &try_want);
+    if (slot_reserve(d, s, std::max(s.cand_cap, cand_want), stats ? std::max(s.tries.cap, try_want) : s.tries.cap))
+        return -1;
+    // the table: the segments that have tiles, then a word per tile
+    const size_t tab_bytes = (size_t)n_tab * sizeof(adsb::BatchSeg) + (size_t)L.tiles * sizeof(uint32_t);
+    HIP_TRY(d, d->batch_tab.reserve(tab_bytes));
+    adsb::BatchSeg *seg_h = reinterpret_cast<adsb::BatchSeg *>(d->batch_tab.host.p);
+    uint32_t *tile_h = reinterpret_cast<uint32_t *>(seg_h + n_tab);
+    uint32_t row = 0;
+    for (uint32_t k = L.seg_first; k < L.seg_end; k++) {
+        const adsb_batch_segment &sg = d->batch_segs[k];
+        if (sg.tiles == 0)
+            continue;
+        // in the launch's coordinates the capture's pair 0 is pair `origin`: the buffer holds pairs from there on, and nothing
+        // below it exists (a stream's start: silence, air.c:33)
+        const int64_t origin = (int64_t)(sg.base - L.g_begin) - (int64_t)sg.o_begin;
+        adsb::BatchSeg &b = seg_h[row];
+        b.x = (uint64_t)(uintptr_t)p[sg.capture];
+        b.pbuf0 = origin;
+        b.p_lo = origin;
+        b.p_hi = origin + (int64_t)(n[sg.capture] / 2);
+        b.g_begin = sg.base - L.g_begin;
+        b.g_end = b.g_begin + (sg.o_end - sg.o_begin);
+        b.first_tile = sg.first_tile;
+        b.pad = 0;
+        for (uint32_t t = 0; t < sg.tiles; t++)
+            tile_h[sg.first_tile + t] = row;
+        row++;
+    }
+    hipStream_t ls = d->stream;
+    HIP_TRY(d, hipMemcpyAsync(d->batch_tab.dev, d->batch_tab.host, tab_bytes, hipMemcpyHostToDevice, ls));
+    const adsb::BatchSeg *seg_d = reinterpret_cast<const adsb::BatchSeg *>(d->batch_tab.dev.p);
+    const uint32_t *tile_d = reinterpret_cast<const uint32_t *>(seg_d + n_tab);
+
+    adsb::ScanArgs &a = s.args;
+    a = adsb::ScanArgs{};
+    a.g_begin = 0; // the launch's own coordinates: g_rel = virtual offset - L.g_begin
+    a.g_end = L.g_end - L.g_begin;
+    fill_scan_args(d, a);
+    a.passes = L.passes;
+    a.big_tiles = 0;
+    a.counters = s.d_counters; // zero: cleared at creation, and the report kernel behind every scan leaves them so
+    a.profile = d->cfg.profile ? 1 : 0;
+    s.streaming = false;
+    s.tries_on_device = s.try_regions = false;
+    s.epoch_base = 0;
+    s.ntiles = L.tiles;
+    if (slot_order_behind_count(d, s, ls)) // (as slot_launch: what may still use the slot's past)
+        return -1;
+    const auto t_wait = clk::now();
+    for (int attempt = 0;; attempt++) {
+        s.ev_cur ^= 1;
+        if (slot_settle_profile(d, s, s.ev_cur))
+            return -1;
+        s.ev_offsets[s.ev_cur] = offsets;
+        if (s.launch_stream && s.launch_stream != ls)
+            HIP_TRY(d, hipStreamWaitEvent(ls, s.ev_ready[s.ev_cur ^ 1], 0));
+        s.launch_stream = ls;
+        a.gen = ++d->launch_gen * 0x9E3779B9u + 0x7F4A7C15u;
+        a.cands = s.cands;
+        a.cand_cap = (uint32_t)std::min<size_t>(s.cand_cap, 0xFFFFFFFFu);
+        a.tries = s.tries;
+        a.try_cap = (uint32_t)std::min<size_t>(s.tries.cap, 0xFFFFFFFFu);
+        a.report = s.hc();
+        s.busy = true; // (a failure from here on leaves a launch in flight: adsb_reset waits for it)
+        HIP_TRY(d, adsb::launch_scan_batch(a, seg_d, tile_d, L.tiles, stats, ls));
+        HIP_TRY(d, hipEventRecord(s.ev_ready[s.ev_cur], ls));
+        WAIT_EVENT(d, s.ev_ready[s.ev_cur], "a batch scan launch");
+        s.busy = false;
+        s.prof_pending[s.ev_cur] = d->cfg.profile != 0;
+        if (slot_settle_profile(d, s, s.ev_cur))
+            return -1;
+        d->prof.launches++;
+        d->prof.offsets += offsets;
+        d->prof.last_offsets = offsets;
+        const size_t nc = s.hc()[0], nt = s.hc()[1];
+        if (nc <= s.cand_cap && nt <= s.tries.cap)
+            break;
+        // the counters keep counting past the capacities: one repeat with exact sizes suffices (slot_collect)
+        if (attempt >= 2)
+            return d->fail("record buffers overflowed repeatedly (%zu candidates, %zu tries)", nc, nt);
+        d->prof.relaunches++;
+        if (slot_reserve(d, s, std::max(s.cand_cap, nc + nc / 8 + 64), std::max(s.tries.cap, nt + nt / 8 + 64)))
+            return -1;
+    }
+    const auto t_host = clk::now();
+    d->prof.wait_ms += std::chrono::duration<double, std::milli>(t_host - t_wait).count();
+    const size_t nc = s.hc()[0], nt = s.hc()[1];
+    sort_order(d, s.cands, nc);
+    if (nt)
+        sort_tries(d, s.tries, nt);
+    d->prof.candidates += nc;
+    d->prof.tries += nt;
+    const size_t at = d->batch_cands.size();
+    d->batch_cands.resize(at + nc);
+    for (size_t i = 0; i < nc; i++) {
+        const uint32_t *r = s.cands + (size_t)d->order[i] * adsb::kCandWords;
+        adsb_candidate &c = d->batch_cands[at + i];
+        std::memset(&c, 0, sizeof c);
+        c.g = L.g_begin + r[0];
+        c.pw = r[1];
+        std::memcpy(c.frame, &r[2], 14);
+        c.len = (uint8_t)((r[5] >> 16) & 0xFF);
+        c.reserved = (uint8_t)((r[5] >> 24) & 1u);
+    }
+    const size_t tat = d->batch_tries.size();
+    d->batch_tries.resize(tat + nt);
+    for (size_t i = 0; i < nt; i++)
+        d->batch_tries[tat + i] = (((uint64_t)(s.tries[i] >> 2) + L.g_begin) << 2) | (s.tries[i] & 3u);
+    d->prof.host_ms += std::chrono::duration<double, std::milli>(clk::now() - t_host).count();
+    return 0;
+}
+
+long decode_batch(adsb_decoder *d, size_t n_captures, const void *const *p, const size_t *n, const adsb_frame **frames,
+                  uint64_t *first, adsb_stats *stats)
+{
+    using clk = std::chrono::steady_clock;
+    size_t bad = 0;
+    // A batch is whole streams, ended: like adsb_decode_device it leaves the handle finished, whether it succeeds or not,
+    // so a push without adsb_reset is refused and never meets batch_stats or the batch's frames.
+    d->finished = true;
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &d->n_cus, batch_forced_passes(d->dbg.passes), d->batch_segs,
+                            d->batch_launches, &bad))
+        return d->fail("internal: capture %zu is too long for a batch", bad); // (batch_refusal has looked)
+    d->batch_cands.clear();
+    d->batch_tries.clear();
+    for (const adsb_batch_launch &L : d->batch_launches)
+        if (batch_launch_collect(d, L, p, n))
+            return -1;
+    const auto t_host = clk::now();
+    d->batch_per.resize(n_captures); // every capture's table: the caller's `stats`, and the sum adsb_get_stats answers
+    const bool ok = adsb::batch_resolve(d->batch_res, n_captures, n, d->batch_segs.data(), d->batch_segs.size(), d->batch_cands.data(),
+                                        d->batch_cands.size(), d->batch_tries.data(), d->batch_tries.size(), d->batch_frames, first,
+                                        d->batch_per.data(), d->batch_cbuf, d->batch_tbuf);
+    if (!ok) {
+        d->batch_frames.clear();
+        return d->fail("internal: a record of a batch launch lies in no capture's offsets");
+    }
+    std::memset(&d->batch_stats, 0, sizeof d->batch_stats);
+    for (size_t i = 0; i < n_captures; i++) {
+        const adsb_stats &st = d->batch_per[i];
+        for (int k = 0; k < 3; k++) {
+            d->batch_stats.try_[k] += st.try_[k];
+            d->batch_stats.ok[k] += st.ok[k];
+        }
+        d->batch_stats.fixed += st.fixed;
+        if (stats)
+            stats[i] = st;
+    }
+    d->batch_stats_on = true;
+    d->prof.host_ms += std::chrono::duration<double, std::milli>(clk::now() - t_host).count();
+    *frames = d->batch_frames.empty() ? nullptr : d->batch_frames.data();
+    return (long)d->batch_frames.size();
+}
+
+
+// Room in a device scratch buffer of the handle's.
+template <class T> int batch_grow(adsb_decoder *d, const char *what, const char *of, adsb::Buf<T> &buf, size_t bytes)
+{
+    if (buf.reserve(bytes / sizeof(T)) == hipSuccess)
+        return 0;
+    (void)hipGetLastError();
+    return d->fail("%s: cannot allocate %zu bytes of device scratch for %s", what, bytes, of);
+}
+
+// The packed captures at src[] (device memory, 4-byte aligned) -> uint16 samples in batch_unpacked, capture i from at[i] on (a
+// 128-byte boundary), by ONE launch on the handle's stream: the batch scan that follows on that stream reads behind it.
+int batch_unpack(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n, std::vector<const void *> &at)
+{
+    at.assign(n_captures, nullptr);
+    size_t bytes = 0, rows = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+        rows += n[i] != 0;
+    }
+    if (batch_grow(d, what, "the unpacked samples (2 bytes per sample)", d->batch_unpacked, bytes))
+        return -1;
+    const size_t tab_bytes = (rows + 1) * sizeof(adsb::Unpack12Seg);
+    HIP_TRY(d, d->unpack_tab.reserve(tab_bytes));
+    adsb::Unpack12Seg *tab = reinterpret_cast<adsb::Unpack12Seg *>(d->unpack_tab.host.p);
+    size_t off = 0, row = 0;
+    uint64_t groups = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        at[i] = reinterpret_cast<const char *>(d->batch_unpacked.p) + off;
+        if (n[i]) {
+            tab[row].src = (uint64_t)(uintptr_t)src[i];
+            tab[row].dst16 = off / 16;
+            tab[row].g_first = groups;
+            row++;
+            groups += n[i] / adsb::kPackedGroupSamples;
+        }
+        off += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+    }
+    tab[row] = adsb::Unpack12Seg{0, 0, groups}; // behind the last row: where its groups end
+    if (groups == 0)
+        return 0;
+    HIP_TRY(d, hipMemcpyAsync(d->unpack_tab.dev, d->unpack_tab.host, tab_bytes, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(d, adsb::launch_unpack12_batch(d->batch_unpacked, reinterpret_cast<const adsb::Unpack12Seg *>(d->unpack_tab.dev.p), (uint32_t)row, groups,
+                                           d->stream));
+    return 0;
+}
+
+// unpack, decode; and the stream idle behind it whatever the result (a batch without an offset launches no scan that would have
+// been waited for: the table and the scratch are the next call's to rewrite)
+long decode_batch_packed(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n,
+                         const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    std::vector<const void *> at;
+    d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
+    if (batch_unpack(d, what, n_captures, src, n, at))
+        return -1;
+    const long k = decode_batch(d, n_captures, at.data(), n, frames, first, stats);
+    WAIT_STREAM(d, d->stream, "the scan stream");
+    return k;
+}
+
+} // namespace
+
+extern "C" {
+
+long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
+                              const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal(d, "adsb_decode_batch_device", n_captures, device_samples, n, true, 16, false))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    return decode_batch(d, n_captures, device_samples, n, frames, first, stats);
+}
+
+long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n,
+                            const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal(d, "adsb_decode_batch_host", n_captures, reinterpret_cast<const void *const *>(samples), n, false, 16, false))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    // every capture at a 128-byte boundary of one scratch array of the handle's
+    std::vector<size_t> off(n_captures);
+    size_t bytes = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        off[i] = bytes;
+        bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+    }
+    if (batch_grow(d, "adsb_decode_batch_host", "the captures", d->batch_in, bytes))
+        return -1;
+    std::vector<const void *> at(n_captures);
+    for (size_t i = 0; i < n_captures; i++) {
+        uint8_t *dst = d->batch_in + off[i];
+        at[i] = dst;
+        if (n[i])
+            HIP_TRY(d, hipMemcpyAsync(dst, samples[i], n[i] * sizeof(uint16_t), hipMemcpyHostToDevice,
+                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
+    }
+    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the scan needs no event)
+        WAIT_STREAM(d, cs, "a copy stream");
+    return decode_batch(d, n_captures, at.data(), n, frames, first, stats);
+}
+
+long adsb_decode_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n,
+                                     const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal(d, "adsb_decode_batch_device_packed", n_captures, device_packed, n, true, 4, true))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    return decode_batch_packed(d, "adsb_decode_batch_device_packed", n_captures, device_packed, n, frames, first, stats);
+}
+
+long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const void *const *packed, const size_t *n,
+                                   const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    const char *what = "adsb_decode_batch_host_packed";
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal(d, what, n_captures, packed, n, false, 4, true))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    // only the packed bytes cross the link: every capture's at a 16-byte boundary of one landing buffer of the handle's
+    size_t bytes = 0;
+    for (size_t i = 0; i < n_captures; i++)
+        bytes += (ADSB_PACKED12_BYTES(n[i]) + 15) & ~(size_t)15;
+    if (batch_grow(d, what, "the packed captures (1.5 bytes per sample)", d->batch_land, bytes))
+        return -1;
+    std::vector<const void *> land(n_captures);
+    size_t off = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        land[i] = d->batch_land + off;
+        if (n[i])
+            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, packed[i], ADSB_PACKED12_BYTES(n[i]), hipMemcpyHostToDevice,
+                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
+        off += (ADSB_PACKED12_BYTES(n[i]) + 15) & ~(size_t)15;
+    }
+    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the unpack needs no event)
+        WAIT_STREAM(d, cs, "a copy stream");
+    return decode_batch_packed(d, what, n_captures, land.data(), n, frames, first, stats);
+}
+
+long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, adsb_batch_segment *segs, size_t seg_cap,
+                       adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
+{
+    if ((n_captures && !n) || (seg_cap && !segs) || (launch_cap && !launches) || !n_launches)
+        return -1;
+    std::vector<adsb_batch_segment> sv;
+    std::vector<adsb_batch_launch> lv;
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), sv, lv, nullptr))
+        return -1;
+    if (!sv.empty() && seg_cap)
+        std::memcpy(segs, sv.data(), std::min(seg_cap, sv.size()) * sizeof sv[0]);
+    if (!lv.empty() && launch_cap)
+        std::memcpy(launches, lv.data(), std::min(launch_cap, lv.size()) * sizeof lv[0]);
+    *n_launches = lv.size();
+    return (long)sv.size();
+}
+
+long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes, const adsb_candidate *cands, size_t n_cands,
+                        const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first, adsb_stats *stats)
+{
+    if ((n_captures && !n) || (n_cands && !cands) || (n_tries && !tries) || (frame_cap && !frames) || !first)
+        return -1;
+    std::vector<adsb_batch_segment> sv;
+    std::vector<adsb_batch_launch> lv;
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), sv, lv, nullptr))
+        return -1;
+    adsb::Resolver r;
+    std::vector<adsb_frame> out;
+    std::vector<adsb_candidate> cbuf;
+    std::vector<uint64_t> tbuf;
+    if (!adsb::batch_resolve(r, n_captures, n, sv.data(), sv.size(), cands, n_cands, tries, n_tries, out, first, stats, cbuf, tbuf))
+        return -1;
+    if (!out.empty() && out.size() <= frame_cap)
+        std::memcpy(frames, out.data(), out.size() * sizeof out[0]);
+    return (long)out.size();
+}
+
+} // extern "C"

@@ -22,7 +22,7 @@ extern "C" {
 
 int adsb_abi_version(void) { return ADSB_ABI_VERSION; }
 
-// decoder.hip's host side is built with -mavx2 (adsbdec_amd/_build.py says why); this file is not.  adsb_create asks here,
+// The host side of the decoder*.hip units is built with -mavx2 (adsbdec_amd/_build.py says why); this file is not.  adsb_create asks here,
 // before anything else, whether the host can run it: a C string to show, or NULL.
 const char *adsb_host_cpu_refusal(void)
 {

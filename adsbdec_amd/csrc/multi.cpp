@@ -196,7 +196,7 @@ inline double worker_limit_s(const adsb_config &cfg)
 } // namespace
 
 // The one call of this file that a decoder backend may lack: the sanitizer harness links multi.cpp against a table look-up in
-// place of decoder.hip (tests/cpp/multi_tsan.cpp), which has no long streams.  In the library the symbol is always there.
+// place of the decoder*.hip units (tests/cpp/multi_tsan.cpp), which has no long streams.  In the library the symbol is always there.
 extern "C" int adsb_set_long_stream(adsb_decoder *d, int on) __attribute__((weak));
 // ... and the two batch calls, which that backend has not either: a batch job then fails with a message.
 extern "C" long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n,

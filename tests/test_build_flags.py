@@ -95,7 +95,7 @@ def test_atomic_optimizer_off_and_bitop3_gate(isa):
 
 
 def test_host_side_is_built_for_avx2_and_the_refusal_is_not():
-    """decoder.hip's host side (hand-off check, resolver, frame writer) is built with -mavx2 (adsbdec_amd/_build.py: 2 % of a
+    """The host side of the decoder*.hip units (hand-off check, resolver, frame writer) is built with -mavx2 (adsbdec_amd/_build.py: 2 % of a
     call); the function that tells adsb_create whether the host can run that, and the rest of host_abi.cpp, are not."""
     from adsbdec_amd import _build, capi
     lib = _build.build()
