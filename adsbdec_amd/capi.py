@@ -77,7 +77,8 @@ class DebugConfig(C.Structure):
     """adsb_debug_config (include/adsbdec_amd_diag.h): the test knobs behind adsb_config.debug."""
     _fields_ = [("struct_size", C.c_uint32), ("queue_cap", C.c_int32), ("cand_cap", C.c_int32), ("try_cap", C.c_int32),
                 ("clist_cap", C.c_int32), ("no_streaming", C.c_int32), ("frames_cap", C.c_int32), ("reader_min_tiles", C.c_int32),
-                ("shard_head", C.c_int32), ("passes", C.c_int32), ("big_tiles", C.c_int32), ("gang_min", C.c_int32)]
+                ("shard_head", C.c_int32), ("passes", C.c_int32), ("big_tiles", C.c_int32), ("gang_min", C.c_int32),
+                ("batch_launch_offsets", C.c_int32)]
 
 
 class ConfigV4(C.Structure):
@@ -141,6 +142,15 @@ SYMBOLS = {
     "adsb_batch_resolve": (C.c_long, [C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Candidate), C.c_size_t,
                                       C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(Frame), C.c_size_t, C.POINTER(C.c_uint64),
                                       C.POINTER(Stats)]),
+    "adsb_batch_layout_ex": (C.c_long, [C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_uint64, C.POINTER(BatchSegment),
+                                        C.c_size_t, C.POINTER(BatchLaunch), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "adsb_batch_resolve_ex": (C.c_long, [C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_uint64, C.POINTER(Candidate),
+                                         C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(Frame), C.c_size_t,
+                                         C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_batch_records": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(Candidate)), C.POINTER(C.c_size_t),
+                                     C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(BatchSegment)),
+                                     C.POINTER(C.c_size_t), C.POINTER(C.POINTER(BatchLaunch)), C.POINTER(C.c_size_t)]),
+    "adsb_batch_unpacked_copy": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "adsb_push_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_push_packed_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_push_device_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -291,7 +301,7 @@ def format_frame(fr: dict, outformat: int) -> bytes:
 
 
 DEBUG_KNOBS = ("queue_cap", "cand_cap", "try_cap", "clist_cap", "no_streaming", "frames_cap", "reader_min_tiles", "shard_head",
-               "passes", "big_tiles", "gang_min")
+               "passes", "big_tiles", "gang_min", "batch_launch_offsets")
 
 
 def make_config(df18: bool = False, device: int = -1, collect_stats: bool = False,
@@ -514,6 +524,30 @@ class Decoder:
             self._check(-1, "adsb_decode_batch_host_packed")
         return self._batch_result(self._out, first, st, k, stats)
 
+    def batch_records(self):
+        """adsb_batch_records: what the last decode_batch* call collected -> (candidates as tuples (virtual g, pw, frame bytes,
+        reserved), tries: uint64 (virtual g << 2 | code), segments, launches: lists of dicts as batch_layout gives them)."""
+        cands, tries = C.POINTER(Candidate)(), C.POINTER(C.c_uint64)()
+        segs, launches = C.POINTER(BatchSegment)(), C.POINTER(BatchLaunch)()
+        nc, nt, ns, nl = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self._L.adsb_batch_records(self._h, C.byref(cands), C.byref(nc), C.byref(tries), C.byref(nt), C.byref(segs),
+                                               C.byref(ns), C.byref(launches), C.byref(nl)), "adsb_batch_records")
+        if nc.value:
+            raw = np.ctypeslib.as_array(C.cast(cands, C.POINTER(C.c_uint8)), shape=(nc.value, C.sizeof(Candidate))).copy()
+            g, pw = raw[:, 0:8].copy().view(np.uint64)[:, 0], raw[:, 8:12].copy().view(np.uint32)[:, 0]
+            out = [(int(g[i]), int(pw[i]), raw[i, 13:13 + raw[i, 12]].tobytes(), int(raw[i, 27])) for i in range(nc.value)]
+        else:
+            out = []
+        t = np.ctypeslib.as_array(tries, shape=(nt.value,)).copy() if nt.value else np.empty(0, np.uint64)
+        return out, t, [_struct_dict(segs[i]) for i in range(ns.value)], [_struct_dict(launches[i]) for i in range(nl.value)]
+
+    def batch_unpacked(self, capture: int, n: int):
+        """adsb_batch_unpacked_copy: the first n unpacked samples of capture `capture` of the last decode_batch*_packed call, as
+        the batch unpack kernel left them (n may reach into the pad behind the capture, up to its 128-byte-rounded slot)."""
+        out = np.empty(n, dtype=np.uint16)
+        self._check(self._L.adsb_batch_unpacked_copy(self._h, capture, out.ctypes.data, n), "adsb_batch_unpacked_copy")
+        return out
+
     def decode_packed(self, buf: np.ndarray, chunk: int | None = None, mode: str = "sync"):
         """decode() for packed bytes: chunk counts samples (a multiple of 8); the same three modes."""
         assert buf.dtype == np.uint8 and buf.size % 12 == 0
@@ -734,20 +768,24 @@ class Resolver:
         return _stats_to_dict(st)
 
 
-def batch_layout(ns, cus: int = 0, passes: int = 0):
-    """adsb_batch_layout -> (segments, launches) as lists of dicts, or None when the batch is refused (a capture of 2^32 samples)."""
+def _struct_dict(o):
+    return {f: int(getattr(o, f)) for f, _ in o._fields_ if f != "pad"}
+
+
+def batch_layout(ns, cus: int = 0, passes: int = 0, launch_offsets: int = 0):
+    """adsb_batch_layout_ex -> (segments, launches) as lists of dicts, or None when the batch is refused (a capture of 2^32 samples).
+    launch_offsets: adsb_debug_config.batch_launch_offsets (0: the default limit of a launch)."""
     L = load()
     k = len(ns)
     n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
     nl = C.c_size_t(0)
-    ns_ = L.adsb_batch_layout(k, n, cus, passes, None, 0, None, 0, C.byref(nl))
+    ns_ = L.adsb_batch_layout_ex(k, n, cus, passes, launch_offsets, None, 0, None, 0, C.byref(nl))
     if ns_ < 0:
         return None
     segs, launches = (BatchSegment * max(1, ns_))(), (BatchLaunch * max(1, nl.value))()
-    if L.adsb_batch_layout(k, n, cus, passes, segs, ns_, launches, nl.value, C.byref(nl)) != ns_:
+    if L.adsb_batch_layout_ex(k, n, cus, passes, launch_offsets, segs, ns_, launches, nl.value, C.byref(nl)) != ns_:
         raise AdsbError("adsb_batch_layout failed")
-    as_dict = lambda o: {f: int(getattr(o, f)) for f, _ in o._fields_ if f != "pad"}
-    return [as_dict(segs[i]) for i in range(ns_)], [as_dict(launches[i]) for i in range(nl.value)]
+    return [_struct_dict(segs[i]) for i in range(ns_)], [_struct_dict(launches[i]) for i in range(nl.value)]
 
 
 def multi_batch_plan(ns, n_workers: int, batch_bytes: int = 0, packed: bool = False):
@@ -764,8 +802,8 @@ def multi_batch_plan(ns, n_workers: int, batch_bytes: int = 0, packed: bool = Fa
     return [int(v) for v in rng], [int(subs[i]) for i in range(nsub + 1)]
 
 
-def batch_resolve(ns, cands, tries, cus: int = 0, passes: int = 0):
-    """adsb_batch_resolve: cands = list of (virtual g, pw, frame bytes) ascending, tries = uint64 (g << 2 | code) ascending ->
+def batch_resolve(ns, cands, tries, cus: int = 0, passes: int = 0, launch_offsets: int = 0):
+    """adsb_batch_resolve_ex (launch_offsets as batch_layout): cands = list of (virtual g, pw, frame bytes) ascending, tries = uint64 (g << 2 | code) ascending ->
     (per-capture frame lists, per-capture Try/Ok tables)."""
     L = load()
     k = len(ns)
@@ -779,7 +817,7 @@ def batch_resolve(ns, cands, tries, cus: int = 0, passes: int = 0):
     first, st = (C.c_uint64 * (k + 1))(), (Stats * max(1, k))()
     cap = len(cands) + 1
     out = (Frame * cap)()
-    total = L.adsb_batch_resolve(k, n, cus, passes, arr, len(cands), t.ctypes.data_as(C.POINTER(C.c_uint64)), t.size, out, cap, first, st)
+    total = L.adsb_batch_resolve_ex(k, n, cus, passes, launch_offsets, arr, len(cands), t.ctypes.data_as(C.POINTER(C.c_uint64)), t.size, out, cap, first, st)
     if total < 0 or total > cap:
         raise AdsbError("adsb_batch_resolve failed")
     return ([_frames_to_dicts(out[int(first[i]):int(first[i + 1])], int(first[i + 1] - first[i])) for i in range(k)],

@@ -14,7 +14,9 @@
 // Tiles never straddle two captures: capture i's offsets take ceil(offsets / tile) tiles of their own, the last one partly
 // filled -- the price of ONE K (passes per tile) per launch, which choose_batch_passes() keeps small.
 // A capture whose offsets do not fit what is left of a launch (kBatchMaxLaunchOffsets) starts the next one; one that does not
-// fit a launch at all is cut into SEGMENTS of whole tiles, a launch each.
+// fit a launch at all is cut into SEGMENTS of whole tiles, a launch each.  Both decisions read ONE limit, which a test may lower
+// (adsb_debug_config.batch_launch_offsets, batch_launch_limit) so that cut captures and roll-overs go through the kernel at
+// sizes a test can afford.
 //
 // Resolve: a launch is collected after completion (sorted loose list + try list, as the stateless shard scan's), split at the
 // virtual bases, and every capture goes through adsb::Resolver on its own -- reset, its candidates and tries rebased to offsets
@@ -71,12 +73,19 @@ inline int choose_batch_passes(const adsb_batch_segment *segs, size_t a, size_t 
     return best;
 }
 
+// The most virtual offsets a launch may cover: `wanted` (adsb_debug_config.batch_launch_offsets) where it holds a tile of a split
+// launch at least and stays within what g_rel can say, else the default.
+inline uint64_t batch_launch_limit(uint64_t wanted, int split_k)
+{
+    return (wanted >= batch_tile_offsets(split_k) && wanted <= kBatchMaxLaunchOffsets) ? wanted : kBatchMaxLaunchOffsets;
+}
+
 // Lay n_captures captures of n[i] samples out.  passes_cap(offsets, ctx): the K an ordinary launch of so many offsets takes;
-// forced_passes > 0: that K for every launch (adsb_debug_config.passes).  Every capture has at least one segment (an empty one
-// when it has no offsets), in capture order; a launch's segments are consecutive.  false: a capture has 2^32 samples or more
-// (*bad = its index) -- a batch has no long-stream mode.
+// forced_passes > 0: that K for every launch (adsb_debug_config.passes); launch_offsets: batch_launch_limit's `wanted`.  Every
+// capture has at least one segment (an empty one when it has no offsets), in capture order; a launch's segments are consecutive.
+// false: a capture has 2^32 samples or more (*bad = its index) -- a batch has no long-stream mode.
 inline bool batch_layout(size_t n_captures, const size_t *n, int (*passes_cap)(uint64_t, void *), void *ctx, int forced_passes,
-                         std::vector<adsb_batch_segment> &segs, std::vector<adsb_batch_launch> &launches, size_t *bad)
+                         uint64_t launch_offsets, std::vector<adsb_batch_segment> &segs, std::vector<adsb_batch_launch> &launches, size_t *bad)
 {
     segs.clear();
     launches.clear();
@@ -115,7 +124,8 @@ inline bool batch_layout(size_t n_captures, const size_t *n, int (*passes_cap)(u
         cur.g_begin = V;
     };
     const int split_k = forced_passes > 0 ? forced_passes : kBatchSplitPasses;
-    const uint64_t split_piece = kBatchMaxLaunchOffsets / batch_tile_offsets(split_k) * batch_tile_offsets(split_k);
+    const uint64_t limit = batch_launch_limit(launch_offsets, split_k);
+    const uint64_t split_piece = limit / batch_tile_offsets(split_k) * batch_tile_offsets(split_k);
     for (size_t i = 0; i < n_captures; i++) {
         const uint64_t n_off = batch_offsets(n[i]), power = batch_power(n[i]);
         uint64_t o = 0;
@@ -123,13 +133,13 @@ inline bool batch_layout(size_t n_captures, const size_t *n, int (*passes_cap)(u
             const uint64_t rest = n_off - o;
             if (segs.size() == cur.seg_first)
                 cur.g_begin = V; // a launch's g_rel counts from its first segment
-            else if (rest > kBatchMaxLaunchOffsets - std::min(kBatchMaxLaunchOffsets, V - cur.g_begin))
+            else if (rest > limit - std::min(limit, V - cur.g_begin))
                 close(0); // does not fit what is left of this launch: the next one (which starts at V)
             adsb_batch_segment sg{};
             sg.capture = i;
             sg.o_begin = o;
             sg.base = V;
-            const bool piece = rest > kBatchMaxLaunchOffsets; // too long for any launch: whole tiles of it, a launch of their own
+            const bool piece = rest > limit; // too long for any launch: whole tiles of it, a launch of their own
             sg.o_end = piece ? o + split_piece : n_off;
             segs.push_back(sg);
             // what the segment's offsets read: up to a window beyond the last one; a capture's last segment, up to its last power sample

@@ -16,6 +16,8 @@ int batch_passes_cap(uint64_t n_offsets, void *cus) { return adsb::choose_passes
 
 inline int batch_forced_passes(int passes) { return (passes >= 2 && passes <= adsb::kMaxPasses) ? passes : 0; }
 
+inline uint64_t batch_wanted_limit(int32_t knob) { return knob > 0 ? (uint64_t)knob : 0; } // (batch_launch_limit judges it)
+
 // The refusals of adsb_decode_batch_*, before anything of the handle changes.  A device pointer must be aligned to `align`
 // bytes; packed captures come in whole 8-sample groups.
 int batch_refusal(adsb_decoder *d, const char *what, size_t n_captures, const void *const *p, const size_t *n, bool device,
@@ -175,8 +177,8 @@ long decode_batch(adsb_decoder *d, size_t n_captures, const void *const *p, cons
     // A batch is whole streams, ended: like adsb_decode_device it leaves the handle finished, whether it succeeds or not,
     // so a push without adsb_reset is refused and never meets batch_stats or the batch's frames.
     d->finished = true;
-    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &d->n_cus, batch_forced_passes(d->dbg.passes), d->batch_segs,
-                            d->batch_launches, &bad))
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &d->n_cus, batch_forced_passes(d->dbg.passes),
+                            batch_wanted_limit(d->dbg.batch_launch_offsets), d->batch_segs, d->batch_launches, &bad))
         return d->fail("internal: capture %zu is too long for a batch", bad); // (batch_refusal has looked)
     d->batch_cands.clear();
     d->batch_tries.clear();
@@ -224,6 +226,7 @@ template <class T> int batch_grow(adsb_decoder *d, const char *what, const char 
 int batch_unpack(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n, std::vector<const void *> &at)
 {
     at.assign(n_captures, nullptr);
+    d->batch_unpacked_at.clear(); // (adsb_batch_unpacked_copy: what this call has)
     size_t bytes = 0, rows = 0;
     for (size_t i = 0; i < n_captures; i++) {
         bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
@@ -238,6 +241,7 @@ int batch_unpack(adsb_decoder *d, const char *what, size_t n_captures, const voi
     uint64_t groups = 0;
     for (size_t i = 0; i < n_captures; i++) {
         at[i] = reinterpret_cast<const char *>(d->batch_unpacked.p) + off;
+        d->batch_unpacked_at.push_back(off / sizeof(uint16_t));
         if (n[i]) {
             tab[row].src = (uint64_t)(uintptr_t)src[i];
             tab[row].dst16 = off / 16;
@@ -247,6 +251,7 @@ int batch_unpack(adsb_decoder *d, const char *what, size_t n_captures, const voi
         }
         off += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
     }
+    d->batch_unpacked_at.push_back(off / sizeof(uint16_t));
     tab[row] = adsb::Unpack12Seg{0, 0, groups}; // behind the last row: where its groups end
     if (groups == 0)
         return 0;
@@ -363,14 +368,14 @@ long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const voi
     return decode_batch_packed(d, what, n_captures, land.data(), n, frames, first, stats);
 }
 
-long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, adsb_batch_segment *segs, size_t seg_cap,
-                       adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
+long adsb_batch_layout_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, adsb_batch_segment *segs,
+                          size_t seg_cap, adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
 {
     if ((n_captures && !n) || (seg_cap && !segs) || (launch_cap && !launches) || !n_launches)
         return -1;
     std::vector<adsb_batch_segment> sv;
     std::vector<adsb_batch_launch> lv;
-    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), sv, lv, nullptr))
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), launch_offsets, sv, lv, nullptr))
         return -1;
     if (!sv.empty() && seg_cap)
         std::memcpy(segs, sv.data(), std::min(seg_cap, sv.size()) * sizeof sv[0]);
@@ -380,14 +385,21 @@ long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, 
     return (long)sv.size();
 }
 
-long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes, const adsb_candidate *cands, size_t n_cands,
-                        const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first, adsb_stats *stats)
+long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, adsb_batch_segment *segs, size_t seg_cap,
+                       adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
+{
+    return adsb_batch_layout_ex(n_captures, n, cus, passes, 0, segs, seg_cap, launches, launch_cap, n_launches);
+}
+
+long adsb_batch_resolve_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, const adsb_candidate *cands,
+                           size_t n_cands, const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first,
+                           adsb_stats *stats)
 {
     if ((n_captures && !n) || (n_cands && !cands) || (n_tries && !tries) || (frame_cap && !frames) || !first)
         return -1;
     std::vector<adsb_batch_segment> sv;
     std::vector<adsb_batch_launch> lv;
-    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), sv, lv, nullptr))
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), launch_offsets, sv, lv, nullptr))
         return -1;
     adsb::Resolver r;
     std::vector<adsb_frame> out;
@@ -398,6 +410,56 @@ long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes,
     if (!out.empty() && out.size() <= frame_cap)
         std::memcpy(frames, out.data(), out.size() * sizeof out[0]);
     return (long)out.size();
+}
+
+long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes, const adsb_candidate *cands, size_t n_cands,
+                        const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first, adsb_stats *stats)
+{
+    return adsb_batch_resolve_ex(n_captures, n, cus, passes, 0, cands, n_cands, tries, n_tries, frames, frame_cap, first, stats);
+}
+
+int adsb_batch_records(adsb_decoder *d, const adsb_candidate **cands, size_t *n_cands, const uint64_t **tries, size_t *n_tries,
+                       const adsb_batch_segment **segs, size_t *n_segs, const adsb_batch_launch **launches, size_t *n_launches)
+{
+    if (!d)
+        return -1;
+    if (cands)
+        *cands = d->batch_cands.data();
+    if (n_cands)
+        *n_cands = d->batch_cands.size();
+    if (tries)
+        *tries = d->batch_tries.data();
+    if (n_tries)
+        *n_tries = d->batch_tries.size();
+    if (segs)
+        *segs = d->batch_segs.data();
+    if (n_segs)
+        *n_segs = d->batch_segs.size();
+    if (launches)
+        *launches = d->batch_launches.data();
+    if (n_launches)
+        *n_launches = d->batch_launches.size();
+    return 0;
+}
+
+int adsb_batch_unpacked_copy(adsb_decoder *d, size_t capture, uint16_t *dst_u16, size_t n)
+{
+    if (!d)
+        return -1;
+    // batch_unpacked_at: where every capture of the last packed batch starts in the scratch (samples), and where the last one's slot ends
+    if (capture + 1 >= d->batch_unpacked_at.size())
+        return d->fail("adsb_batch_unpacked_copy: the last packed batch call had no capture %zu", capture);
+    const size_t at = d->batch_unpacked_at[capture], slot = d->batch_unpacked_at[capture + 1] - at;
+    if (n > slot)
+        return d->fail("adsb_batch_unpacked_copy: capture %zu has a slot of %zu samples, %zu were asked for", capture, slot, n);
+    if (n == 0)
+        return 0;
+    if (!dst_u16)
+        return d->fail("adsb_batch_unpacked_copy: NULL destination");
+    HIP_TRY(d, hipSetDevice(d->device));
+    HIP_TRY(d, hipMemcpyAsync(dst_u16, d->batch_unpacked.p + at, n * sizeof(uint16_t), hipMemcpyDeviceToHost, d->stream));
+    WAIT_STREAM(d, d->stream, "the copy of a batch's unpacked samples");
+    return 0;
 }
 
 } // extern "C"

@@ -30,6 +30,10 @@ typedef struct adsb_debug_config {
     int32_t big_tiles;        /* tiles of a launch that take all its passes; the rest four (scan_kernel.h tile_passes) */
     int32_t gang_min;         /* host_threads >= 3: batches of at least this many records go through the gang
                                  (default: 2048 records decided ahead, 1024 frames written)                           */
+    int32_t batch_launch_offsets; /* adsb_decode_batch_*: the most virtual offsets a launch may cover, in place of 2^30 - 28 x 8020
+                                 (csrc/batch.hpp): captures are cut into segments and roll over into later launches at test sizes.
+                                 Honoured from one tile of a split launch (28 x 1720 offsets; `passes` forced: a tile of those) up
+                                 to the default; anything else is the default */
 } adsb_debug_config;
 
 /* A CRC-valid candidate before greedy resolution (what one GPU emits for the
@@ -260,6 +264,10 @@ typedef struct adsb_batch_launch {
  * has one or more, in capture order) and *n_launches, or -1 (a capture of 2^32 samples or more: a batch has no long-stream mode). */
 long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, adsb_batch_segment *segs, size_t seg_cap,
                        adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches);
+/* The same under adsb_debug_config.batch_launch_offsets = launch_offsets (0, or a value that knob does not honour: the default):
+ * what a handle created with that knob lays out. */
+long adsb_batch_layout_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, adsb_batch_segment *segs,
+                          size_t seg_cap, adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches);
 /* What adsb_decode_batch_* does with the records of its launches: cands (ascending g) and tries (ascending (g << 2) | code) of the
  * whole batch in the VIRTUAL offsets of that layout -> per capture the frames the reference decodes from it alone (g and ts from
  * 0; demod.c:89,99,125-141, air.c:94-99 through adsb_resolver's code), capture i's at frames[first[i] .. first[i+1]) (first:
@@ -268,6 +276,24 @@ long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, 
 long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes, const adsb_candidate *cands, size_t n_cands,
                         const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first,
                         adsb_stats *stats);
+/* The same for records in the virtual offsets of adsb_batch_layout_ex(..., launch_offsets, ...). */
+long adsb_batch_resolve_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, const adsb_candidate *cands,
+                           size_t n_cands, const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first,
+                           adsb_stats *stats);
+/* What the last adsb_decode_batch_* call on d collected, before the per-capture resolve, as read-only views: the sorted candidates
+ * of all its launches and their try words ((g << 2) | code; none without collect_stats), both in VIRTUAL offsets, and the layout
+ * it used (segments, launches: a record of capture i at offset o lies at segs[k].base + o - segs[k].o_begin of the segment k of
+ * that capture with o_begin <= o < o_end).  This is the kernels' own output offset by offset -- the frames of a call show only what
+ * the greedy chain visits.  Valid until the next call on the handle; filled also when the call failed in the resolve (a record
+ * outside every segment).  Any of the pointers may be NULL.  0, or -1 (no handle). */
+int adsb_batch_records(adsb_decoder *d, const adsb_candidate **cands, size_t *n_cands, const uint64_t **tries, size_t *n_tries,
+                       const adsb_batch_segment **segs, size_t *n_segs, const adsb_batch_launch **launches, size_t *n_launches);
+/* The first n unpacked samples of capture `capture` of the last adsb_decode_batch_*_packed call on d, as the batch unpack kernel
+ * (csrc/unpack12_batch.hip) left them in the handle's scratch -> dst_u16 (host memory), by a copy on the handle's stream that is
+ * waited for.  n may reach past the capture's samples to the end of its slot (every capture starts at a 128-byte boundary of the
+ * scratch: up to 63 samples of pad, which no kernel writes).  -1 (with a message) for a capture index that call did not have or
+ * an n beyond that capture's slot. */
+int adsb_batch_unpacked_copy(adsb_decoder *d, size_t capture, uint16_t *dst_u16, size_t n);
 
 /* ---- a batch over the devices of adsb_multi (adsb_multi_decode_batch_*; csrc/multi.cpp), without a device ------------------------
  * The plan, a pure function: n_captures captures of n[i] samples over n_workers workers.  Worker w gets the captures

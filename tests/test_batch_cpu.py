@@ -34,17 +34,32 @@ def test_entry_points_are_declared_exported_and_bound(capi):
     exported = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
     L = capi.load()
     for name, header in (("adsb_decode_batch_device", main), ("adsb_decode_batch_host", main),
-                         ("adsb_batch_layout", diag), ("adsb_batch_resolve", diag)):
+                         ("adsb_batch_layout", diag), ("adsb_batch_resolve", diag), ("adsb_batch_layout_ex", diag),
+                         ("adsb_batch_resolve_ex", diag), ("adsb_batch_records", diag), ("adsb_batch_unpacked_copy", diag)):
         assert re.search(r"\b%s\s*\(" % name, header), name
         assert re.search(r"\b%s\b" % name, exported) and name in capi.SYMBOLS and hasattr(L, name), name
     assert hasattr(capi.Decoder, "decode_batch") and hasattr(capi.Decoder, "decode_batch_device")
+    assert hasattr(capi.Decoder, "batch_records") and hasattr(capi.Decoder, "batch_unpacked")
     assert L.adsb_abi_version() == 5
+    # the hooks are the diag header's, and the knob that cuts captures at test sizes is the last member of the knob struct
+    assert "adsb_batch_records" not in main and "adsb_batch_unpacked_copy" not in main and "batch_launch_offsets" not in main
+    assert re.search(r"int32_t\s+batch_launch_offsets\s*;\s*}\s*adsb_debug_config\s*;", diag)
+    assert capi.DebugConfig._fields_[-1][0] == "batch_launch_offsets" == capi.DEBUG_KNOBS[-1]
+    assert [f for f, _ in capi.DebugConfig._fields_[1:]] == list(capi.DEBUG_KNOBS)
+    assert L.adsb_batch_records(None, None, None, None, None, None, None, None, None) == -1
+    assert L.adsb_batch_unpacked_copy(None, 0, None, 0) == -1
     # NULL handle: -1, nothing touched
     assert L.adsb_decode_batch_device(None, 0, None, None, None, None, None) == -1
     assert L.adsb_decode_batch_host(None, 0, None, None, None, None, None) == -1
 
 
-def check_layout(ns, segs, launches):
+def launch_limit(launch_offsets, passes):
+    """batch.hpp batch_launch_limit: the knob is honoured from one tile of a split launch (K = 7, or the forced K) up to the
+    default."""
+    return launch_offsets if RUN * owned_runs(passes or 7) <= launch_offsets <= MAX_LAUNCH else MAX_LAUNCH
+
+
+def check_layout(ns, segs, launches, limit=MAX_LAUNCH):
     assert [s["capture"] for s in segs] == sorted(s["capture"] for s in segs)
     assert sorted(set(s["capture"] for s in segs)) == list(range(len(ns)))          # every capture has a segment
     by_capture = {}
@@ -73,7 +88,7 @@ def check_layout(ns, segs, launches):
         seen = L["seg_end"]
         assert 2 <= L["passes"] <= 32
         tile = RUN * owned_runs(L["passes"])
-        assert L["g_end"] - L["g_begin"] <= MAX_LAUNCH and L["g_begin"] % RUN == 0
+        assert L["g_end"] - L["g_begin"] <= limit and L["g_begin"] % RUN == 0
         t = 0
         for s in mine:
             assert s["launch"] == li and s["first_tile"] == t
@@ -84,6 +99,9 @@ def check_layout(ns, segs, launches):
             assert n_off == 0 or (L["g_begin"] <= s["base"] and s["base"] + n_off <= L["g_end"])
             if s is not by_capture[s["capture"]][-1]:
                 assert n_off % tile == 0                                            # a cut capture is cut between tiles
+                assert len(mine) == 1 and n_off == limit // tile * tile             # ... into launches of their own, as full as whole tiles go
+            else:
+                assert n_off <= limit                                               # what fits a launch is not cut
             t += s["tiles"]
         assert t == L["tiles"]
     assert seen == len(segs)
@@ -103,6 +121,33 @@ def test_layout_properties(capi):
             segs, launches = capi.batch_layout(ns, passes=passes)
             check_layout(ns, segs, launches)
             assert passes == 0 or all(L["passes"] == passes for L in launches)
+    # the same under a lowered launch limit (adsb_debug_config.batch_launch_offsets): tile multiples at K = 2, 7 and 32, with and
+    # without forced passes -- honoured or not, by batch_launch_limit's rule.  Pieces and roll-overs in almost every case.
+    t2, t7, t32 = (RUN * owned_runs(k) for k in (2, 7, 32))
+    small = [v for v in special if v < 1 << 31]
+    mixes = [[1 << 18] * 9 + [81960 + 8 * k for k in range(6)], [1 << 20] * 3 + [90_000] * 40]
+    for _ in range(10):
+        k = int(rng.integers(3, 40))
+        ns = [int(v) for v in np.concatenate([rng.integers(0, 1 << int(rng.integers(18, 25)), size=k), rng.choice(small, 3)])]
+        rng.shuffle(ns)
+        mixes.append(ns)
+    honoured = cut = rolled = 0
+    for ns in mixes:
+        for launch_offsets, passes in ((3 * t2, 2), (3 * t2, 0), (t2, 2), (2 * t7, 0), (2 * t7, 7), (t7, 0), (5 * t7 + 28, 2), (t32, 32),
+                                       (t32, 0), (3 * t32, 7), (t7 - 28, 0), (MAX_LAUNCH + 28, 0)):
+            limit = launch_limit(launch_offsets, passes)
+            assert (limit == launch_offsets) == (launch_offsets not in (t7 - 28, MAX_LAUNCH + 28) and (launch_offsets, passes) != (3 * t2, 0))
+            segs, launches = capi.batch_layout(ns, passes=passes, launch_offsets=launch_offsets)
+            check_layout(ns, segs, launches, limit)
+            assert passes == 0 or all(L["passes"] == passes for L in launches)
+            if limit == MAX_LAUNCH:
+                assert (segs, launches) == capi.batch_layout(ns, passes=passes)
+                continue
+            honoured += 1
+            cut += len(segs) > len(ns)
+            # a roll-over: a launch that ended because the next capture did not fit what was left of it, not on a cut
+            rolled += any(segs[L["seg_first"]]["capture"] != segs[L["seg_first"] - 1]["capture"] for L in launches[1:])
+    assert honoured == 9 * len(mixes) and 10 * cut >= 8 * honoured and 10 * rolled >= 8 * honoured, (honoured, cut, rolled)
     # nine buffers of 256 Mi samples are more than 2^30 offsets: two launches or more
     assert len(capi.batch_layout([1 << 28] * 9)[1]) >= 2
     # 256 captures of 1 Mi samples are one launch of seven passes, eleven tiles a capture (the quantisation loss: 1.3 %)
@@ -132,27 +177,30 @@ def seeded_capture(i):
                        for k, s in enumerate(starts)], 6.0, 7000 + i)
 
 
-@pytest.mark.parametrize("df18", [False, True])
-def test_resolve_per_capture_equals_the_oracle(capi, oracle, df18):
-    """Every CRC-valid candidate and every try of 20 seeded captures, shifted to the layout's virtual offsets, concatenated
-    and sorted: per capture, frames (g, ts, pw, bytes) and Try/Ok table are oracle.decode's of that capture alone."""
+def _resolve_equals_the_oracle(capi, oracle, df18, launch_offsets):
     caps = [seeded_capture(i) for i in range(20)]
     ns = [int(x.size) for x in caps]
-    segs, launches = capi.batch_layout(ns)
-    check_layout(ns, segs, launches)
+    segs, launches = capi.batch_layout(ns, launch_offsets=launch_offsets)
+    check_layout(ns, segs, launches, launch_limit(launch_offsets, 0))
     cands, tries = [], []
+    n_cut = 0
     for s in segs:
-        assert s["o_begin"] == 0                                       # (none of these is cut)
+        n_cut += s["o_begin"] != 0
         x = caps[s["capture"]]
-        if s["o_end"] == 0:
+        if s["o_end"] == s["o_begin"]:
             continue
-        c, t = oracle.scan_all(oracle.power(x), 0, s["o_end"], df18)
-        cands += [(g + s["base"], pw, fr) for g, pw, fr in c]
-        tries.append(t + np.uint64(s["base"] << 2))
+        c, t = oracle.scan_all(oracle.power(x), s["o_begin"], s["o_end"], df18)
+        shift = s["base"] - s["o_begin"]
+        cands += [(g + shift, pw, fr) for g, pw, fr in c]
+        tries.append(t + np.uint64(shift << 2))
+    if launch_offsets == 0:
+        assert n_cut == 0                                              # (none of these is cut)
+    else:                                                              # most are, and the launches are many: records on both sides of every cut
+        assert n_cut >= 14 and len(launches) > n_cut and len({s["capture"] for s in segs if s["o_begin"]}) >= 12
     assert cands == sorted(cands, key=lambda c: c[0])
     tries = np.concatenate(tries) if tries else np.empty(0, np.uint64)
     assert np.all(np.diff(tries.astype(np.int64)) >= 0)
-    frames, stats = capi.batch_resolve(ns, cands, tries)
+    frames, stats = capi.batch_resolve(ns, cands, tries, launch_offsets=launch_offsets)
     visited, with_frames = 0, 0
     for i, x in enumerate(caps):
         want, wstats = oracle.decode(x, df18=df18)
@@ -166,7 +214,23 @@ def test_resolve_per_capture_equals_the_oracle(capi, oracle, df18):
     g_gap = segs[0]["base"] + segs[0]["o_end"] + 5
     bad = sorted(cands + [(g_gap, 1, bytes(14))], key=lambda c: c[0])
     with pytest.raises(capi.AdsbError):
-        capi.batch_resolve(ns, bad, tries)
+        capi.batch_resolve(ns, bad, tries, launch_offsets=launch_offsets)
+    return frames
+
+
+@pytest.mark.parametrize("df18", [False, True])
+def test_resolve_per_capture_equals_the_oracle(capi, oracle, df18):
+    """Every CRC-valid candidate and every try of 20 seeded captures, shifted to the layout's virtual offsets, concatenated
+    and sorted: per capture, frames (g, ts, pw, bytes) and Try/Ok table are oracle.decode's of that capture alone."""
+    _resolve_equals_the_oracle(capi, oracle, df18, 0)
+
+
+@pytest.mark.parametrize("df18", [False, True])
+def test_resolve_of_cut_captures_equals_the_oracle(capi, oracle, df18):
+    """The same through a layout whose launches hold one K = 7 tile (adsb_debug_config.batch_launch_offsets): the captures
+    are cut into pieces and remainders, a launch each -- the oracle's real records on both sides of every cut, where
+    test_resolve_rebases_records_on_both_sides_of_a_cut has hand-made ones.  Same frames, same tables."""
+    _resolve_equals_the_oracle(capi, oracle, df18, RUN * owned_runs(7))
 
 
 def test_resolve_rebases_records_on_both_sides_of_a_cut(capi):

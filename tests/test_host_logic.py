@@ -82,7 +82,7 @@ def test_config_abi_guard_and_growth_rule(capi):
     L = capi.load()
     assert L.adsb_abi_version() == 5
     assert capi.Config.abi.offset == 4 and capi.Config.host_threads.offset == 52 and capi.Config.debug.offset == 64
-    assert C.sizeof(capi.Config) == 72 and C.sizeof(capi.DebugConfig) == 48
+    assert C.sizeof(capi.Config) == 72 and C.sizeof(capi.DebugConfig) == 52
     cfg = capi.Config()
     C.memset(C.byref(cfg), 0xEE, C.sizeof(cfg))
     L.adsb_config_init(C.byref(cfg), C.sizeof(cfg))
@@ -110,7 +110,9 @@ def test_config_abi_guard_and_growth_rule(capi):
     assert not L.adsb_create(legacy) and b"adsb_config.abi" in L.adsb_last_error(None)
     # the test knobs: copied at adsb_create, their struct has a size of its own
     cfg = capi.make_config(debug_queue_cap=256, debug_gang_min=1)
-    assert cfg.debug and cfg._debug.queue_cap == 256 and cfg._debug.gang_min == 1 and cfg._debug.struct_size == 48
+    assert cfg.debug and cfg._debug.queue_cap == 256 and cfg._debug.gang_min == 1 and cfg._debug.struct_size == 52
+    assert not L.adsb_create(C.byref(cfg)) and b"no HIP device" in L.adsb_last_error(None)
+    cfg._debug.struct_size = 48                        # the struct as it was before batch_launch_offsets: still read, like any that ends early
     assert not L.adsb_create(C.byref(cfg)) and b"no HIP device" in L.adsb_last_error(None)
     cfg._debug.struct_size = 4000
     assert not L.adsb_create(C.byref(cfg)) and b"adsb_debug_config.struct_size" in L.adsb_last_error(None)
