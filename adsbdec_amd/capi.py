@@ -199,6 +199,10 @@ SYMBOLS = {
     "adsb_multi_worker_placement": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(WorkerPlacement)]),
     "adsb_resolver_advance_stream": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64,
                                                 C.c_uint64, C.c_uint64, C.c_int]),
+    "adsb_handoff_finish": (C.c_long, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64,
+                                       C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                       C.POINTER(Candidate), C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_size_t,
+                                       C.POINTER(C.c_size_t)]),
     "adsb_scan_shard_resolved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint64,
                                            C.POINTER(ShardHead), C.POINTER(Frame), C.c_size_t, C.POINTER(Candidate),
                                            C.c_size_t]),

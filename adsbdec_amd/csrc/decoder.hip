@@ -1,12 +1,6 @@
-// decoder.hip -- the stream machinery of libadsbdec_amd.so's host side: device staging, kernel launches, the collect of a
-// launch's records (while it runs, or after), the count passes, and the C-ABI calls of include/adsbdec_amd.h that push,
-// finish and read a stream.  Everything that runs per record or per tile is here; the handle itself and the units beside
-// this one: decoder_state.hpp.
-#include <new>
-#include <thread>
-
-#include <sched.h>
-
+// decoder.hip -- the stream machinery of libadsbdec_amd.so's host side: device staging, kernel launches, the count passes,
+// and the C-ABI calls of include/adsbdec_amd.h that push, finish and read a stream.  What a launch leaves behind is collected
+// in decoder_collect.hip; the handle itself and the units beside this one: decoder_state.hpp.
 #include "decoder_state.hpp"
 #include "packed12.h"
 #include "seam_kernel.h"
@@ -86,7 +80,7 @@ bool shard_too_long(adsb_decoder *d, const char *what, uint64_t first_sample, ui
     return true;
 }
 
-static int slot_reserve_device_tries(adsb_decoder *d, ScanSlot &s, size_t want_list, size_t want_tiles)
+int slot_reserve_device_tries(adsb_decoder *d, ScanSlot &s, size_t want_list, size_t want_tiles)
 {
     if (want_list > s.d_try_cap || want_tiles > s.d_try_tiles) {
         want_list = std::max(want_list, s.d_try_cap);
@@ -158,20 +152,41 @@ int slot_order_behind_count(adsb_decoder *d, ScanLaunch &s, hipStream_t st)
     return 0;
 }
 
-static int slot_launch(adsb_decoder *d, ScanSlot &s)
+// Begin a launch on a slot, on stream `ls`: the event pair flips, the profile of the launch that used this copy last is
+// settled, the launch is ordered behind the slot's previous one where that ran on the other stream, and it is given its tag
+// and the slot's counters and loose list.
+int slot_begin_launch(adsb_decoder *d, ScanSlot &s, hipStream_t ls, uint64_t offsets)
 {
-    const bool stats = d->cfg.collect_stats != 0;
     s.ev_cur ^= 1;
     if (slot_settle_profile(d, s, s.ev_cur)) // two launches old: normally read long ago
         return -1;
-    s.ev_offsets[s.ev_cur] = s.args.g_end - s.args.g_begin;
+    s.ev_offsets[s.ev_cur] = offsets;
+    if (s.launch_stream && s.launch_stream != ls) // the slot's previous launch (its report kernel zeroes the counters) ran on the other stream
+        HIP_TRY(d, hipStreamWaitEvent(ls, s.ev_ready[s.ev_cur ^ 1], 0));
+    s.launch_stream = ls;
+    s.args.gen = ++d->launch_gen * 0x9E3779B9u + 0x7F4A7C15u;
+    // d_counters are zero here: cleared at creation, and the report kernel behind every scan leaves them so
+    s.args.counters = s.d_counters;
+    s.args.cands = s.cands;
+    s.args.cand_cap = (uint32_t)std::min<size_t>(s.cand_cap, 0xFFFFFFFFu);
+    s.args.profile = d->cfg.profile ? 1 : 0;
+    s.args.report = s.hc();
+    return 0;
+}
+
+int slot_launch(adsb_decoder *d, ScanSlot &s)
+{
+    const bool stats = d->cfg.collect_stats != 0;
+    const int slot_index = (int)(&s - d->slots);
+    hipStream_t ls = (d->alt_next && d->stream2 && (slot_index & 1)) ? d->stream2.st : d->stream.st;
+    if (slot_begin_launch(d, s, ls, s.args.g_end - s.args.g_begin))
+        return -1;
     s.ntiles = adsb::tile_count(s.args.g_end - s.args.g_begin, s.args.big_tiles, s.args.passes);
     // A stream's statistics run keeps the try words on the device (counted there after
     // resolution); a per-shard scan hands the list back, sorted, so it needs the list
     // complete on the host: collect after completion.
     s.tries_on_device = stats && !d->sink.cands;
     s.streaming = !d->no_streaming && (!stats || s.tries_on_device);
-    s.args.gen = ++d->launch_gen * 0x9E3779B9u + 0x7F4A7C15u;
     if (s.streaming) {
         // a line per tile (marker + padding) + two granules per record (sized like the loose list)
         const size_t want_granules = 2 * s.cand_cap + 4 * (size_t)s.ntiles + 64;
@@ -186,14 +201,6 @@ static int slot_launch(adsb_decoder *d, ScanSlot &s)
         s.args.hand = nullptr;
         s.args.hand_cap = 0;
     }
-    s.args.counters = s.d_counters;
-    s.args.cands = s.cands;
-    s.args.cand_cap = (uint32_t)std::min<size_t>(s.cand_cap, 0xFFFFFFFFu);
-    const int slot_index = (int)(&s - d->slots);
-    hipStream_t ls = (d->alt_next && d->stream2 && (slot_index & 1)) ? d->stream2.st : d->stream.st;
-    if (s.launch_stream && s.launch_stream != ls) // the slot's previous launch (its report kernel zeroes the counters) ran on the other stream
-        HIP_TRY(d, hipStreamWaitEvent(ls, s.ev_ready[s.ev_cur ^ 1], 0));
-    s.launch_stream = ls;
     if (slot_order_behind_count(d, s, ls))
         return -1;
     // debug_try_cap (tests of the relaunch path) wants every try on the launch-wide list
@@ -204,9 +211,6 @@ static int slot_launch(adsb_decoder *d, ScanSlot &s)
     s.args.try_cap = (uint32_t)std::min<size_t>(s.tries_on_device ? s.d_try_cap : s.tries.cap, 0xFFFFFFFFu);
     s.args.try_counts = s.try_regions ? s.d_try_counts : nullptr;
     s.args.try_list_first = s.try_regions ? (uint32_t)(s.d_try_tiles * adsb::kTryRegion) : 0u;
-    // d_counters are zero here: cleared at creation, and the report kernel behind every scan leaves them so
-    s.args.profile = d->cfg.profile ? 1 : 0;
-    s.args.report = s.hc();
     if (s.epoch_base) {
         // the kernel sees a fresh stream whose sample 0 is input sample w * 2^32: r mod 7, the run boundaries and the typed-load
         // alignment are the epoch's (P is a multiple of 4 pairs); pairs of the epoch before read as silence, and no offset of
@@ -231,378 +235,6 @@ static int slot_launch(adsb_decoder *d, ScanSlot &s)
                 return -1;
     s.busy = true;
     return 0;
-}
-
-// LSD radix sort of the record indices by their 30-bit g_rel (3 x 10 bits).
-void sort_order(adsb_decoder *d, const uint32_t *recs, size_t n)
-{
-    d->order.resize(n);
-    d->scratch_a.resize(n);
-    d->scratch_b.resize(n);
-    uint32_t *idx = d->order.data(), *tmp = d->scratch_a.data(), *key = d->scratch_b.data();
-    bool sorted = true;
-    for (size_t i = 0; i < n; i++) {
-        idx[i] = (uint32_t)i;
-        key[i] = recs[i * adsb::kCandWords];
-        if (i && key[i] < key[i - 1])
-            sorted = false;
-    }
-    if (sorted)
-        return;
-    for (int shift = 0; shift < 30; shift += 10) {
-        uint32_t hist[1025] = {0};
-        for (size_t i = 0; i < n; i++)
-            hist[((key[idx[i]] >> shift) & 1023u) + 1]++;
-        for (int b = 0; b < 1024; b++)
-            hist[b + 1] += hist[b];
-        for (size_t i = 0; i < n; i++)
-            tmp[hist[(key[idx[i]] >> shift) & 1023u]++] = idx[i];
-        std::swap(idx, tmp);
-    }
-    if (idx != d->order.data())
-        std::memcpy(d->order.data(), idx, n * sizeof(uint32_t)); // odd number of passes
-}
-
-void sort_tries(adsb_decoder *d, uint32_t *t, size_t n)
-{
-    bool sorted = true;
-    for (size_t i = 1; i < n && sorted; i++)
-        sorted = t[i] >= t[i - 1];
-    if (sorted)
-        return;
-    d->scratch_a.resize(n);
-    uint32_t *src = t, *dst = d->scratch_a.data();
-    for (int shift = 0; shift < 32; shift += 11) {
-        uint32_t hist[2049] = {0};
-        for (size_t i = 0; i < n; i++)
-            hist[((src[i] >> shift) & 2047u) + 1]++;
-        for (int b = 0; b < 2048; b++)
-            hist[b + 1] += hist[b];
-        for (size_t i = 0; i < n; i++)
-            dst[hist[(src[i] >> shift) & 2047u]++] = src[i];
-        std::swap(src, dst);
-    }
-    if (src != t)
-        std::memcpy(t, src, n * sizeof(uint32_t));
-}
-
-// Hand sorted records to the sink (a caller's vectors or the stream's resolver).
-// Record i is the 6 dwords {g_rel, pw, frame | len << 16 | flags << 24} at
-// recs[order[i] * words + off] (loose list / gathered copy: words 6, off 0; hand-off
-// stream consumed in place: words 4 = granule index, off 1).
-static void deliver(adsb_decoder *d, const ScanLaunch &s, const uint32_t *recs, const uint32_t *order, size_t nc, int words,
-             int off, const uint32_t *tries, size_t nt, uint64_t g_complete)
-{
-    d->prof.candidates += nc;
-    d->prof.tries += nt;
-    if (d->sink.cands) {
-        for (size_t i = 0; i < nc; i++) {
-            const uint32_t *r = recs + (size_t)order[i] * words + off;
-            adsb_candidate c;
-            std::memset(&c, 0, sizeof c);
-            std::memcpy(c.frame, &r[2], 14);
-            c.len = (uint8_t)((r[5] >> 16) & 0xFF);
-            c.reserved = (uint8_t)((r[5] >> 24) & 1u);
-            // (a stream record may stand for the same frame at up to three consecutive offsets: scan_kernel_format.h)
-            for (uint32_t k = 0, nk = words == adsb::kGranuleWords ? adsb::rec_copies(r) : 1u; k < nk; k++) {
-                c.g = s.args.g_begin + r[0] + k;
-                c.pw = k ? r[5 + k] : r[1];
-                d->sink.cands->push_back(c);
-            }
-        }
-        for (size_t i = 0; i < nt; i++)
-            d->sink.tries->push_back((((uint64_t)(tries[i] >> 2) + s.args.g_begin) << 2) | (tries[i] & 3u));
-    } else if (nt == 0) {
-        d->res.capture_head(recs, order, nc, words, off, s.args.g_begin);
-        d->res.advance_device(recs, order, nc, words, off, s.args.g_begin, power_samples_produced(d->n_samples),
-                              g_complete);
-    } else {
-        d->res.feed_device(recs, order, nc, words, off, s.args.g_begin, tries, nt);
-        d->res.advance(power_samples_produced(d->n_samples), g_complete);
-    }
-}
-
-// (the reading side of the hand-off stream -- HandCursor, StreamReader, the two consumer loops -- is host-only code:
-// handoff.hpp)
-
-// "has the launch behind these bytes ended?" for handoff.hpp: ctx is the launch's completion event
-static int launch_done(void *ctx)
-{
-    const hipError_t q = hipEventQuery(static_cast<hipEvent_t>(ctx));
-    return q == hipErrorNotReady ? 0 : q == hipSuccess ? 1 : -1;
-}
-
-static adsb::HandJob hand_job(const ScanSlot &s)
-{
-    adsb::HandJob j;
-    j.hand = s.hand;
-    j.ntiles = s.ntiles;
-    j.gen = s.args.gen;
-    j.cap = s.args.hand_cap;
-    j.done = launch_done;
-    j.ctx = s.ev_ready[s.ev_cur];
-    return j;
-}
-
-// Tiles [from, upto) of the launch's hand-off stream (d->tile_start / d->tile_count say where each one's records lie) go to
-// the sink: a caller's vectors, or the stream's resolver, which walks the ranges where they lie.  Returns the records handed on.
-static size_t deliver_tiles(adsb_decoder *d, ScanSlot &s, uint32_t from, uint32_t upto)
-{
-    const uint32_t *t_start = d->tile_start.data(), *t_count = d->tile_count.data();
-    const uint64_t g_complete = std::min<uint64_t>(
-        s.args.g_end, s.args.g_begin + adsb::kRun * adsb::tile_first_run(upto, s.args.big_tiles, s.args.passes));
-    size_t nc = 0;
-    if (d->sink.cands) { // per-shard scan: the caller's vectors
-        std::vector<uint32_t> &order = d->order; // the records in ascending g (granule indices)
-        order.clear();
-        for (uint32_t u = from; u < upto; u++)
-            for (uint32_t i = 0, b = t_start[u], n = t_count[u]; i < n; i++)
-                order.push_back(b + 2 * i);
-        nc = order.size();
-        deliver(d, s, s.hand, order.data(), nc, adsb::kGranuleWords, 0, nullptr, 0, g_complete);
-    } else { // the stream's resolver walks the tile ranges where they lie
-        for (uint32_t u = from; u < upto; u++)
-            nc += t_count[u];
-        d->prof.candidates += nc;
-        if (d->res.head_wanted(s.args.g_begin + adsb::kRun * adsb::tile_first_run(from, s.args.big_tiles, s.args.passes)))
-            d->res.capture_head_tiles(s.hand, t_start, t_count, from, upto, s.args.g_begin);
-        d->res.advance_tiles(s.hand, t_start, t_count, from, upto, s.args.g_begin, power_samples_produced(d->n_samples), g_complete);
-    }
-    return nc;
-}
-
-// Streaming collect: consume the oldest scan WHILE its kernel is still running, so
-// that resolving overlaps the scan.  The hand-off stream (scan_kernel.h) is read strictly
-// sequentially -- one prefetchable stream of device-written lines, no directory to poll:
-// a marker says which tile follows, how many records, and what their XOR must be; the
-// records are checked where they lie (16-byte loads) and later resolved in place.  Tiles
-// reserve their ranges in COMPLETION order, so a tile that finished early waits (start and
-// count noted) until every tile before it is in; the resolver is fed whenever the device
-// leaves the host nothing to read, or a group of tiles has accumulated.
-// Returns 1 if a tile reported records on the loose list (or the stream is full): the
-// caller then finishes the launch through the collect-after-completion path, from tile
-// *resume_tile on.
-// The handle's second host thread (handoff.hpp StreamReader), kept on the caller's L3.  cfg.host_threads = 2 starts it with the
-// handle; 0 (auto) the first time a launch follows one that handed over kAutoReaderRecords or more -- at the channel's
-// capacity one thread needs four times the kernel's time for a launch's records, and reading + checking on one thread while
-// the caller resolves takes a quarter off that; under ordinary traffic the thread never exists.
-constexpr uint64_t kAutoReaderRecords = 65536, kAutoReaderMinRecords = 16384;
-
-// Did the previous launch of this handle hand over a record per 2 048 offsets or more (and 16 384 at least)?  The traffic of a
-// channel does not change from one launch to the next: the host side starts its helper threads on this (slot_collect), and the
-// next launch takes tiles of six passes instead of seven (adsb::choose_passes).
-static inline bool last_launch_was_dense(const adsb_decoder *d)
-{
-    const uint64_t dense_from = std::max<uint64_t>(kAutoReaderMinRecords, std::min<uint64_t>(kAutoReaderRecords, d->last_launch_offsets / 2048));
-    return d->last_launch_records >= dense_from;
-}
-void start_reader(adsb_decoder *d)
-{
-    if (d->reader || d->reader_failed)
-        return;
-    d->reader = new (std::nothrow) adsb::StreamReader;
-    if (d->reader) {
-        d->reader->on_start = [](void *ctx) { (void)hipSetDevice(static_cast<adsb_decoder *>(ctx)->device); }; // launch_done()
-        d->reader->on_start_ctx = d;
-        try {
-            d->reader->start();
-        } catch (...) { // no thread to be had: the calling thread consumes the stream alone, as without the option
-            delete d->reader;
-            d->reader = nullptr;
-        }
-    }
-    if (d->reader) {
-        d->reader->place = true;
-        d->reader->placed_l3 = adsb::place_reader_thread(d->reader->th, sched_getcpu());
-    } else {
-        d->reader_failed = true;
-    }
-}
-
-// More hands for a channel at its capacity (gang.hpp): the calling thread decides, `helpers` threads on its L3 write the frames.
-void start_gang(adsb_decoder *d, int helpers)
-{
-    if (d->gang || d->gang_failed)
-        return;
-    d->gang = new (std::nothrow) adsb::FormatGang;
-    if (d->gang && !d->gang->start(helpers)) { // no thread to be had: the calling thread writes its frames itself, as without
-        delete d->gang;
-        d->gang = nullptr;
-    }
-    if (!d->gang) {
-        d->gang_failed = true;
-        return;
-    }
-    const int cpu = sched_getcpu();
-    for (std::thread &t : d->gang->threads())
-        d->gang_l3 = adsb::place_reader_thread(t, cpu);
-}
-
-constexpr int kAutoGangHelpers = 4; // (measured on the dense capture: profiles/r5_gang_runs.txt)
-
-static int slot_collect_streaming(adsb_decoder *d, ScanSlot &s, uint32_t *resume_tile, uint32_t *tiles_in, bool *tries_listed)
-{
-    using clk = std::chrono::steady_clock;
-    const auto t_begin = clk::now();
-
-    std::vector<uint32_t> &t_start = d->tile_start; // per tile: granule index of its first record ...
-    std::vector<uint32_t> &t_count = d->tile_count; // ... and its record count (~0u: not in yet)
-    t_start.assign(s.ntiles, 0u);
-    t_count.assign(s.ntiles, ~0u);
-    uint32_t delivered = 0; // every tile below has been handed to the resolver
-    uint64_t recs_handed = 0;
-    bool overflowed = false;
-    double dbg[3] = {0, 0, 0};
-    const bool dbg_on = tuning_env("ADSB_DEBUG_HOST") != nullptr;
-    double wait_ms = 0;
-    auto t_last_wait = t_begin;
-    // With more hands (gang.hpp) a batch is handed to the resolver LATE: meanwhile one of the gang's threads decides it ahead
-    // (Resolver::speculate_tiles), and the resolver only takes the decisions over.  A flush is cut into batches of kAheadTiles
-    // tiles, so that several threads decide side by side and the last batch of a launch is a short one; a batch goes on
-    // as soon as it has been decided (looked at with every flush), at the latest when kMaxHeld are waiting.
-    constexpr int kMaxHeld = 12;
-    constexpr uint32_t kAheadTiles = 64;
-    uint32_t held[kMaxHeld][2];
-    int n_held = 0;
-    bool ahead = false;                    // (set below, once it is known whether this launch goes through the gang)
-    auto deliver_held = [&](int keep, bool only_ready) { // the oldest first, until `keep` are left
-        size_t nc = 0;
-        int k = 0;
-        for (; n_held - k > keep && (!only_ready || d->res.ahead_ready()); k++)
-            nc += deliver_tiles(d, s, held[k][0], held[k][1]);
-        for (int i = k; i < n_held; i++)
-            held[i - k][0] = held[i][0], held[i - k][1] = held[i][1];
-        n_held -= k;
-        return nc;
-    };
-    auto flush = [&](uint32_t upto) { // tiles [delivered, upto): their ranges, one after the other, are sorted
-        clk::time_point tp;
-        if (dbg_on)
-            tp = clk::now();
-        size_t nc = 0;
-        if (ahead) {
-            for (uint32_t from = delivered; from < upto;) {
-                const uint32_t to = std::min(upto, from + kAheadTiles);
-                if (n_held == kMaxHeld)
-                    nc += deliver_held(kMaxHeld - 1, false);
-                if (d->res.speculate_tiles(s.hand, d->tile_start.data(), d->tile_count.data(), from, to, s.args.g_begin)) {
-                    held[n_held][0] = from, held[n_held][1] = to;
-                    n_held++;
-                    d->prof.gang_batches++;
-                } else { // (a batch too small to be worth it: in its turn, by this thread)
-                    nc += deliver_held(0, false);
-                    nc += deliver_tiles(d, s, from, to);
-                }
-                from = to;
-            }
-            nc += deliver_held(0, true);
-        } else {
-            nc += deliver_tiles(d, s, delivered, upto);
-        }
-        delivered = upto;
-        recs_handed += nc;
-        if (dbg_on) {
-            dbg[1] += std::chrono::duration<double, std::micro>(clk::now() - tp).count();
-            dbg[2] += 1;
-            if (tuning_env("ADSB_DEBUG_TIMELINE"))
-                fprintf(stderr, "  t=%.1f us: tiles < %u resolved (%zu records), waited %.1f us so far\n",
-                        std::chrono::duration<double, std::micro>(clk::now() - t_begin).count(), upto, nc, wait_ms * 1e3);
-        }
-    };
-    const adsb::HandJob job = hand_job(s);
-    adsb::CollectEnd end;
-    // "a channel near its capacity" is a DENSITY: 65 536 records out of a full launch's 128 Mi offsets = one per 2 048 (a full
-    // channel has one per 1 090).  Round 6: a shorter launch -- a 128 Mi-sample shard of the multi-GPU driver is 64 Mi offsets,
-    // 61 k records on a full channel -- counts by the same density, from 16 384 records on (below that a launch is resolved
-    // faster than five threads are woken).
-    const bool after_dense = d->cfg.host_threads == 0 && last_launch_was_dense(d);
-    if (after_dense) {
-        start_reader(d);
-        cpu_set_t allowed; // (six threads that poll need cores of their own: on a small or confined host, round 4's pair)
-        if (sched_getaffinity(0, sizeof allowed, &allowed) != 0 || CPU_COUNT(&allowed) >= 2 * (kAutoGangHelpers + 2))
-            start_gang(d, kAutoGangHelpers);
-    }
-    // (a batch decided ahead packs an offset relative to the launch's first into 31 bits: chunk_offsets() keeps a launch below
-    // 2^30 offsets -- kMaxLaunchOffsets -- and this says so where it matters)
-    const bool with_gang = d->gang && !d->sink.cands && (uint64_t)s.args.hand_cap * adsb::kGranuleWords * 4 <= adsb::kDecMaxStreamBytes &&
-                           s.args.g_end - s.args.g_begin < (1ull << 31) && (d->cfg.host_threads >= 3 || after_dense);
-    if (d->dbg.gang_min > 0) {
-        d->res.set_gang(with_gang ? d->gang : nullptr, (size_t)d->dbg.gang_min);
-        d->res.set_ahead_min_records((size_t)d->dbg.gang_min);
-    } else {
-        d->res.set_gang(with_gang ? d->gang : nullptr);
-    }
-    if (with_gang) {
-        const int cpu = sched_getcpu(); // the caller may have moved since the threads were placed
-        const int l3 = adsb::l3_of_cpu(cpu);
-        if (l3 >= 0 && l3 != d->gang_l3)
-            for (std::thread &t : d->gang->threads())
-                d->gang_l3 = adsb::place_reader_thread(t, cpu);
-        d->gang->begin();
-        ahead = true;
-        d->prof.gang_launches++;
-    }
-    if (d->reader && s.ntiles >= d->reader_min_tiles && (d->cfg.host_threads >= 2 || after_dense)) {
-        adsb::StreamReader &rd = *d->reader;
-        if (rd.place) { // the caller may have moved since the thread was placed
-            const int cpu = sched_getcpu();
-            const int l3 = adsb::l3_of_cpu(cpu);
-            if (l3 >= 0 && l3 != rd.placed_l3)
-                rd.placed_l3 = adsb::place_reader_thread(rd.th, cpu);
-        }
-        auto idle = [&]() -> bool { // batches that have been decided meanwhile go on while the device is behind
-            if (!n_held || !d->res.ahead_ready())
-                return false;
-            clk::time_point tp;
-            if (dbg_on)
-                tp = clk::now();
-            recs_handed += deliver_held(0, true);
-            if (dbg_on)
-                dbg[1] += std::chrono::duration<double, std::micro>(clk::now() - tp).count();
-            return true;
-        };
-        end = adsb::collect_behind_reader(rd, job, t_start.data(), t_count.data(), delivered, flush, wait_ms, t_last_wait, idle);
-        if (dbg_on)
-            fprintf(stderr, "stream reader thread: busy %.1f us, waits %.1f us\n", rd.busy_ms * 1e3, rd.wait_ms * 1e3);
-    } else {
-        end = adsb::collect_alone(job, t_start.data(), t_count.data(), delivered, flush, wait_ms, t_last_wait);
-    }
-    if (n_held) { // the batches that were still waiting for their turn
-        const auto tp = clk::now();
-        recs_handed += deliver_held(0, false);
-        if (dbg_on)
-            dbg[1] += std::chrono::duration<double, std::micro>(clk::now() - tp).count();
-    }
-    if (end.status < 0 && with_gang) {
-        d->res.sync();
-        d->gang->end();
-    }
-    if (end.status == -1)
-        return d->fail("hand-off stream corrupt at granule %u (tile %u twice)", end.pos, end.tile);
-    if (end.status == -2)
-        return d->fail("scan kernel finished without publishing granule %u (tile %u of %u pending)", end.pos, end.tile, s.ntiles);
-    overflowed = end.status == 1;
-    if (with_gang) { // the frames of this launch are whole before its stream is touched again (and before anyone counts the time)
-        d->res.sync();
-        d->gang->end();
-    }
-    if (dbg_on)
-        fprintf(stderr, "gang: %s, ahead %d, frames taken over so far %llu\n", with_gang ? "on" : "off", (int)ahead,
-                (unsigned long long)d->res.ahead_taken());
-    if (dbg_on)
-        fprintf(stderr,
-                "stream collect: %.1f us in all, resolve %.1f us in %d batches, waits %.1f us; %.1f us after the last wait\n",
-                std::chrono::duration<double, std::micro>(clk::now() - t_begin).count(), dbg[1], (int)dbg[2], wait_ms * 1e3,
-                std::chrono::duration<double, std::micro>(clk::now() - t_last_wait).count());
-    const double total_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
-    d->prof.wait_ms += wait_ms;
-    d->prof.host_ms += total_ms - wait_ms;
-    *resume_tile = delivered;
-    *tiles_in = end.frontier;
-    *tries_listed = end.tries_listed;
-    d->last_launch_records = recs_handed; // (a launch that is finished after completion adds its part there)
-    d->last_launch_offsets = s.args.g_end - s.args.g_begin;
-    return overflowed ? 1 : 0;
 }
 
 // Device-side visited-try count of a statistics run (scan_kernel.h TryCountArgs):
@@ -757,217 +389,6 @@ int read_tries(adsb_decoder *d)
     if (acc[3])
         return d->fail("undecided tries exceeded the carry buffer (%u entries)", kCarryCap);
     d->res.set_tries(acc[0], acc[1], acc[2]);
-    return 0;
-}
-
-// Wait for the oldest scan in flight and hand its records on, in ascending g.
-static int slot_collect(adsb_decoder *d)
-{
-    ScanSlot &s = d->slots[d->slot_head];
-    using clk = std::chrono::steady_clock;
-    uint32_t resume_tile = 0, tiles_in = 0;
-    bool partial = false; // tiles below resume_tile were already delivered
-    bool relaunched = false;
-    bool tries_listed = false; // (statistics runs) some tile's tries are on the launch-wide list: its length comes with the counters
-    if (s.streaming) {
-        const int rc = slot_collect_streaming(d, s, &resume_tile, &tiles_in, &tries_listed);
-        if (rc < 0)
-            return -1;
-        partial = rc == 1;
-    }
-    if (s.streaming && !partial && !tries_listed && (!s.tries_on_device || s.try_regions)) {
-        // Every tile has been published and consumed and none used the loose list -- nor, in a statistics
-        // run, the launch-wide try list: a tile that overflows its survivor queue says so in its marker (kMarkTries:
-        // its records are in the stream and have been handed on like any other's), and the tries of all others are
-        // in their regions.  The launch-wide counters have nothing to add, so
-        // do not wait for them (nor for the kernel's end event -- the profile reads that later).
-        s.prof_pending[s.ev_cur] = d->cfg.profile != 0;
-        d->prof.launches++;
-        d->prof.offsets += s.args.g_end - s.args.g_begin;
-        d->prof.last_offsets = s.args.g_end - s.args.g_begin;
-        if (s.tries_on_device) {
-            if (d->final_follows && d->slot_count == 1) { // (see below)
-                d->deferred_slot = &s;
-                d->deferred_n = 0;
-                d->deferred_base = s.args.g_begin;
-            } else if (count_tries_pass(d, &s, s.d_tries, s.d_try_counts, 0, s.args.g_begin, false)) {
-                return -1;
-            }
-        }
-        s.busy = false;
-        d->slot_head = (d->slot_head + 1) % kSlots;
-        d->slot_count--;
-        return 0;
-    }
-    const auto t_wait = clk::now();
-    for (int attempt = 0;; attempt++) {
-        if (s.streaming && !partial) {
-            // every tile has been consumed: the kernel is ending and its report is microseconds
-            // away -- poll for it instead of going to sleep in hipEventSynchronize
-            WAIT_EVENT(d, s.ev_ready[s.ev_cur], "the end of a scan launch whose every tile has been consumed");
-        } else {
-            WAIT_EVENT(d, s.ev_ready[s.ev_cur], "a scan launch");
-        }
-        s.prof_pending[s.ev_cur] = d->cfg.profile != 0;
-        if (slot_settle_profile(d, s, s.ev_cur))
-            return -1;
-        d->prof.launches++;
-        d->prof.offsets += s.args.g_end - s.args.g_begin;
-        d->prof.last_offsets = s.args.g_end - s.args.g_begin;
-        const size_t nc = s.hc()[0], nt = s.hc()[1];
-        if (nc <= s.cand_cap && nt <= (s.tries_on_device ? s.d_try_cap : s.tries.cap))
-            break;
-        // Sparse output sized for far more than noise produces; the counters keep
-        // counting past the capacity, so one repeat with exact sizes suffices.
-        if (attempt >= 2)
-            return d->fail("record buffers overflowed repeatedly (%zu candidates, %zu tries)", nc, nt);
-        d->prof.relaunches++;
-        relaunched = true;
-        WAIT_STREAM(d, s.launch_stream ? s.launch_stream : d->stream, "the launch's stream");
-        if (slot_reserve(d, s, std::max(s.cand_cap, nc + nc / 8 + 64),
-                         s.tries_on_device ? s.tries.cap : std::max(s.tries.cap, nt + nt / 8 + 64)))
-            return -1;
-        if (s.tries_on_device && slot_reserve_device_tries(d, s, std::max(s.d_try_cap, nt + nt / 8 + 64), s.d_try_tiles))
-            return -1;
-        if (slot_launch(d, s))
-            return -1;
-        // the repeat is consumed after completion: tiles below resume_tile (if any)
-        // were delivered by the first run and are skipped by the gather below
-    }
-    const auto t_host = clk::now();
-    d->prof.wait_ms += std::chrono::duration<double, std::milli>(t_host - t_wait).count();
-    const size_t nc = s.hc()[0], nt = s.hc()[1];
-    if (!s.streaming) {
-        // collect-after-completion: everything is in the launch-wide lists, in arrival order
-        sort_order(d, s.cands, nc);
-        if (nt && !s.tries_on_device)
-            sort_tries(d, s.tries, nt);
-        const size_t nt_host = s.tries_on_device ? 0 : nt;
-        deliver(d, s, s.cands, d->order.data(), nc, adsb::kCandWords, 0, s.tries, nt_host, s.args.g_end);
-    } else if (partial) {
-        // Some tile could not put all its records into the hand-off stream (staged list or survivor queue overflowed, its
-        // range did not fit): those records are on the loose list, which is only complete now that the kernel has ended.
-        // Every granule that was ever written is in: walk the stream again from its start (a missing or non-fitting marker
-        // ends it), note where each tile's records lie, sort the LOOSE records (few) and hand the tiles on in order -- runs of
-        // tiles that are whole in the stream where they lie, like the streaming collect does; a tile with loose records, or
-        // none in the stream at all, merged on the way.  (Round 3 gathered and sorted everything that was left: 4 ms for
-        // the 311 k records of a dense launch in which ONE early tile had overflowed.)
-        std::vector<uint32_t> &t_start = d->tile_start, &t_count = d->tile_count;
-        // (the streaming collect went on reading and checking behind the first tile that held it up: when it got to the end
-        // of the launch, where every tile's records lie is known already)
-        d->last_launch_records = std::max<uint64_t>(d->last_launch_records, s.hc()[2] / 2); // (an estimate from the granules the stream used)
-        const bool walked = tiles_in == s.ntiles && !relaunched;
-        if (!walked) {
-            t_start.assign(s.ntiles, 0u);
-            t_count.assign(s.ntiles, ~0u);
-        }
-        const uint32_t lim = walked ? 0u : (uint32_t)std::min<size_t>(s.hc()[2], s.args.hand_cap);
-        for (uint32_t pos = 0; pos < lim;) {
-            const uint32_t *m = s.hand + (size_t)pos * adsb::kGranuleWords;
-            const uint32_t tile = m[0], nf = m[1], n = nf & 0xFFFFu;
-            if (tile >= s.ntiles || (nf & adsb::kMarkNoFit) || (uint64_t)pos + 1 + 2ull * n > lim || t_count[tile] != ~0u)
-                break;
-            uint32_t a[4] = {0, 0, 0, 0}, sum = 0, lo, hi;
-            for (uint32_t k = 0; k < 8 * n; k++)
-                a[k & 3] ^= m[4 + k];
-            for (uint32_t r = 0; r < n; r++)
-                sum += adsb::record_term(r, m[4 + 8 * r], m[5 + 8 * r]);
-            adsb::marker_check(tile, nf, s.args.gen, a[0], a[1], a[2], a[3], sum, lo, hi);
-            if (m[2] != lo || m[3] != hi)
-                break;
-            t_start[tile] = pos + 1;
-            t_count[tile] = n;
-            pos += std::max(adsb::marker_granules(nf), adsb::stream_granules(n));
-        }
-        // The loose list may also hold records of tiles the streamed part has already delivered: after a relaunch (record
-        // buffers regrown) every tile runs again, and whether a tile's range fits the stream depends on completion order.
-        const uint64_t resume_rel = (uint64_t)adsb::kRun * adsb::tile_first_run(resume_tile, s.args.big_tiles, s.args.passes);
-        d->gather.clear();
-        for (size_t i = 0; i < nc; i++) {
-            const uint32_t *w = s.cands + i * adsb::kCandWords;
-            if (w[0] >= resume_rel)
-                d->gather.insert(d->gather.end(), w, w + adsb::kCandWords);
-        }
-        const size_t n_loose = d->gather.size() / adsb::kCandWords;
-        sort_order(d, d->gather.data(), n_loose);
-        const std::vector<uint32_t> loose_order(d->order.begin(), d->order.begin() + (ptrdiff_t)n_loose); // (deliver() reuses d->order)
-        std::vector<uint32_t> &merged = d->scratch_b; // one tile's records, kCandWords each, ascending
-        std::vector<uint32_t> iota;
-        size_t li = 0;
-        uint32_t run_from = resume_tile;
-        for (uint32_t u = resume_tile; u < s.ntiles; u++) {
-            const uint64_t hi_rel = (uint64_t)adsb::kRun * adsb::tile_first_run(u + 1, s.args.big_tiles, s.args.passes);
-            size_t lj = li;
-            while (lj < n_loose && d->gather[(size_t)loose_order[lj] * adsb::kCandWords] < hi_rel)
-                lj++;
-            if (t_count[u] != ~0u && lj == li)
-                continue; // whole in the stream: part of the current run
-            if (u > run_from)
-                deliver_tiles(d, s, run_from, u);
-            // this tile: its records in the stream (if it got that far) merged with its loose ones, both ascending
-            merged.clear();
-            const uint32_t ns = t_count[u] == ~0u ? 0u : t_count[u];
-            const uint32_t *sr = s.hand + (size_t)t_start[u] * adsb::kGranuleWords;
-            uint32_t si = 0;
-            while (si < ns || li < lj) {
-                const uint32_t *lw = li < lj ? d->gather.data() + (size_t)loose_order[li] * adsb::kCandWords : nullptr;
-                const uint32_t *sw = si < ns ? sr + (size_t)si * 2 * adsb::kGranuleWords : nullptr;
-                if (sw && (!lw || sw[0] <= lw[0])) {
-                    // {g_rel, pw, w0, w1}{w2, w3, pw', pw''}: the first six words, once per offset the record stands for (a run
-                    // of copies is never interleaved with a loose record: the offsets are consecutive and every offset yields
-                    // at most one candidate -- but a loose one may lie INSIDE the run only if it is one of its offsets, which
-                    // the tile would have staged with the others; so the run goes in whole)
-                    for (uint32_t k = 0, nk = adsb::rec_copies(sw); k < nk; k++) {
-                        const uint32_t one[adsb::kCandWords] = {sw[0] + k, k ? sw[5 + k] : sw[1], sw[2], sw[3], sw[4],
-                                                                 sw[5] & ~(3u << adsb::kRecCopiesShift)};
-                        merged.insert(merged.end(), one, one + adsb::kCandWords);
-                    }
-                    si++;
-                } else {
-                    merged.insert(merged.end(), lw, lw + adsb::kCandWords);
-                    li++;
-                }
-            }
-            const size_t nm = merged.size() / adsb::kCandWords;
-            iota.resize(nm);
-            for (size_t i = 0; i < nm; i++)
-                iota[i] = (uint32_t)i;
-            const uint64_t g_complete = std::min<uint64_t>(s.args.g_end, s.args.g_begin + hi_rel);
-            deliver(d, s, merged.data(), iota.data(), nm, adsb::kCandWords, 0, nullptr, 0, g_complete);
-            run_from = u + 1;
-        }
-        if (s.ntiles > run_from)
-            deliver_tiles(d, s, run_from, s.ntiles);
-    } else if (nc != 0) {
-        return d->fail("internal: %zu loose records without a tile overflow flag", nc);
-    }
-    if (s.tries_on_device) {
-        if (d->final_follows && d->slot_count == 1) {
-            // last launch of the stream: its tries are counted by the end-of-stream pass, which
-            // runs right after the final resolver step -- one device round trip instead of two
-            d->deferred_slot = &s;
-            d->deferred_n = (uint32_t)nt;
-            d->deferred_base = s.args.g_begin;
-        } else if (count_tries_pass(d, &s, s.d_tries, s.d_try_counts, (uint32_t)nt, s.args.g_begin, false)) {
-            return -1;
-        }
-    }
-    d->res.sync(); // (tiles handed on after completion may have gone to the gang as well)
-    if (d->gang)
-        d->gang->end(); // ... and FormatGang::post() begins the gang again by itself: without this the helpers would poll on until
-                        // the next launch that goes through the gang -- under traffic that has turned sparse, until adsb_destroy
-    d->prof.host_ms += std::chrono::duration<double, std::milli>(clk::now() - t_host).count();
-    s.busy = false;
-    d->slot_head = (d->slot_head + 1) % kSlots;
-    d->slot_count--;
-    return 0;
-}
-
-int scan_drain(adsb_decoder *d)
-{
-    while (d->slot_count)
-        if (slot_collect(d))
-            return -1;
     return 0;
 }
 

@@ -40,7 +40,7 @@ int batch_refusal(adsb_decoder *d, const char *what, size_t n_captures, const vo
     return 0;
 }
 
-// One launch of the batch: table up, scan, wait, regrow and repeat on overflow (as slot_collect does), then the sorted
+// One launch of the batch: table up, scan, wait, regrow and repeat on overflow (by slot_collect's steps), then the sorted
 // records and tries behind d->batch_cands / batch_tries, in virtual offsets.
 int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void *const *p, const size_t *n)
 {
@@ -97,8 +97,6 @@ int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void
     fill_scan_args(d, a);
     a.passes = L.passes;
     a.big_tiles = 0;
-    a.counters = s.d_counters; // zero: cleared at creation, and the report kernel behind every scan leaves them so
-    a.profile = d->cfg.profile ? 1 : 0;
     s.streaming = false;
     s.tries_on_device = s.try_regions = false;
     s.epoch_base = 0;
@@ -106,40 +104,26 @@ int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void
     if (slot_order_behind_count(d, s, ls)) // (as slot_launch: what may still use the slot's past)
         return -1;
     const auto t_wait = clk::now();
+    // (slot_collect's loop -- await_counters -- waits for a launch that is in flight and relaunches through slot_launch; this one
+    // launches itself, every time round, and waits at once: the two share their steps, not the loop)
     for (int attempt = 0;; attempt++) {
-        s.ev_cur ^= 1;
-        if (slot_settle_profile(d, s, s.ev_cur))
+        if (slot_begin_launch(d, s, ls, offsets))
             return -1;
-        s.ev_offsets[s.ev_cur] = offsets;
-        if (s.launch_stream && s.launch_stream != ls)
-            HIP_TRY(d, hipStreamWaitEvent(ls, s.ev_ready[s.ev_cur ^ 1], 0));
-        s.launch_stream = ls;
-        a.gen = ++d->launch_gen * 0x9E3779B9u + 0x7F4A7C15u;
-        a.cands = s.cands;
-        a.cand_cap = (uint32_t)std::min<size_t>(s.cand_cap, 0xFFFFFFFFu);
         a.tries = s.tries;
         a.try_cap = (uint32_t)std::min<size_t>(s.tries.cap, 0xFFFFFFFFu);
-        a.report = s.hc();
         s.busy = true; // (a failure from here on leaves a launch in flight: adsb_reset waits for it)
         HIP_TRY(d, adsb::launch_scan_batch(a, seg_d, tile_d, L.tiles, stats, ls));
         HIP_TRY(d, hipEventRecord(s.ev_ready[s.ev_cur], ls));
         WAIT_EVENT(d, s.ev_ready[s.ev_cur], "a batch scan launch");
         s.busy = false;
-        s.prof_pending[s.ev_cur] = d->cfg.profile != 0;
+        book_launch(d, s, offsets);
         if (slot_settle_profile(d, s, s.ev_cur))
             return -1;
-        d->prof.launches++;
-        d->prof.offsets += offsets;
-        d->prof.last_offsets = offsets;
-        const size_t nc = s.hc()[0], nt = s.hc()[1];
-        if (nc <= s.cand_cap && nt <= s.tries.cap)
-            break;
-        // the counters keep counting past the capacities: one repeat with exact sizes suffices (slot_collect)
-        if (attempt >= 2)
-            return d->fail("record buffers overflowed repeatedly (%zu candidates, %zu tries)", nc, nt);
-        d->prof.relaunches++;
-        if (slot_reserve(d, s, std::max(s.cand_cap, nc + nc / 8 + 64), std::max(s.tries.cap, nt + nt / 8 + 64)))
+        const int again = regrow_if_overflowed(d, s, attempt); // (the stream it waits for first is idle here)
+        if (again < 0)
             return -1;
+        if (!again)
+            break;
     }
     const auto t_host = clk::now();
     d->prof.wait_ms += std::chrono::duration<double, std::milli>(t_host - t_wait).count();
@@ -151,16 +135,8 @@ int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void
     d->prof.tries += nt;
     const size_t at = d->batch_cands.size();
     d->batch_cands.resize(at + nc);
-    for (size_t i = 0; i < nc; i++) {
-        const uint32_t *r = s.cands + (size_t)d->order[i] * adsb::kCandWords;
-        adsb_candidate &c = d->batch_cands[at + i];
-        std::memset(&c, 0, sizeof c);
-        c.g = L.g_begin + r[0];
-        c.pw = r[1];
-        std::memcpy(c.frame, &r[2], 14);
-        c.len = (uint8_t)((r[5] >> 16) & 0xFF);
-        c.reserved = (uint8_t)((r[5] >> 24) & 1u);
-    }
+    for (size_t i = 0; i < nc; i++)
+        d->batch_cands[at + i] = adsb::record_candidate(s.cands + (size_t)d->order[i] * adsb::kCandWords, L.g_begin);
     const size_t tat = d->batch_tries.size();
     d->batch_tries.resize(tat + nt);
     for (size_t i = 0; i < nt; i++)

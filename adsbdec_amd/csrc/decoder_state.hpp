@@ -1,10 +1,11 @@
 // decoder_state.hpp -- what the units of the library's host side share (internal): the handle and its launch slots, the
 // waits with a deadline, and the functions one unit calls in another.
-//   decoder.hip            the stream machinery: staging, launch, hand-off collect, count passes; the push calls
+//   decoder.hip            the stream machinery: staging, launch, count passes; the push calls
+//   decoder_collect.hip    the collect of a launch's records, while it runs (the hand-off stream) or after, and its steps
 //   decoder_lifecycle.hip  create, destroy, reset; the device, NUMA and pinned-memory helpers
 //   decoder_batch.hip      a batch of independent captures (adsb_decode_batch_*)
 //   decoder_shard.hip      the shard calls of the multi-GPU driver (adsb_scan_shard*, adsb_shard_begin / _end)
-// Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder.hip.
+// Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -195,8 +196,9 @@ struct adsb_decoder {
 
     adsb_profile prof{};
     adsb::Resolver res;
-    std::vector<uint32_t> order, scratch_a, scratch_b, gather, tile_start, tile_count;
-    adsb::StreamReader *reader = nullptr;    // the thread that reads the hand-off stream (slot_collect_streaming): cfg.host_threads = 2
+    std::vector<uint32_t> order, scratch_a, scratch_b, tile_start, tile_count;
+    adsb::FinishScratch finish_scratch; // a launch that is finished after completion (handoff.hpp)
+    adsb::StreamReader *reader = nullptr;    // the thread that reads the hand-off stream (decoder_collect.hip): cfg.host_threads = 2
                                              // from the start, 0 (auto) from the first launch that follows a dense one
     bool reader_failed = false;              // no thread could be had: do not try again
     adsb::FormatGang *gang = nullptr;        // the threads that write the frames of dense launches (gang.hpp): cfg.host_threads >= 3, or auto
@@ -384,17 +386,27 @@ inline uint64_t power_samples_produced(uint64_t n_samples)
     return 2 * (n_samples / 4); // air.c:59-92: two power samples per four input samples
 }
 
+// Did the previous launch of this handle hand over a record per 2 048 offsets or more (and 16 384 at least)?  The traffic of a
+// channel does not change from one launch to the next: the host side starts its helper threads on this (decoder_collect.hip
+// choose_helpers), and the next launch takes tiles of six passes instead of seven (adsb::choose_passes).
+constexpr uint64_t kAutoReaderRecords = 65536, kAutoReaderMinRecords = 16384;
+inline bool last_launch_was_dense(const adsb_decoder *d)
+{
+    const uint64_t dense_from = std::max<uint64_t>(kAutoReaderMinRecords, std::min<uint64_t>(kAutoReaderRecords, d->last_launch_offsets / 2048));
+    return d->last_launch_records >= dense_from;
+}
+
 // ---- what one unit calls in another, each per launch or per API call ----
 // decoder.hip
 int scan_submit(adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, uint64_t buf_n, uint64_t g_begin, uint64_t g_end);
-int scan_drain(adsb_decoder *d);
 int slot_reserve(adsb_decoder *d, ScanSlot &s, size_t want_cands, size_t want_tries);
+int slot_reserve_device_tries(adsb_decoder *d, ScanSlot &s, size_t want_list, size_t want_tiles);
 int slot_settle_profile(adsb_decoder *d, ScanSlot &s, int copy);
 int slot_order_behind_count(adsb_decoder *d, ScanLaunch &s, hipStream_t st);
+int slot_begin_launch(adsb_decoder *d, ScanSlot &s, hipStream_t ls, uint64_t offsets);
+int slot_launch(adsb_decoder *d, ScanSlot &s);
 void fill_scan_args(const adsb_decoder *d, ScanArgs &a);
 void scan_record_room(const adsb_decoder *d, uint64_t n_offsets, size_t *cand_want, size_t *try_want);
-void sort_order(adsb_decoder *d, const uint32_t *recs, size_t n);
-void sort_tries(adsb_decoder *d, uint32_t *t, size_t n);
 int count_flush(adsb_decoder *d);
 int count_tries_pass(adsb_decoder *d, ScanLaunch *slot, const uint32_t *tries, const uint32_t *try_counts, uint32_t n_tries,
                      uint64_t g_base, bool final);
@@ -403,6 +415,15 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight = false);
 int wait_last_copy(adsb_decoder *d);
 bool stream_too_long(adsb_decoder *d, size_t n);
 bool shard_too_long(adsb_decoder *d, const char *what, uint64_t first_sample, uint64_t n, uint64_t total_samples);
+// decoder_collect.hip
+int slot_collect(adsb_decoder *d);
+int scan_drain(adsb_decoder *d);
+void sort_order(adsb_decoder *d, const uint32_t *recs, size_t n);
+void sort_tries(adsb_decoder *d, uint32_t *t, size_t n);
+void deliver(adsb_decoder *d, const ScanLaunch &s, const uint32_t *recs, const uint32_t *order, size_t nc, int words, int off,
+             const uint32_t *tries, size_t nt, uint64_t g_complete);
+void book_launch(adsb_decoder *d, ScanSlot &s, uint64_t offsets);
+int regrow_if_overflowed(adsb_decoder *d, ScanSlot &s, int attempt);
 void start_reader(adsb_decoder *d);
 void start_gang(adsb_decoder *d, int helpers);
 // decoder_lifecycle.hip

@@ -5,13 +5,16 @@
 // (output.c:159-202).  Here the producer is a GPU that cannot take a mutex, so the consumer polls memory the device
 // writes and decides from the bytes alone when a tile is complete:
 //   HandCursor    where the host stands in one launch's stream: marker check, tile ranges, frontier
+//   walk_what_is_there   the cursor over bytes nothing will complete any more (an ended launch, an image): one look per marker
 //   StreamReader  cfg.host_threads = 2: a thread of the handle's own that runs the cursor and publishes the frontier
 //   collect_alone / collect_behind_reader   the two consumer loops (the calling thread resolves through `flush`)
+//   finish_after_completion   an ended launch some of whose records are on the loose list: tile by tile, both sources merged
+// The stream is walked by HandCursor and by nothing else: whoever needs tile ranges goes through one of the three loops.
 //
 // Host-only code: no HIP in here.  The one question only the device runtime can answer -- "has the launch behind these
 // bytes ended?" -- comes in as a callback, so that the whole of this file is built and run WITHOUT a GPU: the format is
-// pinned by tests/test_handoff_cpu.py (adsb_handoff_walk), the threading by tests/cpp/handoff_tsan.cpp under
-// ThreadSanitizer and AddressSanitizer with a thread that plays the device (random completion order, torn writes).
+// pinned by tests/test_handoff_cpu.py (adsb_handoff_walk, adsb_handoff_finish), the threading by tests/cpp/handoff_tsan.cpp
+// under ThreadSanitizer and AddressSanitizer with a thread that plays the device (random completion order, torn writes).
 // x86-64 only (SSE2 loads, `pause`): the hosts MI355X ships in.
 #pragma once
 
@@ -20,8 +23,10 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <thread>
+#include <vector>
 
 #if !defined(__x86_64__)
 #error "handoff.hpp reads the device's stores with SSE2 loads and paces its polls with `pause`: x86-64 hosts only (the hosts MI355X ships in); see DESIGN.md section 4"
@@ -30,6 +35,7 @@
 #include <pthread.h>
 #include <sched.h>
 
+#include "../../include/adsbdec_amd_diag.h"
 #include "scan_kernel_format.h"
 
 namespace adsb {
@@ -44,6 +50,17 @@ struct HandJob {
     // (adsb_handoff_walk over an image of a stream: one look).
     int (*done)(void *ctx) = nullptr;
     void *ctx = nullptr;
+};
+
+// How a collect ended: 0 every tile is in and has been handed on; 1 finish after completion (a tile has records on the loose
+// list, or the stream is full: tiles from `delivered` on wait for the launch's end); -1 the stream is corrupt (a tile twice);
+// -2 the launch ended and the bytes never came.  pos / tile: where the cursor stood; frontier: every tile below is in the stream
+// and checked (t_start / t_count say where), whether or not it could be handed on yet: those below `hold` could.
+struct CollectEnd {
+    int status = 0;
+    uint32_t pos = 0, tile = 0, frontier = 0, hold = ~0u;
+    bool tries_listed = false; // kMarkTries seen: the launch-wide try list is in use, its length comes with the launch's counters
+    uint32_t deliverable() const { return std::min(frontier, hold); }
 };
 
 struct HandCursor {
@@ -150,17 +167,28 @@ struct HandCursor {
             frontier++;
         return 0;
     }
+    // The loop over the cursor has ended with `status` (as CollectEnd says; 0: every tile is in -- but one of them may hold)
+    CollectEnd ended(int status) const
+    {
+        CollectEnd e;
+        e.status = status == 0 && hold != ~0u ? 1 : status;
+        e.pos = pos, e.tile = tile, e.frontier = frontier, e.hold = hold;
+        e.tries_listed = tries_listed;
+        return e;
+    }
 };
 
-// How a collect ended: 0 every tile is in and has been handed on; 1 finish after completion (a tile has records on the loose
-// list, or the stream is full: tiles from `delivered` on wait for the launch's end); -1 the stream is corrupt (a tile twice);
-// -2 the launch ended and the bytes never came.  pos / tile: where the cursor stood; frontier: every tile below is in the
-// stream and checked (t_start / t_count say where), whether or not it could be handed on yet.
-struct CollectEnd {
+// The launch behind these bytes has ended, or there never was one (job.done is null): walk what is there, one look per marker.
+// Fills t_start / t_count (the caller has set every count to ~0u).  Ends like a collect, and -2 says that the bytes at the
+// cursor are no valid marker of this launch: a foreign tile, a range past the capacity, a check that fails.
+inline CollectEnd walk_what_is_there(const HandJob &job, uint32_t *t_start, uint32_t *t_count)
+{
+    HandCursor cur(job, t_start, t_count);
     int status = 0;
-    uint32_t pos = 0, tile = 0, frontier = 0;
-    bool tries_listed = false; // kMarkTries seen: the launch-wide try list is in use, its length comes with the launch's counters
-};
+    while (status == 0 && cur.frontier < job.ntiles)
+        status = cur.pos >= cur.cap ? 1 : !cur.tile_in() ? -2 : cur.take();
+    return cur.ended(status);
+}
 
 // A decoder's second host thread (cfg.host_threads = 2): it reads and checks the hand-off stream of the launch being
 // collected and publishes how far the stream is complete, while the calling thread resolves behind it.  One thread
@@ -223,13 +251,7 @@ struct StreamReader {
             if (cur.deliverable() - published >= kPublishEvery)
                 frontier.store(published = cur.deliverable(), std::memory_order_release);
         }
-        if (status == 0 && cur.hold != ~0u)
-            status = 1;
-        end.status = status;
-        end.pos = cur.pos;
-        end.tile = cur.tile;
-        end.frontier = cur.frontier;
-        end.tries_listed = cur.tries_listed;
+        end = cur.ended(status);
         wait_ms = cur.wait_ms;
         busy_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count() - cur.wait_ms;
         frontier.store(cur.deliverable(), std::memory_order_release); // (what the caller may hand on: tiles below the first that holds)
@@ -369,10 +391,10 @@ CollectEnd collect_alone(const HandJob &job, uint32_t *t_start, uint32_t *t_coun
                          HandCursor::clk::time_point &t_last_wait)
 {
     HandCursor cur(job, t_start, t_count);
-    CollectEnd end;
+    int status = 0;
     while (cur.frontier < job.ntiles) {
         if (cur.pos >= cur.cap) { // the stream is full: the rest of the launch is on the loose list
-            end.status = 1;
+            status = 1;
             break;
         }
         if (!cur.tile_in()) {
@@ -382,27 +404,21 @@ CollectEnd collect_alone(const HandJob &job, uint32_t *t_start, uint32_t *t_coun
                 continue;
             }
             if (!cur.wait_tile()) {
-                end.status = -2;
+                status = -2;
                 break;
             }
         }
-        const int rc = cur.take();
-        if (rc != 0) {
-            end.status = rc;
+        if ((status = cur.take()) != 0)
             break;
-        }
         if (cur.deliverable() > delivered &&
             cur.deliverable() - delivered >= (job.ntiles - delivered > kCollectTailTiles ? kCollectGroup : kCollectTailGroup))
             flush(cur.deliverable());
     }
-    if (end.status >= 0 && cur.deliverable() > delivered)
+    if (status >= 0 && cur.deliverable() > delivered)
         flush(cur.deliverable());
-    if (end.status == 0 && cur.hold != ~0u)
-        end.status = 1;
-    end.pos = cur.pos;
-    end.frontier = cur.frontier;
-    end.tries_listed = cur.tries_listed;
-    end.tile = end.status == -2 ? cur.frontier : cur.tile;
+    CollectEnd end = cur.ended(status);
+    if (status == -2)
+        end.tile = cur.frontier;
     wait_ms = cur.wait_ms;
     t_last_wait = cur.t_last_wait;
     return end;
@@ -456,6 +472,127 @@ CollectEnd collect_behind_reader(StreamReader &rd, const HandJob &job, uint32_t 
     if (end.status == -2)
         end.tile = delivered;
     return end;
+}
+
+// ---- a launch that is finished after completion --------------------------------------------------------------------------
+// A record of the loose list: the six words {g_rel, pw, frame | len << 16 | flags << 24} (scan_kernel.h kCandWords).  A record
+// of the stream begins with the same six and may stand for up to three copies (scan_kernel_format.h).
+constexpr int kLooseWords = 6;
+
+// Copy k of record r (k > 0: a stream record's further copies) as the candidate at offset g_base + g_rel + k.
+inline adsb_candidate record_candidate(const uint32_t *r, uint64_t g_base, uint32_t k = 0)
+{
+    adsb_candidate c;
+    std::memset(&c, 0, sizeof c);
+    c.g = g_base + r[0] + k;
+    c.pw = rec_pw(r, k);
+    std::memcpy(c.frame, &r[2], 14);
+    c.len = (uint8_t)((r[5] >> 16) & 0xFF);
+    c.reserved = (uint8_t)((r[5] >> 24) & 1u);
+    return c;
+}
+
+// LSD radix sort of the record indices by their 30-bit g_rel (3 x 10 bits): order[0 .. n) afterwards; tmp and key are scratch.
+inline void order_by_g_rel(const uint32_t *recs, size_t n, std::vector<uint32_t> &order, std::vector<uint32_t> &scratch_tmp,
+                           std::vector<uint32_t> &scratch_key)
+{
+    order.resize(n);
+    scratch_tmp.resize(n);
+    scratch_key.resize(n);
+    uint32_t *idx = order.data(), *tmp = scratch_tmp.data(), *key = scratch_key.data();
+    bool sorted = true;
+    for (size_t i = 0; i < n; i++) {
+        idx[i] = (uint32_t)i;
+        key[i] = recs[i * kLooseWords];
+        if (i && key[i] < key[i - 1])
+            sorted = false;
+    }
+    if (sorted)
+        return;
+    for (int shift = 0; shift < 30; shift += 10) {
+        uint32_t hist[1025] = {0};
+        for (size_t i = 0; i < n; i++)
+            hist[((key[idx[i]] >> shift) & 1023u) + 1]++;
+        for (int b = 0; b < 1024; b++)
+            hist[b + 1] += hist[b];
+        for (size_t i = 0; i < n; i++)
+            tmp[hist[(key[idx[i]] >> shift) & 1023u]++] = idx[i];
+        std::swap(idx, tmp);
+    }
+    if (idx != order.data())
+        std::memcpy(order.data(), idx, n * sizeof(uint32_t)); // odd number of passes
+}
+
+struct FinishScratch {
+    std::vector<uint32_t> loose, order, tmp, key; // the loose records that are still to be handed on, and their order
+    std::vector<uint32_t> merged;                 // one tile's records, kLooseWords each, ascending
+};
+
+// Some tile could not put all its records into the hand-off stream (staged list or survivor queue overflowed, its range did
+// not fit): those records are on the loose list, which is only complete now that the kernel has ended.  t_start / t_count say
+// where each tile's records lie in the stream (~0u: nowhere).  Tiles [resume_tile, ntiles) are handed on in order: runs of
+// tiles that are whole in the stream where they lie -- tiles(from, upto) -- like the streaming collect does; a tile with loose
+// records, or none in the stream at all, merged on the way -- records(ptr, n, g_complete): n records of kLooseWords words,
+// ascending, and everything below g_complete has then been handed on.  The LOOSE records (few) are sorted for it.  (Round 3
+// gathered and sorted everything that was left: 4 ms for the 311 k records of a dense launch in which ONE early tile had
+// overflowed.)
+// tile_first(u): the first offset of tile u relative to g_begin (scan_kernel.h's geometry, which needs HIP and so comes in as a
+// callable); loose: n_loose_all records of the launch's loose list, in arrival order.
+template <class TileFirst, class Tiles, class Records>
+void finish_after_completion(const uint32_t *hand, const uint32_t *t_start, const uint32_t *t_count, uint32_t ntiles, uint32_t resume_tile,
+                             uint64_t g_begin, uint64_t g_end, TileFirst &&tile_first, const uint32_t *loose_all, size_t n_loose_all,
+                             FinishScratch &sc, Tiles &&tiles, Records &&records)
+{
+    // The loose list may also hold records of tiles the streamed part has already delivered: after a relaunch (record
+    // buffers regrown) every tile runs again, and whether a tile's range fits the stream depends on completion order.
+    const uint64_t resume_rel = tile_first(resume_tile);
+    sc.loose.clear();
+    for (size_t i = 0; i < n_loose_all; i++) {
+        const uint32_t *w = loose_all + i * kLooseWords;
+        if (w[0] >= resume_rel)
+            sc.loose.insert(sc.loose.end(), w, w + kLooseWords);
+    }
+    const size_t n_loose = sc.loose.size() / kLooseWords;
+    order_by_g_rel(sc.loose.data(), n_loose, sc.order, sc.tmp, sc.key);
+    size_t li = 0;
+    uint32_t run_from = resume_tile;
+    for (uint32_t u = resume_tile; u < ntiles; u++) {
+        const uint64_t hi_rel = tile_first(u + 1);
+        size_t lj = li;
+        while (lj < n_loose && sc.loose[(size_t)sc.order[lj] * kLooseWords] < hi_rel)
+            lj++;
+        if (t_count[u] != ~0u && lj == li)
+            continue; // whole in the stream: part of the current run
+        if (u > run_from)
+            tiles(run_from, u);
+        // this tile: its records in the stream (if it got that far) merged with its loose ones, both ascending
+        sc.merged.clear();
+        const uint32_t ns = t_count[u] == ~0u ? 0u : t_count[u];
+        const uint32_t *sr = hand + (size_t)t_start[u] * kGranuleWords;
+        uint32_t si = 0;
+        while (si < ns || li < lj) {
+            const uint32_t *lw = li < lj ? sc.loose.data() + (size_t)sc.order[li] * kLooseWords : nullptr;
+            const uint32_t *sw = si < ns ? sr + (size_t)si * 2 * kGranuleWords : nullptr;
+            if (sw && (!lw || sw[0] <= lw[0])) {
+                // {g_rel, pw, w0, w1}{w2, w3, pw', pw''}: the first six words, once per offset the record stands for (a run
+                // of copies is never interleaved with a loose record: the offsets are consecutive and every offset yields
+                // at most one candidate -- but a loose one may lie INSIDE the run only if it is one of its offsets, which
+                // the tile would have staged with the others; so the run goes in whole)
+                for (uint32_t k = 0, nk = rec_copies(sw); k < nk; k++) {
+                    const uint32_t one[kLooseWords] = {sw[0] + k, rec_pw(sw, k), sw[2], sw[3], sw[4], sw[5] & ~(3u << kRecCopiesShift)};
+                    sc.merged.insert(sc.merged.end(), one, one + kLooseWords);
+                }
+                si++;
+            } else {
+                sc.merged.insert(sc.merged.end(), lw, lw + kLooseWords);
+                li++;
+            }
+        }
+        records(sc.merged.data(), sc.merged.size() / kLooseWords, std::min<uint64_t>(g_end, g_begin + hi_rel));
+        run_from = u + 1;
+    }
+    if (ntiles > run_from)
+        tiles(run_from, ntiles);
 }
 
 } // namespace adsb

@@ -1,5 +1,5 @@
 // host_abi.cpp -- the part of the C-ABI (include/adsbdec_amd.h) that needs no device: configuration defaults, shard
-// planning, the greedy resolver handle, the stitcher, the hand-off stream walk.  Built without HIP, so that the same
+// planning, the greedy resolver handle, the stitcher, the hand-off stream's walk and its finish after completion.  Built without HIP, so that the same
 // object links into libadsbdec_amd.so and into the sanitizer harnesses under tests/cpp/ (which run where no GPU is).
 #include <algorithm>
 #include <cstddef>
@@ -9,13 +9,45 @@
 #include <vector>
 
 #include "../../include/adsbdec_amd_diag.h"
+#include "batch.hpp"
 #include "handoff.hpp"
 #include "resolver.hpp"
 #include "stitch.hpp"
 
 namespace {
 inline uint64_t round_down(uint64_t v, uint64_t q) { return v - v % q; }
-using adsb::HandCursor;
+
+// An image of a hand-off stream as the cursor wants it: the checks read 16-byte granules with aligned loads, so they walk a
+// 64-byte-aligned copy.  No launch is behind these bytes: job.done stays null, every wait is one look.
+struct StreamImage {
+    void *copy = nullptr;
+    adsb::HandJob job;
+    StreamImage(const void *stream, size_t granules, uint32_t n_tiles, uint32_t gen)
+    {
+        const size_t bytes = granules * adsb::kGranuleWords * sizeof(uint32_t);
+        if (posix_memalign(&copy, 64, bytes ? bytes : 64) != 0) {
+            copy = nullptr;
+            return;
+        }
+        std::memcpy(copy, stream, bytes);
+        job.hand = static_cast<const uint32_t *>(copy);
+        job.ntiles = n_tiles;
+        job.gen = gen;
+        job.cap = (uint32_t)granules;
+    }
+    ~StreamImage() { free(copy); }
+};
+
+// The first offset of a launch's tile, relative to the launch's: scan_kernel.h tile_first_run x kRun (that header needs HIP).
+// A tile of k passes owns batch_tile_offsets(k) offsets -- batch.hpp's restatement, which decoder_batch.hip holds to
+// scan_kernel.h -- and the tiles from `big_tiles` on (0: none) are tiles of four passes (kTaperPasses).
+uint64_t tile_first_offset(uint32_t tile, uint32_t big_tiles, int k)
+{
+    constexpr int kTaper = 4;
+    if (big_tiles == 0 || tile <= big_tiles || k <= kTaper)
+        return tile * adsb::batch_tile_offsets(k);
+    return big_tiles * adsb::batch_tile_offsets(k) + (tile - big_tiles) * adsb::batch_tile_offsets(kTaper);
+}
 } // namespace
 
 extern "C" {
@@ -228,40 +260,14 @@ long adsb_handoff_walk(const void *stream, size_t granules, uint32_t n_tiles, ui
 {
     if (!stream || !tile_start || !tile_count || !status || granules > 0xFFFFFFFFull)
         return -1;
-    // the checks read 16-byte granules with aligned loads: walk a 64-byte-aligned copy
-    const size_t bytes = granules * adsb::kGranuleWords * sizeof(uint32_t);
-    void *copy = nullptr;
-    if (posix_memalign(&copy, 64, bytes ? bytes : 64) != 0)
+    const StreamImage img(stream, granules, n_tiles, gen);
+    if (!img.copy)
         return -1;
-    std::memcpy(copy, stream, bytes);
     for (uint32_t t = 0; t < n_tiles; t++)
         tile_start[t] = 0, tile_count[t] = ~0u;
-    adsb::HandJob job;
-    job.hand = static_cast<const uint32_t *>(copy);
-    job.ntiles = n_tiles;
-    job.gen = gen;
-    job.cap = (uint32_t)granules;
-    HandCursor cur(job, tile_start, tile_count); // (no launch behind these bytes: job.done stays null, every wait is one look)
-    *status = 0;
-    while (cur.frontier < n_tiles) {
-        if (cur.pos >= cur.cap) {
-            *status = 1;
-            break;
-        }
-        if (!cur.wait_tile()) { // (no launch behind these bytes: one look)
-            *status = 2;
-            break;
-        }
-        const int rc = cur.take();
-        if (rc != 0) {
-            *status = rc < 0 ? -1 : 1;
-            break;
-        }
-    }
-    if (*status == 0 && cur.hold != ~0u)
-        *status = 1; // every tile is in, but from the one that holds on they wait for the launch's end
-    free(copy);
-    return (long)cur.deliverable();
+    const adsb::CollectEnd end = adsb::walk_what_is_there(img.job, tile_start, tile_count);
+    *status = end.status == -2 ? 2 : end.status; // (1 also: every tile is in, but from the one that holds on they wait for the launch's end)
+    return (long)end.deliverable();
 }
 
 // The streaming collect's hand-over to the resolver, over an image of a stream: every tile must be in (adsb_handoff_walk's
@@ -273,38 +279,76 @@ long adsb_resolver_advance_stream(adsb_resolver *r, const void *stream, size_t g
 {
     if (!r || !stream || granules > 0xFFFFFFFFull || n_tiles == 0)
         return -1;
-    const size_t bytes = granules * adsb::kGranuleWords * sizeof(uint32_t);
-    void *copy = nullptr;
-    if (posix_memalign(&copy, 64, bytes ? bytes : 64) != 0)
+    const StreamImage img(stream, granules, n_tiles, gen);
+    if (!img.copy)
         return -1;
-    std::memcpy(copy, stream, bytes);
     std::vector<uint32_t> ts(n_tiles, 0u), tc(n_tiles, ~0u);
-    adsb::HandJob job;
-    job.hand = static_cast<const uint32_t *>(copy);
-    job.ntiles = n_tiles;
-    job.gen = gen;
-    job.cap = (uint32_t)granules;
-    HandCursor cur(job, ts.data(), tc.data());
+    if (adsb::walk_what_is_there(img.job, ts.data(), tc.data()).status != 0)
+        return -1;
     long rc = (long)n_tiles;
-    while (cur.frontier < n_tiles)
-        if (cur.pos >= cur.cap || !cur.wait_tile() || cur.take() != 0) {
-            rc = -1;
-            break;
-        }
-    if (rc >= 0 && cur.hold != ~0u)
+    try {
+        if (with_head)
+            r->r.capture_head_tiles(img.job.hand, ts.data(), tc.data(), 0, n_tiles, g_base);
+        r->r.advance_tiles(img.job.hand, ts.data(), tc.data(), 0, n_tiles, g_base, power_samples, g_complete);
+    } catch (const std::exception &) {
         rc = -1;
-    if (rc >= 0) {
-        try {
-            if (with_head)
-                r->r.capture_head_tiles(job.hand, ts.data(), tc.data(), 0, n_tiles, g_base);
-            r->r.advance_tiles(job.hand, ts.data(), tc.data(), 0, n_tiles, g_base, power_samples, g_complete);
-        } catch (const std::exception &) {
-            rc = -1;
-        }
-        r->r.sync(); // (the gang's threads read the records where they lie: in the copy)
     }
-    free(copy);
+    r->r.sync(); // (the gang's threads read the records where they lie: in the copy)
     return rc;
+}
+
+// What the decoder does with a launch that has ended with records on the loose list (decoder_collect.hip), over an image of
+// its stream: the same walk, the same adsb::finish_after_completion; the two hand-overs append to `out` what the decoder's
+// give to its sink.
+long adsb_handoff_finish(const void *stream, size_t granules, uint32_t n_tiles, uint32_t gen, int passes, uint32_t big_tiles,
+                         uint64_t g_begin, uint64_t g_end, uint32_t resume_tile, const uint32_t *loose, size_t n_loose,
+                         const uint32_t *tile_start, const uint32_t *tile_count, adsb_candidate *out, size_t out_cap,
+                         uint64_t *handed, uint64_t *g_complete, size_t handover_cap, size_t *n_handovers)
+{
+    if (!stream || granules > 0xFFFFFFFFull || passes < 2 || passes > 32 || resume_tile > n_tiles || g_end < g_begin ||
+        (n_loose && !loose) || !tile_start != !tile_count || (out_cap && !out) || (handover_cap && (!handed || !g_complete)) || !n_handovers)
+        return -1;
+    const StreamImage img(stream, granules, n_tiles, gen);
+    if (!img.copy)
+        return -1;
+    std::vector<uint32_t> ts(n_tiles, 0u), tc(n_tiles, ~0u);
+    if (tile_start) { // where every tile's records lie is known from an earlier walk
+        ts.assign(tile_start, tile_start + n_tiles);
+        tc.assign(tile_count, tile_count + n_tiles);
+    } else {
+        adsb::walk_what_is_there(img.job, ts.data(), tc.data()); // (whatever ends the walk: the tiles behind it are loose-only)
+    }
+    const auto tile_first = [&](uint32_t u) { return tile_first_offset(u, big_tiles, passes); };
+    size_t n_out = 0, n_over = 0;
+    const auto handover = [&](uint64_t upto_g) {
+        if (n_over < handover_cap)
+            handed[n_over] = n_out, g_complete[n_over] = upto_g;
+        n_over++;
+    };
+    const auto put = [&](const uint32_t *r, uint32_t k) {
+        if (n_out < out_cap)
+            out[n_out] = adsb::record_candidate(r, g_begin, k);
+        n_out++;
+    };
+    adsb::FinishScratch scratch;
+    adsb::finish_after_completion(
+        img.job.hand, ts.data(), tc.data(), n_tiles, resume_tile, g_begin, g_end, tile_first, loose, n_loose, scratch,
+        [&](uint32_t from, uint32_t upto) {
+            for (uint32_t u = from; u < upto; u++)
+                for (uint32_t i = 0; i < tc[u]; i++) {
+                    const uint32_t *r = img.job.hand + (size_t)(ts[u] + 2 * i) * adsb::kGranuleWords;
+                    for (uint32_t k = 0, nk = adsb::rec_copies(r); k < nk; k++)
+                        put(r, k);
+                }
+            handover(std::min<uint64_t>(g_end, g_begin + tile_first(upto)));
+        },
+        [&](const uint32_t *recs, size_t n, uint64_t upto_g) {
+            for (size_t i = 0; i < n; i++)
+                put(recs + i * adsb::kLooseWords, 0);
+            handover(upto_g);
+        });
+    *n_handovers = n_over;
+    return (long)n_out;
 }
 
 } // extern "C"

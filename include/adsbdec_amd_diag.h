@@ -95,6 +95,23 @@ long adsb_handoff_walk(const void *stream, size_t granules, uint32_t n_tiles, ui
  * expanded candidates; with_head != 0 also copies the head candidates of a chain (adsb_resolver_head).  Returns n_tiles or -1. */
 long adsb_resolver_advance_stream(adsb_resolver *r, const void *stream, size_t granules, uint32_t n_tiles, uint32_t gen,
                                   uint64_t g_base, uint64_t power_samples, uint64_t g_complete, int with_head);
+/* adsb_handoff_finish: what the decoder does with a launch that has ended with records on the LOOSE list -- a tile's staged
+ * list or survivor queue overflowed, or its range did not fit the stream -- over such an image, by the decoder's own code.  The
+ * launch covered the offsets [g_begin, g_end) with n_tiles tiles of `passes` passes (2..32), those from big_tiles on (0: none)
+ * of four; `granules` is what of the stream may be read (the launch's count of granules used, at most the array's size);
+ * tiles below resume_tile were handed on while the launch ran.  loose: n_loose records of six words {g_rel, pw, frame bytes |
+ * len << 16 | flags << 24}, in any order.  The image is walked until the first marker that does not validate (also: a tile
+ * flagged 0x20000, a tile a second time; none of them is an error here) -- or, tile_start / tile_count not NULL (n_tiles
+ * entries each, as adsb_handoff_walk fills them), the ranges of an earlier walk are taken as they are.  Then the tiles from
+ * resume_tile on are handed on in order: runs of tiles whose records are all in the stream as they lie there, a tile that has
+ * loose records (those below resume_tile's first offset are dropped: they were handed on before) merged from both sources.
+ * out receives the candidates in hand-over order, a record that stands for copies expanded (at most out_cap are written);
+ * hand-over i is out[handed[i-1] .. handed[i]) and says that every offset below g_complete[i] has been handed on (at most
+ * handover_cap entries are written, *n_handovers = how many there were).  Returns the number of candidates, or -1. */
+long adsb_handoff_finish(const void *stream, size_t granules, uint32_t n_tiles, uint32_t gen, int passes, uint32_t big_tiles,
+                         uint64_t g_begin, uint64_t g_end, uint32_t resume_tile, const uint32_t *loose, size_t n_loose,
+                         const uint32_t *tile_start, const uint32_t *tile_count, adsb_candidate *out, size_t out_cap,
+                         uint64_t *handed, uint64_t *g_complete, size_t handover_cap, size_t *n_handovers);
 
 /* Scan a stand-alone device buffer that holds stream samples
  * [first_sample, first_sample+n) for the owned offsets [g_begin, g_end) and

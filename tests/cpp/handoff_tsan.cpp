@@ -1,6 +1,6 @@
 // handoff_tsan.cpp -- the host side of the device -> host hand-off (adsbdec_amd/csrc/handoff.hpp: HandCursor, StreamReader,
-// collect_alone, collect_behind_reader) and the resolver behind it (resolver.hpp advance_tiles), with a THREAD playing the
-// device.  Built twice by tests/test_sanitizers.py: -fsanitize=thread, and -fsanitize=address,undefined.  No GPU.
+// collect_alone, collect_behind_reader, finish_after_completion) and the resolver behind it (resolver.hpp advance_tiles), with a
+// THREAD playing the device.  Built twice by tests/test_sanitizers.py: -fsanitize=thread, and -fsanitize=address,undefined.  No GPU.
 //
 // The "device" writes a launch's stream the way the kernel does, and worse: tiles reserve their ranges in a random
 // completion order; the stream's memory starts out holding a valid stream of ANOTHER launch (other gen: stale bytes that
@@ -8,9 +8,12 @@
 // the marker first, last or in between; some tiles reserve more lines than they keep records for; some launches overflow
 // the stream, flag a tile "finish after completion", publish a tile twice, or never publish one at all.
 // The consumers must deliver exactly the records that were written, tile by tile in ascending order, report the right end
-// status, and -- what the sanitizers are here for -- do so without a data race or a bad access in their OWN
+// status, a launch that asks to be finished after completion must then hand on the sorted union of what its stream and its
+// loose list hold, and -- what the sanitizers are here for -- do so without a data race or a bad access in their OWN
 // synchronisation.  (The device's stores and the cursor's polling loads are the one deliberate exception: see
 // HandCursor::tile_in.)
+#include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -169,6 +172,84 @@ static Launch make_launch(std::mt19937 &rng, int round)
     return L;
 }
 
+// A launch that ended "finish after completion": what the decoder then does (decoder_collect.hip), over the stream the device
+// thread has written.  The tiles that did not fit the stream are on a loose list (shuffled: arrival order), a tile flagged
+// kMarkOver has loose records between its stream records, and some loose records belong to tiles that were delivered long ago.
+// Every record of the tiles from `delivered` on must be handed on once, by hand-overs whose g_complete ascend to g_end.
+static bool finish_pass(const uint32_t *hand, const Launch &L, uint32_t delivered, std::mt19937 &rng, int round, uint64_t &records_merged)
+{
+    using Rec = std::array<uint32_t, kLooseWords>;
+    std::vector<Rec> loose, want;
+    for (uint32_t k = 0, next = 0; k < L.ntiles; k++) {
+        const uint32_t t = L.order[k], base = next;
+        next += L.reserve[t];
+        const bool in_stream = base + L.reserve[t] <= L.cap;
+        for (uint32_t i = 0; i < L.n[t]; i++) {
+            uint32_t w[8];
+            record_words(L.gen, t, i, w);
+            if (!in_stream)
+                w[0] = t * kTileOffsets + 5 + 130 * i; // (a loose record is found by its offset: inside its tile, as the kernel's are)
+            const Rec r = {w[0], w[1], w[2], w[3], w[4], w[5]};
+            if (!in_stream)
+                loose.push_back(r);
+            if (t >= delivered)
+                want.push_back(r);
+        }
+        if (L.flags[t] & kMarkOver)
+            for (uint32_t j = 0; j < 3; j++) { // between its stream records (7, 607, 1207 ..)
+                const Rec r = {t * kTileOffsets + 300 + 600 * j, 77 + j, 0x8Du, j, t, 14u << 16};
+                loose.push_back(r);
+                want.push_back(r);
+            }
+    }
+    if (delivered)
+        loose.push_back(Rec{3, 1, 0x5Du, 0, 0, 7u << 16}); // of tile 0, which went on while the launch ran: not again
+    std::shuffle(loose.begin(), loose.end(), rng);
+    std::sort(want.begin(), want.end());
+    std::vector<uint32_t> t_start(L.ntiles, 0), t_count(L.ntiles, ~0u);
+    HandJob job;
+    job.hand = hand;
+    job.ntiles = L.ntiles;
+    job.gen = L.gen;
+    job.cap = L.cap;
+    walk_what_is_there(job, t_start.data(), t_count.data());
+    const uint64_t g_end = (uint64_t)L.ntiles * kTileOffsets - 17; // (the launch ends inside its last tile)
+    std::vector<Rec> got;
+    std::vector<uint64_t> complete;
+    FinishScratch scratch;
+    finish_after_completion(
+        hand, t_start.data(), t_count.data(), L.ntiles, delivered, 0, g_end, [](uint32_t u) { return (uint64_t)u * kTileOffsets; },
+        loose.empty() ? nullptr : loose[0].data(), loose.size(), scratch,
+        [&](uint32_t from, uint32_t upto) {
+            for (uint32_t u = from; u < upto; u++)
+                for (uint32_t i = 0; i < t_count[u]; i++) {
+                    const uint32_t *r = hand + 4 * (size_t)(t_start[u] + 2 * i);
+                    got.push_back(Rec{r[0], r[1], r[2], r[3], r[4], r[5]});
+                }
+            complete.push_back(std::min<uint64_t>(g_end, (uint64_t)upto * kTileOffsets));
+        },
+        [&](const uint32_t *recs, size_t n, uint64_t g_complete) {
+            for (size_t i = 0; i < n; i++) {
+                const uint32_t *r = recs + i * kLooseWords;
+                if (i && r[0] < r[-kLooseWords]) {
+                    fprintf(stderr, "round %d: a merged tile is not ascending\n", round);
+                    got.clear();
+                    return;
+                }
+                got.push_back(Rec{r[0], r[1], r[2], r[3], r[4], r[5]});
+            }
+            complete.push_back(g_complete);
+        });
+    std::sort(got.begin(), got.end()); // (this model's tiles overlap in g_rel: the hand-overs are compared as the sorted union)
+    if (got != want || complete.empty() || complete.back() != g_end || !std::is_sorted(complete.begin(), complete.end())) {
+        fprintf(stderr, "round %d: finish after completion handed on %zu records in %zu hand-overs, %zu were expected from tile %u on\n", round,
+                got.size(), complete.size(), want.size(), delivered);
+        return false;
+    }
+    records_merged += got.size();
+    return true;
+}
+
 static int run(int rounds, StreamReader &reader);
 
 int main(int argc, char **argv)
@@ -183,7 +264,7 @@ int main(int argc, char **argv)
 static int run(int rounds, StreamReader &reader)
 {
     std::mt19937 rng(20260001);
-    uint64_t tiles_checked = 0, records_checked = 0, frames = 0;
+    uint64_t tiles_checked = 0, records_checked = 0, frames = 0, records_finished = 0;
     int ends[4] = {0, 0, 0, 0};
     uint32_t *hand = nullptr;
     const size_t hand_granules = 1u << 18;
@@ -272,11 +353,13 @@ static int run(int rounds, StreamReader &reader)
             return 1;
         }
         ends[want == 0 ? 0 : want == 1 ? 1 : want == -1 ? 2 : 3]++;
+        if (want == 1 && !finish_pass(hand, L, delivered, rng, round, records_finished))
+            return 1;
         frames += res.pending();
     }
     free(hand);
-    printf("ok: %d launches (%d complete, %d finish-after-completion, %d tile-twice, %d never-published), %llu tiles, %llu records checked, %llu frames resolved\n",
+    printf("ok: %d launches (%d complete, %d finish-after-completion, %d tile-twice, %d never-published), %llu tiles, %llu records checked, %llu frames resolved, %llu records finished after completion\n",
            rounds, ends[0], ends[1], ends[2], ends[3], (unsigned long long)tiles_checked, (unsigned long long)records_checked,
-           (unsigned long long)frames);
+           (unsigned long long)frames, (unsigned long long)records_finished);
     return 0;
 }

@@ -684,7 +684,7 @@ def test_streaming_handoff_is_stable_over_many_launches(oracle, dec_factory, tor
 @pytest.mark.parametrize("threads", [2, 5])
 def test_reader_thread_consumes_the_handoff_stream(capi, oracle, dec_factory, torch_cuda, threads):
     """cfg.host_threads = 2: a second host thread reads and checks the hand-off stream while the caller resolves behind
-    it (decoder.hip StreamReader); cfg.host_threads = 5: that thread, and three more that decide every batch of tiles ahead
+    it (handoff.hpp StreamReader); cfg.host_threads = 5: that thread, and three more that decide every batch of tiles ahead
     of the caller and write the frames (gang.hpp, Resolver::speculate_tiles).  Same frames, same statistics, on every path a
     launch's collect can take: rotating captures on one handle (stale bytes of the previous launch must not be taken),
     chunked pushes, a statistics run, tiles that flag "finish after completion" (staged-list overflow, loose list, relaunch)."""

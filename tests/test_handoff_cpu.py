@@ -1,4 +1,4 @@
-"""The host's reading of the device -> host hand-off stream (decoder.hip HandCursor), on CPU.
+"""The host's reading of the device -> host hand-off stream (handoff.hpp HandCursor), on CPU.
 
 adsb_handoff_walk runs the streaming collect's own marker / checksum / frontier code over an image of a stream in
 ordinary memory.  The images are built here from the documented format (include/adsbdec_amd.h, scan_kernel.h) with an
@@ -231,32 +231,43 @@ def _frame_words(frame: bytes):
     return w
 
 
-def _stream_of(tiles, gen, collapse, tile_offsets=48_160):
-    """tiles: per tile a list of candidates (g_rel, pw, frame) in ascending g_rel.  collapse: runs of the same frame at
+def _records_of(cands, collapse):
+    """The record granules of one tile's candidates (g_rel, pw, frame), ascending.  collapse: runs of the same frame at
     consecutive offsets become one record of up to three (what the kernel writes since round 5); else one record each."""
+    recs, i = [], 0
+    while i < len(cands):
+        g, pw, fr = cands[i]
+        run = 1
+        if collapse:
+            while run < 3 and i + run < len(cands) and cands[i + run][0] == g + run and cands[i + run][2] == fr:
+                run += 1
+        w = _frame_words(fr)
+        pws = [cands[i + k][1] for k in range(run)] + [0, 0]
+        recs.append([g, pw, w[0], w[1]])
+        recs.append([w[2], w[3] | ((run - 1) << 25), pws[1] if run > 1 else 0, pws[2] if run > 2 else 0])
+        i += run
+    return recs
+
+
+def _put_tile(img, ti, cands, collapse, flags=0):
+    """Tile ti's marker and records at the image's end; it reserved for its candidates and may have kept fewer records."""
+    recs = _records_of(cands, collapse)
+    n = len(recs) // 2
+    nf = n | flags | (((len(cands) * 2 + 1 + 3) // 4) << LINES_SHIFT)
+    lo, hi = check_words(ti, nf, img.gen, recs)
+    p = img.pos
+    img.w[4 * p:4 * p + 4] = (ti, nf, lo, hi)
+    if n:
+        img.w[4 * (p + 1):4 * (p + 1 + 2 * n)] = np.asarray(recs, np.uint32).reshape(-1)
+    img.pos += max(((len(cands) * 2 + 1 + 3) // 4) * 4, stream_granules(n))
+    img.where[ti] = (p + 1, n)
+
+
+def _stream_of(tiles, gen, collapse, tile_offsets=48_160):
+    """tiles: per tile a list of candidates (g_rel, pw, frame) in ascending g_rel, written in tile order."""
     img = Image(16 + sum(4 + 2 * len(t) for t in tiles) * 2, gen)
     for ti, cands in enumerate(tiles):
-        recs, i = [], 0
-        while i < len(cands):
-            g, pw, fr = cands[i]
-            run = 1
-            if collapse:
-                while run < 3 and i + run < len(cands) and cands[i + run][0] == g + run and cands[i + run][2] == fr:
-                    run += 1
-            w = _frame_words(fr)
-            pws = [cands[i + k][1] for k in range(run)] + [0, 0]
-            recs.append([g, pw, w[0], w[1]])
-            recs.append([w[2], w[3] | ((run - 1) << 25), pws[1] if run > 1 else 0, pws[2] if run > 2 else 0])
-            i += run
-        n = len(recs) // 2
-        nf = n | (((len(cands) * 2 + 1 + 3) // 4) << LINES_SHIFT)          # the tile reserved for its candidates, kept fewer records
-        lo, hi = check_words(ti, nf, gen, recs)
-        p = img.pos
-        img.w[4 * p:4 * p + 4] = (ti, nf, lo, hi)
-        if n:
-            img.w[4 * (p + 1):4 * (p + 1 + 2 * n)] = np.asarray(recs, np.uint32).reshape(-1)
-        img.pos += max(((len(cands) * 2 + 1 + 3) // 4) * 4, stream_granules(n))
-        img.where[ti] = (p + 1, n)
+        _put_tile(img, ti, cands, collapse)
     return img
 
 
@@ -340,3 +351,226 @@ def test_records_that_stand_for_copies_resolve_like_their_expansion(capi, seed):
         assert got == [(f["g"], f["ts"], f["pw"], bytes(f["frame"])) for f in alone.drain()] == ref[chain]
         assert L.adsb_resolver_set_threads(gang._h, 0, 0) == 0
         alone.close(), gang.close()
+
+
+# ---- a launch that is finished after completion (handoff.hpp finish_after_completion, through adsb_handoff_finish) ---------
+# The decoder's own code for a launch that has ended with records on the loose list, against a model written from the
+# format: the stream up to the first marker that does not validate, the loose list, sorted.
+def tile_first(u, passes, big_tiles):
+    """First offset of tile u relative to the launch's (scan_kernel.h): a tile of K passes owns 252 K - 44 runs of 28 offsets;
+    the tiles from big_tiles on (0: none) take four passes."""
+    own = lambda k: 28 * (252 * k - 44)
+    if big_tiles == 0 or u <= big_tiles or passes <= 4:
+        return u * own(passes)
+    return big_tiles * own(passes) + (u - big_tiles) * own(4)
+
+
+def model_walk(img, n_tiles, granules):
+    """{tile: its records, expanded by their copies, as (g_rel, pw, frame bytes)} of the tiles that are in the stream: markers
+    are read one after the other until the first that does not validate -- a foreign tile, a range past `granules`, check words
+    that do not fit, the NOFIT flag, a tile a second time."""
+    tiles, pos = {}, 0
+    while pos < granules and len(tiles) < n_tiles:
+        tile, nf, lo, hi = (int(v) for v in img.w[4 * pos:4 * pos + 4])
+        n = nf & 0xFFFF
+        if tile >= n_tiles or nf & NOFIT or pos + 1 + 2 * n > granules or tile in tiles:
+            break
+        recs = img.w[4 * (pos + 1):4 * (pos + 1 + 2 * n)].reshape(-1, 4)
+        if (lo, hi) != check_words(tile, nf, img.gen, recs):
+            break
+        out = []
+        for a, b in zip(recs[0::2], recs[1::2]):
+            w3 = int(b[1])
+            frame = b"".join(int(v).to_bytes(4, "little") for v in (a[2], a[3], b[0])) + (w3 & 0xFFFF).to_bytes(2, "little")
+            for k in range(1 + ((w3 >> 25) & 3)):
+                out.append((int(a[0]) + k, int(a[1]) if k == 0 else int(b[1 + k]), frame[:(w3 >> 16) & 0xFF]))
+        tiles[tile] = out
+        pos += max((nf >> LINES_SHIFT) * 4, stream_granules(n))
+    return tiles
+
+
+def loose_words(cands):
+    return [[g, pw] + _frame_words(fr) for g, pw, fr in cands]
+
+
+def finish(capi, img, n_tiles, passes, big_tiles, g_begin, g_end, resume_tile, loose, granules=None, ranges=None):
+    """adsb_handoff_finish -> (candidates as (g, pw, frame bytes), hand-overs as (candidates so far, g_complete))."""
+    L = capi.load()
+    buf = np.ascontiguousarray(img.w)
+    lw = np.ascontiguousarray(np.asarray(loose_words(loose), np.uint32).reshape(-1))
+    out, cap = (capi.Candidate * 4096)(), 4096
+    handed, complete, n_over = (C.c_uint64 * 64)(), (C.c_uint64 * 64)(), C.c_size_t(0)
+    ts = tc = None
+    if ranges is not None:
+        ts, tc = (C.c_uint32 * n_tiles)(*ranges[0]), (C.c_uint32 * n_tiles)(*ranges[1])
+    n = L.adsb_handoff_finish(buf.ctypes.data, granules if granules is not None else buf.size // 4, n_tiles, img.gen, passes, big_tiles,
+                              g_begin, g_end, resume_tile, lw.ctypes.data_as(C.POINTER(C.c_uint32)) if len(loose) else None, len(loose),
+                              ts, tc, out, cap, handed, complete, 64, C.byref(n_over))
+    assert 0 <= n <= cap and n_over.value <= 64
+    return ([(out[i].g, out[i].pw, bytes(out[i].frame[:out[i].len])) for i in range(n)],
+            [(int(handed[i]), int(complete[i])) for i in range(n_over.value)])
+
+
+class Launch:
+    """A launch of 8 tiles that ends mid-tile, its candidates per tile, and what became of them: `stream` lists the tiles that
+    are in the stream in completion order, with their flags; loose[u] are tile u's candidates on the loose list."""
+    n_tiles, g_begin = 8, 28 * 1_000_003
+
+    def __init__(self, passes=2, big_tiles=0, seed=0):
+        self.passes, self.big_tiles, self.rng = passes, big_tiles, np.random.default_rng(700 + seed)
+        self.first = [tile_first(u, passes, big_tiles) for u in range(self.n_tiles + 1)]
+        self.g_end = self.g_begin + self.first[-1] - 4_321           # not on a tile boundary
+        self.stream_cands = [[] for _ in range(self.n_tiles)]
+        self.loose = [[] for _ in range(self.n_tiles)]
+
+    def frame(self):
+        return bytes(self.rng.integers(0, 256, 14 if self.rng.random() < 0.7 else 7, dtype=np.uint8).tolist())
+
+    def offsets(self, u, n):
+        """n ascending offsets of tile u, relative to the launch, at least 8 apart, below g_end"""
+        lo, hi = self.first[u], min(self.first[u + 1], self.g_end - self.g_begin)
+        return sorted(lo + 8 * int(k) for k in self.rng.choice((hi - lo) // 8, n, replace=False))
+
+    def fill(self, u, n_stream, n_loose, copies=True):
+        """tile u: n_stream candidates for the stream (some of them runs of copies of one frame) and n_loose for the loose list"""
+        offs = self.offsets(u, n_stream + n_loose)
+        to_loose = set(int(k) for k in self.rng.choice(len(offs), n_loose, replace=False))
+        for k, g in enumerate(offs):
+            fr = self.frame()
+            if k in to_loose:
+                self.loose[u].append((g, int(self.rng.integers(1, 1 << 20)), fr))
+            else:
+                for c in range(int(self.rng.integers(1, 4)) if copies else 1):
+                    self.stream_cands[u].append((g + c, int(self.rng.integers(1, 1 << 20)), fr))
+
+    def image(self, stream, tail=None):
+        """stream: [(tile, flags)] in completion order; tail: a marker written behind them -- ("nofit", tile) or ("again", tile)"""
+        img = Image(64 + 4 * sum(2 + len(c) for c in self.stream_cands), gen=0x51DE + self.passes)
+        for u, flags in stream:
+            _put_tile(img, u, self.stream_cands[u], True, flags)
+        if tail and tail[0] == "nofit":
+            img.tile(tail[1], 5, flags=NOFIT)
+        if tail and tail[0] == "again":
+            _put_tile(img, tail[1], self.stream_cands[tail[1]], True)
+        return img
+
+    def all_loose(self):
+        flat = [c for t in self.loose for c in t]
+        return [flat[i] for i in self.rng.permutation(len(flat))]       # arrival order: any
+
+
+def check_finish(capi, launch, img, resume_tile, granules=None, ranges=None):
+    """The three properties of a finish after completion; returns (hand-overs, the model's tiles in the stream)."""
+    granules = img.w.size // 4 if granules is None else granules
+    in_stream = model_walk(img, launch.n_tiles, granules)
+    loose = launch.all_loose()
+    resume_rel = launch.first[resume_tile]
+    want = sorted([c for u, t in in_stream.items() if u >= resume_tile for c in t] + [c for c in loose if c[0] >= resume_rel])
+    want = [(launch.g_begin + g, pw, fr) for g, pw, fr in want]
+    got, overs = finish(capi, img, launch.n_tiles, launch.passes, launch.big_tiles, launch.g_begin, launch.g_end, resume_tile, loose,
+                        granules=granules, ranges=ranges)
+    assert got == want and len(want) > 0
+    completes = [gc for _, gc in overs]
+    assert completes == sorted(completes) and completes[-1] == launch.g_end and overs[-1][0] == len(got)
+    lo_n, lo_g = 0, launch.g_begin + resume_rel
+    for n, gc in overs:
+        assert lo_n <= n and all(lo_g <= c[0] < gc for c in got[lo_n:n]), (lo_n, n, lo_g, gc)
+        lo_n, lo_g = n, gc
+    return overs, in_stream
+
+
+@pytest.mark.parametrize("passes,big_tiles", [(2, 0), (7, 3)])
+def test_finish_merges_an_early_overflowed_tile_with_its_loose_records(capi, passes, big_tiles):
+    """Tile 1 flagged OVER: its stream records interleave with its loose ones; among them a record of three copies with a
+    loose record directly before and directly behind the run.  Every other tile is whole in the stream.  Once with the
+    smallest tiles, once with tiles of seven passes that taper to four from tile 3 on."""
+    la = Launch(passes, big_tiles)
+    for u in range(la.n_tiles):
+        la.fill(u, 6, 3 if u == 1 else 0)
+    g, fr = la.first[1] + 4, la.frame()                               # (fill() keeps to multiples of 8: these five offsets are free)
+    la.stream_cands[1] = sorted(la.stream_cands[1] + [(g + 1 + c, 100 + c, fr) for c in range(3)])
+    la.loose[1] += [(g, 7, la.frame()), (g + 4, 9, la.frame())]
+    img = la.image([(u, OVER if u == 1 else 0) for u in (2, 0, 1, 3, 5, 4, 7, 6)])
+    assert (1 << 25) * 2 in [int(w) & (3 << 25) for w in img.w[4 * img.where[1][0]:][5:8 * img.where[1][1]:8]]   # the run is ONE record
+    overs, in_stream = check_finish(capi, la, img, 0)
+    assert len(in_stream) == 8 and len(overs) == 3                    # tile 0 | tile 1 merged | tiles 2..7 as they lie
+    assert [gc - la.g_begin for _, gc in overs[:2]] == [la.first[1], la.first[2]]
+
+
+def test_finish_takes_every_tile_behind_a_nofit_marker_from_the_loose_list(capi):
+    la = Launch()
+    for u in range(la.n_tiles):
+        la.fill(u, 5, 0) if u in (0, 1, 2, 4) else la.fill(u, 0, 4)
+    img = la.image([(1, 0), (0, 0), (2, 0), (4, 0)], tail=("nofit", 3))
+    overs, in_stream = check_finish(capi, la, img, 0)
+    assert sorted(in_stream) == [0, 1, 2, 4]                          # the walk ended at tile 3's marker
+    assert len(overs) == 6                                            # tiles 0..2 | 3 | 4 | 5 | 6 | 7
+
+
+def test_finish_does_not_deliver_loose_records_below_the_resume_tile_again(capi):
+    """Tiles 0..2 went on while the launch ran; after a relaunch the loose list holds records of theirs as well."""
+    la = Launch()
+    for u in range(la.n_tiles):
+        la.fill(u, 5, 3 if u in (1, 2, 4) else 0)
+    img = la.image([(u, OVER if u in (1, 2, 4) else 0) for u in range(la.n_tiles)])
+    overs, _ = check_finish(capi, la, img, 3)
+    assert sum(len(t) for t in la.loose[:3]) == 6 and len(overs) == 3   # tile 3 | tile 4 merged | 5..7
+
+
+def test_finish_of_a_full_stream_whose_capacity_cuts_a_range(capi):
+    la = Launch()
+    for u in range(la.n_tiles):
+        la.fill(u, 6, 0) if u < 4 else la.fill(u, 0, 5)
+    la.stream_cands[5] = [(g, pw, fr) for g, pw, fr in la.loose[5]]   # tile 5's range is in the image, but past the capacity
+    img = la.image([(0, 0), (1, 0), (3, 0), (2, 0), (5, 0)])
+    cut = img.where[5][0] + 3                                         # the marker and one record are inside, the rest is not
+    overs, in_stream = check_finish(capi, la, img, 2, granules=cut)
+    assert sorted(in_stream) == [0, 1, 2, 3] and len(overs) == 5      # tiles 2..3 | 4 | 5 | 6 | 7
+
+
+def test_finish_ends_its_walk_quietly_at_a_tile_that_appears_twice(capi):
+    la = Launch()
+    for u in range(la.n_tiles):
+        la.fill(u, 5, 0) if u < 4 else la.fill(u, 0, 4)
+    img = la.image([(0, 0), (1, 0), (2, 0), (3, 0)], tail=("again", 2))
+    overs, in_stream = check_finish(capi, la, img, 1)                 # (check_finish asserts that the call answered)
+    assert sorted(in_stream) == [0, 1, 2, 3] and len(overs) == 5      # tiles 1..3 | 4 | 5 | 6 | 7
+
+
+def test_finish_over_the_ranges_of_an_earlier_walk_gives_the_same_hand_overs(capi):
+    la = Launch()
+    for u in range(la.n_tiles):
+        la.fill(u, 6, 2 if u in (2, 6) else 0)
+    img = la.image([(u, OVER if u in (2, 6) else 0) for u in (1, 0, 3, 2, 4, 6, 5, 7)])
+    f, st, ts, tc = walk(capi, img, la.n_tiles)
+    assert (f, st) == (2, 1) and M32 not in tc                        # the streaming collect read on behind tile 2: every tile is in
+    rewalked, _ = check_finish(capi, la, img, 2)
+    walked, _ = check_finish(capi, la, img, 2, ranges=(ts, tc))
+    assert walked == rewalked and len(walked) == 4                    # 2 merged | 3..5 | 6 merged | 7
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_finish_of_random_launches(capi, seed):
+    """Eight tiles in a random completion order; the stream ends behind some of them (a NOFIT marker, or its capacity), some of
+    those in it overflowed.  Every seed has a tile merged from both sources, a run of two or more whole tiles and a tile that
+    is on the loose list only -- asserted from the model's own bookkeeping."""
+    la = Launch(seed=seed)
+    rng = la.rng
+    a = int(rng.integers(1, 7))                                       # tiles a, a + 1: whole in the stream ...
+    before = int(rng.integers(0, a))                                  # ... behind a tile that held the streaming collect up
+    other = int(rng.choice([u for u in range(8) if u not in (a, a + 1, before)]))
+    m, l = (before, other) if rng.random() < 0.5 else (other, before)   # merged; loose only
+    kind = {u: ("whole" if u in (a, a + 1) else "merged" if u == m else "loose" if u == l else str(rng.choice(["whole", "merged", "loose"])))
+            for u in range(8)}
+    for u in range(8):
+        la.fill(u, 0 if kind[u] == "loose" else int(rng.integers(1, 9)), 0 if kind[u] == "whole" else int(rng.integers(1, 6)))
+    order = [int(u) for u in rng.permutation([u for u in range(8) if kind[u] != "loose"])]
+    missing = [u for u in range(8) if kind[u] == "loose"]
+    resume = min([u for u in range(8) if kind[u] != "whole"])         # the first tile that held the streaming collect up
+    img = la.image([(u, OVER if kind[u] == "merged" else 0) for u in order], tail=("nofit", missing[0]) if seed % 2 else None)
+    overs, in_stream = check_finish(capi, la, img, resume)
+    assert sorted(in_stream) == sorted(order)
+    whole = [u >= resume and u in in_stream and not la.loose[u] for u in range(8)]
+    assert any(u >= resume and u in in_stream and in_stream[u] and la.loose[u] for u in range(8))
+    assert any(whole[u] and whole[u + 1] for u in range(7))
+    assert any(u >= resume and u not in in_stream and la.loose[u] for u in range(8))

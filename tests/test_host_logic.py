@@ -511,7 +511,7 @@ def test_build_follows_the_headers_the_compiler_read(tmp_path):
     deps = _build._recorded_deps(obj)
     gang = os.path.normpath(os.path.join(_build.CSRC, "gang.hpp"))
     assert deps and gang in deps and os.path.normpath(os.path.join(ROOT, "include", "adsbdec_amd_diag.h")) in deps
-    for o in ("scan_kernel.hip.o", "decoder.hip.o", "decoder_lifecycle.hip.o", "decoder_batch.hip.o", "decoder_shard.hip.o", "multi.cpp.o"):
+    for o in ("scan_kernel.hip.o", "decoder.hip.o", "decoder_collect.hip.o", "decoder_lifecycle.hip.o", "decoder_batch.hip.o", "decoder_shard.hip.o", "multi.cpp.o"):
         assert _build._recorded_deps(os.path.join(_build.LIBDIR, o)), o
     assert os.path.normpath(os.path.join(_build.CSRC, "slicer_bits.h")) in _build._recorded_deps(os.path.join(_build.LIBDIR, "scan_kernel.hip.o"))
     assert not _build._stale(obj, os.path.join(_build.CSRC, "host_abi.cpp"))

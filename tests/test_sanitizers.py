@@ -1,8 +1,8 @@
 """The library's threaded host code under ThreadSanitizer and AddressSanitizer / UBSan, without a GPU.
 
 Two harnesses (tests/cpp/), each built twice with g++:
-  handoff_tsan.cpp  the reading side of the device -> host hand-off (handoff.hpp: HandCursor, StreamReader and the two
-                    consumer loops) + the resolver behind it, with a thread that plays the device: random completion
+  handoff_tsan.cpp  the reading side of the device -> host hand-off (handoff.hpp: HandCursor, StreamReader, the two
+                    consumer loops and the finish after completion) + the resolver behind it, with a thread that plays the device: random completion
                     order, torn and stale writes, overflow, a tile twice, a tile never;
   multi_tsan.cpp    the multi-GPU driver (multi.cpp: workers, job hand-over, stitch, gather, fallback, error paths) against
                     a fake device backend whose scan is a table look-up; everything behind the scan is the product's code.
@@ -47,6 +47,8 @@ def test_handoff_reader_under_sanitizers(tmp_path, san):
     out = _run(_build(tmp_path, "handoff_tsan.cpp", san), 32)
     # every way a collect can end was exercised, by one thread and by two
     assert "16 complete, 8 finish-after-completion, 4 tile-twice, 4 never-published" in out, out
+    # ... and each of the eight launches that asked for it was finished after completion: the sorted union of stream and loose list
+    assert int(out.split(" records finished after completion")[0].split()[-1]) > 1000, out
 
 
 @pytest.mark.parametrize("san", ["tsan", "asan"])
