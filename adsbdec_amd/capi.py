@@ -105,6 +105,15 @@ class WorkerPlacement(C.Structure):
                 ("local_fraction", C.c_double)]
 
 
+class FormatReport(C.Structure):
+    _fields_ = [("converted", C.c_uint64), ("inexact", C.c_uint64), ("clamped", C.c_uint64)]
+
+
+# fmt of the _as calls: the airspy_rx -t numbers (include/adsbdec_amd.h)
+FMT_FLOAT32_REAL, FMT_INT16_REAL, FMT_UINT16_REAL, FMT_RAW = 1, 3, 4, 5
+FMT_DTYPES = {FMT_FLOAT32_REAL: np.dtype("<f4"), FMT_INT16_REAL: np.dtype("<i2"), FMT_UINT16_REAL: np.dtype("<u2"), FMT_RAW: np.dtype("<u2")}
+
+
 class Profile(C.Structure):
     _fields_ = [("launches", C.c_uint64), ("relaunches", C.c_uint64), ("offsets", C.c_uint64),
                 ("kernel_ms", C.c_double), ("last_kernel_ms", C.c_double), ("last_offsets", C.c_uint64),
@@ -161,6 +170,18 @@ SYMBOLS = {
                                                    C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     "adsb_decode_batch_host_packed": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                  C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_format_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "adsb_push_as": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "adsb_push_async_as": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "adsb_push_device_as": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "adsb_push_device_final_as": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "adsb_decode_device_as": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Frame))]),
+    "adsb_decode_batch_device_as": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                               C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_decode_batch_host_as": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                             C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
+    "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_multi_decode_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int,
                                                 C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     "adsb_multi_decode_batch_files": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_int,
@@ -577,6 +598,100 @@ class Decoder:
                 else:
                     self._check(self._L.adsb_push_packed(self._h, b.ctypes.data, b.size // 12 * 8), "adsb_push_packed")
                     b[:] = 0xFF             # the buffer is the caller's again
+                out += self.drain()
+            self.finish()
+            out += self.drain()
+        return out
+
+    # ---- signed 16-bit / float32 real input (include/adsbdec_amd.h: fmt is the airspy_rx -t number), converted on the GPU
+    @staticmethod
+    def _as_arg(fmt, x):
+        if isinstance(x, tuple):
+            return x
+        assert fmt not in FMT_DTYPES or x.dtype == FMT_DTYPES[fmt], (fmt, x.dtype)
+        assert x.flags["C_CONTIGUOUS"]
+        return x.ctypes.data, x.size
+
+    def push_as(self, fmt: int, x, mode: str = "sync"):
+        """adsb_push_as (mode "sync") / adsb_push_async_as ("async": x stays borrowed until the next push/finish/sync returns);
+        x = ndarray of the format's dtype, or (ptr, n)."""
+        ptr, n = self._as_arg(fmt, x)
+        if mode == "async":
+            self._check(self._L.adsb_push_async_as(self._h, fmt, ptr, n), "adsb_push_async_as")
+        elif mode == "sync":
+            self._check(self._L.adsb_push_as(self._h, fmt, ptr, n), "adsb_push_as")
+        else:
+            raise ValueError(mode)
+
+    def push_device_as(self, fmt: int, ptr: int, n: int, final: bool = False):
+        if final:
+            self._check(self._L.adsb_push_device_final_as(self._h, fmt, ptr, n), "adsb_push_device_final_as")
+        else:
+            self._check(self._L.adsb_push_device_as(self._h, fmt, ptr, n), "adsb_push_device_as")
+
+    def decode_device_as_raw(self, fmt: int, ptr: int, n: int):
+        """adsb_decode_device_as -> (Frame pointer, count), as decode_device_raw."""
+        k = self._L.adsb_decode_device_as(self._h, fmt, ptr, n, self._out_ref)
+        if k < 0:
+            self._check(-1, "adsb_decode_device_as")
+        return self._out, k
+
+    def decode_device_as(self, fmt: int, ptr: int, n: int):
+        out, k = self.decode_device_as_raw(fmt, ptr, n)
+        return _frames_to_dicts(out, k)
+
+    def decode_batch_device_as(self, fmt: int, ptrs, ns, stats: bool = False):
+        """adsb_decode_batch_device_as: captures of format fmt resident in HBM -> what decode_batch_device gives for their raw twins."""
+        k = len(ns)
+        p = (C.c_void_p * max(1, k))(*[int(v) if v else None for v in ptrs])
+        n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        if self._L.adsb_decode_batch_device_as(self._h, fmt, k, p, n, self._out_ref, first, st) < 0:
+            self._check(-1, "adsb_decode_batch_device_as")
+        return self._batch_result(self._out, first, st, k, stats)
+
+    def decode_batch_as(self, fmt: int, arrays, stats: bool = False):
+        """The same for arrays of the format's dtype in host memory: adsb_decode_batch_host_as."""
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        assert all(fmt not in FMT_DTYPES or a.dtype == FMT_DTYPES[fmt] for a in arrays)
+        k = len(arrays)
+        p = (C.c_void_p * max(1, k))(*[a.ctypes.data if a.size else None for a in arrays])
+        n = (C.c_size_t * max(1, k))(*[a.size for a in arrays])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        if self._L.adsb_decode_batch_host_as(self._h, fmt, k, p, n, self._out_ref, first, st) < 0:
+            self._check(-1, "adsb_decode_batch_host_as")
+        return self._batch_result(self._out, first, st, k, stats)
+
+    def format_report(self):
+        """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""
+        r = FormatReport()
+        self._check(self._L.adsb_get_format_report(self._h, C.byref(r)), "adsb_get_format_report")
+        return int(r.converted), int(r.inexact), int(r.clamped)
+
+    def decode_as(self, fmt: int, x: np.ndarray, chunk: int | None = None, mode: str = "sync"):
+        """decode() for samples of format fmt: chunk counts samples (any number); the same three modes."""
+        self.reset()
+        chunk = chunk or max(1, x.size)
+        pieces = [x[i:i + chunk] for i in range(0, x.size, chunk)]
+        out = []
+        if mode == "sync":
+            for p in pieces:
+                self.push_as(fmt, p)
+            self.finish()
+            return self.drain()
+        if mode not in ("async", "overlap"):
+            raise ValueError(mode)
+        nbuf = 2 if mode == "async" else 1
+        elem = x.dtype.itemsize
+        with PinnedBuffers(nbuf, max(1, (min(chunk, max(1, x.size)) * elem + 1) // 2)) as bufs:
+            for k, p in enumerate(pieces):
+                b = bufs[k % nbuf].view(np.uint8)[: p.size * elem].view(x.dtype)
+                b[:] = p                    # async: the push from this buffer was two calls ago; overlap: the copy is over
+                self.push_as(fmt, b, "async" if mode == "async" else "sync")
+                if mode == "overlap":
+                    b.view(np.uint8)[:] = 0xFF   # the buffer is the caller's again
                 out += self.drain()
             self.finish()
             out += self.drain()

@@ -15,6 +15,12 @@
  *     -p            EXTENSION: the file holds Airspy packed 12-bit samples (adsbdec_amd.h: the format; -p as in
  *                   airspy_rx), unpacked on the GPU.  A trailing partial group (file size % 12 != 0) is not decoded and
  *                   stderr says how many bytes were ignored.  Not with -G (the multi-GPU driver reads uint16 files only).
+ *     -t type       EXTENSION: the sample type of the file, numbered as airspy_rx -t numbers them (adsbdec_amd.h: the formats).
+ *                   1 (float32 real) and 3 (signed 16-bit real, what adsbdec's README calls "raw signed 16 bits real") are
+ *                   converted on the GPU; 4 and 5 are the uint16 code this program reads without -t; 0 and 2 (IQ) and
+ *                   anything else are refused.  A trailing partial sample is not decoded and stderr says how many bytes
+ *                   were ignored.  A run in which samples were off the format's grid ends with a line on stderr that says
+ *                   how many: the sign of a wrong -t.  -t 1 and -t 3 not with -p, -G or -B.
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -63,7 +69,8 @@
  * host-to-device copy of one buffer with the scan of the previous one. */
 #define BUF_SAMPLES (16u * 1024u * 1024u)
 #define RING_MAX_BYTES (1024ull * 1024ull * 1024ull)
-/* bytes per ring buffer: BUF_SAMPLES samples, as uint16 (32 MiB) or packed 12-bit with -p (24 MiB: whole 12-byte groups) */
+/* bytes per ring buffer: BUF_SAMPLES samples, as uint16 (32 MiB), packed 12-bit with -p (24 MiB: whole 12-byte groups), or what
+ * adsb_format_bytes says for -t 1 / -t 3 */
 static size_t buf_bytes = (size_t)BUF_SAMPLES * 2;
 
 typedef struct {
@@ -157,7 +164,7 @@ static void *locker_main(void *arg)
 static void usage(void)
 {
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
-    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
+    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
     printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
@@ -167,6 +174,8 @@ static void usage(void)
     printf("\t-x : (extension) repair 1-bit CRC errors in DF17/18 frames\n");
     printf("\t-d k : (extension) use GPU k\n");
     printf("\t-p : (extension) the file holds Airspy packed 12-bit samples (8 samples in 12 bytes), unpacked on the GPU; not with -G\n");
+    printf("\t-t type : (extension) sample type of the file as airspy_rx -t numbers it: 1 float32 real and 3 signed 16 bits real are\n");
+    printf("\t     converted on the GPU, 4 and 5 are the uint16 code (the default); not 0 or 2 (IQ); 1 and 3 not with -p, -G or -B\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
@@ -484,10 +493,12 @@ int main(int argc, char **argv)
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
     int outformat = 0, df18 = 0, fix1 = 0, packed = 0, c;
+    long stype = 5; /* -t: ADSB_FMT_RAW */
+    const char *stype_arg = NULL;
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpd:G:s:l:B:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpd:G:s:l:B:t:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -542,10 +553,33 @@ int main(int argc, char **argv)
         case 'p':
             packed = 1;
             break;
+        case 't': {
+            char *end;
+            stype = strtol(optarg, &end, 10);
+            if (*end || end == optarg)
+                stype = -1;
+            stype_arg = optarg;
+            break;
+        }
         default:
             usage();
             return 1;
         }
+    }
+    const int converted = stype == ADSB_FMT_FLOAT32_REAL || stype == ADSB_FMT_INT16_REAL;
+    if (stype_arg && !converted && stype != ADSB_FMT_UINT16_REAL && stype != ADSB_FMT_RAW) {
+        if (stype == 0 || stype == 2)
+            fprintf(stderr, "-t %ld (%s) is not a real sample type: libairspy has already mixed, filtered and decimated an IQ stream, so it has no "
+                            "raw twin to be decoded as; -t takes 1 (float32 real), 3 (int16 real), 4 or 5 (uint16)\n",
+                    stype, stype == 0 ? "FLOAT32_IQ" : "INT16_IQ");
+        else
+            fprintf(stderr, "-t %s: unknown sample type; -t takes 1 (float32 real), 3 (int16 real), 4 or 5 (uint16)\n", stype_arg);
+        return 1;
+    }
+    if (converted && (packed || ndev || listfile)) {
+        fprintf(stderr, "-t %ld is not supported with %s: %s\n", stype, packed ? "-p" : ndev ? "-G" : "-B",
+                packed ? "a file is packed 12-bit or of that type, not both" : "the multi-GPU driver reads uint16 and packed files only");
+        return 1;
     }
     if (listfile) { /* a batch: its own inputs and outputs -- no -f, no peer; -d and -G exclude each other here too */
         if (filename || outmode != SINK_STDOUT || (ndev && device >= 0)) {
@@ -580,6 +614,9 @@ int main(int argc, char **argv)
     }
     if (packed)
         buf_bytes = (size_t)BUF_SAMPLES / 8 * 12;
+    const size_t elem = converted ? adsb_format_bytes((int)stype, 1) : 2; /* (host arithmetic: no GPU call) */
+    if (converted)
+        buf_bytes = adsb_format_bytes((int)stype, BUF_SAMPLES);
     install_signals();
     sink_init(&out_sink, outmode, rawaddr);
     out_sink.stop = &stop_requested;
@@ -711,7 +748,9 @@ int main(int argc, char **argv)
             const size_t bytes = s->bytes;
             /* a trailing odd byte is dropped, like decodeiq(iqbuff, n / 2) (air.c:239); packed: a trailing partial group (only the
              * last buffer can have one: a full buffer is whole groups) */
-            const size_t n_samples = packed ? bytes / 12 * 8 : bytes / 2;
+            const size_t n_samples = packed ? bytes / 12 * 8 : bytes / elem;
+            if (converted && bytes % elem)
+                fprintf(stderr, "%zu trailing bytes ignored (not a whole %zu-byte sample)\n", bytes % elem, elem);
             if (packed && bytes % 12)
                 fprintf(stderr, "%zu trailing bytes ignored (not a whole 12-byte group of packed samples)\n", bytes % 12);
             if (n_samples) {
@@ -719,6 +758,8 @@ int main(int argc, char **argv)
                 int prc;
                 if (packed)
                     prc = s->registered ? adsb_push_packed_async(dec, s->buf, n_samples) : adsb_push_packed(dec, s->buf, n_samples);
+                else if (converted)
+                    prc = s->registered ? adsb_push_async_as(dec, (int)stype, s->buf, n_samples) : adsb_push_as(dec, (int)stype, s->buf, n_samples);
                 else
                     prc = s->registered ? adsb_push_async(dec, s->buf, n_samples) : adsb_push(dec, s->buf, n_samples);
                 t_push += now_ms() - t_p0;
@@ -786,6 +827,10 @@ int main(int argc, char **argv)
     adsb_stats st;
     if (adsb_get_stats(dec, &st) == 0)
         print_stats(&st);
+    adsb_format_report rep;
+    if (converted && adsb_get_format_report(dec, &rep) == 0 && rep.inexact + rep.clamped > 0)
+        fprintf(stderr, "%llu of %llu samples are not %s values (%llu clamped): is -t right?\n", (unsigned long long)(rep.inexact + rep.clamped),
+                (unsigned long long)rep.converted, stype == ADSB_FMT_INT16_REAL ? "INT16_REAL" : "FLOAT32_REAL", (unsigned long long)rep.clamped);
     /* no adsb_destroy / unregister / free: the process ends here, and tearing the GPU runtime
      * down cleanly costs tens of milliseconds that an offline decode has no use for */
     fflush(stderr);

@@ -3,6 +3,7 @@
 // in decoder_collect.hip; the handle itself and the units beside this one: decoder_state.hpp.
 #include "decoder_state.hpp"
 #include "packed12.h"
+#include "sample_format.h"
 #include "seam_kernel.h"
 
 using namespace adsb;
@@ -639,8 +640,11 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight)
 // packed (adsb_push_packed*): src holds n / 8 groups of packed 12-bit samples (n % 8 == 0, stage_fill % 8 == 0).  The
 // copy lands them in land[] and the unpack kernel writes the samples where the copy would have, on the copy's stream,
 // before the copy's event: to everything that orders against the copies it is part of the copy.
-static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind kind, bool async = false, bool packed = false)
+// conv (adsb_push_as, adsb_push_async_as: kFmtInt16Real / kFmtFloat32Real): src holds n samples of that format; they land in
+// land[] like packed ones and the conversion kernel stands where the unpack does.  Any n, any stage_fill.
+static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind kind, bool async = false, bool packed = false, int conv = 0)
 {
+    const size_t elem = adsb::format_element_bytes(conv);
     const char *p = static_cast<const char *>(src);
     while (n) {
         uint64_t room = d->stage_cap - kStageSlack - d->stage_fill;
@@ -649,7 +653,7 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
         if (room == 0)
             return d->fail("staging buffer exhausted (stage_samples too small)");
         const size_t take = (size_t)std::min<uint64_t>(room, n);
-        const size_t bytes = packed ? take / adsb::kPackedGroupSamples * adsb::kPackedGroupBytes : take * sizeof(uint16_t);
+        const size_t bytes = packed ? take / adsb::kPackedGroupSamples * adsb::kPackedGroupBytes : conv ? take * elem : take * sizeof(uint16_t);
         if (async) {
             d->piece++;
             const int cs = (int)(d->piece % adsb_decoder::kCopyStreams);
@@ -662,6 +666,9 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
             if (packed) {
                 HIP_TRY(d, hipMemcpyAsync(d->land[cs], p, bytes, kind, cstream));
                 HIP_TRY(d, adsb::launch_unpack12(d->stage[d->cur] + d->stage_fill, d->land[cs], take / adsb::kPackedGroupSamples, cstream));
+            } else if (conv) {
+                HIP_TRY(d, hipMemcpyAsync(d->land[cs], p, bytes, kind, cstream));
+                HIP_TRY(d, adsb::launch_convert(conv, d->stage[d->cur] + d->stage_fill, d->land[cs], take, d->d_fmt, cstream));
             } else {
                 HIP_TRY(d, hipMemcpyAsync(d->stage[d->cur] + d->stage_fill, p, bytes, kind, cstream));
             }
@@ -676,6 +683,9 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
             if (packed) {
                 HIP_TRY(d, hipMemcpyAsync(d->land[0], p, bytes, kind, d->stream));
                 HIP_TRY(d, adsb::launch_unpack12(d->stage[d->cur] + d->stage_fill, d->land[0], take / adsb::kPackedGroupSamples, d->stream));
+            } else if (conv) {
+                HIP_TRY(d, hipMemcpyAsync(d->land[0], p, bytes, kind, d->stream));
+                HIP_TRY(d, adsb::launch_convert(conv, d->stage[d->cur] + d->stage_fill, d->land[0], take, d->d_fmt, d->stream));
             } else {
                 HIP_TRY(d, hipMemcpyAsync(d->stage[d->cur] + d->stage_fill, p, bytes, kind, d->stream));
             }
@@ -683,6 +693,10 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
         }
         d->stage_fill += take;
         d->n_samples += take;
+        if (conv) {
+            d->fmt_converted += take;
+            d->fmt_dirty = true;
+        }
         p += bytes;
         n -= take;
         if (process_stage(d, false, async))
@@ -708,8 +722,63 @@ static int packed_refusal(adsb_decoder *d, const char *what, size_t n, uint64_t 
     return 0;
 }
 
+// The converted formats (adsb_*_as; sample_format.h).  What a call needs before its first conversion: the two counters, and
+// landing buffers of land_bytes each (0: none; a host push lands its samples there as a packed one does).  A buffer that has to
+// grow is released first, so what may still read or write it -- an earlier piece's copy or unpack -- is waited for.
+int format_prepare(adsb_decoder *d, const char *what, size_t land_bytes)
+{
+    if (!d->d_fmt) {
+        if (d->d_fmt.reserve(2) != hipSuccess) {
+            (void)hipGetLastError();
+            return d->fail("%s: cannot allocate the format counters on the device", what);
+        }
+        HIP_TRY(d, hipMemsetAsync(d->d_fmt, 0, 2 * sizeof(unsigned long long), d->stream));
+        WAIT_STREAM(d, d->stream, "the scan stream");
+    }
+    for (auto &l : d->land) {
+        if (l.cap >= land_bytes)
+            continue;
+        for (hipStream_t cs : d->copy_stream)
+            WAIT_STREAM(d, cs, "a copy stream");
+        WAIT_STREAM(d, d->stream, "the scan stream");
+        if (l.reserve(land_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return d->fail("%s: cannot allocate a landing buffer of %zu bytes on the device", what, land_bytes);
+        }
+    }
+    return 0;
+}
+
+// The two counters as the device has them once every conversion enqueued so far has ended.
+int format_counters(adsb_decoder *d, unsigned long long out[2])
+{
+    out[0] = out[1] = 0;
+    if (!d->d_fmt)
+        return 0;
+    HIP_TRY(d, hipSetDevice(d->device));
+    for (hipStream_t cs : d->copy_stream)
+        WAIT_STREAM(d, cs, "a copy stream");
+    HIP_TRY(d, hipMemcpyAsync(out, d->d_fmt, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream));
+    WAIT_STREAM(d, d->stream, "the scan stream");
+    return 0;
+}
+
+// What every _as call checks first: the format.  0: converted (*elem bytes per sample); 1: the uint16 code itself; -1: refused.
+int format_dispatch(adsb_decoder *d, const char *what, int fmt, size_t *elem)
+{
+    *elem = adsb::format_element_bytes(fmt);
+    if (*elem)
+        return 0;
+    if (fmt == adsb::kFmtUint16Real || fmt == adsb::kFmtRaw)
+        return 1;
+    if (fmt == 0 || fmt == 2)
+        return d->fail("%s: format %d (%s) is not a real format: libairspy has already mixed, filtered and decimated an IQ stream, so it has no "
+                       "raw twin to be decoded as", what, fmt, fmt == 0 ? "FLOAT32_IQ" : "INT16_IQ");
+    return d->fail("%s: unknown sample format %d (1 FLOAT32_REAL, 3 INT16_REAL, 4 UINT16_REAL, 5 RAW)", what, fmt);
+}
+
 // adsb_push, adsb_push_async and their packed forms: samples in host memory (`packed`: whole groups of 12-bit samples).
-static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async, bool packed, const char *what)
+static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async, bool packed, const char *what, int conv = 0)
 {
     if (!d)
         return -1;
@@ -730,19 +799,21 @@ static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async,
                 return d->fail("packed input: cannot allocate a landing buffer of %zu bytes on the device", bytes);
             }
     }
+    if (conv && format_prepare(d, what, d->stage_cap * adsb::format_element_bytes(conv)))
+        return -1;
     if (async)
-        return push_copy(d, samples, n, hipMemcpyHostToDevice, true, packed);
+        return push_copy(d, samples, n, hipMemcpyHostToDevice, true, packed, conv);
     if (d->cfg.push_overlap) {
         // The caller's ONE buffer (fileInput's iqbuff, air.c:230-239; the callback's transfer, air.c:173-177) is
         // only borrowed until its bytes are on the device: return when the COPY (packed: copy + unpack) has completed and
         // leave the scan in flight -- the host is back in read() while the device scans, and this call has meanwhile collected
         // the frames of the previous one (frames arrive one call late, never reordered; adsb_finish / adsb_sync
         // deliver the rest).  That is adsb_push_async plus the wait for this piece's own copy.
-        if (push_copy(d, samples, n, hipMemcpyHostToDevice, true, packed))
+        if (push_copy(d, samples, n, hipMemcpyHostToDevice, true, packed, conv))
             return -1;
         return wait_last_copy(d);
     }
-    if (push_copy(d, samples, n, hipMemcpyHostToDevice, false, packed))
+    if (push_copy(d, samples, n, hipMemcpyHostToDevice, false, packed, conv))
         return -1;
     if (d->copy_unconfirmed) { // `samples` is only borrowed for the call: no scan behind the last copy has confirmed it
         WAIT_STREAM(d, d->stream, "the scan stream");
@@ -896,6 +967,47 @@ static int push_device_packed_impl(adsb_decoder *d, const void *device_packed, s
     return push_device_impl(d, d->unpacked, n, final);
 }
 
+// adsb_push_device_as and its kin: the checks first (a refused push leaves the handle as it was), at stream position `at`
+static int device_as_refusal(adsb_decoder *d, const char *what, const void *p, size_t n, size_t elem)
+{
+    if ((uintptr_t)p % elem != 0)
+        return d->fail("%s: device pointer %p is not %zu-byte aligned", what, p, elem);
+    if (n && !p)
+        return d->fail("%s: NULL samples", what);
+    return 0;
+}
+
+// convert into the scratch of the packed device pushes (grown to 2 B x n on demand), then push that in place
+static int push_device_as_impl(adsb_decoder *d, int fmt, const void *p, size_t n, bool final, const char *what)
+{
+    if (d->finished)
+        return d->fail("%s after adsb_finish", what);
+    if (final && d->shard_on)
+        return d->fail("a shard stream ends with adsb_shard_end");
+    if (device_as_refusal(d, what, p, n, adsb::format_element_bytes(fmt)) || stream_too_long(d, n))
+        return -1;
+    if (n == 0)
+        return final ? push_device_impl(d, nullptr, 0, true) : 0;
+    HIP_TRY(d, hipSetDevice(d->device));
+    if (format_prepare(d, what, 0))
+        return -1;
+    if (d->unpacked.reserve(n) != hipSuccess) { // (every earlier push into the scratch has completed: push_device_impl returns behind its reads)
+        (void)hipGetLastError();
+        return d->fail("%s: cannot allocate %zu bytes of device scratch for the converted samples (2 bytes per sample)", what,
+                       n * sizeof(uint16_t));
+    }
+    HIP_TRY(d, adsb::launch_convert(fmt, d->unpacked, p, n, d->d_fmt, d->stream));
+    d->fmt_converted += n;
+    d->fmt_dirty = true;
+    if (d->stream2) { // as behind a device push's unpack: the second scan stream waits for the conversion
+        if (!d->ev_unpack)
+            HIP_TRY(d, d->ev_unpack.create(hipEventDisableTiming));
+        HIP_TRY(d, hipEventRecord(d->ev_unpack, d->stream));
+        HIP_TRY(d, hipStreamWaitEvent(d->stream2, d->ev_unpack, 0));
+    }
+    return push_device_impl(d, d->unpacked, n, final);
+}
+
 } // namespace adsb
 
 extern "C" {
@@ -999,6 +1111,108 @@ int adsb_unpack_packed12(void *dst_u16, const void *src, size_t n, void *stream)
                                                    static_cast<hipStream_t>(stream));
         if (e != hipSuccess)
             snprintf(why, sizeof why, "adsb_unpack_packed12: launch failed: %s", hipGetErrorString(e));
+    }
+    if (!why[0])
+        return 0;
+    set_create_error(why);
+    return -1;
+}
+
+size_t adsb_format_bytes(int fmt, size_t n)
+{
+    const size_t elem = adsb::format_element_bytes(fmt);
+    return (elem ? elem : (fmt == adsb::kFmtUint16Real || fmt == adsb::kFmtRaw) ? sizeof(uint16_t) : 0) * n;
+}
+
+int adsb_push_as(adsb_decoder *d, int fmt, const void *samples, size_t n)
+{
+    size_t elem;
+    if (!d)
+        return -1;
+    const int k = format_dispatch(d, "adsb_push_as", fmt, &elem);
+    return k < 0 ? -1 : k ? adsb_push(d, static_cast<const uint16_t *>(samples), n) : push_host(d, samples, n, false, false, "adsb_push_as", fmt);
+}
+
+int adsb_push_async_as(adsb_decoder *d, int fmt, const void *samples, size_t n)
+{
+    size_t elem;
+    if (!d)
+        return -1;
+    const int k = format_dispatch(d, "adsb_push_async_as", fmt, &elem);
+    return k < 0 ? -1 : k ? adsb_push_async(d, static_cast<const uint16_t *>(samples), n) : push_host(d, samples, n, true, false, "adsb_push_async_as", fmt);
+}
+
+int adsb_push_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n)
+{
+    size_t elem;
+    if (!d)
+        return -1;
+    const int k = format_dispatch(d, "adsb_push_device_as", fmt, &elem);
+    return k < 0 ? -1 : k ? adsb_push_device(d, device_samples, n) : push_device_as_impl(d, fmt, device_samples, n, false, "adsb_push_device_as");
+}
+
+int adsb_push_device_final_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n)
+{
+    size_t elem;
+    if (!d)
+        return -1;
+    const int k = format_dispatch(d, "adsb_push_device_final_as", fmt, &elem);
+    return k < 0 ? -1 : k ? adsb_push_device_final(d, device_samples, n) : push_device_as_impl(d, fmt, device_samples, n, true, "adsb_push_device_final_as");
+}
+
+long adsb_decode_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_frame **frames)
+{
+    const char *what = "adsb_decode_device_as";
+    size_t elem;
+    if (!d || !frames)
+        return -1;
+    const int k = format_dispatch(d, what, fmt, &elem);
+    if (k < 0)
+        return -1;
+    if (k)
+        return adsb_decode_device(d, device_samples, n, frames);
+    // refused before the reset: a refused call leaves the handle as it was
+    if (device_as_refusal(d, what, device_samples, n, elem))
+        return -1;
+    if (!d->long_stream && (uint64_t)n >= (1ull << 32)) {
+        stream_too_long(d, n);
+        return -1;
+    }
+    if (adsb_reset(d) != 0 || push_device_as_impl(d, fmt, device_samples, n, true, what) != 0)
+        return -1;
+    return (long)d->res.take(frames);
+}
+
+int adsb_get_format_report(const adsb_decoder *d, adsb_format_report *out)
+{
+    if (!d || !out)
+        return -1;
+    adsb_decoder *m = const_cast<adsb_decoder *>(d); // the counters live on the device until asked for
+    unsigned long long c[2];
+    if (format_counters(m, c))
+        return -1;
+    out->converted = d->fmt_converted;
+    out->inexact = c[0] - d->fmt_base[0];
+    out->clamped = c[1] - d->fmt_base[1];
+    return 0;
+}
+
+int adsb_convert_samples(void *dst_u16, const void *src, int fmt, size_t n, uint64_t *device_counters2, void *stream)
+{
+    char why[200] = "";
+    const size_t elem = adsb::format_element_bytes(fmt);
+    if (!elem)
+        snprintf(why, sizeof why, "adsb_convert_samples: format %d is not converted (1 FLOAT32_REAL, 3 INT16_REAL)", fmt);
+    else if (n && (!dst_u16 || !src))
+        snprintf(why, sizeof why, "adsb_convert_samples: NULL buffer");
+    else if ((uintptr_t)dst_u16 % 2 != 0 || (uintptr_t)src % elem != 0 || (uintptr_t)device_counters2 % 8 != 0)
+        snprintf(why, sizeof why, "adsb_convert_samples: dst must be 2-byte, src %zu-byte and the counters 8-byte aligned (%p, %p, %p)", elem,
+                 dst_u16, src, (void *)device_counters2);
+    else if (n) {
+        const hipError_t e = adsb::launch_convert(fmt, static_cast<uint16_t *>(dst_u16), src, n,
+                                                  reinterpret_cast<unsigned long long *>(device_counters2), static_cast<hipStream_t>(stream));
+        if (e != hipSuccess)
+            snprintf(why, sizeof why, "adsb_convert_samples: launch failed: %s", hipGetErrorString(e));
     }
     if (!why[0])
         return 0;

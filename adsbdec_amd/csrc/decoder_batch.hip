@@ -2,6 +2,7 @@
 // launches borrow a scan slot of the handle's (decoder_state.hpp) and are waited for one by one.
 #include "decoder_state.hpp"
 #include "packed12.h"
+#include "sample_format.h"
 
 using namespace adsb;
 
@@ -251,9 +252,120 @@ long decode_batch_packed(adsb_decoder *d, const char *what, size_t n_captures, c
     return k;
 }
 
+// The captures at src[] (device memory, samples of format fmt, each aligned to its element) -> uint16 samples in batch_unpacked,
+// capture i from at[i] on (a 128-byte boundary), by ONE launch on the handle's stream, which adds the batch's off-grid counts.
+int batch_convert(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
+                  std::vector<const void *> &at)
+{
+    at.assign(n_captures, nullptr);
+    d->batch_unpacked_at.clear();
+    size_t bytes = 0, rows = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+        rows += n[i] != 0;
+    }
+    if (batch_grow(d, what, "the converted samples (2 bytes per sample)", d->batch_unpacked, bytes) || format_prepare(d, what, 0))
+        return -1;
+    const size_t tab_bytes = (rows + 1) * sizeof(adsb::ConvertSeg);
+    HIP_TRY(d, d->unpack_tab.reserve(tab_bytes));
+    adsb::ConvertSeg *tab = reinterpret_cast<adsb::ConvertSeg *>(d->unpack_tab.host.p);
+    size_t off = 0, row = 0;
+    uint64_t groups = 0, samples = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        at[i] = reinterpret_cast<const char *>(d->batch_unpacked.p) + off;
+        d->batch_unpacked_at.push_back(off / sizeof(uint16_t));
+        if (n[i]) {
+            tab[row++] = adsb::ConvertSeg{(uint64_t)(uintptr_t)src[i], off / 16, groups, n[i]};
+            groups += (n[i] + 7) / 8; // (the last group of a capture may be short)
+            samples += n[i];
+        }
+        off += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+    }
+    d->batch_unpacked_at.push_back(off / sizeof(uint16_t));
+    tab[row] = adsb::ConvertSeg{0, 0, groups, 0}; // behind the last row: where its groups end
+    if (groups == 0)
+        return 0;
+    HIP_TRY(d, hipMemcpyAsync(d->unpack_tab.dev, d->unpack_tab.host, tab_bytes, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(d, adsb::launch_convert_batch(fmt, d->batch_unpacked, reinterpret_cast<const adsb::ConvertSeg *>(d->unpack_tab.dev.p), (uint32_t)row,
+                                          groups, d->d_fmt, d->stream));
+    d->fmt_converted += samples;
+    d->fmt_dirty = true;
+    return 0;
+}
+
+// convert, decode; and the stream idle behind it whatever the result (as decode_batch_packed)
+long decode_batch_as(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
+                     const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    std::vector<const void *> at;
+    d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
+    if (batch_convert(d, what, fmt, n_captures, src, n, at))
+        return -1;
+    const long k = decode_batch(d, n_captures, at.data(), n, frames, first, stats);
+    WAIT_STREAM(d, d->stream, "the scan stream");
+    return k;
+}
+
 } // namespace
 
 extern "C" {
+
+long adsb_decode_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
+                                 const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    const char *what = "adsb_decode_batch_device_as";
+    size_t elem;
+    if (!d || !frames || !first)
+        return -1;
+    const int k = format_dispatch(d, what, fmt, &elem);
+    if (k < 0)
+        return -1;
+    if (k)
+        return adsb_decode_batch_device(d, n_captures, device_samples, n, frames, first, stats);
+    if (batch_refusal(d, what, n_captures, device_samples, n, true, (unsigned)elem, false))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    return decode_batch_as(d, what, fmt, n_captures, device_samples, n, frames, first, stats);
+}
+
+long adsb_decode_batch_host_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
+                               const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    const char *what = "adsb_decode_batch_host_as";
+    size_t elem;
+    if (!d || !frames || !first)
+        return -1;
+    const int k = format_dispatch(d, what, fmt, &elem);
+    if (k < 0)
+        return -1;
+    if (k)
+        return adsb_decode_batch_host(d, n_captures, reinterpret_cast<const uint16_t *const *>(samples), n, frames, first, stats);
+    if (batch_refusal(d, what, n_captures, samples, n, false, (unsigned)elem, false))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    // every capture's samples at a 16-byte boundary of the landing buffer the packed batches use
+    size_t bytes = 0;
+    for (size_t i = 0; i < n_captures; i++)
+        bytes += (n[i] * elem + 15) & ~(size_t)15;
+    if (batch_grow(d, what, "the captures as they are", d->batch_land, bytes))
+        return -1;
+    std::vector<const void *> land(n_captures);
+    size_t off = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        land[i] = d->batch_land + off;
+        if (n[i])
+            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, samples[i], n[i] * elem, hipMemcpyHostToDevice,
+                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
+        off += (n[i] * elem + 15) & ~(size_t)15;
+    }
+    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the conversion needs no event)
+        WAIT_STREAM(d, cs, "a copy stream");
+    return decode_batch_as(d, what, fmt, n_captures, land.data(), n, frames, first, stats);
+}
 
 long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
                               const adsb_frame **frames, uint64_t *first, adsb_stats *stats)

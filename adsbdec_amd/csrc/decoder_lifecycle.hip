@@ -291,6 +291,12 @@ int adsb_reset(adsb_decoder *d)
     }
     else if (wait_last_copy(d)) // a late asynchronous copy must not land in stage[0] beside the next stream's
         return -1;
+    if (d->fmt_dirty) { // (every conversion of the stream has ended: a push returns behind its scans, or its copy was just waited for)
+        if (format_counters(d, d->fmt_base))
+            return -1;
+        d->fmt_dirty = false;
+    }
+    d->fmt_converted = 0;
     d->piece = 0;
     d->shard_on = false;
     d->final_follows = false;

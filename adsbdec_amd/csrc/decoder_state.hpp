@@ -138,6 +138,10 @@ struct ScanSink { // where collected records go: a caller's vectors, or (null) t
 //   land[2]    host pushes: the packed bytes of a piece land here (one buffer per copy stream, 1.5 B x
 //              stage_cap), and the unpack writes stage[cur] + stage_fill on the stream of that copy
 //   unpacked   device pushes: 2 B x n of scratch, scanned in place like a uint16 push
+// Signed 16-bit and float32 real input (the _as calls) takes the same two roads through convert_samples.hip: host pushes land in
+// land[] (2 B or 4 B x stage_cap each) and are converted into stage[cur] + stage_fill, device pushes are converted into `unpacked`;
+// a batch is converted into batch_unpacked by one launch (its table: unpack_tab; _host: the captures land in batch_land).
+//   d_fmt      two counters the conversions add to: samples off their format's grid (inexact), and clamped ones
 // A batch of captures (adsb_decode_batch_*, batch.hpp) is scanned in place too, by launches of scan_batch_kernel:
 //   batch_tab  a launch's segment table and its tile -> segment words (scan_kernel.h BatchSeg), uploaded from its pinned half
 //   batch_in   adsb_decode_batch_host: the captures, each at a 128-byte boundary
@@ -260,6 +264,11 @@ struct adsb_decoder {
     adsb::Buf<uint8_t> land[kCopyStreams];
     adsb::Buf<uint16_t> unpacked;  // unpacked.cap samples
     adsb::Event ev_unpack;         // behind a device push's unpack: the second scan stream waits for it
+    // converted formats (adsb_*_as): the device's counters run on for the life of the handle; adsb_reset notes where they stand
+    adsb::Buf<unsigned long long> d_fmt; // {inexact, clamped}, allocated by the first _as call that converts
+    uint64_t fmt_converted = 0;          // samples converted since adsb_create / adsb_reset
+    unsigned long long fmt_base[2] = {0, 0};
+    bool fmt_dirty = false;              // a conversion has been enqueued since fmt_base was read
 
     // Shard-stream mode (adsb_shard_begin .. adsb_shard_end): the stream starts at sample shard_first instead of 0, ends
     // behind offset shard_g_end instead of at the end-of-file horizon, and the resolver runs in chain mode.
@@ -414,6 +423,9 @@ int read_tries(adsb_decoder *d);
 int process_stage(adsb_decoder *d, bool final, bool in_flight = false);
 int wait_last_copy(adsb_decoder *d);
 bool stream_too_long(adsb_decoder *d, size_t n);
+int format_prepare(adsb_decoder *d, const char *what, size_t land_bytes);
+int format_counters(adsb_decoder *d, unsigned long long out[2]);
+int format_dispatch(adsb_decoder *d, const char *what, int fmt, size_t *elem);
 bool shard_too_long(adsb_decoder *d, const char *what, uint64_t first_sample, uint64_t n, uint64_t total_samples);
 // decoder_collect.hip
 int slot_collect(adsb_decoder *d);

@@ -1,0 +1,104 @@
+"""Signed 16-bit real and float32 real samples (include/adsbdec_amd.h: the formats; airspy_rx -t 3 and -t 1) in plain numpy: the
+test-side definition, independent of the library's conversion kernels, and a converter for capture files.
+
+    INT16_REAL    x = (code - 2048) << 4;  code = (x >> 4) + 2048;  inexact iff x & 15
+    FLOAT32_REAL  x = (code - 2048) / 2048;  r = rint(2048 x) (ties to even), code = r + 2048 clamped to [0, 4095];
+                  clamped iff r + 2048 is outside [0, 4095] or x is +-Inf or NaN (NaN -> 2048), else inexact iff
+                  (code - 2048) / 2048 is not x (-0.0 is exact; every non-zero denormal is inexact)
+
+    python -m adsbdec_amd.sample_formats -t 3 in.u16 out.s16          # uint16 capture -> int16 real (-t 1: float32 real)
+    python -m adsbdec_amd.sample_formats -t 3 --back in.s16 out.u16   # and back; stderr counts what was off the grid
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+
+import numpy as np
+
+FLOAT32_REAL, INT16_REAL = 1, 3
+DTYPES = {FLOAT32_REAL: np.dtype("<f4"), INT16_REAL: np.dtype("<i2")}
+NAMES = {FLOAT32_REAL: "FLOAT32_REAL", INT16_REAL: "INT16_REAL"}
+
+
+def _codes(x) -> np.ndarray:
+    x = np.asarray(x)
+    if x.size and int(x.max()) > 0xFFF:
+        raise ValueError("codes above 4095 have no value in this format")
+    return x.astype(np.int32)
+
+
+def to_int16_real(x) -> np.ndarray:
+    """uint16 codes 0..4095 -> int16 samples."""
+    return ((_codes(x) - 2048) * 16).astype("<i2")
+
+
+def to_float32_real(x) -> np.ndarray:
+    """uint16 codes 0..4095 -> float32 samples in [-1, 1)."""
+    return ((_codes(x) - 2048) / 2048.0).astype("<f4")
+
+
+def flags_int16_real(x) -> tuple[np.ndarray, np.ndarray]:
+    """int16 samples -> (codes, inexact mask)."""
+    x = np.asarray(x, dtype=np.int16).astype(np.int32)
+    return (np.floor_divide(x, 16) + 2048).astype(np.uint16), (x % 16) != 0
+
+
+def flags_float32_real(x) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """float32 samples -> (codes, inexact mask, clamped mask), in binary64, where 2048 x is exact for every binary32 x."""
+    x = np.asarray(x, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = x.astype(np.float64)                             # (a signalling NaN raises "invalid" in the cast)
+        nan = np.isnan(v)
+        r = np.rint(np.where(nan, 0.0, v) * 2048.0)          # np.rint: ties to even
+        clamped = nan | (r < -2048.0) | (r > 2047.0)         # (+-Inf: r is +-Inf)
+        c = np.clip(r, -2048.0, 2047.0)
+        inexact = ~clamped & (c / 2048.0 != v)               # (-0.0 == 0.0; a denormal is not 0)
+    return (c + 2048.0).astype(np.uint16), inexact, clamped
+
+
+def from_int16_real(x):
+    """int16 samples -> (codes, inexact, clamped = 0)."""
+    codes, inexact = flags_int16_real(x)
+    return codes, int(inexact.sum()), 0
+
+
+def from_float32_real(x):
+    """float32 samples -> (codes, inexact, clamped): a sample is counted once, clamped wins."""
+    codes, inexact, clamped = flags_float32_real(x)
+    return codes, int(inexact.sum()), int(clamped.sum())
+
+
+def to_format(fmt: int, x) -> np.ndarray:
+    return to_int16_real(x) if fmt == INT16_REAL else to_float32_real(x)
+
+
+def from_format(fmt: int, x):
+    return from_int16_real(x) if fmt == INT16_REAL else from_float32_real(x)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m adsbdec_amd.sample_formats", description=__doc__.split("\n\n")[0])
+    ap.add_argument("-t", type=int, choices=sorted(DTYPES), required=True, help="1 = FLOAT32_REAL, 3 = INT16_REAL (as airspy_rx -t)")
+    ap.add_argument("src")
+    ap.add_argument("dst")
+    ap.add_argument("--back", action="store_true", help="the format -> uint16 codes instead of uint16 codes -> the format")
+    a = ap.parse_args(argv)
+    dt = DTYPES[a.t] if a.back else np.dtype("<u2")
+    b = np.fromfile(a.src, dtype=np.uint8)
+    cut = b.size % dt.itemsize
+    if cut:
+        sys.stderr.write(f"{a.src}: {cut} trailing bytes (a partial sample) ignored\n")
+    x = b[: b.size - cut].view(dt)
+    if a.back:
+        codes, inexact, clamped = from_format(a.t, x)
+        if inexact + clamped:
+            sys.stderr.write(f"{a.src}: {inexact + clamped} of {x.size} samples are not {NAMES[a.t]} values ({clamped} clamped)\n")
+        codes.astype("<u2").tofile(a.dst)
+    else:
+        to_format(a.t, x).tofile(a.dst)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,17 +1,14 @@
-/*
- * adsbdec_amd.h -- C-ABI of libadsbdec_amd.so: the MI355X (gfx950) drop-in for the offline "-f" demodulation path of TLeconte/adsbdec.
- * Everything a drop-in host and a multi-GPU host call; the primitives underneath (resolver handle, hand-off walker, shard scans,
- * stitcher) and the test knobs are in adsbdec_amd_diag.h.  The reference has no plugin/FFI interface: one prototype (adsbdec.h:5) plus
- * extern C functions with file-scope state.  Each entry point names the reference seam it stands behind (file:line);
- * INTEGRATION.md shows the change in air.c / output.c that binds them.  Conventions follow the reference: int 0 / -1 with a message
- * from adsb_last_error() (the reference prints to stderr, air.c:113-118); one producer thread per handle (decodeiq is not re-entrant:
- * air.c:33-34,49-50, demod.c:86); plain pointers and sizes, no C++/torch types.  HIP is the only implementation: no CPU fallback;
- * adsb_create() fails loudly when no gfx950 device is usable.
- * Input domain.  uint16 samples carrying the Airspy's 12-bit ADC code centred on 2048 (air.c:64).  Results are bit-identical to the
- * reference for every code in [0, 4095] and up to |x-2048| <= ~23 000 (the preamble sums still fit an int); beyond, the reference's
- * `int p1 = float + float` (demod.c:102-105) overflows -- undefined, wraps with gcc -- while this library compares un-wrapped values:
- * accepted, no parity claimed.  Streams end below 2^32 samples (the reference's `fidx` wraps there, SURVEY Q13: a push that
- * would reach it fails) unless adsb_set_long_stream is on: any length, decoded as the reference does through every wrap. */
+/* adsbdec_amd.h -- C-ABI of libadsbdec_amd.so: the MI355X (gfx950) drop-in for the offline "-f" demodulation path of TLeconte/adsbdec.
+ * Everything a drop-in host and a multi-GPU host call; the primitives underneath and the test knobs are in adsbdec_amd_diag.h.  The
+ * reference has no plugin/FFI interface: one prototype (adsbdec.h:5) plus extern C functions with file-scope state.  Each
+ * entry point names the reference seam it stands behind (file:line); INTEGRATION.md shows the change in air.c / output.c that binds them.
+ * Conventions follow the reference: int 0 / -1 with a message from adsb_last_error() (air.c:113-118 prints to stderr); one producer thread
+ * per handle (decodeiq is not re-entrant: air.c:33-34,49-50, demod.c:86); plain pointers and sizes.  HIP is the only implementation: no
+ * CPU fallback; adsb_create() fails loudly when no gfx950 device is usable.
+ * Input domain.  uint16 samples carrying the Airspy's 12-bit ADC code centred on 2048 (air.c:64).  Bit-identical to the reference for every
+ * code in [0, 4095] and up to |x-2048| <= ~23 000; beyond, the reference's `int p1 = float + float` (demod.c:102-105) overflows while this
+ * library compares un-wrapped values: accepted, no parity claimed.  Streams end below 2^32 samples (the reference's `fidx` wraps
+ * there, SURVEY Q13: a push that would reach it fails) unless adsb_set_long_stream is on: any length, decoded as the reference does. */
 #ifndef ADSBDEC_AMD_H
 #define ADSBDEC_AMD_H
 #include <stddef.h>
@@ -19,9 +16,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* Bumped when an entry point or struct member changes meaning or place; within one version adsb_config and adsb_profile grow at their
- * END only (adsb_create reads cfg->struct_size bytes, adsb_get_profile passes the caller's size).  5 (round 6): adsb_config carries `abi`
- * (any other value is refused by name: rebuild a binary of ABI <= 4); the debug_* knobs left for adsb_debug_config (diag header). */
+/* Bumped when an entry point or struct member changes meaning or place; within one version adsb_config and adsb_profile grow at their END
+ * only (adsb_create reads cfg->struct_size bytes).  5: adsb_config carries `abi` (any other value is refused); debug_* knobs: diag header. */
 #define ADSB_ABI_VERSION 5
 #define ADSB_PULSEW 5 /* constants of the path (adsbdec.h:1-3, air.c:32,47) */
 #define ADSB_DECOFFSET 1200
@@ -51,22 +47,16 @@ typedef struct adsb_config {
     int32_t profile;        /* time every scan launch on the device's own 100 MHz clock: adsb_profile.kernel_ms   */
     uint64_t stage_samples; /* device staging capacity for adsb_push(); 0 = default (32 Mi)                       */
     void *stream;           /* hipStream_t to launch on; NULL = a stream owned by the handle                      */
-    int32_t all_candidates; /* 1: the device reports EVERY CRC-valid offset; 0 (default): not those the greedy scan can never visit
-                               (same frames, ~4x fewer records)                                                   */
-    int32_t fix_1bit;       /* EXTENSION (the reference's -e does nothing): repair DF17/18 frames whose CRC residual is
-                               the syndrome of one bit in [5,112).  Off by default.                               */
+    int32_t all_candidates; /* 1: the device reports EVERY CRC-valid offset; 0 (default): not those the greedy scan can never visit (same frames) */
+    int32_t fix_1bit;       /* EXTENSION (SURVEY Q8), off by default: repair DF17/18 frames whose CRC residual is the syndrome of one bit in [5,112) */
     int32_t push_overlap;   /* 1: adsb_push() returns once `samples` is COPIED to the device, the scan in flight; a call's frames become
                                drainable during the NEXT push / finish / sync (same frames, same order).  0 (default): when the call returns */
-    int32_t host_threads;   /* Threads that consume the device's hand-off stream (decodeiq, air.c:54, never started one).
-                               1: the calling thread alone, ALWAYS -- the library never starts a thread.  2: + a thread of the handle's own
-                               that reads large launches' stream; N >= 3 (<= 17): + N - 2 that decide batches of tiles ahead and write frames.
-                               0 (default): 1, until a launch hands over a record per 2 048 offsets (a channel near its capacity); then 6,
-                               or 2 below 12 CPUs (what they do and buy: INTEGRATION.md).  adsb_profile.host_threads_running says what
-                               exists; same frames, order and counters whatever the value.                          */
-    int32_t wait_timeout_s; /* no wait for the device lasts longer (0 = default, 120 s): a launch or copy that never completes ends
-                               the call with -1 and adsb_last_error() names what was waited for                    */
-    int32_t warm_start;     /* 1: adsb_create also pays the runtime's first-use costs of copying (first large copy, second copy
-                               engine: 7-9 ms each) beside its other work: for a one-shot process                  */
+    int32_t host_threads;   /* Threads that consume the device's hand-off stream.  1: the calling thread alone, ALWAYS.  2: + a thread of the
+                               handle's own that reads large launches' stream; N >= 3 (<= 17): + N - 2 that decide batches of tiles ahead and
+                               write frames.  0 (default): 1, until a launch hands over a record per 2 048 offsets; then 6, or 2 below 12 CPUs
+                               (INTEGRATION.md).  adsb_profile.host_threads_running says what exists; same frames, order and counters always. */
+    int32_t wait_timeout_s; /* no wait for the device lasts longer (0 = default, 120 s): then -1, adsb_last_error() names what was waited for */
+    int32_t warm_start;     /* 1: adsb_create also pays the runtime's first-use costs of copying (7-9 ms each): for a one-shot process */
     const void *debug;      /* NULL, or an adsb_debug_config (adsbdec_amd_diag.h: test knobs); copied by adsb_create */
 } adsb_config;
 /* Counters accumulate over the life of the handle (adsb_reset keeps them: take differences); the last three members came with ABI 5. */
@@ -99,9 +89,8 @@ int adsb_reset(adsb_decoder *d);
 /* Sample ingress; replaces `decodeiq(const unsigned short *r, const int len)` (air.c:54), called from fileInput (air.c:239) / rx_callback
  * (air.c:175).  `samples` is borrowed for the call.  Any n: the stream is the concatenation of all pushes (the reference needs n % 4 == 0). */
 int adsb_push(adsb_decoder *d, const uint16_t *samples, size_t n);
-/* The same from a double-buffered read loop (fileInput with two iqbuffs): returns once copy and scan of this chunk are ENQUEUED, then
- * collects the PREVIOUS chunk's frames.  `samples` stays borrowed until the next push / finish / sync on the handle returns; frames
- * become drainable one call later, never reordered.  adsb_sync waits for everything. */
+/* The same from a double-buffered read loop: returns once copy and scan of this chunk are ENQUEUED, then collects the PREVIOUS chunk's frames.
+ * `samples` stays borrowed until the next push / finish / sync returns; frames become drainable one call later, in order.  adsb_sync waits for all. */
 int adsb_push_async(adsb_decoder *d, const uint16_t *samples, size_t n);
 int adsb_sync(adsb_decoder *d);
 /* Samples already resident in HBM (no reference counterpart).  A 16-byte aligned pointer at a stream position that is a
@@ -118,32 +107,49 @@ long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *co
                               const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n,
                             const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
-/* Airspy packed 12-bit input (air.c:120,128,150-151,173-177: the reference asks libairspy for packing, then turns it off).  A group
- * is 8 samples s0..s7 (12-bit codes, air.c:64) in three little-endian 32-bit words w0 w1 w2; read as ONE 96-bit big-endian number
- * w0:w1:w2 it is s0 s1 .. s7, 12 bits each, most significant first (written from this definition, not checked against libairspy):
+/* Airspy packed 12-bit input (air.c:120,128,150-151,173-177).  A group is 8 samples s0..s7 (12-bit codes, air.c:64) in three little-endian 32-bit
+ * words w0 w1 w2; as ONE 96-bit big-endian number w0:w1:w2 it is s0 .. s7, most significant first (from this definition, not checked against libairspy):
  *   s0 = w0 >> 20,  s1 = (w0 >> 8) & 0xfff,  s2 = (w0 & 0xff) << 4 | w1 >> 28,  s3 = (w1 >> 16) & 0xfff,  s4 = (w1 >> 4) & 0xfff,
  *   s5 = (w1 & 0xf) << 8 | w2 >> 24,  s6 = (w2 >> 12) & 0xfff,  s7 = w2 & 0xfff.
- * n counts SAMPLES: n % 8 == 0, ADSB_PACKED12_BYTES(n) bytes are read, at a stream position that is a multiple of 8 (uint16 and packed
- * pushes mix there); device pointers 4-byte aligned.  Otherwise -1, handle unchanged.  Frames, ts, Try/Ok, counters and contracts: the
- * uint16 calls'.  Extra device memory the handle keeps (grown on demand, freed by adsb_destroy): host pushes, two landing buffers of
- * 1.5 B x stage_samples; device pushes, a scratch of 2 B x n: unpacked there, then scanned. */
+ * n counts SAMPLES: n % 8 == 0, ADSB_PACKED12_BYTES(n) bytes are read, at a stream position that is a multiple of 8 (uint16 and packed pushes mix
+ * there); device pointers 4-byte aligned.  Otherwise -1, handle unchanged.  Frames, ts, Try/Ok, counters and contracts: the uint16 calls'.  Extra device
+ * memory the handle keeps (grown on demand): host pushes, two landing buffers of 1.5 B x stage_samples; device pushes, a scratch of 2 B x n. */
 #define ADSB_PACKED12_BYTES(n) ((n) / 8 * 12)
 int adsb_push_packed(adsb_decoder *d, const void *packed, size_t n);
 int adsb_push_packed_async(adsb_decoder *d, const void *packed, size_t n);
 int adsb_push_device_packed(adsb_decoder *d, const void *device_packed, size_t n);
 int adsb_push_device_packed_final(adsb_decoder *d, const void *device_packed, size_t n);
 long adsb_decode_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_frame **frames);
-/* adsb_decode_batch_device / _host for packed captures (n[i] counts samples): results, first / stats and the handle's state as theirs,
- * capture i decoded as its unpacked twin alone.  Refused by capture index, handle unchanged: n[i] % 8 != 0, a _device pointer not 4-byte
- * aligned, NULL with n[i] > 0, n[i] >= 2^32.  Extra device memory, kept as above: a scratch of 2 B x sum n (captures at 128-byte
- * boundaries) that ONE launch unpacks into; _host: + a landing buffer of 1.5 B x sum n. */
+/* adsb_decode_batch_device / _host for packed captures (n[i] counts samples): results, first / stats and the handle's state as theirs, capture i
+ * decoded as its unpacked twin alone.  Refused by capture index, handle unchanged: n[i] % 8 != 0, a _device pointer not 4-byte aligned, NULL with
+ * n[i] > 0, n[i] >= 2^32.  Extra device memory: a scratch of 2 B x sum n (captures at 128-byte boundaries), ONE launch; _host: + 1.5 B x sum n. */
 long adsb_decode_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n,
                                      const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const void *const *packed, const size_t *n,
                                    const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
-/* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps at
- * every 2^32 samples, bit for bit.  Only on a fresh or reset handle before the first push (else -1); sticky across adsb_reset.
- * The shard calls keep their 2^32 limit.  adsb_get_wraps: wraps so far, and offsets that went through the seam kernel. */
+/* Other REAL sample formats, converted to the uint16 code on the GPU; fmt is the airspy_rx -t number (from the definitions below, not checked against
+ * libairspy).  3 INT16_REAL: int16 x = (code - 2048) << 4; code = (x >> 4) + 2048; inexact iff x & 15.  1 FLOAT32_REAL: x = (code - 2048) / 2048;
+ * r = rint(2048 x), code = r + 2048 clamped to [0, 4095] -- clamped: outside, +-Inf, NaN (-> 2048); else inexact iff (code - 2048) / 2048 is not x
+ * (every denormal is, -0.0 is not).  4 UINT16_REAL, 5 RAW: the uint16 call of the same kind and its rules.  0, 2 (IQ: no raw twin), anything else: -1.
+ * Any n at any stream position, mixing with the other pushes; device pointers aligned to the element, else -1, handle unchanged.  Frames, ts, Try/Ok
+ * and contracts: the uint16 calls'.  Extra device memory, kept as for packed input: host pushes, two landing buffers of (2 or 4) B x stage_samples;
+ * device pushes and batches, the packed calls' scratch (2 B x n; ONE conversion launch per batch); _batch_host: + (2 or 4) B x sum n. */
+enum { ADSB_FMT_FLOAT32_REAL = 1, ADSB_FMT_INT16_REAL = 3, ADSB_FMT_UINT16_REAL = 4, ADSB_FMT_RAW = 5 };
+size_t adsb_format_bytes(int fmt, size_t n); /* bytes of n samples (0: a format that is refused) */
+int adsb_push_as(adsb_decoder *d, int fmt, const void *samples, size_t n);
+int adsb_push_async_as(adsb_decoder *d, int fmt, const void *samples, size_t n);
+int adsb_push_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n);
+int adsb_push_device_final_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n);
+long adsb_decode_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_frame **frames);
+long adsb_decode_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
+                                 const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
+long adsb_decode_batch_host_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
+                               const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
+/* Since adsb_create / adsb_reset: samples converted, and those off their format's grid (a wrong fmt shows here).  Waits for the conversions enqueued. */
+typedef struct adsb_format_report { uint64_t converted, inexact, clamped; } adsb_format_report;
+int adsb_get_format_report(const adsb_decoder *d, adsb_format_report *out);
+/* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
+ * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. */
 int adsb_set_long_stream(adsb_decoder *d, int on);
 int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
 int adsb_finish(adsb_decoder *d); /* end of input (EOF, air.c:241-244): the remaining offsets and the end-of-file horizon (SURVEY Q10) */
@@ -165,20 +171,17 @@ int adsb_get_stats(const adsb_decoder *d, adsb_stats *out);
 int adsb_get_profile_sized(const adsb_decoder *d, adsb_profile *out, size_t size);
 #define adsb_get_profile(d, out) adsb_get_profile_sized((d), (out), sizeof(adsb_profile))
 const char *adsb_last_error(const adsb_decoder *d); /* last error text of a handle, or of the last failed adsb_create() when d == NULL */
-/* formatpkt() (output.c:204-262, WITH_AIR).  outformat 0 = AVR "*hex;\n", 1 = AVR-MLAT "@ts48hex;\n", 2 = Beast.
- * pkt must hold 256 bytes.  Returns the packet length. */
+/* formatpkt() (output.c:204-262, WITH_AIR).  outformat 0 = AVR "*hex;\n", 1 = AVR-MLAT "@ts48hex;\n", 2 = Beast; pkt holds 256 bytes.  The length. */
 int adsb_format_frame(const adsb_frame *f, int outformat, char *pkt);
-/* The CPUs local to HIP device `device` (/sys/bus/pci/devices/<bdf>/local_cpulist, e.g. "0-63,128-191") and its NUMA node: the thread that
- * feeds a handle polls memory the device writes, 2.5-3 x slower from the far socket.  The string's length, 0 when the platform does not
- * say, -1 on error / node or -1. */
+/* The CPUs local to HIP device `device` (local_cpulist, e.g. "0-63,128-191") and its NUMA node: the thread that feeds a handle polls memory the
+ * device writes, 2.5-3 x slower from the far socket.  The string's length, 0 when the platform does not say, -1 on error / node or -1. */
 int adsb_device_cpulist(int device, char *out, size_t cap);
 int adsb_device_numa_node(int device);
 /* Splits the offsets [0, power_samples - ADSB_WINDOW] of one stream over n_shards owners (SURVEY.md 8e).  Shard i owns [g_begin[i], g_end[i])
  * (g_begin % 28 == 0) and needs the samples [first_sample[i], + n_samples[i]): 2 408 of halo.  Returns the shards used (<= n_shards). */
 int adsb_plan_shards(uint64_t total_samples, int n_shards, uint64_t *g_begin, uint64_t *g_end, uint64_t *first_sample, uint64_t *n_samples);
-/* ---- ONE process, several GPUs (csrc/multi.cpp): the host of BASELINE configs[3] / configs[4] ---------------------
- * A worker thread and a decoder handle per device; no collective on the data path.  Stands where
- * fileInput's loop (air.c:217-246) hands its buffers to decodeiq and the frames come back in ascending order for netout (output.c:159-182). */
+/* ---- ONE process, several GPUs (csrc/multi.cpp): the host of BASELINE configs[3] / configs[4].  A worker thread and a decoder handle per device; no
+ * collective on the data path.  Stands where fileInput's loop (air.c:217-246) feeds decodeiq and netout (output.c:159-182) takes frames. */
 typedef struct adsb_multi adsb_multi;
 typedef struct adsb_multi_info { /* of the last adsb_multi_decode_* call */
     int32_t shards;         /* shards the capture was cut into (streams decoded side by side, for the stream calls)  */
@@ -198,13 +201,11 @@ typedef struct adsb_multi_info { /* of the last adsb_multi_decode_* call */
 adsb_multi *adsb_multi_create(const adsb_config *cfg, int n_devices, const int *devices);
 void adsb_multi_destroy(adsb_multi *m);
 int adsb_multi_devices(const adsb_multi *m);
-/* configs[4]: ONE capture, time-sharded over as many devices as it is worth (>= 128 Ki offsets per shard); each worker feeds its halo'd
- * slice in 32 MiB pieces (a piece's copy under the scan of the one before) and resolves its shard while its kernels run; the calling
- * thread stitches and the workers gather.  Returns the number of frames, in the reference's order, *frames valid until the next call on
- * m; -1 on failure (after a worker was given up -- adsb_multi_last_error says so -- the handle only answers -1, and that call's SOURCE
- * buffers must stay alive: the worker may come back).  _host: the capture lies in host memory (page-lock it, or every piece goes through
- * the runtime's bounce buffers); _file: every worker reads its own slice of a regular file into page-locked buffers of its own;
- * _device: slice i is resident in the HBM of worker i's device and holds the samples adsb_multi_plan says. */
+/* configs[4]: ONE capture, time-sharded over as many devices as it is worth (>= 128 Ki offsets per shard); each worker feeds its halo'd slice in
+ * 32 MiB pieces and resolves its shard while its kernels run; the calling thread stitches and the workers gather.  Returns the number of frames, in
+ * the reference's order, *frames valid until the next call on m; -1 on failure (after a worker was given up -- adsb_multi_last_error says so -- the
+ * handle only answers -1, and that call's SOURCE buffers must stay alive).  _host: the capture lies in host memory (page-lock it); _file: every worker
+ * reads its own slice of a regular file; _device: slice i is resident in the HBM of worker i's device and holds the samples adsb_multi_plan says. */
 long adsb_multi_decode_host(adsb_multi *m, const uint16_t *samples, size_t n, const adsb_frame **frames);
 long adsb_multi_decode_file(adsb_multi *m, const char *path, const adsb_frame **frames);
 long adsb_multi_decode_device(adsb_multi *m, uint64_t total_samples, const void *const *slices, int n_slices, const adsb_frame **frames);
@@ -219,12 +220,11 @@ int adsb_multi_decode_streams_file(adsb_multi *m, int n_streams, const char *con
 long adsb_multi_stream_frames(const adsb_multi *m, int stream, const adsb_frame **frames);
 int adsb_multi_stream_stats(const adsb_multi *m, int stream, adsb_stats *out);
 int adsb_multi_get_info(const adsb_multi *m, adsb_multi_info *out);
-/* n_captures INDEPENDENT captures over the devices: each worker decodes a contiguous range of them (balanced by the offsets to scan) in
- * sub-batches of at most batch_bytes of sample data (default 256 MiB; diag header: adsb_multi_set_batch_bytes), one
- * adsb_decode_batch_host[_packed] each.  packed != 0: Airspy packed 12-bit.  Results as adsb_decode_batch_host's, in capture order, valid
- * until the next call on m; adsb_multi_get_stats: the sum.  _files: capture i is the regular file paths[i], read by its worker into
- * page-locked buffers (uint16: size / 2 samples; packed: its whole 12-byte groups).  -1, no partial result: a worker failed, or a file
- * is unreadable (the message names index and path). */
+/* n_captures INDEPENDENT captures over the devices: each worker decodes a contiguous range of them (balanced by the offsets to scan) in sub-batches
+ * of at most batch_bytes of sample data (default 256 MiB; diag header: adsb_multi_set_batch_bytes), one adsb_decode_batch_host[_packed] each.
+ * packed != 0: Airspy packed 12-bit.  Results as adsb_decode_batch_host's, in capture order, valid until the next call on m; adsb_multi_get_stats: the
+ * sum.  _files: capture i is the regular file paths[i] (uint16: size / 2 samples; packed: its whole 12-byte groups).  -1, no partial result: a worker
+ * failed, or a file is unreadable (the message names index and path). */
 long adsb_multi_decode_batch_host(adsb_multi *m, size_t n_captures, const void *const *samples, const size_t *n, int packed,
                                   const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_multi_decode_batch_files(adsb_multi *m, size_t n_captures, const char *const *paths, int packed,

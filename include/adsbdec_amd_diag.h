@@ -349,6 +349,13 @@ int adsb_host_release_mapped(void *p); /* adsb_host_free's first look (1: p was 
  * pushes run.  0, or -1 with the reason in adsb_last_error(NULL). */
 int adsb_unpack_packed12(void *dst_u16, const void *src, size_t n, void *stream);
 
+/* ---- the conversion of signed 16-bit / float32 real input on its own (adsbdec_amd.h: the formats; csrc/convert_samples.hip) ------
+ * n samples of fmt (1 FLOAT32_REAL, 3 INT16_REAL) in device memory at src (aligned to the element) -> n uint16 samples at dst_u16 (any
+ * 2-byte alignment), enqueued on `stream` (a hipStream_t; NULL: the null stream): the caller synchronizes.  device_counters2: NULL, or
+ * two uint64 in device memory that the samples' inexact and clamped counts are ADDED to.  The kernel the _as pushes run.  0, or -1
+ * with the reason in adsb_last_error(NULL); nothing is written then. */
+int adsb_convert_samples(void *dst_u16, const void *src, int fmt, size_t n, uint64_t *device_counters2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
