@@ -274,6 +274,12 @@ SYMBOLS = {
                                   C.c_uint64, C.POINTER(Candidate), C.c_size_t,
                                   C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_size_t,
                                   C.POINTER(C.c_size_t)]),
+    "adsb_scan_wrap_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint64,
+                                        C.c_uint64, C.POINTER(Candidate), C.c_size_t,
+                                        C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_size_t,
+                                        C.POINTER(C.c_size_t)]),
+    "adsb_seam_power": (C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64,
+                                   C.POINTER(C.c_float), C.c_size_t]),
 }
 
 _lib = None
@@ -747,21 +753,39 @@ class Decoder:
             self._check(self._L.adsb_get_profile(self._h, C.byref(p)), "adsb_get_profile")
         return {k: getattr(p, k) for k, _ in Profile._fields_}
 
-    def scan_shard(self, ptr: int, first_sample: int, n: int, g_begin: int, g_end: int,
-                   cand_cap: int = 1 << 16, try_cap: int = 1 << 20):
-        """Stateless per-shard scan -> (Candidate array, count, tries ndarray)."""
+    def _scan_call(self, fn, name, ptr, first_sample, n, g_begin, g_end, cand_cap, try_cap):
+        """adsb_scan_shard or its twin, with the arrays grown until they hold the answer."""
         while True:
             cands = (Candidate * cand_cap)()
             tries = np.empty(try_cap, dtype=np.uint64)
             nc, nt = C.c_size_t(0), C.c_size_t(0)
-            rc = self._L.adsb_scan_shard(self._h, ptr, first_sample, n, g_begin, g_end, cands, cand_cap,
-                                         C.byref(nc), tries.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                         try_cap, C.byref(nt))
+            rc = fn(self._h, ptr, first_sample, n, g_begin, g_end, cands, cand_cap,
+                    C.byref(nc), tries.ctypes.data_as(C.POINTER(C.c_uint64)), try_cap, C.byref(nt))
             if rc == -2:
                 cand_cap, try_cap = max(cand_cap, nc.value), max(try_cap, nt.value)
                 continue
-            self._check(rc, "adsb_scan_shard")
+            self._check(rc, name)
             return cands, nc.value, tries[: nt.value].copy()
+
+    def scan_shard(self, ptr: int, first_sample: int, n: int, g_begin: int, g_end: int,
+                   cand_cap: int = 1 << 16, try_cap: int = 1 << 20):
+        """Stateless per-shard scan -> (Candidate array, count, tries ndarray)."""
+        return self._scan_call(self._L.adsb_scan_shard, "adsb_scan_shard", ptr, first_sample, n, g_begin, g_end, cand_cap, try_cap)
+
+    def scan_wrap_window(self, ptr: int, first_sample: int, n: int, g_begin: int, g_end: int,
+                         cand_cap: int = 1 << 14, try_cap: int = 1 << 16):
+        """adsb_scan_wrap_window (a handle with long_stream): scan_shard at absolute stream positions, through the wraps."""
+        return self._scan_call(self._L.adsb_scan_wrap_window, "adsb_scan_wrap_window", ptr, first_sample, n, g_begin, g_end,
+                               cand_cap, try_cap)
+
+    def seam_power(self, ptr: int, first_sample: int, n: int, P: int, g_begin: int, g_end: int) -> np.ndarray:
+        """adsb_seam_power: the float32 power samples g_begin .. g_end - 2 + 1196 of one seam launch at the wrap P."""
+        out = np.empty(1196 + 28 + 1196, dtype=np.float32)
+        k = self._L.adsb_seam_power(self._h, ptr, first_sample, n, P, g_begin, g_end,
+                                    out.ctypes.data_as(C.POINTER(C.c_float)), out.size)
+        if k < 0:
+            self._check(-1, "adsb_seam_power")
+        return out[:k].copy()
 
     def decode(self, x: np.ndarray, chunk: int | None = None, mode: str = "sync"):
         """Whole-buffer convenience: push (optionally in chunks), finish, drain.

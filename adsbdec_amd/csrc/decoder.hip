@@ -393,6 +393,27 @@ int read_tries(adsb_decoder *d)
     return 0;
 }
 
+// What a seam launch over the offsets [g_begin, g_end) of the wrap at P is given: the buffer, the handle's settings and tables.
+static adsb::SeamArgs seam_args(const adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, uint64_t buf_n, uint64_t P, uint64_t g_begin,
+                                uint64_t g_end)
+{
+    adsb::SeamArgs a{};
+    a.x = reinterpret_cast<const uint32_t *>(buf);
+    a.pbuf0 = (int64_t)(buf_first / 2);
+    a.p_lo = a.pbuf0;
+    a.p_hi = a.pbuf0 + (int64_t)(buf_n / 2);
+    a.boundary = P;
+    a.g_begin = g_begin;
+    a.g_end = g_end;
+    a.df18 = d->cfg.df18 ? 1 : 0;
+    a.synd = d->d_synd;
+    a.fix_tab = d->cfg.fix_1bit ? d->d_fix : nullptr;
+    a.fix_mul = d->fix_mul;
+    a.want_tries = d->cfg.collect_stats ? 1 : 0;
+    a.out = d->seam_out;
+    return a;
+}
+
 // Offsets [g_begin, g_end) among the seam offsets of the wrap at power sample P (seam_kernel.h): one small launch, waited for.
 // Every launch before it is collected first, so its records reach the sink in offset order between those of the launches on
 // either side, and its tries are counted by a pass of their own between theirs.  Once per 2^32 samples: the wait costs
@@ -411,20 +432,7 @@ static int seam_scan(adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, u
     ScanLaunch &s = d->seam_slot;
     if (slot_order_behind_count(d, s, d->stream)) // (statistics runs: the count pass over the previous seam launch's tries reads seam_out)
         return -1;
-    adsb::SeamArgs a{};
-    a.x = reinterpret_cast<const uint32_t *>(buf);
-    a.pbuf0 = (int64_t)(buf_first / 2);
-    a.p_lo = a.pbuf0;
-    a.p_hi = a.pbuf0 + (int64_t)(buf_n / 2);
-    a.boundary = P;
-    a.g_begin = g_begin;
-    a.g_end = g_end;
-    a.df18 = d->cfg.df18 ? 1 : 0;
-    a.synd = d->d_synd;
-    a.fix_tab = d->cfg.fix_1bit ? d->d_fix : nullptr;
-    a.fix_mul = d->fix_mul;
-    a.want_tries = stats ? 1 : 0;
-    a.out = d->seam_out;
+    const adsb::SeamArgs a = seam_args(d, buf, buf_first, buf_n, P, g_begin, g_end);
     HIP_TRY(d, adsb::launch_seam(a, d->stream));
     HIP_TRY(d, hipEventRecord(s.ev_ready[0], d->stream));
     WAIT_EVENT(d, s.ev_ready[0], "a seam launch");
@@ -1288,6 +1296,39 @@ int adsb_get_profile_sized(const adsb_decoder *d, adsb_profile *out, size_t size
     p.host_threads_running = (d->reader ? 1u : 0u) + (d->gang ? (uint32_t)d->gang->helpers() : 0u);
     std::memcpy(out, &p, std::min(size, sizeof p));
     return 0;
+}
+
+// ---- diagnostics: the power samples of ONE seam launch (adsbdec_amd_diag.h) ----
+long adsb_seam_power(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, uint64_t P, uint64_t g_begin,
+                     uint64_t g_end, float *power, size_t power_cap)
+{
+    if (!d || !device_samples || !power)
+        return -1;
+    if (!d->long_stream || !d->seam_out)
+        return d->fail("adsb_seam_power: the handle was not given adsb_set_long_stream");
+    if (P == 0 || P % adsb::kEpoch != 0 || g_begin >= g_end || g_begin < adsb::seam_first(P) || g_end > adsb::seam_end(P))
+        return d->fail("adsb_seam_power: [g_begin, g_end) must be a range of the seam offsets [P - %d, P + %d) of a wrap P = w * 2^31, w >= 1",
+                       adsb::kSeamWindow, adsb::kSeamBehind);
+    if (first_sample % 8 || (uintptr_t)device_samples % 16 || n > (1ull << 62))
+        return d->fail("adsb_seam_power: buffer must start at a multiple of 8 samples, 16-byte aligned");
+    const size_t n_pow = (size_t)(g_end - g_begin) - 1 + adsb::kSeamWindow;
+    if (power_cap < n_pow)
+        return d->fail("adsb_seam_power: the launch has %zu power samples, the array holds %zu", n_pow, power_cap);
+    HIP_TRY(d, hipSetDevice(d->device));
+    if (scan_drain(d))
+        return -1;
+    if (slot_order_behind_count(d, d->seam_slot, d->stream)) // (a count pass may still read seam_out)
+        return -1;
+    adsb::Buf<float, adsb::Mem::Pinned> pw;
+    HIP_TRY(d, pw.reserve(n_pow));
+    adsb::SeamArgs a = seam_args(d, static_cast<const uint16_t *>(device_samples), first_sample, n, P, g_begin, g_end);
+    a.want_tries = 0;
+    a.power_out = pw;
+    HIP_TRY(d, adsb::launch_seam(a, d->stream));
+    HIP_TRY(d, hipEventRecord(d->seam_slot.ev_ready[0], d->stream));
+    WAIT_EVENT(d, d->seam_slot.ev_ready[0], "a seam launch");
+    std::memcpy(power, pw.p, n_pow * sizeof(float));
+    return (long)n_pow;
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
 // decoder_shard.hip -- the shard calls of the multi-GPU driver (multi.cpp): a range of a stream's offsets scanned
 // by a handle of its own, the records handed back or resolved in chain mode.  (The handle: decoder_state.hpp.)
 #include "decoder_state.hpp"
+#include "seam_kernel.h"
 
 using namespace adsb;
 
@@ -96,19 +97,11 @@ int scan_shard_resolved_core(adsb_decoder *d, const void *device_samples, uint64
     return 0;
 }
 
-} // namespace
-
-extern "C" {
-
-// ---- stateless per-shard scan (multi-GPU path, SURVEY.md 8e) -----------------
-int adsb_scan_shard(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n,
-                    uint64_t g_begin, uint64_t g_end, adsb_candidate *cands, size_t cand_cap,
-                    size_t *n_cands, uint64_t *tries, size_t try_cap, size_t *n_tries)
+// The stateless scan of a window that its caller has checked: sorted candidates and try words of [g_begin, g_end) into the
+// caller's arrays (adsb_scan_shard, adsb_scan_wrap_window).
+int scan_window(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, uint64_t g_begin, uint64_t g_end,
+                adsb_candidate *cands, size_t cand_cap, size_t *n_cands, uint64_t *tries, size_t try_cap, size_t *n_tries)
 {
-    if (!d || !device_samples || !n_cands || !n_tries)
-        return -1;
-    if (shard_window_refusal(d, "adsb_scan_shard", device_samples, first_sample, n, g_begin, g_end, 0))
-        return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     std::vector<adsb_candidate> cv;
     std::vector<uint64_t> tv;
@@ -133,6 +126,55 @@ int adsb_scan_shard(adsb_decoder *d, const void *device_samples, uint64_t first_
     if (!tv.empty())
         std::memcpy(tries, tv.data(), tv.size() * sizeof(uint64_t));
     return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- stateless per-shard scan (multi-GPU path, SURVEY.md 8e) -----------------
+int adsb_scan_shard(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n,
+                    uint64_t g_begin, uint64_t g_end, adsb_candidate *cands, size_t cand_cap,
+                    size_t *n_cands, uint64_t *tries, size_t try_cap, size_t *n_tries)
+{
+    if (!d || !device_samples || !n_cands || !n_tries)
+        return -1;
+    if (shard_window_refusal(d, "adsb_scan_shard", device_samples, first_sample, n, g_begin, g_end, 0))
+        return -1;
+    return scan_window(d, device_samples, first_sample, n, g_begin, g_end, cands, cand_cap, n_cands, tries, try_cap, n_tries);
+}
+
+// adsb_scan_shard for a handle with adsb_set_long_stream: a window at absolute stream positions, cut at the wraps as a stream's
+// own scan is (scan_submit: the seam kernel for [P - 1196, P + 28), epoch-relative launches on either side).
+int adsb_scan_wrap_window(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, uint64_t g_begin,
+                          uint64_t g_end, adsb_candidate *cands, size_t cand_cap, size_t *n_cands, uint64_t *tries, size_t try_cap,
+                          size_t *n_tries)
+{
+    const char *what = "adsb_scan_wrap_window";
+    if (!d || !device_samples || !n_cands || !n_tries)
+        return -1;
+    if (!d->long_stream)
+        return d->fail("%s: the handle was not given adsb_set_long_stream (below 2^32 samples: adsb_scan_shard)", what);
+    if (first_sample % 8 || (uintptr_t)device_samples % 16)
+        return d->fail("%s: buffer must start at a multiple of 8 samples, 16-byte aligned", what);
+    if (first_sample > (1ull << 62) || n > (1ull << 62) || g_begin > (1ull << 61) || g_end > (1ull << 61))
+        return d->fail("%s: stream position beyond 2^62", what);
+    {   // (scannable_end: a stream's pushes cut a seam range anywhere, an epoch's launches at its run boundaries)
+        const uint64_t P = round_down(g_begin, adsb::kEpoch), r = g_begin - P;
+        const bool in_seam = (P && r < (uint64_t)adsb::kSeamBehind) || r >= adsb::kEpoch - adsb::kSeamWindow;
+        if (!in_seam && r % 28)
+            return d->fail("%s: g_begin must be a run boundary of its epoch ((g_begin - P) %% 28 == 0, P = w * 2^31) or a seam offset", what);
+    }
+    if (g_end > g_begin) {
+        const uint64_t need_lo = g_begin >= 6 ? 2 * (g_begin - 6) : 0;
+        const uint64_t need_hi = 2 * (g_end - 1 + ADSB_WINDOW);
+        if (first_sample > need_lo || first_sample + n < need_hi)
+            return d->fail("%s: buffer does not cover the window of the owned offsets", what);
+    }
+    const uint64_t seam_before = d->seam_offsets; // (a stream's count, adsb_get_wraps: this call is no part of a stream)
+    const int rc = scan_window(d, device_samples, first_sample, n, g_begin, g_end, cands, cand_cap, n_cands, tries, try_cap, n_tries);
+    d->seam_offsets = seam_before;
+    return rc;
 }
 
 int adsb_scan_shard_host(adsb_decoder *d, const uint16_t *host_samples, uint64_t first_sample, size_t n, uint64_t g_begin,

@@ -33,6 +33,9 @@ struct SeamArgs {
     // out + kSeamOutHeader, try words ((g - g_begin) << 2) | code from out + kSeamOutHeader + kCandWords * kSeamMaxOffsets.
     // Neither list is sorted.  Every CRC-valid offset is reported (no never-visited filter).
     uint32_t *out;
+    // diagnostics (adsb_seam_power): null in every launch a stream makes.  Set: the launch's n_pow = g_end - g_begin - 1 + kSeamWindow
+    // power samples, power_out[i] = power sample g_begin + i, as the offsets' tests read them.
+    float *power_out;
 };
 constexpr size_t kSeamOutWords = kSeamOutHeader + (6 + 1) * (size_t)kSeamMaxOffsets;
 

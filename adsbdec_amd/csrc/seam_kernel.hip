@@ -105,6 +105,9 @@ __global__ __launch_bounds__(kSeamThreads) void seam_kernel(const SeamArgs a)
         pw[i] = (m >= P - 1 && m <= P + 5) ? power_transient(a, m, lt) : power_in_epoch(a, m);
     }
     __syncthreads();
+    if (a.power_out) // (each lane the samples it computed)
+        for (int i = tid; i < n_pow; i += kSeamThreads)
+            a.power_out[i] = pw[i];
     for (int v = tid; v < kSeamWords; v += kSeamThreads) {
         uint32_t w = 0;
         for (int j = 0; j < 28; j++) {

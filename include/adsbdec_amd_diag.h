@@ -134,6 +134,24 @@ int adsb_scan_shard_host(adsb_decoder *d, const uint16_t *host_samples, uint64_t
                          uint64_t g_begin, uint64_t g_end, adsb_candidate *cands, size_t cand_cap,
                          size_t *n_cands, uint64_t *tries, size_t try_cap, size_t *n_tries);
 
+/* ---- streams of 2^32 samples and more (adsb_set_long_stream), offset by offset ----------------------------------------------
+ * adsb_scan_wrap_window: adsb_scan_shard's twin for a handle with adsb_set_long_stream on.  first_sample, g_begin and g_end are
+ * ABSOLUTE stream positions, at or beyond 2^32 samples too; the window is scanned by the launches a stream makes over it
+ * (air.c:34: the reference's counter wraps every 2^32 samples): the seam kernel for the offsets [P - 1196, P + 28) around a wrap
+ * at power sample P = w * 2^31, launches in epoch-relative indices on either side.  Sorted candidates, and with collect_stats
+ * the try words; no stream state is touched.  The buffer rules are adsb_scan_shard's, but for g_begin: a run boundary of its own
+ * epoch ((g_begin - P) % 28 == 0) outside the seam offsets, any offset inside them (a stream's pushes cut a seam anywhere).
+ * -1 with a message on a handle without the switch.  adsb_scan_shard and its relatives keep their limit at 2^32. */
+int adsb_scan_wrap_window(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n,
+                          uint64_t g_begin, uint64_t g_end, adsb_candidate *cands, size_t cand_cap,
+                          size_t *n_cands, uint64_t *tries, size_t try_cap, size_t *n_tries);
+/* adsb_seam_power: ONE seam launch over the offsets [g_begin, g_end) inside [P - 1196, P + 28) of the wrap at P (same handle; the buffer's
+ * ALIGNMENT rules are adsb_scan_shard's, it need not cover the launch's window: pairs it does not hold read as silence), and the power samples it computed (air.c:69-76,84-91; P - 1 ..
+ * P + 5 by the ring as the wrapped counter finds it): power[i] = power sample g_begin + i, for i < g_end - g_begin - 1 + 1196.
+ * Returns that count, or -1 with a message (a range outside the seam offsets, power_cap too small, no switch). */
+long adsb_seam_power(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, uint64_t P,
+                     uint64_t g_begin, uint64_t g_end, float *power, size_t power_cap);
+
 /* ---- time-sharded stream, resolved where the records are (BASELINE configs[4]) ---------------
  * adsb_scan_shard + one resolver on one rank funnels every candidate of the stream through a single thread.  The
  * scalable form: every rank resolves its OWN shard while its kernel runs -- the greedy rule of demod.c:89,128,134,141
