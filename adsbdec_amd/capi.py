@@ -111,6 +111,9 @@ class FormatReport(C.Structure):
 
 # fmt of the _as calls: the airspy_rx -t numbers (include/adsbdec_amd.h)
 FMT_FLOAT32_REAL, FMT_INT16_REAL, FMT_UINT16_REAL, FMT_RAW = 1, 3, 4, 5
+# fmt of the _iq calls (complex captures): arrays of shape (n, 2) = (I, Q), or flat ones of 2 n scalars
+FMT_FLOAT32_IQ, FMT_INT16_IQ = 0, 2
+IQ_DTYPES = {FMT_FLOAT32_IQ: np.dtype("<f4"), FMT_INT16_IQ: np.dtype("<i2")}
 FMT_DTYPES = {FMT_FLOAT32_REAL: np.dtype("<f4"), FMT_INT16_REAL: np.dtype("<i2"), FMT_UINT16_REAL: np.dtype("<u2"), FMT_RAW: np.dtype("<u2")}
 
 
@@ -180,6 +183,17 @@ SYMBOLS = {
                                                C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     "adsb_decode_batch_host_as": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                              C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_iq_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "adsb_push_iq": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "adsb_push_iq_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "adsb_push_device_iq": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "adsb_push_device_iq_final": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "adsb_decode_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Frame))]),
+    "adsb_decode_batch_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                               C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_decode_batch_host_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                             C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_multi_decode_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int,
@@ -668,6 +682,88 @@ class Decoder:
         st = (Stats * max(1, k))()
         if self._L.adsb_decode_batch_host_as(self._h, fmt, k, p, n, self._out_ref, first, st) < 0:
             self._check(-1, "adsb_decode_batch_host_as")
+        return self._batch_result(self._out, first, st, k, stats)
+
+    # ---- complex captures (include/adsbdec_amd.h: the _iq calls; fmt 0 FLOAT32_IQ, 2 INT16_IQ); n counts COMPLEX samples
+    @staticmethod
+    def _iq_arg(fmt, x):
+        if isinstance(x, tuple):
+            return x
+        assert fmt not in IQ_DTYPES or x.dtype == IQ_DTYPES[fmt], (fmt, x.dtype)
+        assert x.flags["C_CONTIGUOUS"] and x.size % 2 == 0
+        return x.ctypes.data, x.size // 2
+
+    def push_iq(self, fmt: int, x, mode: str = "sync"):
+        """adsb_push_iq (mode "sync") / adsb_push_iq_async ("async": x stays borrowed until the next push/finish/sync returns);
+        x = ndarray of (I, Q) scalars of the format's dtype, or (ptr, n complex samples)."""
+        ptr, n = self._iq_arg(fmt, x)
+        if mode == "async":
+            self._check(self._L.adsb_push_iq_async(self._h, fmt, ptr, n), "adsb_push_iq_async")
+        elif mode == "sync":
+            self._check(self._L.adsb_push_iq(self._h, fmt, ptr, n), "adsb_push_iq")
+        else:
+            raise ValueError(mode)
+
+    def push_device_iq(self, fmt: int, ptr: int, n: int, final: bool = False):
+        if final:
+            self._check(self._L.adsb_push_device_iq_final(self._h, fmt, ptr, n), "adsb_push_device_iq_final")
+        else:
+            self._check(self._L.adsb_push_device_iq(self._h, fmt, ptr, n), "adsb_push_device_iq")
+
+    def decode_device_iq(self, fmt: int, ptr: int, n: int):
+        """adsb_decode_device_iq: one complex capture resident in HBM -> its frames."""
+        k = self._L.adsb_decode_device_iq(self._h, fmt, ptr, n, self._out_ref)
+        if k < 0:
+            self._check(-1, "adsb_decode_device_iq")
+        return _frames_to_dicts(self._out, k)
+
+    def decode_iq(self, fmt: int, x: np.ndarray, chunk: int | None = None, mode: str = "sync"):
+        """decode() for a complex capture in host memory: chunk counts complex samples (any number); mode "sync" or "async"."""
+        x = np.ascontiguousarray(x).reshape(-1, 2)
+        self.reset()
+        chunk = chunk or max(1, len(x))
+        pieces = [x[i:i + chunk] for i in range(0, len(x), chunk)]
+        out = []
+        if mode == "sync":
+            for p in pieces:
+                self.push_iq(fmt, p)
+            self.finish()
+            return self.drain()
+        if mode != "async":
+            raise ValueError(mode)
+        elem = x.dtype.itemsize * 2
+        with PinnedBuffers(2, max(1, (min(chunk, max(1, len(x))) * elem + 1) // 2)) as bufs:
+            for k, p in enumerate(pieces):
+                b = bufs[k % 2].view(np.uint8)[: len(p) * elem].view(x.dtype)
+                b[:] = p.reshape(-1)        # the push from this buffer was two calls ago
+                self.push_iq(fmt, b, "async")
+                out += self.drain()
+            self.finish()
+            out += self.drain()
+        return out
+
+    def decode_batch_device_iq(self, fmt: int, ptrs, ns, stats: bool = False):
+        """adsb_decode_batch_device_iq: complex captures resident in HBM (ns in complex samples) -> what decode_batch_device gives."""
+        k = len(ns)
+        p = (C.c_void_p * max(1, k))(*[int(v) if v else None for v in ptrs])
+        n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        if self._L.adsb_decode_batch_device_iq(self._h, fmt, k, p, n, self._out_ref, first, st) < 0:
+            self._check(-1, "adsb_decode_batch_device_iq")
+        return self._batch_result(self._out, first, st, k, stats)
+
+    def decode_batch_iq(self, fmt: int, arrays, stats: bool = False):
+        """The same for arrays of (I, Q) scalars in host memory: adsb_decode_batch_host_iq."""
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        assert all((fmt not in IQ_DTYPES or a.dtype == IQ_DTYPES[fmt]) and a.size % 2 == 0 for a in arrays)
+        k = len(arrays)
+        p = (C.c_void_p * max(1, k))(*[a.ctypes.data if a.size else None for a in arrays])
+        n = (C.c_size_t * max(1, k))(*[a.size // 2 for a in arrays])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        if self._L.adsb_decode_batch_host_iq(self._h, fmt, k, p, n, self._out_ref, first, st) < 0:
+            self._check(-1, "adsb_decode_batch_host_iq")
         return self._batch_result(self._out, first, st, k, stats)
 
     def format_report(self):

@@ -21,6 +21,8 @@
  *                   anything else are refused.  A trailing partial sample is not decoded and stderr says how many bytes
  *                   were ignored.  A run in which samples were off the format's grid ends with a line on stderr that says
  *                   how many: the sign of a wrong -t.  -t 1 and -t 3 not with -p, -G or -B.
+ *     -q type       EXTENSION: the file holds COMPLEX samples at 10 MS/s, numbered as airspy_rx -t numbers them: 2 INT16_IQ (its
+ *                   default), 0 FLOAT32_IQ (adsbdec_amd.h: the _iq calls).  Not with -t, -p, -G or -B; a file below 2^31 samples.
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -164,7 +166,7 @@ static void *locker_main(void *arg)
 static void usage(void)
 {
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
-    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
+    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-q type] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
     printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
@@ -176,6 +178,8 @@ static void usage(void)
     printf("\t-p : (extension) the file holds Airspy packed 12-bit samples (8 samples in 12 bytes), unpacked on the GPU; not with -G\n");
     printf("\t-t type : (extension) sample type of the file as airspy_rx -t numbers it: 1 float32 real and 3 signed 16 bits real are\n");
     printf("\t     converted on the GPU, 4 and 5 are the uint16 code (the default); not 0 or 2 (IQ); 1 and 3 not with -p, -G or -B\n");
+    printf("\t-q type : (extension) the file holds COMPLEX samples at 10 MS/s, as airspy_rx -t numbers them: 2 signed 16 bits IQ (airspy_rx's\n");
+    printf("\t     default), 0 float32 IQ (quantised to the int16 grid on the GPU); not with -t, -p, -G or -B\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
@@ -495,10 +499,12 @@ int main(int argc, char **argv)
     int outformat = 0, df18 = 0, fix1 = 0, packed = 0, c;
     long stype = 5; /* -t: ADSB_FMT_RAW */
     const char *stype_arg = NULL;
+    long qtype = -1; /* -q: ADSB_FMT_INT16_IQ / ADSB_FMT_FLOAT32_IQ */
+    const char *qtype_arg = NULL;
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpd:G:s:l:B:t:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpd:G:s:l:B:t:q:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -561,6 +567,14 @@ int main(int argc, char **argv)
             stype_arg = optarg;
             break;
         }
+        case 'q': {
+            char *end;
+            qtype = strtol(optarg, &end, 10);
+            if (*end || end == optarg)
+                qtype = -1;
+            qtype_arg = optarg;
+            break;
+        }
         default:
             usage();
             return 1;
@@ -581,6 +595,18 @@ int main(int argc, char **argv)
                 packed ? "a file is packed 12-bit or of that type, not both" : "the multi-GPU driver reads uint16 and packed files only");
         return 1;
     }
+    if (qtype_arg && qtype != ADSB_FMT_INT16_IQ && qtype != ADSB_FMT_FLOAT32_IQ) {
+        fprintf(stderr, "-q %s: not an IQ sample type; -q takes 2 (int16 IQ) or 0 (float32 IQ), real samples go with -t\n", qtype_arg);
+        return 1;
+    }
+    if (qtype_arg && (stype_arg || packed || ndev || listfile)) {
+        fprintf(stderr, "-q %ld is not supported with %s: %s\n", qtype, stype_arg ? "-t" : packed ? "-p" : ndev ? "-G" : "-B",
+                stype_arg ? "a file holds real samples (-t) or IQ samples (-q), not both"
+                : packed  ? "a file is packed 12-bit real or IQ, not both"
+                          : "the multi-GPU driver reads uint16 and packed files only");
+        return 1;
+    }
+    const int iq = qtype_arg != NULL;
     if (listfile) { /* a batch: its own inputs and outputs -- no -f, no peer; -d and -G exclude each other here too */
         if (filename || outmode != SINK_STDOUT || (ndev && device >= 0)) {
             usage();
@@ -614,9 +640,11 @@ int main(int argc, char **argv)
     }
     if (packed)
         buf_bytes = (size_t)BUF_SAMPLES / 8 * 12;
-    const size_t elem = converted ? adsb_format_bytes((int)stype, 1) : 2; /* (host arithmetic: no GPU call) */
+    const size_t elem = iq ? adsb_iq_bytes((int)qtype, 1) : converted ? adsb_format_bytes((int)stype, 1) : 2; /* (host arithmetic: no GPU call) */
     if (converted)
         buf_bytes = adsb_format_bytes((int)stype, BUF_SAMPLES);
+    if (iq)
+        buf_bytes = adsb_iq_bytes((int)qtype, BUF_SAMPLES / 2);
     install_signals();
     sink_init(&out_sink, outmode, rawaddr);
     out_sink.stop = &stop_requested;
@@ -711,7 +739,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
         return 255; /* runOutput() == -1 -> exit status 255 (main.c:101-105) */
     }
-    if (adsb_set_long_stream(dec, 1) != 0) { /* always: the reference reads a file of any length (its counter wraps, air.c:34) */
+    if (!iq && adsb_set_long_stream(dec, 1) != 0) { /* always: the reference reads a file of any length (its counter wraps, air.c:34) */
         fprintf(stderr, "adsb_set_long_stream() failed: %s\n", adsb_last_error(dec));
         return 255;
     }
@@ -749,14 +777,16 @@ int main(int argc, char **argv)
             /* a trailing odd byte is dropped, like decodeiq(iqbuff, n / 2) (air.c:239); packed: a trailing partial group (only the
              * last buffer can have one: a full buffer is whole groups) */
             const size_t n_samples = packed ? bytes / 12 * 8 : bytes / elem;
-            if (converted && bytes % elem)
+            if ((converted || iq) && bytes % elem)
                 fprintf(stderr, "%zu trailing bytes ignored (not a whole %zu-byte sample)\n", bytes % elem, elem);
             if (packed && bytes % 12)
                 fprintf(stderr, "%zu trailing bytes ignored (not a whole 12-byte group of packed samples)\n", bytes % 12);
             if (n_samples) {
                 const double t_p0 = now_ms();
                 int prc;
-                if (packed)
+                if (iq)
+                    prc = s->registered ? adsb_push_iq_async(dec, (int)qtype, s->buf, n_samples) : adsb_push_iq(dec, (int)qtype, s->buf, n_samples);
+                else if (packed)
                     prc = s->registered ? adsb_push_packed_async(dec, s->buf, n_samples) : adsb_push_packed(dec, s->buf, n_samples);
                 else if (converted)
                     prc = s->registered ? adsb_push_async_as(dec, (int)stype, s->buf, n_samples) : adsb_push_as(dec, (int)stype, s->buf, n_samples);
@@ -831,6 +861,9 @@ int main(int argc, char **argv)
     if (converted && adsb_get_format_report(dec, &rep) == 0 && rep.inexact + rep.clamped > 0)
         fprintf(stderr, "%llu of %llu samples are not %s values (%llu clamped): is -t right?\n", (unsigned long long)(rep.inexact + rep.clamped),
                 (unsigned long long)rep.converted, stype == ADSB_FMT_INT16_REAL ? "INT16_REAL" : "FLOAT32_REAL", (unsigned long long)rep.clamped);
+    if (iq && qtype == ADSB_FMT_FLOAT32_IQ && adsb_get_format_report(dec, &rep) == 0 && rep.inexact + rep.clamped > 0)
+        fprintf(stderr, "%llu of %llu float scalars were rounded to the int16 grid (%llu clamped): expected of a float32 IQ capture\n",
+                (unsigned long long)(rep.inexact + rep.clamped), (unsigned long long)rep.converted, (unsigned long long)rep.clamped);
     /* no adsb_destroy / unregister / free: the process ends here, and tearing the GPU runtime
      * down cleanly costs tens of milliseconds that an offline decode has no use for */
     fflush(stderr);

@@ -1,5 +1,5 @@
 // convert_samples.hip -- signed 16-bit real and float32 real samples (include/adsbdec_amd.h: the formats) -> the uint16 samples the
-// scan reads, and a count of the samples that do not lie on their format's grid.
+// scan reads (and the float32 scalars of FLOAT32_IQ -> the int16 scalars the IQ scan reads: one more instantiation), and a count of the samples that do not lie on their format's grid.
 //
 // A separate, memory-bound pass for unpack12.hip's reason: the scan kernel converts uint16 to f32 inside its typed buffer loads
 // at no VALU cost, and it is VALU-bound.  (Scaling float input into the FIR instead would not even be exact: DESIGN.md section 4.)
@@ -22,12 +22,14 @@ namespace {
 template <int FMT> struct Element;
 template <> struct Element<kFmtInt16Real> { typedef uint16_t type; };
 template <> struct Element<kFmtFloat32Real> { typedef uint32_t type; };
+template <> struct Element<kConvFloat32Iq> { typedef uint32_t type; };
 
 typedef const __attribute__((address_space(1))) uint16_t *global_u16;
 typedef const __attribute__((address_space(1))) uint32_t *global_u32;
 template <int FMT> struct GlobalElement;
 template <> struct GlobalElement<kFmtInt16Real> { typedef global_u16 type; };
 template <> struct GlobalElement<kFmtFloat32Real> { typedef global_u32 type; };
+template <> struct GlobalElement<kConvFloat32Iq> { typedef global_u32 type; };
 
 struct Counts {
     uint32_t inexact = 0, clamped = 0;
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(256) void convert_kernel(uint16_t *__restrict__ dst
         const size_t base = i - threadIdx.x % warpSize;                    // a multiple of 64: the block and the stride are
         size_t at = i;
         uint4 out;
-        if (FMT == kFmtFloat32Real && base + 64 <= groups)
+        if (sizeof(typename Element<FMT>::type) == 4 && base + 64 <= groups) // (the float32 formats, real and IQ)
             out = convert_wave_of_groups<FMT>(s, base, c, &at);
         else if (i < groups)
             out = convert_group<FMT>(s + 8 * i, c);
@@ -203,6 +205,10 @@ hipError_t launch_convert(int fmt, uint16_t *dst, const void *src, size_t n, uns
         hipLaunchKernelGGL((convert_kernel<kFmtFloat32Real, true>), dim3(blocks), dim3(256), 0, stream, dst, f32, n, head, counters);
     else if (fmt == kFmtFloat32Real)
         hipLaunchKernelGGL((convert_kernel<kFmtFloat32Real, false>), dim3(blocks), dim3(256), 0, stream, dst, f32, n, head, counters);
+    else if (fmt == kConvFloat32Iq && counters)
+        hipLaunchKernelGGL((convert_kernel<kConvFloat32Iq, true>), dim3(blocks), dim3(256), 0, stream, dst, f32, n, head, counters);
+    else if (fmt == kConvFloat32Iq)
+        hipLaunchKernelGGL((convert_kernel<kConvFloat32Iq, false>), dim3(blocks), dim3(256), 0, stream, dst, f32, n, head, counters);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
@@ -218,6 +224,8 @@ hipError_t launch_convert_batch(int fmt, uint16_t *dst, const ConvertSeg *tab_de
         hipLaunchKernelGGL(convert_batch_kernel<kFmtInt16Real>, dim3(blocks), dim3(kConvertChunk), 0, stream, dst, tab_device, n_rows, groups, counters);
     else if (fmt == kFmtFloat32Real)
         hipLaunchKernelGGL(convert_batch_kernel<kFmtFloat32Real>, dim3(blocks), dim3(kConvertChunk), 0, stream, dst, tab_device, n_rows, groups, counters);
+    else if (fmt == kConvFloat32Iq)
+        hipLaunchKernelGGL(convert_batch_kernel<kConvFloat32Iq>, dim3(blocks), dim3(kConvertChunk), 0, stream, dst, tab_device, n_rows, groups, counters);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

@@ -224,6 +224,8 @@ int slot_launch(adsb_decoder *d, ScanSlot &s)
         ka.p_lo = std::max<int64_t>(ka.p_lo - P, 0);
         ka.p_hi -= P;
         HIP_TRY(d, adsb::launch_scan(ka, stats, ls));
+    } else if (d->kind == adsb::kKindIq && !d->sink.cands) { // (a stateless shard scan on a handle that holds an IQ stream is a real one)
+        HIP_TRY(d, adsb::launch_scan_iq(s.args, stats, ls));
     } else {
         HIP_TRY(d, adsb::launch_scan(s.args, stats, ls));
     }
@@ -533,6 +535,7 @@ int scan_submit(adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, uint64
         a.g_begin = g_begin;
         a.g_end = g_stop;
         fill_scan_args(d, a);
+        // (choose_passes's table was measured with the real kernel; IQ launches use it as it is: nobody has measured theirs)
         a.passes = (d->dbg.passes >= 2 && d->dbg.passes <= adsb::kMaxPasses) ? d->dbg.passes
                                                                                          : adsb::choose_passes(n_off, d->n_cus, last_launch_was_dense(d));
         a.big_tiles = adsb::choose_big_tiles(n_off, a.passes, d->n_cus, d->dbg.big_tiles);
@@ -585,7 +588,8 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight)
     // At EOF a trailing partial quad still makes the reference produce two (garbage)
     // power samples (air.c:59 loop bound); they can never be read by a visited
     // offset but they count for the `aidx >= APBUFFSZ` test.
-    const uint64_t m_ref = final ? 2 * ((d->n_samples + 3) / 4) : m_real;
+    // (An IQ stream has no quads: its power samples enter two at a time and a trailing odd one is never seen.)
+    const uint64_t m_ref = final && d->kind != adsb::kKindIq ? 2 * ((d->n_samples + 3) / 4) : m_real;
     if (!in_flight) // (in flight: the records below g_scanned are not all in yet; slot_collect advanced as far as they are)
         d->res.advance(m_ref, d->g_scanned);
     if (final)
@@ -652,7 +656,7 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight)
 // land[] like packed ones and the conversion kernel stands where the unpack does.  Any n, any stage_fill.
 static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind kind, bool async = false, bool packed = false, int conv = 0)
 {
-    const size_t elem = adsb::format_element_bytes(conv);
+    const size_t elem = adsb::convert_element_bytes(conv);
     const char *p = static_cast<const char *>(src);
     while (n) {
         uint64_t room = d->stage_cap - kStageSlack - d->stage_fill;
@@ -785,19 +789,35 @@ int format_dispatch(adsb_decoder *d, const char *what, int fmt, size_t *elem)
     return d->fail("%s: unknown sample format %d (1 FLOAT32_REAL, 3 INT16_REAL, 4 UINT16_REAL, 5 RAW)", what, fmt);
 }
 
+// The stream's kind is fixed by its first push with samples; a push of the other kind is refused, the handle as it was.
+int kind_refusal(adsb_decoder *d, const char *what, int kind)
+{
+    static const char *const names[] = {"", "real", "IQ"};
+    if (kind == adsb::kKindIq && d->long_stream)
+        return d->fail("%s: a long-stream handle (adsb_set_long_stream) takes real samples only, not IQ ones: the counter wrap it follows is "
+                       "the FIR ring's (air.c:34) and an IQ stream has no ring", what);
+    if (d->kind != adsb::kKindNone && d->kind != kind)
+        return d->fail("%s: the stream holds %s samples (its first push fixed that) and %s samples cannot follow them: adsb_reset starts a "
+                       "fresh stream", what, names[d->kind], names[kind]);
+    return 0;
+}
+
 // adsb_push, adsb_push_async and their packed forms: samples in host memory (`packed`: whole groups of 12-bit samples).
-static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async, bool packed, const char *what, int conv = 0)
+// kind: kKindIq from the _iq calls, whose n counts 16-bit units (fmt 2) or float scalars (fmt 0): two per complex sample.
+static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async, bool packed, const char *what, int conv = 0,
+                     int kind = adsb::kKindReal)
 {
     if (!d)
         return -1;
     if (d->finished)
         return d->fail("%s after adsb_finish", what);
-    if ((packed && packed_refusal(d, what, n, d->n_samples)) || stream_too_long(d, n))
+    if (kind_refusal(d, what, kind) || (packed && packed_refusal(d, what, n, d->n_samples)) || stream_too_long(d, n))
         return -1;
     if (n == 0)
         return 0;
     if (!samples)
         return d->fail("%s: NULL samples", what);
+    d->kind = kind;
     HIP_TRY(d, hipSetDevice(d->device));
     if (packed) { // the landing buffers, one per copy stream: a handle that never sees packed input has none
         const size_t bytes = d->stage_cap / adsb::kPackedGroupSamples * adsb::kPackedGroupBytes;
@@ -807,7 +827,7 @@ static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async,
                 return d->fail("packed input: cannot allocate a landing buffer of %zu bytes on the device", bytes);
             }
     }
-    if (conv && format_prepare(d, what, d->stage_cap * adsb::format_element_bytes(conv)))
+    if (conv && format_prepare(d, what, d->stage_cap * adsb::convert_element_bytes(conv)))
         return -1;
     if (async)
         return push_copy(d, samples, n, hipMemcpyHostToDevice, true, packed, conv);
@@ -833,7 +853,7 @@ static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async,
 // adsb_push_device, optionally followed by adsb_finish in the same pass (`final`):
 // the last in-place scan then runs to the exact end of the stream and no tail has to
 // be staged.
-static int push_device_impl(adsb_decoder *d, const void *device_samples, size_t n, bool final)
+static int push_device_impl(adsb_decoder *d, const void *device_samples, size_t n, bool final, int kind = adsb::kKindReal)
 {
     if (!d)
         return -1;
@@ -841,10 +861,12 @@ static int push_device_impl(adsb_decoder *d, const void *device_samples, size_t 
         return d->fail("adsb_push_device after adsb_finish");
     if (final && d->shard_on)
         return d->fail("a shard stream ends with adsb_shard_end");
-    if (stream_too_long(d, n))
+    if (kind_refusal(d, "adsb_push_device", kind) || stream_too_long(d, n))
         return -1;
     if (n && !device_samples)
         return d->fail("adsb_push_device: NULL samples");
+    if (n)
+        d->kind = kind;
     HIP_TRY(d, hipSetDevice(d->device));
     const uint16_t *p = static_cast<const uint16_t *>(device_samples);
     const bool aligned = (d->n_samples % 8 == 0) && ((uintptr_t)p % 16 == 0);
@@ -893,7 +915,7 @@ static int push_device_impl(adsb_decoder *d, const void *device_samples, size_t 
         if (rc)
             return -1;
         const auto t2 = clk::now();
-        d->res.advance(2 * ((total + 3) / 4), d->g_scanned); // EOF rule: see process_stage()
+        d->res.advance(d->kind == adsb::kKindIq ? m_real : 2 * ((total + 3) / 4), d->g_scanned); // EOF rule: see process_stage()
         if (d->cfg.collect_stats && count_tries_pass(d, d->deferred_slot, d->deferred_slot ? d->deferred_slot->d_tries.p : nullptr,
                                                         d->deferred_slot ? d->deferred_slot->d_try_counts.p : nullptr, d->deferred_n, d->deferred_base, true))
             return -1; // tries beyond the final position are never visited
@@ -955,7 +977,7 @@ static int push_device_packed_impl(adsb_decoder *d, const void *device_packed, s
         return d->fail("%s after adsb_finish", what);
     if (final && d->shard_on)
         return d->fail("a shard stream ends with adsb_shard_end");
-    if (packed_device_refusal(d, device_packed, n, d->n_samples, what) || stream_too_long(d, n))
+    if (kind_refusal(d, what, adsb::kKindReal) || packed_device_refusal(d, device_packed, n, d->n_samples, what) || stream_too_long(d, n))
         return -1;
     if (n == 0)
         return final ? push_device_impl(d, nullptr, 0, true) : 0;
@@ -986,16 +1008,17 @@ static int device_as_refusal(adsb_decoder *d, const char *what, const void *p, s
 }
 
 // convert into the scratch of the packed device pushes (grown to 2 B x n on demand), then push that in place
-static int push_device_as_impl(adsb_decoder *d, int fmt, const void *p, size_t n, bool final, const char *what)
+// (kind: kKindIq from the _iq calls with fmt = kConvFloat32Iq, n counting float scalars)
+static int push_device_as_impl(adsb_decoder *d, int fmt, const void *p, size_t n, bool final, const char *what, int kind = adsb::kKindReal)
 {
     if (d->finished)
         return d->fail("%s after adsb_finish", what);
     if (final && d->shard_on)
         return d->fail("a shard stream ends with adsb_shard_end");
-    if (device_as_refusal(d, what, p, n, adsb::format_element_bytes(fmt)) || stream_too_long(d, n))
+    if (kind_refusal(d, what, kind) || device_as_refusal(d, what, p, n, adsb::convert_element_bytes(fmt)) || stream_too_long(d, n))
         return -1;
     if (n == 0)
-        return final ? push_device_impl(d, nullptr, 0, true) : 0;
+        return final ? push_device_impl(d, nullptr, 0, true, kind) : 0;
     HIP_TRY(d, hipSetDevice(d->device));
     if (format_prepare(d, what, 0))
         return -1;
@@ -1013,12 +1036,115 @@ static int push_device_as_impl(adsb_decoder *d, int fmt, const void *p, size_t n
         HIP_TRY(d, hipEventRecord(d->ev_unpack, d->stream));
         HIP_TRY(d, hipStreamWaitEvent(d->stream2, d->ev_unpack, 0));
     }
-    return push_device_impl(d, d->unpacked, n, final);
+    return push_device_impl(d, d->unpacked, n, final, kind);
+}
+
+// ---- complex samples (the _iq calls; include/adsbdec_amd.h) ----
+// What every _iq call checks before anything of the handle changes.  n counts complex samples; the stream counts 16-bit units
+// (two per complex sample), so everything behind these checks is the uint16 machinery with 2 n.
+int iq_refusal(adsb_decoder *d, const char *what, int fmt, const void *p, size_t n, bool device, uint64_t at_units)
+{
+    if (fmt != 0 && fmt != 2)
+        return d->fail("%s: format %d is not an IQ format (0 FLOAT32_IQ, 2 INT16_IQ; real samples go through the _as calls)", what, fmt);
+    if ((uint64_t)n >= (1ull << 31) || at_units + 2 * (uint64_t)n >= (1ull << 32))
+        return d->fail("%s: the stream would reach 2^31 complex samples (%llu + %zu): IQ streams end below", what,
+                       (unsigned long long)(at_units / 2), n);
+    if (n && !p)
+        return d->fail("%s: NULL samples", what);
+    if (device && (uintptr_t)p % 4 != 0)
+        return d->fail("%s: device pointer %p is not 4-byte aligned", what, p);
+    return 0;
+}
+
+static int push_host_iq(adsb_decoder *d, int fmt, const void *samples, size_t n, bool async, const char *what)
+{
+    if (!d)
+        return -1;
+    if (iq_refusal(d, what, fmt, samples, n, false, d->n_samples))
+        return -1;
+    return push_host(d, samples, 2 * n, async, false, what, fmt == 0 ? adsb::kConvFloat32Iq : 0, adsb::kKindIq);
+}
+
+// fmt 2 is scanned where it lies under the uint16 rule (16-byte aligned, at a multiple of 4 complex samples; else staged);
+// fmt 0 is converted into the scratch of the other converted device pushes first.
+static int push_device_iq(adsb_decoder *d, int fmt, const void *p, size_t n, bool final, const char *what, bool checked = false)
+{
+    if (!d)
+        return -1;
+    if (!checked && iq_refusal(d, what, fmt, p, n, true, d->n_samples))
+        return -1;
+    if (d->finished)
+        return d->fail("%s after adsb_finish", what);
+    if (kind_refusal(d, what, adsb::kKindIq))
+        return -1;
+    if (n == 0 && !final)
+        return 0;
+    if (fmt == 0)
+        return push_device_as_impl(d, adsb::kConvFloat32Iq, p, 2 * n, final, what, adsb::kKindIq);
+    return push_device_impl(d, p, 2 * n, final, adsb::kKindIq);
 }
 
 } // namespace adsb
 
 extern "C" {
+
+size_t adsb_iq_bytes(int fmt, size_t n)
+{
+    return fmt == 2 ? 4 * n : fmt == 0 ? 8 * n : 0;
+}
+
+int adsb_push_iq(adsb_decoder *d, int fmt, const void *samples, size_t n)
+{
+    return push_host_iq(d, fmt, samples, n, false, "adsb_push_iq");
+}
+
+int adsb_push_iq_async(adsb_decoder *d, int fmt, const void *samples, size_t n)
+{
+    return push_host_iq(d, fmt, samples, n, true, "adsb_push_iq_async");
+}
+
+int adsb_push_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n)
+{
+    return push_device_iq(d, fmt, device_samples, n, false, "adsb_push_device_iq");
+}
+
+int adsb_push_device_iq_final(adsb_decoder *d, int fmt, const void *device_samples, size_t n)
+{
+    return push_device_iq(d, fmt, device_samples, n, true, "adsb_push_device_iq_final");
+}
+
+long adsb_decode_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_frame **frames)
+{
+    const char *what = "adsb_decode_device_iq";
+    if (!d || !frames)
+        return -1;
+    // refused before the reset, at the position the reset will set: a refused call leaves the handle as it was
+    if (iq_refusal(d, what, fmt, device_samples, n, true, 0) || (d->long_stream && kind_refusal(d, what, adsb::kKindIq)))
+        return -1;
+    if (adsb_reset(d) != 0 || push_device_iq(d, fmt, device_samples, n, true, what, true) != 0)
+        return -1;
+    return (long)d->res.take(frames);
+}
+
+int adsb_convert_iq_float32(void *dst_i16, const void *src, size_t n_scalars, uint64_t *device_counters2, void *stream)
+{
+    char why[200] = "";
+    if (n_scalars && (!dst_i16 || !src))
+        snprintf(why, sizeof why, "adsb_convert_iq_float32: NULL buffer");
+    else if ((uintptr_t)dst_i16 % 2 != 0 || (uintptr_t)src % 4 != 0 || (uintptr_t)device_counters2 % 8 != 0)
+        snprintf(why, sizeof why, "adsb_convert_iq_float32: dst must be 2-byte, src 4-byte and the counters 8-byte aligned (%p, %p, %p)", dst_i16, src,
+                 (void *)device_counters2);
+    else if (n_scalars) {
+        const hipError_t e = adsb::launch_convert(adsb::kConvFloat32Iq, static_cast<uint16_t *>(dst_i16), src, n_scalars,
+                                                  reinterpret_cast<unsigned long long *>(device_counters2), static_cast<hipStream_t>(stream));
+        if (e != hipSuccess)
+            snprintf(why, sizeof why, "adsb_convert_iq_float32: launch failed: %s", hipGetErrorString(e));
+    }
+    if (!why[0])
+        return 0;
+    set_create_error(why);
+    return -1;
+}
 
 int adsb_push(adsb_decoder *d, const uint16_t *samples, size_t n)
 {

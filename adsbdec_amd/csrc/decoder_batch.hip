@@ -113,7 +113,10 @@ int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void
         a.tries = s.tries;
         a.try_cap = (uint32_t)std::min<size_t>(s.tries.cap, 0xFFFFFFFFu);
         s.busy = true; // (a failure from here on leaves a launch in flight: adsb_reset waits for it)
-        HIP_TRY(d, adsb::launch_scan_batch(a, seg_d, tile_d, L.tiles, stats, ls));
+        if (d->kind == adsb::kKindIq)
+            HIP_TRY(d, adsb::launch_scan_batch_iq(a, seg_d, tile_d, L.tiles, stats, ls));
+        else
+            HIP_TRY(d, adsb::launch_scan_batch(a, seg_d, tile_d, L.tiles, stats, ls));
         HIP_TRY(d, hipEventRecord(s.ev_ready[s.ev_cur], ls));
         WAIT_EVENT(d, s.ev_ready[s.ev_cur], "a batch scan launch");
         s.busy = false;
@@ -306,9 +309,114 @@ long decode_batch_as(adsb_decoder *d, const char *what, int fmt, size_t n_captur
     return k;
 }
 
+// ---- batches of IQ captures (adsb_decode_batch_*_iq) ----
+// n[] counts complex samples.  The batch machinery counts 16-bit units and ends a capture by the real streams' rule (a trailing
+// partial quad still yields two power samples); an IQ capture's power samples enter in twos and a trailing odd one is never seen
+// (air.c:94-99), which is exactly what the machinery does for the capture WITHOUT that sample: units[i] = 4 (n[i] / 2).
+int batch_refusal_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *p, const size_t *n, bool device)
+{
+    if (n_captures && (!p || !n))
+        return d->fail("%s: NULL capture arrays", what);
+    if (fmt != 0 && fmt != 2)
+        return iq_refusal(d, what, fmt, nullptr, 0, device, 0);
+    if (d->long_stream)
+        return kind_refusal(d, what, adsb::kKindIq);
+    char who[96];
+    for (size_t i = 0; i < n_captures; i++) {
+        snprintf(who, sizeof who, "%s: capture %zu", what, i);
+        if (iq_refusal(d, who, fmt, p[i], n[i], device, 0))
+            return -1;
+    }
+    return 0;
+}
+
+// The captures in device memory at src[] (fmt 2: int16 pairs, 4-byte aligned; fmt 0: float pairs) -> frames.  Whatever is not
+// 16-byte aligned int16 goes through scratch first: fmt 0 by the batch conversion launch, a misaligned fmt-2 capture by a copy.
+long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
+                     const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    std::vector<size_t> units(n_captures), scalars(n_captures);
+    for (size_t i = 0; i < n_captures; i++) {
+        units[i] = 4 * (n[i] / 2);
+        scalars[i] = 2 * n[i];
+    }
+    std::vector<const void *> at(src, src + n_captures);
+    d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
+    if (fmt == 0) {
+        if (batch_convert(d, what, adsb::kConvFloat32Iq, n_captures, src, scalars.data(), at))
+            return -1;
+    } else {
+        size_t bytes = 0;
+        for (size_t i = 0; i < n_captures; i++)
+            if ((uintptr_t)src[i] % 16 != 0)
+                bytes += (units[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+        if (bytes && batch_grow(d, what, "the captures that are not 16-byte aligned", d->batch_unpacked, bytes))
+            return -1;
+        size_t off = 0;
+        for (size_t i = 0; i < n_captures; i++) {
+            if ((uintptr_t)src[i] % 16 == 0)
+                continue;
+            at[i] = reinterpret_cast<const char *>(d->batch_unpacked.p) + off;
+            if (units[i])
+                HIP_TRY(d, hipMemcpyAsync(const_cast<void *>(at[i]), src[i], units[i] * sizeof(uint16_t), hipMemcpyDeviceToDevice, d->stream));
+            off += (units[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+        }
+    }
+    d->kind = adsb::kKindIq; // (behind the reset: the batch launches are scan_iq_batch_kernel's)
+    const long k = decode_batch(d, n_captures, at.data(), units.data(), frames, first, stats);
+    WAIT_STREAM(d, d->stream, "the scan stream");
+    return k;
+}
+
 } // namespace
 
 extern "C" {
+
+long adsb_decode_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
+                                 const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    const char *what = "adsb_decode_batch_device_iq";
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal_iq(d, what, fmt, n_captures, device_samples, n, true))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    return decode_batch_iq(d, what, fmt, n_captures, device_samples, n, frames, first, stats);
+}
+
+long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
+                               const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    const char *what = "adsb_decode_batch_host_iq";
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal_iq(d, what, fmt, n_captures, samples, n, false))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    // every capture as it is at a 128-byte boundary of the landing buffer the other host batches use
+    const size_t elem = fmt == 0 ? 8 : 4;
+    size_t bytes = 0;
+    for (size_t i = 0; i < n_captures; i++)
+        bytes += (n[i] * elem + 127) & ~(size_t)127;
+    if (batch_grow(d, what, "the captures as they are", d->batch_land, bytes))
+        return -1;
+    std::vector<const void *> land(n_captures);
+    size_t off = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        land[i] = d->batch_land + off;
+        if (n[i])
+            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, samples[i], n[i] * elem, hipMemcpyHostToDevice,
+                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
+        off += (n[i] * elem + 127) & ~(size_t)127;
+    }
+    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again)
+        WAIT_STREAM(d, cs, "a copy stream");
+    return decode_batch_iq(d, what, fmt, n_captures, land.data(), n, frames, first, stats);
+}
 
 long adsb_decode_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats)

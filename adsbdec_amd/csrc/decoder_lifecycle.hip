@@ -305,6 +305,7 @@ int adsb_reset(adsb_decoder *d)
     d->deferred_base = 0;
     d->sink = ScanSink{};
     d->n_samples = 0;
+    d->kind = adsb::kKindNone;
     d->g_scanned = 0;
     d->seam_offsets = 0;
     d->finished = false;

@@ -9,6 +9,11 @@
 //                 [0, 4095].  Clamped iff r + 2048 lies outside [0, 4095] or x is +-Inf or NaN (NaN -> 2048).  Otherwise inexact iff
 //                 (code - 2048) / 2048 is not the value x: -0.0 is exact, every non-zero denormal is inexact (-> 2048) -- decided
 //                 on the bit pattern, so the answer is the same whatever the denormal mode of the unit that runs this.
+//   FLOAT32_IQ    (the _iq calls, fmt 0) one SCALAR of a complex sample, nominal range [-1, 1): r = rint(32768 x), ties to even,
+//                 clamped to [-32768, 32767] -- the int16 scalar of INT16_IQ (fmt 2), which the scan then reads.  Clamped iff r lies
+//                 outside or x is +-Inf or NaN (NaN -> 0).  Otherwise inexact iff r is not 32768 x: -0.0 is exact, every non-zero
+//                 denormal is inexact (-> 0), decided on the bit pattern as for FLOAT32_REAL.  A quantisation to 1/16 ADC LSB:
+//                 libairspy's float path need not sit on that grid, so real fmt-0 files are expected to report inexact samples.
 // A sample is counted at most once; clamped wins.
 #pragma once
 
@@ -23,10 +28,17 @@ namespace adsb {
 // fmt values of the _as calls: the numbers airspy_rx -t takes
 constexpr int kFmtFloat32Real = 1, kFmtInt16Real = 3, kFmtUint16Real = 4, kFmtRaw = 5;
 
+// The library's own number for the scalars of FLOAT32_IQ where a conversion is named (launch_convert*, push_copy's conv): not an
+// airspy_rx -t number -- that one is 0, which the _as calls refuse -- and no _as call accepts it (format_element_bytes: 0).
+constexpr int kConvFloat32Iq = 8;
+
 constexpr uint32_t kSampleExact = 0, kSampleInexact = 1, kSampleClamped = 2;
 
 // bytes per sample of a converted format (0: not one)
 ADSB_HD constexpr size_t format_element_bytes(int fmt) { return fmt == kFmtFloat32Real ? 4 : fmt == kFmtInt16Real ? 2 : 0; }
+
+// bytes per element of anything a conversion kernel reads: the _as formats and the scalars of FLOAT32_IQ
+ADSB_HD constexpr size_t convert_element_bytes(int conv) { return conv == kConvFloat32Iq ? 4 : format_element_bytes(conv); }
 
 // x: the 16 bits of the sample.  Returns the code; *what = kSampleExact / kSampleInexact.
 ADSB_HD inline uint32_t int16_real_code(uint32_t x, uint32_t *what)
@@ -54,9 +66,25 @@ ADSB_HD inline uint32_t float32_real_code(uint32_t bits, uint32_t *what)
     return (uint32_t)((int32_t)rc + 2048);
 }
 
+// bits: the 32 bits of one scalar of a FLOAT32_IQ sample.  Returns the int16 scalar as its 16 bits; *what as float32_real_code.
+ADSB_HD inline uint32_t float32_iq_code(uint32_t bits, uint32_t *what)
+{
+    const uint32_t e = (bits >> 23) & 0xffu, m = bits & 0x7fffffu;
+    const bool nan = e == 0xffu && m != 0;
+    float x;
+    __builtin_memcpy(&x, &bits, sizeof x);
+    const float y = x * 32768.0f; // exact (a power of two) for a normal x, or +-Inf; a denormal x is judged by its bits below
+    const float r = rintf(y);     // ties to even
+    const bool lo = r < -32768.0f, hi = r > 32767.0f; // (both false for NaN; +-Inf ends here)
+    const float rc = nan ? 0.0f : lo ? -32768.0f : hi ? 32767.0f : r;
+    const bool off = e == 0 ? m != 0 : !(r == y); // +-0.0 is the grid point 0; a denormal rounds to 0 and is not 0
+    *what = (nan || lo || hi) ? kSampleClamped : off ? kSampleInexact : kSampleExact;
+    return (uint32_t)(int32_t)rc & 0xffffu;
+}
+
 template <int FMT> ADSB_HD inline uint32_t sample_code(uint32_t bits, uint32_t *what)
 {
-    return FMT == kFmtInt16Real ? int16_real_code(bits, what) : float32_real_code(bits, what);
+    return FMT == kFmtInt16Real ? int16_real_code(bits, what) : FMT == kConvFloat32Iq ? float32_iq_code(bits, what) : float32_real_code(bits, what);
 }
 
 // convert_samples.hip, the captures of a batch in one launch (the scheme of packed12.h's Unpack12Seg).  A capture of n samples is
@@ -86,7 +114,7 @@ ADSB_HD inline uint32_t convert_row(const ConvertSeg *tab, uint32_t lo, uint32_t
 }
 
 #ifdef __HIPCC__
-// n samples of format fmt (kFmtFloat32Real / kFmtInt16Real) at src (aligned to the element) -> n uint16 codes at dst (2-byte
+// n samples of format fmt (kFmtFloat32Real / kFmtInt16Real; kConvFloat32Iq: n scalars -> n int16) at src (aligned to the element) -> n uint16 codes at dst (2-byte
 // aligned), enqueued on `stream`; counters: NULL, or two uint64 in device memory that the samples' inexact and clamped counts are
 // ADDED to (only where they are not zero).
 hipError_t launch_convert(int fmt, uint16_t *dst, const void *src, size_t n, unsigned long long *counters, hipStream_t stream);

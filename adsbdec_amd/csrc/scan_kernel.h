@@ -194,6 +194,11 @@ struct BatchSeg {
 // segs and tile_seg (n_tiles words) are device memory
 hipError_t launch_scan_batch(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
                              hipStream_t stream);
+// The same two launches for a stream of complex int16 samples (scan_iq_kernel.hip): x holds (I, Q) of ONE sample per word, and
+// pbuf0 / p_lo / p_hi / g count complex samples -- power sample m is sample m.  Geometry, LDS, records and tries as above.
+hipError_t launch_scan_iq(const ScanArgs &args, bool stats, hipStream_t stream);
+hipError_t launch_scan_batch_iq(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
+                                hipStream_t stream);
 // the report kernel of launch_scan on its own (scan_kernel.hip)
 hipError_t launch_report(const ScanArgs &args, hipStream_t stream);
 // Device-to-device copy of n uint16 samples by the library's own kernel (the staging tail: see scan_kernel.hip).

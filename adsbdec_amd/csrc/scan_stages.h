@@ -229,6 +229,41 @@ __device__ __noinline__ uint32_t pw_at(const uint32_t *__restrict__ x, int64_t p
     return pw_compute(raw, g);
 }
 
+// ---- the IQ front end's slow path (scan_iq_kernel.hip) ----
+// The power sample of ONE complex sample d = (I, Q), two little-endian int16 in a word: i = I / 16, q = Q / 16 (exact: ADC-code
+// units, include/adsbdec_amd.h), a = fl(fl(i i) + fl(q q)) -- two rounded products, one rounded sum, nothing fused.
+__device__ __forceinline__ float iq_power(uint32_t d)
+{
+    const float i = (float)(int)(int16_t)(uint16_t)(d & 0xFFFFu) * 0.0625f, q = (float)((int)d >> 16) * 0.0625f;
+    return i * i + q * q;
+}
+
+// pw of the offset g of an IQ stream (demod.c:102-105,127,133): power sample m IS complex sample m, so the four samples at
+// g + {0, 10, 35, 45} are four loads; a sample outside the buffer reads as (0, 0).
+__device__ __noinline__ uint32_t pw_at_iq(const uint32_t *__restrict__ x, int64_t pbuf0, int64_t p_lo, int64_t p_hi, int64_t g)
+{
+    const int off[4] = {0, 10, 35, 45};
+    float a[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int64_t pi = g + off[k];
+        a[k] = iq_power((pi >= p_lo && pi < p_hi) ? x[pi - pbuf0] : 0u);
+    }
+    const int p1 = __float2int_rz(a[0] + a[1]);
+    const int p2 = __float2int_rz(a[2] + a[3]);
+    return (uint32_t)((p1 + p2) / 4);
+}
+
+// pw of offset g by the front end of the kernel the stages are built into
+template <bool kIq>
+__device__ __forceinline__ uint32_t pw_of(const uint32_t *__restrict__ x, int64_t pbuf0, int64_t p_lo, int64_t p_hi, int64_t g)
+{
+    if constexpr (kIq)
+        return pw_at_iq(x, pbuf0, p_lo, p_hi, g);
+    else
+        return pw_at(x, pbuf0, p_lo, p_hi, g);
+}
+
 // One 16-byte granule of the hand-off stream, written THROUGH to host memory (sc0 sc1).
 // A plain store may sit in the L2 until its line is evicted or the kernel ends (measured:
 // single tiles reaching the host ~30 us after their neighbours, which stalls the host's
@@ -443,12 +478,152 @@ __device__ __forceinline__ void stage_a(const uint32_t *__restrict__ xin, const 
     }
 }
 
+// ------------------------------ Stage A, IQ front end ------------------------------
+// The same tile, the same passes, lanes and lane stride for a stream of complex int16 samples (scan_iq_kernel.hip): power
+// sample m is |sample m|^2, so a run of 28 is the lane's own 28 pairs -- 112 bytes, no pre-halo -- and 56 products and 28
+// sums stand where the FIR's 616 instructions do.  The loads are stage_a's typed ones with the SIGNED scaled number format
+// (the load path converts int16 to f32, exactly), fourteen of 8 bytes; their destination select is x z y w, so that a load
+// leaves (I0, I1) and (Q0, Q1) in two register pairs and the squares and the sum of two samples are three packed operations.
+// The 2^-8 that brings I^2 + Q^2 to ADC-code units is one more packed multiplication per two samples: a power of two
+// commutes with every rounding here (no overflow, no underflow: |I| <= 2^15).
+__device__ __forceinline__ void stage_a_iq(const uint32_t *__restrict__ xin, const int64_t pbuf0, const int64_t p_lo,
+                                           const int64_t p_hi, const int64_t t0, const int K, const int wave, const int lane,
+                                           uint32_t *pl_d, uint32_t *pl_e1, uint32_t *pl_e2)
+{
+    auto first_run = [&](int ps) { return kWaveRuns * (kWaves * ps + wave); };
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll 1
+    for (int pass = 0; pass < K; pass++) {
+        const int v0 = first_run(pass); // first run of this wave in this pass
+        const int v = v0 + lane;
+        const int64_t wlo = t0 + (int64_t)kRun * v0; // lane 0's first pair: a multiple of 28, so of 4 (16 bytes)
+        // wave-uniform: every pair this wave loads lies inside the buffer
+        const bool interior = (wlo >= p_lo) && (wlo + kRun * 64 <= p_hi);
+        f32x4 tl[14]; // tl[k] = (I, I', Q, Q') of pairs 2k, 2k+1 of the run
+        if (interior) {
+            const uint64_t wbase = (uint64_t)(xin + (wlo - pbuf0));
+            i32x4 rs;
+            rs.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)wbase);
+            rs.y = __builtin_amdgcn_readfirstlane((int)((uint32_t)(wbase >> 32) & 0xFFFFu)); // stride 0: raw buffer
+            rs.z = 64 * kRun * 4;                                                             // bytes
+            rs.w = (int)(4u | 6u << 3 | 5u << 6 | 7u << 9 /* dst_sel xzyw */ | 3u << 12 /* SSCALED */ | 12u << 15 /* 16_16_16_16 */);
+            const int voff = lane * (kRun * 4);
+            asm volatile("buffer_load_format_xyzw %0, %14, %15, 0 offen\n\t"
+                         "buffer_load_format_xyzw %1, %14, %15, 0 offen offset:8\n\t"
+                         "buffer_load_format_xyzw %2, %14, %15, 0 offen offset:16\n\t"
+                         "buffer_load_format_xyzw %3, %14, %15, 0 offen offset:24\n\t"
+                         "buffer_load_format_xyzw %4, %14, %15, 0 offen offset:32\n\t"
+                         "buffer_load_format_xyzw %5, %14, %15, 0 offen offset:40\n\t"
+                         "buffer_load_format_xyzw %6, %14, %15, 0 offen offset:48\n\t"
+                         "buffer_load_format_xyzw %7, %14, %15, 0 offen offset:56\n\t"
+                         "buffer_load_format_xyzw %8, %14, %15, 0 offen offset:64\n\t"
+                         "buffer_load_format_xyzw %9, %14, %15, 0 offen offset:72\n\t"
+                         "buffer_load_format_xyzw %10, %14, %15, 0 offen offset:80\n\t"
+                         "buffer_load_format_xyzw %11, %14, %15, 0 offen offset:88\n\t"
+                         "buffer_load_format_xyzw %12, %14, %15, 0 offen offset:96\n\t"
+                         "buffer_load_format_xyzw %13, %14, %15, 0 offen offset:104"
+                         "\n\ts_waitcnt vmcnt(0)"
+                         : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]), "=&v"(tl[4]), "=&v"(tl[5]), "=&v"(tl[6]),
+                           "=&v"(tl[7]), "=&v"(tl[8]), "=&v"(tl[9]), "=&v"(tl[10]), "=&v"(tl[11]), "=&v"(tl[12]),
+                           "=&v"(tl[13])
+                         : "v"(voff), "s"(rs)
+                         : "memory");
+        } else {
+            // the ragged end of a buffer (and whatever lies below its first pair): plain loads, converted here; a missing
+            // pair is (0, 0)
+            int lane_here = lane;
+            asm volatile("" : "+v"(lane_here)); // (opaque, as in stage_a: nothing of this rare path is precomputed per tile and spilled)
+            const int64_t pr0 = wlo + (int64_t)(kRun * lane_here);
+#pragma unroll
+            for (int k = 0; k < 14; k++) {
+                const int64_t pa = pr0 + 2 * k, pb = pa + 1;
+                const uint32_t d0 = (pa >= p_lo && pa < p_hi) ? xin[pa - pbuf0] : 0u;
+                const uint32_t d1 = (pb >= p_lo && pb < p_hi) ? xin[pb - pbuf0] : 0u;
+                tl[k] = f32x4{(float)(int)(int16_t)(uint16_t)(d0 & 0xFFFFu), (float)(int)(int16_t)(uint16_t)(d1 & 0xFFFFu),
+                              (float)((int)d0 >> 16), (float)((int)d1 >> 16)};
+            }
+        }
+        // a[0..27]: this run; a[28..43]: the first 16 samples of the next run (next lane)
+        float a[44];
+#pragma unroll
+        for (int k = 0; k < 14; k++) {
+            const f32x2 ii = {tl[k].x, tl[k].y}, qq = {tl[k].z, tl[k].w};
+            const f32x2 scale = {0.00390625f, 0.00390625f}; // 2^-8: (I / 16)^2 + (Q / 16)^2
+            f32x2 s = (ii * ii + qq * qq) * scale;
+            asm volatile("" : "+v"(s)); // (the 28 samples first, in this order, then the planes: 96 registers hold either, not a mix)
+            a[2 * k] = s.x;
+            a[2 * k + 1] = s.y;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            a[28 + k] = from_next_lane(a[k]);
+
+        // demod.c:102-105: every preamble sum is c[k] = (int)(a[k] + a[k+10]).  The
+        // truncated value is kept as a float (v_trunc_f32 == the C conversion for the
+        // magnitudes in the input domain); the integer comparisons `c > 2 c'` are
+        // decided by the SIGN of 2 c' - c, which one fused multiply-add gives exactly
+        // (a single rounding cannot change the sign of a non-zero difference and an
+        // exact zero stays zero).
+        //
+        // Packing: every operation here combines index k with k + 5 or k + 10, so the
+        // usual (k, k+1) register pairs cannot feed v_pk_* on both sides (5 is odd).
+        // Pairs (k, k+2) for k mod 5 in {0, 1} can -- the partner set is closed under
+        // +5 -- and leave k mod 5 == 4 as scalar operations: 4 of 5 values are packed.
+        float c[34], dv[28], e1v[28], e2v[28];
+#pragma unroll
+        for (int k = 0; k < 33; k++) {
+            if (k % 5 < 2) {
+                const f32x2 lo = {a[k], a[k + 2]}, hi = {a[k + 10], a[k + 12]};
+                const f32x2 sum = lo + hi;
+                c[k] = __builtin_truncf(sum.x);
+                c[k + 2] = __builtin_truncf(sum.y);
+            } else if (k % 5 == 4) {
+                c[k] = __builtin_truncf(a[k] + a[k + 10]);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < 28; m++) {
+            if (m % 5 < 2 && m + 2 < 28) {
+                const f32x2 am = {a[m], a[m + 2]}, an = {a[m + 5], a[m + 7]};
+                const f32x2 cm = {c[m], c[m + 2]}, cn = {c[m + 5], c[m + 7]};
+                const f32x2 two = {2.0f, 2.0f};
+                const f32x2 dd = an - am;
+                const f32x2 x1 = __builtin_elementwise_fma(cn, two, -cm);
+                const f32x2 x2 = __builtin_elementwise_fma(cm, two, -cn);
+                dv[m] = dd.x, dv[m + 2] = dd.y;
+                e1v[m] = x1.x, e1v[m + 2] = x1.y;
+                e2v[m] = x2.x, e2v[m + 2] = x2.y;
+            } else if (m % 5 == 4 || (m % 5 < 2 && m + 2 >= 28)) {
+                dv[m] = a[m + 5] - a[m];
+                e1v[m] = __builtin_fmaf(c[m + 5], 2.0f, -c[m]);
+                e2v[m] = __builtin_fmaf(c[m], 2.0f, -c[m + 5]);
+            }
+        }
+
+        uint32_t d = 0, e1 = 0, e2 = 0;
+#pragma unroll
+        for (int m = 27; m >= 0; m--) { // bit m of each word <-> sample m of the run
+            d = push_sign(d, __float_as_uint(dv[m]));    // a[m+5] - a[m] < 0:  a[m] > a[m+5]   (demod.c:34)
+            e1 = push_sign(e1, __float_as_uint(e1v[m])); // 2 c[m+5] - c[m] < 0: c[m] > 2 c[m+5] (SN = 2, demod.c:83)
+            e2 = push_sign(e2, __float_as_uint(e2v[m])); // 2 c[m] - c[m+5] < 0: c[m+5] > 2 c[m]
+        }
+        asm volatile("" : "+v"(d), "+v"(e1), "+v"(e2)); // (the words are made by every lane: the arithmetic is not to sink under the branch)
+        if (lane < kWaveRuns) { // lane 63 only feeds lane 62
+            pl_d[v] = d;
+            pl_e1[v] = e1;
+            pl_e2[v] = e2;
+        }
+    }
+}
+
 // ------------------------------ Stage B ------------------------------
 // Everything behind a tile's planes: gate, survivor queue, slicer + CRC, never-visited filter, ranking, finishing and
 // the hand-off, by the tile's four waves between workgroup barriers.
 // LDS of Stage B: queue[queue_cap], ctl[16] (qcount, qover, cl_n, cl_over, tile_n, tile_over, tile_base, try_base,
 // tile_res, tile_fit, tile_chk[4], tile_lines, tile_sum), cl_rec[clist_cap * kCandWords].
-template <bool kStats>
+// kIq: the kernel's front end is stage_a_iq -- what differs here is pw alone (pw_of).
+template <bool kStats, bool kIq = false>
 __device__ __forceinline__ void stage_b(const ScanArgs &args, const uint32_t tile, const int K, const int64_t t0, const int tid,
                                         const uint32_t *pl_d, const uint32_t *pl_e1, const uint32_t *pl_e2, uint32_t *queue,
                                         uint32_t *qcount, uint32_t *cl_rec, const int clist_cap, uint64_t &stamp_last)
@@ -672,7 +847,7 @@ __device__ __forceinline__ void stage_b(const ScanArgs &args, const uint32_t til
             uint32_t wds[4];
             columns_to_bytes(cw, code == 0, wds);
             wds[3] |= fixed << 24;
-            const uint32_t pw = pw_at(xin, pbuf0, p_lo, p_hi, t0 + (int64_t)kRun * sv + sj);
+            const uint32_t pw = pw_of<kIq>(xin, pbuf0, p_lo, p_hi, t0 + (int64_t)kRun * sv + sj);
             emit_loose(g_rel, pw, wds);
         }
 
@@ -978,7 +1153,7 @@ __device__ __forceinline__ void stage_b(const ScanArgs &args, const uint32_t til
             uint32_t wds[4];
             columns_to_bytes(cw, (e[1] & 0xFFu) == 0, wds);
             wds[3] |= ((e[1] >> 8) & 1u) << 24; // repaired-by-extension flag
-            const uint32_t pw = pw_at(xin, pbuf0, p_lo, p_hi, (int64_t)args.g_begin + e[0]);
+            const uint32_t pw = pw_of<kIq>(xin, pbuf0, p_lo, p_hi, (int64_t)args.g_begin + e[0]);
             fin[0] = e[0], fin[1] = pw, fin[2] = wds[0], fin[3] = wds[1], fin[4] = wds[2], fin[5] = wds[3];
             if (links)
                 pwbuf[tid] = pw;

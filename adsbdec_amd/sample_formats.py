@@ -8,6 +8,16 @@ test-side definition, independent of the library's conversion kernels, and a con
 
     python -m adsbdec_amd.sample_formats -t 3 in.u16 out.s16          # uint16 capture -> int16 real (-t 1: float32 real)
     python -m adsbdec_amd.sample_formats -t 3 --back in.s16 out.u16   # and back; stderr counts what was off the grid
+
+and the two complex formats (airspy_rx -t 2 and -t 0; the library's _iq calls), which have no uint16 twin -- the converter goes
+between the two of them:
+
+    INT16_IQ      int16 (I, Q);  i = I / 16, q = Q / 16;  power sample a = fl(fl(i i) + fl(q q)) in binary32
+    FLOAT32_IQ    float32 (I, Q), nominal [-1, 1);  each scalar r = rint(32768 x) (ties to even) clamped to [-32768, 32767];
+                  clamped iff r is outside or x is +-Inf or NaN (NaN -> 0), else inexact iff r is not 32768 x; then as INT16_IQ
+
+    python -m adsbdec_amd.sample_formats -t 0 in.s16iq out.f32iq      # int16 IQ capture -> float32 IQ (exact)
+    python -m adsbdec_amd.sample_formats -t 0 --back in.f32iq out.s16iq
 """
 from __future__ import annotations
 
@@ -17,8 +27,10 @@ import sys
 import numpy as np
 
 FLOAT32_REAL, INT16_REAL = 1, 3
+FLOAT32_IQ, INT16_IQ = 0, 2
 DTYPES = {FLOAT32_REAL: np.dtype("<f4"), INT16_REAL: np.dtype("<i2")}
-NAMES = {FLOAT32_REAL: "FLOAT32_REAL", INT16_REAL: "INT16_REAL"}
+IQ_DTYPES = {FLOAT32_IQ: np.dtype("<f4"), INT16_IQ: np.dtype("<i2")}
+NAMES = {FLOAT32_REAL: "FLOAT32_REAL", INT16_REAL: "INT16_REAL", FLOAT32_IQ: "FLOAT32_IQ", INT16_IQ: "INT16_IQ"}
 
 
 def _codes(x) -> np.ndarray:
@@ -77,13 +89,71 @@ def from_format(fmt: int, x):
     return from_int16_real(x) if fmt == INT16_REAL else from_float32_real(x)
 
 
+# ---- complex captures ----
+def to_float32_iq(x) -> np.ndarray:
+    """int16 IQ scalars -> float32 IQ scalars (x / 32768: exact), same shape."""
+    return (np.asarray(x, dtype=np.int16).astype(np.float32) / np.float32(32768.0)).astype("<f4")
+
+
+def flags_float32_iq(x) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """float32 IQ scalars -> (int16 scalars, inexact mask, clamped mask), in binary64, where 32768 x is exact or overflows to Inf."""
+    x = np.asarray(x, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = x.astype(np.float64)
+        nan = np.isnan(v)
+        y = np.where(nan, 0.0, v) * 32768.0
+        r = np.rint(y)                                       # np.rint: ties to even
+        clamped = nan | (r < -32768.0) | (r > 32767.0)       # (+-Inf: r is +-Inf)
+        c = np.clip(r, -32768.0, 32767.0)
+        inexact = ~clamped & (c != y)                        # (-0.0 == 0.0; a denormal is not 0)
+    return c.astype(np.int16), inexact, clamped
+
+
+def to_int16_iq(x):
+    """float32 IQ scalars -> (int16 scalars, inexact, clamped): a scalar is counted once, clamped wins."""
+    r, inexact, clamped = flags_float32_iq(x)
+    return r, int(inexact.sum()), int(clamped.sum())
+
+
+def iq_power(x, fmt: int = INT16_IQ) -> np.ndarray:
+    """The power samples of a complex capture (scalars I, Q, I, Q, ...: any shape with an even number of them) as the library
+    defines them: strict binary32, two rounded products and a rounded sum, one power sample per complex sample."""
+    if fmt == FLOAT32_IQ:
+        x = flags_float32_iq(x)[0]
+    elif fmt != INT16_IQ:
+        raise ValueError(f"format {fmt} is not an IQ format")
+    s = np.asarray(x, dtype=np.int16).reshape(-1, 2).astype(np.float32) * np.float32(0.0625)
+    i, q = s[:, 0], s[:, 1]
+    return (i * i + q * q).astype(np.float32)               # (numpy rounds every float32 operation on its own)
+
+
+def _main_iq(a) -> int:
+    dt = IQ_DTYPES[FLOAT32_IQ] if a.back else IQ_DTYPES[INT16_IQ]
+    b = np.fromfile(a.src, dtype=np.uint8)
+    cut = b.size % (2 * dt.itemsize)
+    if cut:
+        sys.stderr.write(f"{a.src}: {cut} trailing bytes (a partial sample) ignored\n")
+    x = b[: b.size - cut].view(dt)
+    if a.back:
+        r, inexact, clamped = to_int16_iq(x)
+        if inexact + clamped:
+            sys.stderr.write(f"{a.src}: {inexact + clamped} of {x.size} scalars are not on the int16 grid ({clamped} clamped)\n")
+        r.astype("<i2").tofile(a.dst)
+    else:
+        to_float32_iq(x).tofile(a.dst)
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m adsbdec_amd.sample_formats", description=__doc__.split("\n\n")[0])
-    ap.add_argument("-t", type=int, choices=sorted(DTYPES), required=True, help="1 = FLOAT32_REAL, 3 = INT16_REAL (as airspy_rx -t)")
+    ap.add_argument("-t", type=int, choices=sorted(DTYPES) + [FLOAT32_IQ], required=True,
+                    help="1 = FLOAT32_REAL, 3 = INT16_REAL (as airspy_rx -t); 0 = between INT16_IQ and FLOAT32_IQ")
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--back", action="store_true", help="the format -> uint16 codes instead of uint16 codes -> the format")
     a = ap.parse_args(argv)
+    if a.t == FLOAT32_IQ:
+        return _main_iq(a)
     dt = DTYPES[a.t] if a.back else np.dtype("<u2")
     b = np.fromfile(a.src, dtype=np.uint8)
     cut = b.size % dt.itemsize

@@ -84,19 +84,16 @@ void adsb_config_init(adsb_config *cfg, size_t struct_size);
 /* The stream state that air.c:33-34,49-50 / demod.c:86 / valid.c:30-31 keep in statics.  NULL on failure
  * (adsb_last_error(NULL) has the reason).  adsb_reset: the same handle, a fresh stream (ring, ts, stats). */
 adsb_decoder *adsb_create(const adsb_config *cfg);
-void adsb_destroy(adsb_decoder *d);
-int adsb_reset(adsb_decoder *d);
+void adsb_destroy(adsb_decoder *d); int adsb_reset(adsb_decoder *d);
 /* Sample ingress; replaces `decodeiq(const unsigned short *r, const int len)` (air.c:54), called from fileInput (air.c:239) / rx_callback
  * (air.c:175).  `samples` is borrowed for the call.  Any n: the stream is the concatenation of all pushes (the reference needs n % 4 == 0). */
 int adsb_push(adsb_decoder *d, const uint16_t *samples, size_t n);
 /* The same from a double-buffered read loop: returns once copy and scan of this chunk are ENQUEUED, then collects the PREVIOUS chunk's frames.
  * `samples` stays borrowed until the next push / finish / sync returns; frames become drainable one call later, in order.  adsb_sync waits for all. */
-int adsb_push_async(adsb_decoder *d, const uint16_t *samples, size_t n);
-int adsb_sync(adsb_decoder *d);
+int adsb_push_async(adsb_decoder *d, const uint16_t *samples, size_t n); int adsb_sync(adsb_decoder *d);
 /* Samples already resident in HBM (no reference counterpart).  A 16-byte aligned pointer at a stream position that is a
  * multiple of 8 samples is scanned in place.  _final = push of the LAST piece + adsb_finish in one pass. */
-int adsb_push_device(adsb_decoder *d, const void *device_samples, size_t n);
-int adsb_push_device_final(adsb_decoder *d, const void *device_samples, size_t n);
+int adsb_push_device(adsb_decoder *d, const void *device_samples, size_t n); int adsb_push_device_final(adsb_decoder *d, const void *device_samples, size_t n);
 /* `adsbdec -f` for ONE capture in HBM: adsb_reset + adsb_push_device_final + adsb_take.  The number of frames (*frames as adsb_take) or -1. */
 long adsb_decode_device(adsb_decoder *d, const void *device_samples, size_t n, const adsb_frame **frames);
 /* n_captures INDEPENDENT captures in as few launches as they fit, each decoded exactly as adsb_decode_device(d, p[i], n[i]) would
@@ -115,10 +112,8 @@ long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *
  * there); device pointers 4-byte aligned.  Otherwise -1, handle unchanged.  Frames, ts, Try/Ok, counters and contracts: the uint16 calls'.  Extra device
  * memory the handle keeps (grown on demand): host pushes, two landing buffers of 1.5 B x stage_samples; device pushes, a scratch of 2 B x n. */
 #define ADSB_PACKED12_BYTES(n) ((n) / 8 * 12)
-int adsb_push_packed(adsb_decoder *d, const void *packed, size_t n);
-int adsb_push_packed_async(adsb_decoder *d, const void *packed, size_t n);
-int adsb_push_device_packed(adsb_decoder *d, const void *device_packed, size_t n);
-int adsb_push_device_packed_final(adsb_decoder *d, const void *device_packed, size_t n);
+int adsb_push_packed(adsb_decoder *d, const void *packed, size_t n); int adsb_push_packed_async(adsb_decoder *d, const void *packed, size_t n);
+int adsb_push_device_packed(adsb_decoder *d, const void *device_packed, size_t n); int adsb_push_device_packed_final(adsb_decoder *d, const void *device_packed, size_t n);
 long adsb_decode_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_frame **frames);
 /* adsb_decode_batch_device / _host for packed captures (n[i] counts samples): results, first / stats and the handle's state as theirs, capture i
  * decoded as its unpacked twin alone.  Refused by capture index, handle unchanged: n[i] % 8 != 0, a _device pointer not 4-byte aligned, NULL with
@@ -134,12 +129,9 @@ long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const voi
  * Any n at any stream position, mixing with the other pushes; device pointers aligned to the element, else -1, handle unchanged.  Frames, ts, Try/Ok
  * and contracts: the uint16 calls'.  Extra device memory, kept as for packed input: host pushes, two landing buffers of (2 or 4) B x stage_samples;
  * device pushes and batches, the packed calls' scratch (2 B x n; ONE conversion launch per batch); _batch_host: + (2 or 4) B x sum n. */
-enum { ADSB_FMT_FLOAT32_REAL = 1, ADSB_FMT_INT16_REAL = 3, ADSB_FMT_UINT16_REAL = 4, ADSB_FMT_RAW = 5 };
-size_t adsb_format_bytes(int fmt, size_t n); /* bytes of n samples (0: a format that is refused) */
-int adsb_push_as(adsb_decoder *d, int fmt, const void *samples, size_t n);
-int adsb_push_async_as(adsb_decoder *d, int fmt, const void *samples, size_t n);
-int adsb_push_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n);
-int adsb_push_device_final_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n);
+enum { ADSB_FMT_FLOAT32_REAL = 1, ADSB_FMT_INT16_REAL = 3, ADSB_FMT_UINT16_REAL = 4, ADSB_FMT_RAW = 5 }; size_t adsb_format_bytes(int fmt, size_t n); /* bytes of n samples (0: a format that is refused) */
+int adsb_push_as(adsb_decoder *d, int fmt, const void *samples, size_t n); int adsb_push_async_as(adsb_decoder *d, int fmt, const void *samples, size_t n);
+int adsb_push_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n); int adsb_push_device_final_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n);
 long adsb_decode_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_frame **frames);
 long adsb_decode_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
@@ -148,23 +140,35 @@ long adsb_decode_batch_host_as(adsb_decoder *d, int fmt, size_t n_captures, cons
 /* Since adsb_create / adsb_reset: samples converted, and those off their format's grid (a wrong fmt shows here).  Waits for the conversions enqueued. */
 typedef struct adsb_format_report { uint64_t converted, inexact, clamped; } adsb_format_report;
 int adsb_get_format_report(const adsb_decoder *d, adsb_format_report *out);
+/* COMPLEX captures at 10 MS/s: airspy_rx -t 2 INT16_IQ (its default) and -t 0 FLOAT32_IQ.  libairspy has already mixed, filtered and decimated them: no raw
+ * twin (the _as calls refuse 0 and 2), but they ARE where demod.c works: power sample a[m] = |sample m|^2, everything behind it the reference's code on that array.
+ * INT16_IQ: little-endian int16 (I, Q); i = I / 16, q = Q / 16, a = fl(fl(i i) + fl(q q)), binary32, nothing fused.  The / 16 puts I, Q in ADC-code units like
+ * (float)r - 2048: demod.c:102-105's int truncation acts at its granularity; pw and the Beast level are on a COMPARABLE scale, not a calibrated one (nobody here
+ * has measured libairspy's filter gain).  FLOAT32_IQ: binary32 (I, Q), nominal [-1, 1); each scalar r = rint(32768 x), ties to even, clamped to [-32768, 32767]
+ * (NaN -> 0, +-Inf clamped), then as INT16_IQ: 1/16 ADC LSB.  libairspy's float path need not sit on that grid: expect adsb_get_format_report's inexact (per
+ * scalar) to be non-zero for real -t 0 files.  Power samples enter in twos (air.c:94-99): a trailing odd sample at adsb_finish is never seen.  n counts COMPLEX
+ * samples.  A stream's kind, real or IQ, is fixed by its first push with samples after adsb_create / adsb_reset; the other kind then returns -1.  Also refused,
+ * handle unchanged: fmt not 0 / 2, NULL with n > 0, a device pointer not 4-byte aligned, a stream reaching 2^31 complex samples, an adsb_set_long_stream handle.
+ * fmt 2 device pointers: in place when 16-byte aligned at a multiple of 4 complex samples, else staged; fmt 0: converted on the GPU (FLOAT32_REAL's buffers). */
+enum { ADSB_FMT_FLOAT32_IQ = 0, ADSB_FMT_INT16_IQ = 2 }; size_t adsb_iq_bytes(int fmt, size_t n); /* bytes of n complex samples: 8 n, 4 n; 0 for anything else */
+int adsb_push_iq(adsb_decoder *d, int fmt, const void *samples, size_t n); int adsb_push_iq_async(adsb_decoder *d, int fmt, const void *samples, size_t n);
+int adsb_push_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n); int adsb_push_device_iq_final(adsb_decoder *d, int fmt, const void *device_samples, size_t n);
+long adsb_decode_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_frame **frames);
+long adsb_decode_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
+                                 const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
+long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
+                               const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 /* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
  * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. */
-int adsb_set_long_stream(adsb_decoder *d, int on);
-int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
+int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
 int adsb_finish(adsb_decoder *d); /* end of input (EOF, air.c:241-244): the remaining offsets and the end-of-file horizon (SURVEY Q10) */
 /* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.  adsb_host_alloc_on binds the
  * memory to the NUMA node of `device` (best effort).  adsb_host_register page-locks memory the caller already owns.  0 / -1. */
-void *adsb_host_alloc(size_t bytes);
-void *adsb_host_alloc_on(size_t bytes, int device);
-void adsb_host_free(void *p);
-int adsb_host_register(void *p, size_t bytes);
-int adsb_host_unregister(void *p);
+void *adsb_host_alloc(size_t bytes); void *adsb_host_alloc_on(size_t bytes, int device);
+void adsb_host_free(void *p); int adsb_host_register(void *p, size_t bytes); int adsb_host_unregister(void *p);
 /* Frame egress: what the reference hands to netout() (output.c:159), in its order.  adsb_drain copies (returns the number, <= cap, or -1);
  * adsb_take hands every pending frame out in place -- valid until the next call that pushes into, finishes, resets or destroys the handle. */
-long adsb_drain(adsb_decoder *d, adsb_frame *out, size_t cap);
-long adsb_take(adsb_decoder *d, const adsb_frame **frames);
-size_t adsb_pending(const adsb_decoder *d);
+long adsb_drain(adsb_decoder *d, adsb_frame *out, size_t cap); long adsb_take(adsb_decoder *d, const adsb_frame **frames); size_t adsb_pending(const adsb_decoder *d);
 /* print_stats() counters (valid.c:84-100); try_ needs collect_stats=1 (counted on the device, fetched by this call). */
 int adsb_get_stats(const adsb_decoder *d, adsb_stats *out);
 /* Fills the first `size` bytes of *out (the macro passes the caller's sizeof: adsb_profile grows at its end). */
@@ -175,8 +179,7 @@ const char *adsb_last_error(const adsb_decoder *d); /* last error text of a hand
 int adsb_format_frame(const adsb_frame *f, int outformat, char *pkt);
 /* The CPUs local to HIP device `device` (local_cpulist, e.g. "0-63,128-191") and its NUMA node: the thread that feeds a handle polls memory the
  * device writes, 2.5-3 x slower from the far socket.  The string's length, 0 when the platform does not say, -1 on error / node or -1. */
-int adsb_device_cpulist(int device, char *out, size_t cap);
-int adsb_device_numa_node(int device);
+int adsb_device_cpulist(int device, char *out, size_t cap); int adsb_device_numa_node(int device);
 /* Splits the offsets [0, power_samples - ADSB_WINDOW] of one stream over n_shards owners (SURVEY.md 8e).  Shard i owns [g_begin[i], g_end[i])
  * (g_begin % 28 == 0) and needs the samples [first_sample[i], + n_samples[i]): 2 408 of halo.  Returns the shards used (<= n_shards). */
 int adsb_plan_shards(uint64_t total_samples, int n_shards, uint64_t *g_begin, uint64_t *g_end, uint64_t *first_sample, uint64_t *n_samples);
@@ -199,15 +202,13 @@ typedef struct adsb_multi_info { /* of the last adsb_multi_decode_* call */
 /* n_devices workers; devices[i] = HIP ordinal of worker i (NULL: 0 .. n_devices-1; an ordinal may repeat: plumbing tests
  * on a one-GPU box).  cfg as for adsb_create (device and stream are ignored).  NULL on failure (adsb_multi_last_error(NULL)). */
 adsb_multi *adsb_multi_create(const adsb_config *cfg, int n_devices, const int *devices);
-void adsb_multi_destroy(adsb_multi *m);
-int adsb_multi_devices(const adsb_multi *m);
+void adsb_multi_destroy(adsb_multi *m); int adsb_multi_devices(const adsb_multi *m);
 /* configs[4]: ONE capture, time-sharded over as many devices as it is worth (>= 128 Ki offsets per shard); each worker feeds its halo'd slice in
  * 32 MiB pieces and resolves its shard while its kernels run; the calling thread stitches and the workers gather.  Returns the number of frames, in
  * the reference's order, *frames valid until the next call on m; -1 on failure (after a worker was given up -- adsb_multi_last_error says so -- the
  * handle only answers -1, and that call's SOURCE buffers must stay alive).  _host: the capture lies in host memory (page-lock it); _file: every worker
  * reads its own slice of a regular file; _device: slice i is resident in the HBM of worker i's device and holds the samples adsb_multi_plan says. */
-long adsb_multi_decode_host(adsb_multi *m, const uint16_t *samples, size_t n, const adsb_frame **frames);
-long adsb_multi_decode_file(adsb_multi *m, const char *path, const adsb_frame **frames);
+long adsb_multi_decode_host(adsb_multi *m, const uint16_t *samples, size_t n, const adsb_frame **frames); long adsb_multi_decode_file(adsb_multi *m, const char *path, const adsb_frame **frames);
 long adsb_multi_decode_device(adsb_multi *m, uint64_t total_samples, const void *const *slices, int n_slices, const adsb_frame **frames);
 int adsb_multi_plan(const adsb_multi *m, uint64_t total_samples, uint64_t *g_begin, uint64_t *g_end,
                     uint64_t *first_sample, uint64_t *n_samples);
@@ -215,10 +216,8 @@ int adsb_multi_get_stats(const adsb_multi *m, adsb_stats *out); /* the stream's 
 /* configs[3]: n_streams INDEPENDENT captures, stream s on worker s mod adsb_multi_devices(m), each with its own ts and
  * statistics -- N times what `adsbdec -f` does (main.c:60-89), side by side.  0 / -1; results per stream afterwards. */
 int adsb_multi_set_long_streams(adsb_multi *m, int on); /* adsb_set_long_stream for the workers of the two stream calls below */
-int adsb_multi_decode_streams_host(adsb_multi *m, int n_streams, const uint16_t *const *samples, const size_t *n);
-int adsb_multi_decode_streams_file(adsb_multi *m, int n_streams, const char *const *paths);
-long adsb_multi_stream_frames(const adsb_multi *m, int stream, const adsb_frame **frames);
-int adsb_multi_stream_stats(const adsb_multi *m, int stream, adsb_stats *out);
+int adsb_multi_decode_streams_host(adsb_multi *m, int n_streams, const uint16_t *const *samples, const size_t *n); int adsb_multi_decode_streams_file(adsb_multi *m, int n_streams, const char *const *paths);
+long adsb_multi_stream_frames(const adsb_multi *m, int stream, const adsb_frame **frames); int adsb_multi_stream_stats(const adsb_multi *m, int stream, adsb_stats *out);
 int adsb_multi_get_info(const adsb_multi *m, adsb_multi_info *out);
 /* n_captures INDEPENDENT captures over the devices: each worker decodes a contiguous range of them (balanced by the offsets to scan) in sub-batches
  * of at most batch_bytes of sample data (default 256 MiB; diag header: adsb_multi_set_batch_bytes), one adsb_decode_batch_host[_packed] each.

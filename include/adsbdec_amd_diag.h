@@ -373,6 +373,8 @@ int adsb_unpack_packed12(void *dst_u16, const void *src, size_t n, void *stream)
  * two uint64 in device memory that the samples' inexact and clamped counts are ADDED to.  The kernel the _as pushes run.  0, or -1
  * with the reason in adsb_last_error(NULL); nothing is written then. */
 int adsb_convert_samples(void *dst_u16, const void *src, int fmt, size_t n, uint64_t *device_counters2, void *stream);
+/* The same for the scalars of FLOAT32_IQ (the _iq calls, fmt 0): n_scalars float32 at src -> n_scalars int16 at dst_i16 (adsbdec_amd.h: r = rint(32768 x)). */
+int adsb_convert_iq_float32(void *dst_i16, const void *src, size_t n_scalars, uint64_t *device_counters2, void *stream);
 
 #ifdef __cplusplus
 }

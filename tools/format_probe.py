@@ -3,6 +3,7 @@
 comparison interleaved.
 
     python tools/format_probe.py [--reps 20] [--out profiles/r11_formats.txt]
+    python tools/format_probe.py --iq [--reps 20] [--out profiles/r14_iq.txt]      # complex captures: see iq_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
     (with counters, and without: a kernel that does not classify its samples at all) and adsb_unpack_packed12 at the same n
@@ -144,13 +145,147 @@ def whole_calls(L, t, conv, reps, lines):
         d.close()
 
 
+def iq_probe(L, reps, lines):
+    """Complex captures (the _iq calls), every comparison interleaved in this one process:
+    (a) the scan kernel's own time (cfg.profile: adsb_profile.big_ms / big_launches) and the call's wall time of
+        adsb_decode_device_iq on 128 Mi complex int16 samples against adsb_decode_device on the 256 Mi-sample real workload --
+        512 MiB each, one frame per millisecond of signal on both sides;
+    (b) the float32 conversion: adsb_convert_iq_float32 alone (device events), and the fmt-0 call against the fmt-2 call;
+    (c) one adsb_decode_batch_device_iq of 256 captures of 512 Ki complex samples against the loop of 256 single calls."""
+    import numpy as np
+    from tools.gen_signal import make_iq_workload
+    NC = 1 << 27
+    real, _ = make_workload(torch, N, seed=1)
+    # the generator is numpy's: one block of 4 Mi complex samples (419 frames, a millisecond slot each), repeated 32 times
+    block, truth = make_iq_workload(1 << 22, seed=1)
+    iq = torch.from_numpy(block.reshape(-1)).cuda().repeat(NC >> 22)
+    iqf = iq.to(torch.float32) / 32768.0
+    torch.cuda.synchronize()
+    d_real, d_iq, d_f = (capi.Decoder(df18=False, profile=True) for _ in range(3))
+    out = C.POINTER(capi.Frame)()
+
+    def kernel_ms(d):
+        p = d.profile()
+        return p["big_ms"], p["big_launches"]
+
+    sides = {
+        "real   adsb_decode_device       256 Mi real samples": (d_real, lambda: L.adsb_decode_device(d_real._h, real.data_ptr(), N, C.byref(out))),
+        "IQ     adsb_decode_device_iq 2  128 Mi complex int16": (d_iq, lambda: L.adsb_decode_device_iq(d_iq._h, 2, iq.data_ptr(), NC, C.byref(out))),
+        "IQ     adsb_decode_device_iq 0  128 Mi complex float": (d_f, lambda: L.adsb_decode_device_iq(d_f._h, 0, iqf.data_ptr(), NC, C.byref(out))),
+    }
+    frames = {}
+    for name, (d, fn) in sides.items():
+        for _ in range(3):
+            frames[name] = fn()
+        assert frames[name] > 0, (name, L.adsb_last_error(d._h))
+    names = list(sides)
+    assert frames[names[1]] == frames[names[2]], frames
+    assert d_f.format_report() == (2 * NC, 0, 0)
+    kms, wall = {k: [] for k in sides}, {k: [] for k in sides}
+    steps = 5
+    for r in range(reps):
+        order = names[r % 3:] + names[:r % 3]
+        for name in order:
+            d, fn = sides[name]
+            m0, l0 = kernel_ms(d)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+            m1, l1 = kernel_ms(d)
+            kms[name].append((m1 - m0) / max(1, l1 - l0))
+    lines += ["# (a) scan kernel on its own clock (cfg.profile, ms per launch) and the call's wall time; 512 MiB of int16 on both sides,",
+              f"#     one frame per ms of signal; {reps} rounds x {steps} calls per side, the sides in rotation; medians (quartiles)",
+              "#   side                                                   frames   kernel ms (q1 .. q3)            call ms   kernel / real (median of rounds)"]
+    base = kms[names[0]]
+    for name in names:
+        q = statistics.quantiles(kms[name], n=4)
+        ratio = med([a / b for a, b in zip(kms[name], base)])
+        lines.append(f"    {name:54s} {frames[name]:7d}   {med(kms[name]):.5f} ({q[0]:.5f} .. {q[2]:.5f})   {med(wall[name]):8.4f}   {ratio:.4f}")
+        print(lines[-1], flush=True)
+
+    # (b) the conversion alone
+    dst = torch.empty(2 * NC, dtype=torch.int16, device="cuda")
+    counters = torch.zeros(2, dtype=torch.int64, device="cuda")
+    conv = {"convert FLOAT32_IQ": lambda: L.adsb_convert_iq_float32(dst.data_ptr(), iqf.data_ptr(), 2 * NC, counters.data_ptr(), None),
+            "FLOAT32_IQ, no count": lambda: L.adsb_convert_iq_float32(dst.data_ptr(), iqf.data_ptr(), 2 * NC, None, None)}
+    ms = {k: [] for k in conv}
+    for rep in range(-3, reps):
+        for name, fn in conv.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            assert fn() == 0, L.adsb_last_error(None)
+            e1.record()
+            e1.synchronize()
+            if rep >= 0:
+                ms[name].append(e0.elapsed_time(e1))
+            if rep == -3:
+                assert torch.equal(dst, iq), f"{name} does not give the int16 capture back"
+    assert counters.cpu().tolist() == [0, 0]
+    lines += ["#", "# (b) the float32 conversion alone: 256 Mi scalars (6 bytes moved per scalar), device events around one launch; median, min, max",
+              "#   kernel                  median ms   min ms   max ms   TB/s (median)   share of 8 TB/s"]
+    for name in conv:
+        m = med(ms[name])
+        rate = 6.0 * 2 * NC / (m * 1e-3)
+        lines.append(f"    {name:22s} {m:10.4f}  {min(ms[name]):7.4f}  {max(ms[name]):7.4f}  {rate * 1e-12:14.3f}  {rate / PEAK:16.3f}")
+        print(lines[-1], flush=True)
+    del dst
+
+    # (c) a batch against the loop of single calls
+    B, n = 256, 1 << 19
+    nn = (C.c_size_t * B)(*([n] * B))
+    first = (C.c_uint64 * (B + 1))()
+    d_batch, d_loop = capi.Decoder(df18=False), capi.Decoder(df18=False)
+    lines += ["#", "# (c) one adsb_decode_batch_device_iq of 256 captures of 512 Ki complex samples (slices of the same buffer) against the loop of",
+              "#     256 adsb_decode_device_iq calls; frames per capture equal; wall time, medians",
+              "#   format        batch ms    loop ms   loop/batch   frames"]
+    for f, buf, el in ((2, iq, 4), (0, iqf, 8)):
+        ptrs = [buf.data_ptr() + el * n * i for i in range(B)]
+        p = (C.c_void_p * B)(*ptrs)
+
+        def batch():
+            t0 = time.perf_counter()
+            k = L.adsb_decode_batch_device_iq(d_batch._h, f, B, p, nn, C.byref(out), first, None)
+            dt = time.perf_counter() - t0
+            assert k >= 0, L.adsb_last_error(d_batch._h)
+            return dt, [int(first[i + 1] - first[i]) for i in range(B)]
+
+        def loop():
+            per = []
+            t0 = time.perf_counter()
+            for i in range(B):
+                per.append(L.adsb_decode_device_iq(d_loop._h, f, ptrs[i], n, d_loop._out_ref))
+            return time.perf_counter() - t0, per
+
+        (_, fb), (_, fl) = batch(), loop()
+        assert fb == fl, f"fmt {f}: frames per capture differ"
+        tb, tl = [], []
+        for _ in range(reps):
+            tb.append(batch()[0])
+            tl.append(loop()[0])
+        lines.append(f"    {'INT16_IQ' if f == 2 else 'FLOAT32_IQ':11s}  {med(tb) * 1e3:9.3f}  {med(tl) * 1e3:9.3f}  {med(tl) / med(tb):10.2f}  {sum(fb):7d}")
+        print(lines[-1], flush=True)
+    for d in (d_real, d_iq, d_f, d_batch, d_loop):
+        d.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11_formats.txt"))
+    ap.add_argument("--iq", action="store_true", help="complex captures (the _iq calls) instead: profiles/r14_iq.txt")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "r14_iq.txt" if a.iq else "r11_formats.txt")
     torch.cuda.set_device(0)
     L = capi.load()
+    if a.iq:
+        lines = ["# tools/format_probe.py --iq: complex captures (scan_iq_kernel.hip, the _iq calls) beside the real-sample kernel, one process,",
+                 f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
+                 "# The IQ capture is one 4 Mi-sample block of tools/gen_signal.py make_iq_workload (seed 1) repeated 32 times.", "#"]
+        iq_probe(L, a.reps, lines)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     t, _ = make_workload(torch, N, seed=1)
     assert int(t.max()) <= 4095 and int(t.min()) >= 0
     conv = {S16: ((t.to(torch.int32) - 2048) * 16).to(torch.int16), F32: (t.to(torch.float32) - 2048.0) / 2048.0}

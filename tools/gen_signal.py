@@ -252,3 +252,62 @@ def make_gate_storm(torch, n: int, seed: int):
     of the offsets pass the preamble test and 7 % pass the DF gate -- ~3 600 survivors per 48 k-offset tile against a queue
     of 1 024, so EVERY tile falls back to its overflow rounds -- and no CRC ever matches."""
     return make_tiled(torch, n, seed, 30.0, 1.0, False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Complex captures at 10 MS/s (airspy_rx -t 2: int16 I, Q), as libairspy hands them on after its fs/4 mix, filter and
+# decimation: a frame is its envelope times a constant phasor.  Plain numpy; tests/golden/iq/generator_digests.json pins it.
+#     (I, Q)[m] = clip(rint(16 (A E[m] (cos phi, sin phi) + N(0, sigma))), -32768, 32767)      A, sigma in ADC-code units
+# Envelope of one frame starting at sample s (10 samples per microsecond): preamble pulses of 5 samples at s+0, s+10, s+35,
+# s+45; data bit i at s+80+10*i: first 5 samples high for 1, last 5 high for 0.
+# ---------------------------------------------------------------------------------------------------------------------
+IQ_FRAME_LONG = 80 + 10 * 112    # 1200 complex samples
+IQ_FRAME_SHORT = 80 + 10 * 56    # 640
+IQ_FRAME_GAP = 10_000            # one frame slot per millisecond of signal at 10 MS/s
+
+
+def iq_frame_envelope(frame: bytes) -> np.ndarray:
+    """0/1 envelope of one frame at 10 samples/us."""
+    nbits = 8 * len(frame)
+    env = np.zeros(80 + 10 * nbits, dtype=np.float32)
+    for s in (0, 10, 35, 45):
+        env[s:s + 5] = 1.0
+    bits = np.unpackbits(np.frombuffer(frame, dtype=np.uint8))
+    first = 80 + 10 * np.arange(nbits) + np.where(bits != 0, 0, 5)
+    env[(first[:, None] + np.arange(5)[None, :]).reshape(-1)] = 1.0
+    return env
+
+
+def iq_synth(n: int, frames, sigma: float, seed: int) -> np.ndarray:
+    """frames: list of (start_sample, frame_bytes, amplitude, phase), amplitude and sigma in ADC-code units (1/16 of the int16
+    scale).  Returns int16 of shape (n, 2).  A start may be negative or reach beyond n: the frame is cut."""
+    rng = np.random.default_rng([seed, 0x1D])
+    sig = np.zeros((n, 2), dtype=np.float64)
+    for start, fr, amp, phi in frames:
+        env = iq_frame_envelope(fr)
+        a, e = max(0, start), min(n, start + len(env))
+        if e <= a:
+            continue
+        sig[a:e, 0] += amp * np.cos(phi) * env[a - start: e - start]
+        sig[a:e, 1] += amp * np.sin(phi) * env[a - start: e - start]
+    if sigma > 0:
+        sig += rng.normal(0.0, sigma, size=(n, 2))
+    return np.clip(np.rint(16.0 * sig), -32768, 32767).astype(np.int16)
+
+
+def make_iq_workload(n: int, seed: int = 1, n_frames: int | None = None, sigma: float = 4.0, amp=(100.0, 1500.0),
+                     dfs=(17, 17, 17, 17, 18, 11)):
+    """A sparse complex capture: one frame per millisecond slot (or n_frames of the slots), DF drawn from dfs, random carrier
+    phase and amplitude per frame, Gaussian noise on I and Q; the int16 output uses all 16 bits (the low four carry the noise).
+    Returns (int16 array of shape (n, 2), truth [(start_sample, frame)])."""
+    rng = np.random.default_rng([seed, 0x1C])
+    slots = n // IQ_FRAME_GAP
+    n_frames = slots if n_frames is None else min(n_frames, slots)
+    which = np.sort(rng.choice(slots, size=n_frames, replace=False)) if n_frames else np.empty(0, int)
+    frames, truth = [], []
+    for w in which:
+        start = int(w) * IQ_FRAME_GAP + int(rng.integers(0, IQ_FRAME_GAP - IQ_FRAME_LONG))
+        fr = make_frame(int(dfs[int(rng.integers(0, len(dfs)))]), rng)
+        frames.append((start, fr, float(rng.uniform(*amp)), float(rng.uniform(0, 2 * np.pi))))
+        truth.append((start, fr))
+    return iq_synth(n, frames, sigma, seed), truth
