@@ -20,7 +20,7 @@ LIB = os.path.join(LIBDIR, "libadsbdec_amd.so")
 CLI = os.path.join(LIBDIR, "adsbdec_amd_cli")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip", "seam_kernel.hip", "decoder.hip", "decoder_collect.hip",
+HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip", "scan_power_kernel.hip", "seam_kernel.hip", "decoder.hip", "decoder_collect.hip",
                "decoder_lifecycle.hip", "decoder_batch.hip", "decoder_shard.hip", "unpack12.hip", "unpack12_batch.hip",
                "convert_samples.hip"]
 C_SOURCES = ["format.c"]

@@ -193,6 +193,15 @@ SYMBOLS = {
                                                C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     "adsb_decode_batch_host_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                              C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_push_power": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_push_power_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_push_device_power": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_push_device_power_final": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_decode_device_power": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Frame))]),
+    "adsb_decode_batch_device_power": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_decode_batch_host_power": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -764,6 +773,86 @@ class Decoder:
         st = (Stats * max(1, k))()
         if self._L.adsb_decode_batch_host_iq(self._h, fmt, k, p, n, self._out_ref, first, st) < 0:
             self._check(-1, "adsb_decode_batch_host_iq")
+        return self._batch_result(self._out, first, st, k, stats)
+
+    # ---- float32 power samples (include/adsbdec_amd.h: the _power calls; the reference's ampbuff stream); n counts power samples
+    @staticmethod
+    def _power_arg(a):
+        if isinstance(a, tuple):
+            return a
+        assert a.dtype == np.dtype("<f4") and a.ndim == 1 and a.flags["C_CONTIGUOUS"], (a.dtype, a.shape)
+        return a.ctypes.data, a.size
+
+    def push_power(self, a, mode: str = "sync"):
+        """adsb_push_power (mode "sync") / adsb_push_power_async ("async": a stays borrowed until the next push/finish/sync returns);
+        a = float32 ndarray of power samples, or (ptr, n)."""
+        ptr, n = self._power_arg(a)
+        if mode == "async":
+            self._check(self._L.adsb_push_power_async(self._h, ptr, n), "adsb_push_power_async")
+        elif mode == "sync":
+            self._check(self._L.adsb_push_power(self._h, ptr, n), "adsb_push_power")
+        else:
+            raise ValueError(mode)
+
+    def push_device_power(self, ptr: int, n: int, final: bool = False):
+        if final:
+            self._check(self._L.adsb_push_device_power_final(self._h, ptr, n), "adsb_push_device_power_final")
+        else:
+            self._check(self._L.adsb_push_device_power(self._h, ptr, n), "adsb_push_device_power")
+
+    def decode_device_power(self, ptr: int, n: int):
+        """adsb_decode_device_power: one capture of power samples resident in HBM -> its frames."""
+        k = self._L.adsb_decode_device_power(self._h, ptr, n, self._out_ref)
+        if k < 0:
+            self._check(-1, "adsb_decode_device_power")
+        return _frames_to_dicts(self._out, k)
+
+    def decode_power(self, a: np.ndarray, chunk: int | None = None, mode: str = "sync"):
+        """decode() for power samples in host memory: chunk counts power samples (any number); mode "sync" or "async"."""
+        a = np.ascontiguousarray(a, dtype="<f4").reshape(-1)
+        self.reset()
+        chunk = chunk or max(1, len(a))
+        pieces = [a[i:i + chunk] for i in range(0, len(a), chunk)]
+        out = []
+        if mode == "sync":
+            for p in pieces:
+                self.push_power(p)
+            self.finish()
+            return self.drain()
+        if mode != "async":
+            raise ValueError(mode)
+        with PinnedBuffers(2, max(1, min(chunk, max(1, len(a))) * 2)) as bufs:   # (PinnedBuffers counts uint16: two per float)
+            for k, p in enumerate(pieces):
+                b = bufs[k % 2].view(np.uint8)[: len(p) * 4].view("<f4")
+                b[:] = p                    # the push from this buffer was two calls ago
+                self.push_power(b, "async")
+                out += self.drain()
+            self.finish()
+            out += self.drain()
+        return out
+
+    def decode_batch_device_power(self, ptrs, ns, stats: bool = False):
+        """adsb_decode_batch_device_power: power captures resident in HBM (ns in power samples) -> what decode_batch_device gives."""
+        k = len(ns)
+        p = (C.c_void_p * max(1, k))(*[int(v) if v else None for v in ptrs])
+        n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        if self._L.adsb_decode_batch_device_power(self._h, k, p, n, self._out_ref, first, st) < 0:
+            self._check(-1, "adsb_decode_batch_device_power")
+        return self._batch_result(self._out, first, st, k, stats)
+
+    def decode_batch_power(self, arrays, stats: bool = False):
+        """The same for float32 arrays in host memory: adsb_decode_batch_host_power."""
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        assert all(a.dtype == np.dtype("<f4") and a.ndim == 1 for a in arrays)
+        k = len(arrays)
+        p = (C.c_void_p * max(1, k))(*[a.ctypes.data if a.size else None for a in arrays])
+        n = (C.c_size_t * max(1, k))(*[a.size for a in arrays])
+        first = (C.c_uint64 * (k + 1))()
+        st = (Stats * max(1, k))()
+        if self._L.adsb_decode_batch_host_power(self._h, k, p, n, self._out_ref, first, st) < 0:
+            self._check(-1, "adsb_decode_batch_host_power")
         return self._batch_result(self._out, first, st, k, stats)
 
     def format_report(self):

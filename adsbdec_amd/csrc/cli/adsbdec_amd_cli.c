@@ -23,6 +23,11 @@
  *                   how many: the sign of a wrong -t.  -t 1 and -t 3 not with -p, -G or -B.
  *     -q type       EXTENSION: the file holds COMPLEX samples at 10 MS/s, numbered as airspy_rx -t numbers them: 2 INT16_IQ (its
  *                   default), 0 FLOAT32_IQ (adsbdec_amd.h: the _iq calls).  Not with -t, -p, -G or -B; a file below 2^31 samples.
+ *     -w            EXTENSION: the file holds float32 POWER samples at 10 MS/s, little-endian: the reference's ampbuff stream itself
+ *                   (adsbdec.h:5), from any front end (adsbdec_amd.h: the _power calls).  Input domain: every sample finite, sign bit
+ *                   clear, below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); outside it nothing is promised or detected.
+ *                   Trailing bytes that do not make a sample are not decoded and stderr says how many.  Not with -t, -q, -p, -G or
+ *                   -B; a file below 2^31 samples.
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -166,7 +171,7 @@ static void *locker_main(void *arg)
 static void usage(void)
 {
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
-    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-q type] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
+    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-q type] [-w] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
     printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
@@ -180,6 +185,8 @@ static void usage(void)
     printf("\t     converted on the GPU, 4 and 5 are the uint16 code (the default); not 0 or 2 (IQ); 1 and 3 not with -p, -G or -B\n");
     printf("\t-q type : (extension) the file holds COMPLEX samples at 10 MS/s, as airspy_rx -t numbers them: 2 signed 16 bits IQ (airspy_rx's\n");
     printf("\t     default), 0 float32 IQ (quantised to the int16 grid on the GPU); not with -t, -p, -G or -B\n");
+    printf("\t-w : (extension) the file holds float32 POWER samples at 10 MS/s (little-endian), the demodulator's own input; every sample finite,\n");
+    printf("\t     sign bit clear and below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); not with -t, -q, -p, -G or -B\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
@@ -496,7 +503,7 @@ int main(int argc, char **argv)
     const char *filename = NULL, *listfile = NULL;
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
-    int outformat = 0, df18 = 0, fix1 = 0, packed = 0, c;
+    int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, c;
     long stype = 5; /* -t: ADSB_FMT_RAW */
     const char *stype_arg = NULL;
     long qtype = -1; /* -q: ADSB_FMT_INT16_IQ / ADSB_FMT_FLOAT32_IQ */
@@ -504,7 +511,7 @@ int main(int argc, char **argv)
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpd:G:s:l:B:t:q:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -559,6 +566,9 @@ int main(int argc, char **argv)
         case 'p':
             packed = 1;
             break;
+        case 'w':
+            power = 1;
+            break;
         case 't': {
             char *end;
             stype = strtol(optarg, &end, 10);
@@ -606,6 +616,14 @@ int main(int argc, char **argv)
                           : "the multi-GPU driver reads uint16 and packed files only");
         return 1;
     }
+    if (power && (stype_arg || qtype_arg || packed || ndev || listfile)) {
+        fprintf(stderr, "-w is not supported with %s: %s\n", stype_arg ? "-t" : qtype_arg ? "-q" : packed ? "-p" : ndev ? "-G" : "-B",
+                stype_arg    ? "a file holds real samples (-t) or power samples (-w), not both"
+                : qtype_arg  ? "a file holds IQ samples (-q) or power samples (-w), not both"
+                : packed     ? "a file is packed 12-bit real or float32 power, not both"
+                             : "the multi-GPU driver reads uint16 and packed files only");
+        return 1;
+    }
     const int iq = qtype_arg != NULL;
     if (listfile) { /* a batch: its own inputs and outputs -- no -f, no peer; -d and -G exclude each other here too */
         if (filename || outmode != SINK_STDOUT || (ndev && device >= 0)) {
@@ -640,11 +658,13 @@ int main(int argc, char **argv)
     }
     if (packed)
         buf_bytes = (size_t)BUF_SAMPLES / 8 * 12;
-    const size_t elem = iq ? adsb_iq_bytes((int)qtype, 1) : converted ? adsb_format_bytes((int)stype, 1) : 2; /* (host arithmetic: no GPU call) */
+    const size_t elem = power ? sizeof(float) : iq ? adsb_iq_bytes((int)qtype, 1) : converted ? adsb_format_bytes((int)stype, 1) : 2; /* (host arithmetic: no GPU call) */
     if (converted)
         buf_bytes = adsb_format_bytes((int)stype, BUF_SAMPLES);
     if (iq)
         buf_bytes = adsb_iq_bytes((int)qtype, BUF_SAMPLES / 2);
+    if (power)
+        buf_bytes = sizeof(float) * (BUF_SAMPLES / 2);
     install_signals();
     sink_init(&out_sink, outmode, rawaddr);
     out_sink.stop = &stop_requested;
@@ -739,7 +759,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
         return 255; /* runOutput() == -1 -> exit status 255 (main.c:101-105) */
     }
-    if (!iq && adsb_set_long_stream(dec, 1) != 0) { /* always: the reference reads a file of any length (its counter wraps, air.c:34) */
+    if (!iq && !power && adsb_set_long_stream(dec, 1) != 0) { /* always: the reference reads a file of any length (its counter wraps, air.c:34) */
         fprintf(stderr, "adsb_set_long_stream() failed: %s\n", adsb_last_error(dec));
         return 255;
     }
@@ -777,14 +797,16 @@ int main(int argc, char **argv)
             /* a trailing odd byte is dropped, like decodeiq(iqbuff, n / 2) (air.c:239); packed: a trailing partial group (only the
              * last buffer can have one: a full buffer is whole groups) */
             const size_t n_samples = packed ? bytes / 12 * 8 : bytes / elem;
-            if ((converted || iq) && bytes % elem)
+            if ((converted || iq || power) && bytes % elem)
                 fprintf(stderr, "%zu trailing bytes ignored (not a whole %zu-byte sample)\n", bytes % elem, elem);
             if (packed && bytes % 12)
                 fprintf(stderr, "%zu trailing bytes ignored (not a whole 12-byte group of packed samples)\n", bytes % 12);
             if (n_samples) {
                 const double t_p0 = now_ms();
                 int prc;
-                if (iq)
+                if (power)
+                    prc = s->registered ? adsb_push_power_async(dec, (const float *)s->buf, n_samples) : adsb_push_power(dec, (const float *)s->buf, n_samples);
+                else if (iq)
                     prc = s->registered ? adsb_push_iq_async(dec, (int)qtype, s->buf, n_samples) : adsb_push_iq(dec, (int)qtype, s->buf, n_samples);
                 else if (packed)
                     prc = s->registered ? adsb_push_packed_async(dec, s->buf, n_samples) : adsb_push_packed(dec, s->buf, n_samples);

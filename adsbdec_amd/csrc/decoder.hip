@@ -226,6 +226,8 @@ int slot_launch(adsb_decoder *d, ScanSlot &s)
         HIP_TRY(d, adsb::launch_scan(ka, stats, ls));
     } else if (d->kind == adsb::kKindIq && !d->sink.cands) { // (a stateless shard scan on a handle that holds an IQ stream is a real one)
         HIP_TRY(d, adsb::launch_scan_iq(s.args, stats, ls));
+    } else if (d->kind == adsb::kKindPower && !d->sink.cands) {
+        HIP_TRY(d, adsb::launch_scan_power(s.args, stats, ls));
     } else {
         HIP_TRY(d, adsb::launch_scan(s.args, stats, ls));
     }
@@ -588,8 +590,8 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight)
     // At EOF a trailing partial quad still makes the reference produce two (garbage)
     // power samples (air.c:59 loop bound); they can never be read by a visited
     // offset but they count for the `aidx >= APBUFFSZ` test.
-    // (An IQ stream has no quads: its power samples enter two at a time and a trailing odd one is never seen.)
-    const uint64_t m_ref = final && d->kind != adsb::kKindIq ? 2 * ((d->n_samples + 3) / 4) : m_real;
+    // (An IQ or power stream has no quads: its power samples enter two at a time and a trailing odd one is never seen.)
+    const uint64_t m_ref = final && !adsb::kind_in_twos(d->kind) ? 2 * ((d->n_samples + 3) / 4) : m_real;
     if (!in_flight) // (in flight: the records below g_scanned are not all in yet; slot_collect advanced as far as they are)
         d->res.advance(m_ref, d->g_scanned);
     if (final)
@@ -789,13 +791,13 @@ int format_dispatch(adsb_decoder *d, const char *what, int fmt, size_t *elem)
     return d->fail("%s: unknown sample format %d (1 FLOAT32_REAL, 3 INT16_REAL, 4 UINT16_REAL, 5 RAW)", what, fmt);
 }
 
-// The stream's kind is fixed by its first push with samples; a push of the other kind is refused, the handle as it was.
+// The stream's kind is fixed by its first push with samples; a push of another kind is refused, the handle as it was.
 int kind_refusal(adsb_decoder *d, const char *what, int kind)
 {
-    static const char *const names[] = {"", "real", "IQ"};
-    if (kind == adsb::kKindIq && d->long_stream)
-        return d->fail("%s: a long-stream handle (adsb_set_long_stream) takes real samples only, not IQ ones: the counter wrap it follows is "
-                       "the FIR ring's (air.c:34) and an IQ stream has no ring", what);
+    static const char *const names[] = {"", "real", "IQ", "power"};
+    if (adsb::kind_in_twos(kind) && d->long_stream)
+        return d->fail("%s: a long-stream handle (adsb_set_long_stream) takes real samples only, not %s ones: the counter wrap it follows is "
+                       "the FIR ring's (air.c:34) and %s stream has no ring", what, names[kind], kind == adsb::kKindIq ? "an IQ" : "a power");
     if (d->kind != adsb::kKindNone && d->kind != kind)
         return d->fail("%s: the stream holds %s samples (its first push fixed that) and %s samples cannot follow them: adsb_reset starts a "
                        "fresh stream", what, names[d->kind], names[kind]);
@@ -803,7 +805,8 @@ int kind_refusal(adsb_decoder *d, const char *what, int kind)
 }
 
 // adsb_push, adsb_push_async and their packed forms: samples in host memory (`packed`: whole groups of 12-bit samples).
-// kind: kKindIq from the _iq calls, whose n counts 16-bit units (fmt 2) or float scalars (fmt 0): two per complex sample.
+// kind: kKindIq from the _iq calls, whose n counts 16-bit units (fmt 2) or float scalars (fmt 0): two per complex sample;
+// kKindPower from the _power calls, whose n counts 16-bit units too: two per power sample.
 static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async, bool packed, const char *what, int conv = 0,
                      int kind = adsb::kKindReal)
 {
@@ -915,7 +918,7 @@ static int push_device_impl(adsb_decoder *d, const void *device_samples, size_t 
         if (rc)
             return -1;
         const auto t2 = clk::now();
-        d->res.advance(d->kind == adsb::kKindIq ? m_real : 2 * ((total + 3) / 4), d->g_scanned); // EOF rule: see process_stage()
+        d->res.advance(adsb::kind_in_twos(d->kind) ? m_real : 2 * ((total + 3) / 4), d->g_scanned); // EOF rule: see process_stage()
         if (d->cfg.collect_stats && count_tries_pass(d, d->deferred_slot, d->deferred_slot ? d->deferred_slot->d_tries.p : nullptr,
                                                         d->deferred_slot ? d->deferred_slot->d_try_counts.p : nullptr, d->deferred_n, d->deferred_base, true))
             return -1; // tries beyond the final position are never visited
@@ -1084,9 +1087,83 @@ static int push_device_iq(adsb_decoder *d, int fmt, const void *p, size_t n, boo
     return push_device_impl(d, p, 2 * n, final, adsb::kKindIq);
 }
 
+// ---- float32 power samples (the _power calls; include/adsbdec_amd.h) ----
+// What every _power call checks before anything of the handle changes.  n counts power samples; the stream counts 16-bit units
+// (two per power sample), so everything behind these checks is INT16_IQ's road with 2 n: copies, staging, compaction, in-place
+// scans, the EOF rule and the count pass -- a power sample is 4 bytes, as a complex int16 sample is.
+int power_refusal(adsb_decoder *d, const char *what, const void *p, size_t n, bool device, uint64_t at_units)
+{
+    if ((uint64_t)n >= (1ull << 31) || at_units + 2 * (uint64_t)n >= (1ull << 32))
+        return d->fail("%s: the stream would reach 2^31 power samples (%llu + %zu): power streams end below", what,
+                       (unsigned long long)(at_units / 2), n);
+    if (n && !p)
+        return d->fail("%s: NULL samples", what);
+    if (device && (uintptr_t)p % 4 != 0)
+        return d->fail("%s: device pointer %p is not 4-byte aligned", what, p);
+    return 0;
+}
+
+static int push_host_power(adsb_decoder *d, const float *samples, size_t n, bool async, const char *what)
+{
+    if (!d)
+        return -1;
+    if (power_refusal(d, what, samples, n, false, d->n_samples))
+        return -1;
+    return push_host(d, samples, 2 * n, async, false, what, 0, adsb::kKindPower);
+}
+
+// scanned where it lies under the uint16 rule (16-byte aligned, at a multiple of 4 power samples; else staged)
+static int push_device_power(adsb_decoder *d, const void *p, size_t n, bool final, const char *what, bool checked = false)
+{
+    if (!d)
+        return -1;
+    if (!checked && power_refusal(d, what, p, n, true, d->n_samples))
+        return -1;
+    if (d->finished)
+        return d->fail("%s after adsb_finish", what);
+    if (kind_refusal(d, what, adsb::kKindPower))
+        return -1;
+    if (n == 0 && !final)
+        return 0;
+    return push_device_impl(d, p, 2 * n, final, adsb::kKindPower);
+}
+
 } // namespace adsb
 
 extern "C" {
+
+int adsb_push_power(adsb_decoder *d, const float *samples, size_t n)
+{
+    return push_host_power(d, samples, n, false, "adsb_push_power");
+}
+
+int adsb_push_power_async(adsb_decoder *d, const float *samples, size_t n)
+{
+    return push_host_power(d, samples, n, true, "adsb_push_power_async");
+}
+
+int adsb_push_device_power(adsb_decoder *d, const void *device_samples, size_t n)
+{
+    return push_device_power(d, device_samples, n, false, "adsb_push_device_power");
+}
+
+int adsb_push_device_power_final(adsb_decoder *d, const void *device_samples, size_t n)
+{
+    return push_device_power(d, device_samples, n, true, "adsb_push_device_power_final");
+}
+
+long adsb_decode_device_power(adsb_decoder *d, const void *device_samples, size_t n, const adsb_frame **frames)
+{
+    const char *what = "adsb_decode_device_power";
+    if (!d || !frames)
+        return -1;
+    // refused before the reset, at the position the reset will set: a refused call leaves the handle as it was
+    if (power_refusal(d, what, device_samples, n, true, 0) || (d->long_stream && kind_refusal(d, what, adsb::kKindPower)))
+        return -1;
+    if (adsb_reset(d) != 0 || push_device_power(d, device_samples, n, true, what, true) != 0)
+        return -1;
+    return (long)d->res.take(frames);
+}
 
 size_t adsb_iq_bytes(int fmt, size_t n)
 {

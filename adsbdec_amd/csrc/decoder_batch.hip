@@ -115,6 +115,8 @@ int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void
         s.busy = true; // (a failure from here on leaves a launch in flight: adsb_reset waits for it)
         if (d->kind == adsb::kKindIq)
             HIP_TRY(d, adsb::launch_scan_batch_iq(a, seg_d, tile_d, L.tiles, stats, ls));
+        else if (d->kind == adsb::kKindPower)
+            HIP_TRY(d, adsb::launch_scan_batch_power(a, seg_d, tile_d, L.tiles, stats, ls));
         else
             HIP_TRY(d, adsb::launch_scan_batch(a, seg_d, tile_d, L.tiles, stats, ls));
         HIP_TRY(d, hipEventRecord(s.ev_ready[s.ev_cur], ls));
@@ -332,8 +334,9 @@ int batch_refusal_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
 
 // The captures in device memory at src[] (fmt 2: int16 pairs, 4-byte aligned; fmt 0: float pairs) -> frames.  Whatever is not
 // 16-byte aligned int16 goes through scratch first: fmt 0 by the batch conversion launch, a misaligned fmt-2 capture by a copy.
+// kind = kKindPower (fmt 2): the captures are float32 power samples, n[] counts them -- the same 4-byte units on the same road.
 long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
-                     const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+                     const adsb_frame **frames, uint64_t *first, adsb_stats *stats, int kind = adsb::kKindIq)
 {
     std::vector<size_t> units(n_captures), scalars(n_captures);
     for (size_t i = 0; i < n_captures; i++) {
@@ -362,15 +365,76 @@ long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
             off += (units[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
         }
     }
-    d->kind = adsb::kKindIq; // (behind the reset: the batch launches are scan_iq_batch_kernel's)
+    d->kind = kind; // (behind the reset: the batch launches are scan_iq_batch_kernel's or scan_power_batch_kernel's)
     const long k = decode_batch(d, n_captures, at.data(), units.data(), frames, first, stats);
     WAIT_STREAM(d, d->stream, "the scan stream");
     return k;
 }
 
+// ---- batches of float32 power captures (adsb_decode_batch_*_power): n[] counts power samples ----
+int batch_refusal_power(adsb_decoder *d, const char *what, size_t n_captures, const void *const *p, const size_t *n, bool device)
+{
+    if (n_captures && (!p || !n))
+        return d->fail("%s: NULL capture arrays", what);
+    if (d->long_stream)
+        return kind_refusal(d, what, adsb::kKindPower);
+    char who[96];
+    for (size_t i = 0; i < n_captures; i++) {
+        snprintf(who, sizeof who, "%s: capture %zu", what, i);
+        if (power_refusal(d, who, p[i], n[i], device, 0))
+            return -1;
+    }
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
+
+long adsb_decode_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
+                                    const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    const char *what = "adsb_decode_batch_device_power";
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal_power(d, what, n_captures, device_samples, n, true))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    return decode_batch_iq(d, what, 2, n_captures, device_samples, n, frames, first, stats, adsb::kKindPower);
+}
+
+long adsb_decode_batch_host_power(adsb_decoder *d, size_t n_captures, const float *const *samples, const size_t *n,
+                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+{
+    const char *what = "adsb_decode_batch_host_power";
+    if (!d || !frames || !first)
+        return -1;
+    if (batch_refusal_power(d, what, n_captures, reinterpret_cast<const void *const *>(samples), n, false))
+        return -1;
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    // every capture as it is at a 128-byte boundary of the landing buffer the other host batches use
+    size_t bytes = 0;
+    for (size_t i = 0; i < n_captures; i++)
+        bytes += (n[i] * sizeof(float) + 127) & ~(size_t)127;
+    if (batch_grow(d, what, "the captures as they are", d->batch_land, bytes))
+        return -1;
+    std::vector<const void *> land(n_captures);
+    size_t off = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        land[i] = d->batch_land + off;
+        if (n[i])
+            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, samples[i], n[i] * sizeof(float), hipMemcpyHostToDevice,
+                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
+        off += (n[i] * sizeof(float) + 127) & ~(size_t)127;
+    }
+    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again)
+        WAIT_STREAM(d, cs, "a copy stream");
+    return decode_batch_iq(d, what, 2, n_captures, land.data(), n, frames, first, stats, adsb::kKindPower);
+}
 
 long adsb_decode_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats)

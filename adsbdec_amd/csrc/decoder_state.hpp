@@ -49,7 +49,10 @@ inline const char *tuning_env(const char *) { return nullptr; }
 constexpr uint64_t kDefaultStageSamples = 32ull << 20; // 64 MiB per staging buffer
 constexpr uint64_t kStageSlack = 4096;                 // samples kept free for alignment padding
 constexpr size_t kInPlaceMinSamples = 1u << 16;
-constexpr int kKindNone = 0, kKindReal = 1, kKindIq = 2; // adsb_decoder::kind
+constexpr int kKindNone = 0, kKindReal = 1, kKindIq = 2, kKindPower = 3; // adsb_decoder::kind
+// the stream's 32-bit units ARE its power samples (complex int16 samples, float32 power samples): no FIR ring, no quads, and
+// the power samples enter the demodulator two at a time (air.c:94-99)
+constexpr bool kind_in_twos(int kind) { return kind == kKindIq || kind == kKindPower; }
 constexpr size_t kSeamSamples = 4096; // > 2*(28+8+1196): enough for the first in-place tile's pre-halo
 constexpr int kSlots = 4;
 constexpr size_t kTryStateBytes = 4 * sizeof(unsigned long long) + 4 * sizeof(uint32_t); // d_try_acc + d_carry_n
@@ -176,7 +179,8 @@ struct adsb_decoder {
     uint64_t g_scanned = 0; // every offset below has been submitted to the device
     bool finished = false;
     // What the stream holds, fixed by its first push with samples after adsb_create / adsb_reset: real samples (the uint16,
-    // packed and _as calls: the FIR front end) or complex ones (the _iq calls: scan_iq_kernel.hip).  The two never mix.
+    // packed and _as calls: the FIR front end), complex ones (the _iq calls: scan_iq_kernel.hip) or float32 power samples (the
+    // _power calls: scan_power_kernel.hip).  They never mix.
     int kind = adsb::kKindNone;
     // Long streams (adsb_set_long_stream): no refusal at 2^32 samples; launches are cut at every wrap of the reference's
     // sample counter and the offsets around it go through the seam kernel (scan_submit, seam_kernel.h)
@@ -432,6 +436,7 @@ int format_counters(adsb_decoder *d, unsigned long long out[2]);
 int format_dispatch(adsb_decoder *d, const char *what, int fmt, size_t *elem);
 int kind_refusal(adsb_decoder *d, const char *what, int kind);
 int iq_refusal(adsb_decoder *d, const char *what, int fmt, const void *p, size_t n, bool device, uint64_t at_units);
+int power_refusal(adsb_decoder *d, const char *what, const void *p, size_t n, bool device, uint64_t at_units);
 bool shard_too_long(adsb_decoder *d, const char *what, uint64_t first_sample, uint64_t n, uint64_t total_samples);
 // decoder_collect.hip
 int slot_collect(adsb_decoder *d);

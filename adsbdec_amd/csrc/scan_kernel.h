@@ -199,6 +199,11 @@ hipError_t launch_scan_batch(const ScanArgs &args, const BatchSeg *segs, const u
 hipError_t launch_scan_iq(const ScanArgs &args, bool stats, hipStream_t stream);
 hipError_t launch_scan_batch_iq(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
                                 hipStream_t stream);
+// ... and for a stream of float32 power samples (scan_power_kernel.hip): x holds ONE binary32 power sample per word, the
+// reference's ampbuff; pbuf0 / p_lo / p_hi / g count power samples.
+hipError_t launch_scan_power(const ScanArgs &args, bool stats, hipStream_t stream);
+hipError_t launch_scan_batch_power(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
+                                   hipStream_t stream);
 // the report kernel of launch_scan on its own (scan_kernel.hip)
 hipError_t launch_report(const ScanArgs &args, hipStream_t stream);
 // Device-to-device copy of n uint16 samples by the library's own kernel (the staging tail: see scan_kernel.hip).

@@ -1,15 +1,17 @@
-// scan_iq_kernel.hip -- the scan kernels for a stream of COMPLEX int16 samples at 10 MS/s (airspy_rx -t 2; DESIGN.md
-// "IQ captures"), for gfx950.  libairspy has already done what the FIR of scan_kernel.hip does -- the fs/4 mix, the half-band
-// filter, the decimation -- so power sample m is |sample m|^2 and everything behind the power samples is the reference's
-// demodulator unchanged: Stage A's plane arithmetic and all of Stage B are the code of scan_stages.h that scan_kernel and
-// scan_batch_kernel run.  What is this unit's own is the front end (stage_a_iq: typed signed loads, 56 products and 28 sums
-// per run) and pw's four loads (pw_at_iq).  A complex sample is 4 bytes, as the (I, Q) pair of real samples behind one power
-// sample is: ScanArgs, the tile geometry, the LDS, the hand-off stream and the count pass are scan_kernel's, with x the
-// complex samples and pbuf0 / p_lo / p_hi their indices.
+// scan_power_kernel.hip -- the scan kernels for a stream of float32 POWER samples at 10 MS/s (DESIGN.md "Power samples"), for
+// gfx950.  The stream is the reference's `ampbuff` itself (adsbdec.h:5: deqframe(const float *ampbuff, const int len)): the
+// caller's front end -- another SDR, a filter of their own, a tensor computed on the GPU -- has done everything that comes
+// before it, and everything behind it is the reference's demodulator unchanged: Stage A's plane arithmetic and all of Stage B
+// are the code of scan_stages.h that the other scan units run.  What is this unit's own is the front end (stage_a_power:
+// seven 16-byte loads per run, nothing computed) and pw's four loads (pw_at_power).  A power sample is 4 bytes, as a complex
+// int16 sample is: ScanArgs, the tile geometry, the LDS, the hand-off stream and the count pass are scan_iq_kernel's, with x
+// the floats and pbuf0 / p_lo / p_hi their indices.
+//
+// Input domain (include/adsbdec_amd.h): finite, sign bit clear, below 2^29; subnormals included -- stage_a_power says where
+// that matters.  Outside it the reference itself is undefined behaviour and nothing is promised here.
 //
 // A translation unit of its own: tests/test_build_flags.py counts the kernels and the fused operations of scan_kernel.hip's.
-// The arithmetic is binary32 multiply, then add (-ffp-contract=off); the only fused operations here are the sign tests of
-// the plane arithmetic.
+// The only fused operations here are the sign tests of the plane arithmetic (-ffp-contract=off).
 #undef ADSB_PHASE_STAMPS // (a measurement build's per-phase clocks, scan_stamps.h, are scan_kernel.hip's alone)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,7 +23,7 @@ namespace adsb {
 
 // One tile of either entry: the planes' pad words, Stage A, a barrier, Stage B, the profile clocks.
 template <bool kStats>
-__device__ __forceinline__ void scan_iq_tile(const ScanArgs &args, const int K, const int64_t t0, const uint64_t prof_begin, uint32_t *smem)
+__device__ __forceinline__ void scan_power_tile(const ScanArgs &args, const int K, const int64_t t0, const uint64_t prof_begin, uint32_t *smem)
 {
     const int nplane = kPassRuns * K + kPlanePad;
     uint32_t *pl_d = smem;
@@ -42,9 +44,9 @@ __device__ __forceinline__ void scan_iq_tile(const ScanArgs &args, const int K, 
     }
 
     uint64_t stamp_last = 0;
-    stage_a_iq(args.x, args.pbuf0, args.p_lo, args.p_hi, t0, K, wave, lane, pl_d, pl_e1, pl_e2);
+    stage_a_power(args.x, args.pbuf0, args.p_lo, args.p_hi, t0, K, wave, lane, pl_d, pl_e1, pl_e2);
     __syncthreads();
-    stage_b<kStats, kFrontIq>(args, blockIdx.x, K, t0, tid, pl_d, pl_e1, pl_e2, queue, qcount, cl_rec, args.clist_cap, stamp_last);
+    stage_b<kStats, kFrontPower>(args, blockIdx.x, K, t0, tid, pl_d, pl_e1, pl_e2, queue, qcount, cl_rec, args.clist_cap, stamp_last);
 
     if (args.profile) { // the launch's duration is (latest tile end) - (earliest tile start)
         __syncthreads();
@@ -66,9 +68,9 @@ __device__ __forceinline__ void stagger_start()
     }
 }
 
-// scan_kernel for complex samples: the tiles partition one stream
+// scan_kernel for power samples: the tiles partition one stream
 template <bool kStats>
-__global__ __launch_bounds__(kThreads, kMinWaves) void scan_iq_kernel(const ScanArgs args)
+__global__ __launch_bounds__(kThreads, kMinWaves) void scan_power_kernel(const ScanArgs args)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int K = tile_passes(blockIdx.x, args.big_tiles, args.passes);
@@ -76,12 +78,12 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void scan_iq_kernel(const Scan
     const uint64_t prof_begin = args.profile ? __builtin_amdgcn_s_memrealtime() : 0;
     const int64_t t0 = // first owned offset
         (int64_t)args.g_begin + (int64_t)kRun * (int64_t)tile_first_run(blockIdx.x, args.big_tiles, args.passes);
-    scan_iq_tile<kStats>(args, K, t0, prof_begin, smem);
+    scan_power_tile<kStats>(args, K, t0, prof_begin, smem);
 }
 
-// scan_batch_kernel for complex samples: the tiles belong to the captures of a batch (scan_kernel.h BatchSeg)
+// scan_batch_kernel for power samples: the tiles belong to the captures of a batch (scan_kernel.h BatchSeg)
 template <bool kStats>
-__global__ __launch_bounds__(kThreads, kMinWaves) void scan_iq_batch_kernel(const ScanArgs launch, const BatchSeg *__restrict__ segs,
+__global__ __launch_bounds__(kThreads, kMinWaves) void scan_power_batch_kernel(const ScanArgs launch, const BatchSeg *__restrict__ segs,
                                                                             const uint32_t *__restrict__ tile_seg)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -96,33 +98,33 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void scan_iq_batch_kernel(cons
     args.p_hi = sg.p_hi;
     args.g_end = sg.g_end;
     const int64_t t0 = (int64_t)sg.g_begin + (int64_t)kRun * (int64_t)tile_first_run(blockIdx.x - sg.first_tile, 0u, K);
-    scan_iq_tile<kStats>(args, K, t0, prof_begin, smem);
+    scan_power_tile<kStats>(args, K, t0, prof_begin, smem);
 }
 
-hipError_t launch_scan_iq(const ScanArgs &args, bool stats, hipStream_t stream)
+hipError_t launch_scan_power(const ScanArgs &args, bool stats, hipStream_t stream)
 {
     if (args.g_end <= args.g_begin)
         return hipSuccess;
     const unsigned blocks = tile_count(args.g_end - args.g_begin, args.big_tiles, args.passes);
     const size_t lds = lds_bytes(args.passes);
     if (stats)
-        hipLaunchKernelGGL(scan_iq_kernel<true>, dim3(blocks), dim3(kThreads), lds, stream, args);
+        hipLaunchKernelGGL(scan_power_kernel<true>, dim3(blocks), dim3(kThreads), lds, stream, args);
     else
-        hipLaunchKernelGGL(scan_iq_kernel<false>, dim3(blocks), dim3(kThreads), lds, stream, args);
+        hipLaunchKernelGGL(scan_power_kernel<false>, dim3(blocks), dim3(kThreads), lds, stream, args);
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : launch_report(args, stream);
 }
 
-hipError_t launch_scan_batch_iq(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
+hipError_t launch_scan_batch_power(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
                                 hipStream_t stream)
 {
     if (n_tiles == 0)
         return hipSuccess;
     const size_t lds = lds_bytes(args.passes);
     if (stats)
-        hipLaunchKernelGGL(scan_iq_batch_kernel<true>, dim3(n_tiles), dim3(kThreads), lds, stream, args, segs, tile_seg);
+        hipLaunchKernelGGL(scan_power_batch_kernel<true>, dim3(n_tiles), dim3(kThreads), lds, stream, args, segs, tile_seg);
     else
-        hipLaunchKernelGGL(scan_iq_batch_kernel<false>, dim3(n_tiles), dim3(kThreads), lds, stream, args, segs, tile_seg);
+        hipLaunchKernelGGL(scan_power_batch_kernel<false>, dim3(n_tiles), dim3(kThreads), lds, stream, args, segs, tile_seg);
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : launch_report(args, stream);
 }

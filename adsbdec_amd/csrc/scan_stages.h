@@ -254,12 +254,34 @@ __device__ __noinline__ uint32_t pw_at_iq(const uint32_t *__restrict__ x, int64_
     return (uint32_t)((p1 + p2) / 4);
 }
 
-// pw of offset g by the front end of the kernel the stages are built into
-template <bool kIq>
+// ---- the power front end's slow path (scan_power_kernel.hip) ----
+// pw of the offset g of a stream of float32 power samples (demod.c:102-105,127,133): the stream IS the reference's ampbuff, so
+// the four samples at g + {0, 10, 35, 45} are four loads; a sample outside the buffer reads as +0.
+__device__ __noinline__ uint32_t pw_at_power(const uint32_t *__restrict__ x, int64_t pbuf0, int64_t p_lo, int64_t p_hi, int64_t g)
+{
+    const int off[4] = {0, 10, 35, 45};
+    float a[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int64_t pi = g + off[k];
+        a[k] = __uint_as_float((pi >= p_lo && pi < p_hi) ? x[pi - pbuf0] : 0u);
+    }
+    const int p1 = __float2int_rz(a[0] + a[1]);
+    const int p2 = __float2int_rz(a[2] + a[3]);
+    return (uint32_t)((p1 + p2) / 4);
+}
+
+// The front end of the kernel the stages are built into: what Stage A reads and how pw is formed
+constexpr int kFrontReal = 0, kFrontIq = 1, kFrontPower = 2;
+
+// pw of offset g by that front end
+template <int kFront>
 __device__ __forceinline__ uint32_t pw_of(const uint32_t *__restrict__ x, int64_t pbuf0, int64_t p_lo, int64_t p_hi, int64_t g)
 {
-    if constexpr (kIq)
+    if constexpr (kFront == kFrontIq)
         return pw_at_iq(x, pbuf0, p_lo, p_hi, g);
+    else if constexpr (kFront == kFrontPower)
+        return pw_at_power(x, pbuf0, p_lo, p_hi, g);
     else
         return pw_at(x, pbuf0, p_lo, p_hi, g);
 }
@@ -617,13 +639,145 @@ __device__ __forceinline__ void stage_a_iq(const uint32_t *__restrict__ xin, con
     }
 }
 
+// ------------------------------ Stage A, power front end ------------------------------
+// The same tile, the same passes, lanes and lane stride for a stream of float32 POWER samples (scan_power_kernel.hip): the
+// stream is the reference's ampbuff itself, so a run of 28 is the lane's own 28 floats -- 112 bytes, no pre-halo, no
+// conversion, no product: seven untyped 16-byte buffer loads stand where stage_a_iq has fourteen typed ones and 42 packed
+// operations.  The window is stage_a_iq's (a power sample is 4 bytes, as a complex int16 sample is).
+//
+// Subnormal samples are inside the input domain (include/adsbdec_amd.h) and the D plane below decides a[m] > a[m+5] by the
+// sign of the rounded difference a[m+5] - a[m]: that is right for two unequal subnormals only because binary32 subnormals
+// are KEPT by gfx950's VALU in the mode HIP code runs in (the kernel descriptor's float_denorm_mode_32 = 3; the build never
+// asks for flush-to-zero) -- flushed, the difference of two unequal subnormals would be +0 and the bit lost.  The sums
+// c[k] truncate to 0 for them either way.
+__device__ __forceinline__ void stage_a_power(const uint32_t *__restrict__ xin, const int64_t pbuf0, const int64_t p_lo,
+                                              const int64_t p_hi, const int64_t t0, const int K, const int wave, const int lane,
+                                              uint32_t *pl_d, uint32_t *pl_e1, uint32_t *pl_e2)
+{
+    auto first_run = [&](int ps) { return kWaveRuns * (kWaves * ps + wave); };
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll 1
+    for (int pass = 0; pass < K; pass++) {
+        const int v0 = first_run(pass); // first run of this wave in this pass
+        const int v = v0 + lane;
+        const int64_t wlo = t0 + (int64_t)kRun * v0; // lane 0's first sample: a multiple of 28, so of 4 (16 bytes)
+        // wave-uniform: every sample this wave loads lies inside the buffer
+        const bool interior = (wlo >= p_lo) && (wlo + kRun * 64 <= p_hi);
+        f32x4 tl[7]; // tl[k] = samples 4k .. 4k+3 of the run
+        if (interior) {
+            const uint64_t wbase = (uint64_t)(xin + (wlo - pbuf0));
+            i32x4 rs;
+            rs.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)wbase);
+            rs.y = __builtin_amdgcn_readfirstlane((int)((uint32_t)(wbase >> 32) & 0xFFFFu)); // stride 0: raw buffer
+            rs.z = 64 * kRun * 4;                                                             // bytes
+            rs.w = (int)(4u | 5u << 3 | 6u << 6 | 7u << 9 /* dst_sel xyzw */ | 7u << 12 /* FLOAT */ | 4u << 15 /* 32 */);
+            const int voff = lane * (kRun * 4);
+            asm volatile("buffer_load_dwordx4 %0, %7, %8, 0 offen\n\t"
+                         "buffer_load_dwordx4 %1, %7, %8, 0 offen offset:16\n\t"
+                         "buffer_load_dwordx4 %2, %7, %8, 0 offen offset:32\n\t"
+                         "buffer_load_dwordx4 %3, %7, %8, 0 offen offset:48\n\t"
+                         "buffer_load_dwordx4 %4, %7, %8, 0 offen offset:64\n\t"
+                         "buffer_load_dwordx4 %5, %7, %8, 0 offen offset:80\n\t"
+                         "buffer_load_dwordx4 %6, %7, %8, 0 offen offset:96"
+                         "\n\ts_waitcnt vmcnt(0)"
+                         : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]), "=&v"(tl[4]), "=&v"(tl[5]), "=&v"(tl[6])
+                         : "v"(voff), "s"(rs)
+                         : "memory");
+        } else {
+            // the ragged end of a buffer (and whatever lies below its first sample): plain loads; a missing sample is +0
+            int lane_here = lane;
+            asm volatile("" : "+v"(lane_here)); // (opaque, as in stage_a: nothing of this rare path is precomputed per tile and spilled)
+            const int64_t pr0 = wlo + (int64_t)(kRun * lane_here);
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                uint32_t d[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int64_t pi = pr0 + 4 * k + i;
+                    d[i] = (pi >= p_lo && pi < p_hi) ? xin[pi - pbuf0] : 0u;
+                }
+                tl[k] = f32x4{__uint_as_float(d[0]), __uint_as_float(d[1]), __uint_as_float(d[2]), __uint_as_float(d[3])};
+            }
+        }
+        // a[0..27]: this run; a[28..43]: the first 16 samples of the next run (next lane)
+        float a[44];
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            a[4 * k] = tl[k].x;
+            a[4 * k + 1] = tl[k].y;
+            a[4 * k + 2] = tl[k].z;
+            a[4 * k + 3] = tl[k].w;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            a[28 + k] = from_next_lane(a[k]);
+
+        // demod.c:102-105: every preamble sum is c[k] = (int)(a[k] + a[k+10]).  The
+        // truncated value is kept as a float (v_trunc_f32 == the C conversion for the
+        // magnitudes in the input domain); the integer comparisons `c > 2 c'` are
+        // decided by the SIGN of 2 c' - c, which one fused multiply-add gives exactly
+        // (a single rounding cannot change the sign of a non-zero difference and an
+        // exact zero stays zero).
+        //
+        // Packing: every operation here combines index k with k + 5 or k + 10, so the
+        // usual (k, k+1) register pairs cannot feed v_pk_* on both sides (5 is odd).
+        // Pairs (k, k+2) for k mod 5 in {0, 1} can -- the partner set is closed under
+        // +5 -- and leave k mod 5 == 4 as scalar operations: 4 of 5 values are packed.
+        float c[34], dv[28], e1v[28], e2v[28];
+#pragma unroll
+        for (int k = 0; k < 33; k++) {
+            if (k % 5 < 2) {
+                const f32x2 lo = {a[k], a[k + 2]}, hi = {a[k + 10], a[k + 12]};
+                const f32x2 sum = lo + hi;
+                c[k] = __builtin_truncf(sum.x);
+                c[k + 2] = __builtin_truncf(sum.y);
+            } else if (k % 5 == 4) {
+                c[k] = __builtin_truncf(a[k] + a[k + 10]);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < 28; m++) {
+            if (m % 5 < 2 && m + 2 < 28) {
+                const f32x2 am = {a[m], a[m + 2]}, an = {a[m + 5], a[m + 7]};
+                const f32x2 cm = {c[m], c[m + 2]}, cn = {c[m + 5], c[m + 7]};
+                const f32x2 two = {2.0f, 2.0f};
+                const f32x2 dd = an - am;
+                const f32x2 x1 = __builtin_elementwise_fma(cn, two, -cm);
+                const f32x2 x2 = __builtin_elementwise_fma(cm, two, -cn);
+                dv[m] = dd.x, dv[m + 2] = dd.y;
+                e1v[m] = x1.x, e1v[m + 2] = x1.y;
+                e2v[m] = x2.x, e2v[m + 2] = x2.y;
+            } else if (m % 5 == 4 || (m % 5 < 2 && m + 2 >= 28)) {
+                dv[m] = a[m + 5] - a[m];
+                e1v[m] = __builtin_fmaf(c[m + 5], 2.0f, -c[m]);
+                e2v[m] = __builtin_fmaf(c[m], 2.0f, -c[m + 5]);
+            }
+        }
+
+        uint32_t d = 0, e1 = 0, e2 = 0;
+#pragma unroll
+        for (int m = 27; m >= 0; m--) { // bit m of each word <-> sample m of the run
+            d = push_sign(d, __float_as_uint(dv[m]));    // a[m+5] - a[m] < 0:  a[m] > a[m+5]   (demod.c:34)
+            e1 = push_sign(e1, __float_as_uint(e1v[m])); // 2 c[m+5] - c[m] < 0: c[m] > 2 c[m+5] (SN = 2, demod.c:83)
+            e2 = push_sign(e2, __float_as_uint(e2v[m])); // 2 c[m] - c[m+5] < 0: c[m+5] > 2 c[m]
+        }
+        asm volatile("" : "+v"(d), "+v"(e1), "+v"(e2)); // (the words are made by every lane: the arithmetic is not to sink under the branch)
+        if (lane < kWaveRuns) { // lane 63 only feeds lane 62
+            pl_d[v] = d;
+            pl_e1[v] = e1;
+            pl_e2[v] = e2;
+        }
+    }
+}
+
 // ------------------------------ Stage B ------------------------------
 // Everything behind a tile's planes: gate, survivor queue, slicer + CRC, never-visited filter, ranking, finishing and
 // the hand-off, by the tile's four waves between workgroup barriers.
 // LDS of Stage B: queue[queue_cap], ctl[16] (qcount, qover, cl_n, cl_over, tile_n, tile_over, tile_base, try_base,
 // tile_res, tile_fit, tile_chk[4], tile_lines, tile_sum), cl_rec[clist_cap * kCandWords].
-// kIq: the kernel's front end is stage_a_iq -- what differs here is pw alone (pw_of).
-template <bool kStats, bool kIq = false>
+// kFront: the kernel's front end (stage_a, stage_a_iq or stage_a_power) -- what differs here is pw alone (pw_of).
+template <bool kStats, int kFront = kFrontReal>
 __device__ __forceinline__ void stage_b(const ScanArgs &args, const uint32_t tile, const int K, const int64_t t0, const int tid,
                                         const uint32_t *pl_d, const uint32_t *pl_e1, const uint32_t *pl_e2, uint32_t *queue,
                                         uint32_t *qcount, uint32_t *cl_rec, const int clist_cap, uint64_t &stamp_last)
@@ -847,7 +1001,7 @@ __device__ __forceinline__ void stage_b(const ScanArgs &args, const uint32_t til
             uint32_t wds[4];
             columns_to_bytes(cw, code == 0, wds);
             wds[3] |= fixed << 24;
-            const uint32_t pw = pw_of<kIq>(xin, pbuf0, p_lo, p_hi, t0 + (int64_t)kRun * sv + sj);
+            const uint32_t pw = pw_of<kFront>(xin, pbuf0, p_lo, p_hi, t0 + (int64_t)kRun * sv + sj);
             emit_loose(g_rel, pw, wds);
         }
 
@@ -1153,7 +1307,7 @@ __device__ __forceinline__ void stage_b(const ScanArgs &args, const uint32_t til
             uint32_t wds[4];
             columns_to_bytes(cw, (e[1] & 0xFFu) == 0, wds);
             wds[3] |= ((e[1] >> 8) & 1u) << 24; // repaired-by-extension flag
-            const uint32_t pw = pw_of<kIq>(xin, pbuf0, p_lo, p_hi, (int64_t)args.g_begin + e[0]);
+            const uint32_t pw = pw_of<kFront>(xin, pbuf0, p_lo, p_hi, (int64_t)args.g_begin + e[0]);
             fin[0] = e[0], fin[1] = pw, fin[2] = wds[0], fin[3] = wds[1], fin[4] = wds[2], fin[5] = wds[3];
             if (links)
                 pwbuf[tid] = pw;

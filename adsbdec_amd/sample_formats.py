@@ -18,6 +18,11 @@ between the two of them:
 
     python -m adsbdec_amd.sample_formats -t 0 in.s16iq out.f32iq      # int16 IQ capture -> float32 IQ (exact)
     python -m adsbdec_amd.sample_formats -t 0 --back in.f32iq out.s16iq
+
+and float32 POWER samples (the library's _power calls: the reference's ampbuff stream itself, no format of airspy_rx), with the
+numpy statement of their input domain (power_domain_ok) and a converter that writes the power file of an IQ capture:
+
+    python -m adsbdec_amd.sample_formats -t 2 --power in.s16iq out.pw   # iq_power of an int16 IQ capture (-t 0: of a float32 one)
 """
 from __future__ import annotations
 
@@ -127,6 +132,28 @@ def iq_power(x, fmt: int = INT16_IQ) -> np.ndarray:
     return (i * i + q * q).astype(np.float32)               # (numpy rounds every float32 operation on its own)
 
 
+def power_domain_ok(a) -> bool:
+    """The input domain of the _power calls (include/adsbdec_amd.h): every sample finite, its sign bit clear, below 2^29 -- no
+    negative, no -0.0, no NaN, no Inf.  Subnormals are inside.  Decided on the bit patterns."""
+    a = np.ascontiguousarray(a)
+    if a.dtype != np.dtype("<f4"):
+        raise ValueError(f"power samples are float32, not {a.dtype}")
+    bits = a.view("<u4")
+    return bool((bits < np.float32(2.0 ** 29).view("<u4")).all())   # (sign bit set, NaN and Inf are all larger as unsigned words)
+
+
+def _main_power(a) -> int:
+    dt = IQ_DTYPES[a.t]
+    b = np.fromfile(a.src, dtype=np.uint8)
+    cut = b.size % (2 * dt.itemsize)
+    if cut:
+        sys.stderr.write(f"{a.src}: {cut} trailing bytes (a partial sample) ignored\n")
+    pw = iq_power(b[: b.size - cut].view(dt), a.t)
+    assert power_domain_ok(pw)                                       # (|I|, |Q| <= 2048: a power sample is at most 2^23)
+    pw.astype("<f4").tofile(a.dst)
+    return 0
+
+
 def _main_iq(a) -> int:
     dt = IQ_DTYPES[FLOAT32_IQ] if a.back else IQ_DTYPES[INT16_IQ]
     b = np.fromfile(a.src, dtype=np.uint8)
@@ -146,12 +173,19 @@ def _main_iq(a) -> int:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m adsbdec_amd.sample_formats", description=__doc__.split("\n\n")[0])
-    ap.add_argument("-t", type=int, choices=sorted(DTYPES) + [FLOAT32_IQ], required=True,
-                    help="1 = FLOAT32_REAL, 3 = INT16_REAL (as airspy_rx -t); 0 = between INT16_IQ and FLOAT32_IQ")
+    ap.add_argument("-t", type=int, choices=sorted(DTYPES) + [FLOAT32_IQ, INT16_IQ], required=True,
+                    help="1 = FLOAT32_REAL, 3 = INT16_REAL (as airspy_rx -t); 0 = between INT16_IQ and FLOAT32_IQ; with --power: 2 / 0, the format of src")
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--back", action="store_true", help="the format -> uint16 codes instead of uint16 codes -> the format")
+    ap.add_argument("--power", action="store_true", help="src is an IQ capture (-t 2 INT16_IQ, -t 0 FLOAT32_IQ): write its float32 power samples")
     a = ap.parse_args(argv)
+    if a.power:
+        if a.t not in IQ_DTYPES or a.back:
+            ap.error("--power takes -t 2 or -t 0 and no --back")
+        return _main_power(a)
+    if a.t == INT16_IQ:
+        ap.error("-t 2 goes with --power only (the converter between the IQ formats is -t 0)")
     if a.t == FLOAT32_IQ:
         return _main_iq(a)
     dt = DTYPES[a.t] if a.back else np.dtype("<u2")

@@ -1,14 +1,11 @@
 /* adsbdec_amd.h -- C-ABI of libadsbdec_amd.so: the MI355X (gfx950) drop-in for the offline "-f" demodulation path of TLeconte/adsbdec.
  * Everything a drop-in host and a multi-GPU host call; the primitives underneath and the test knobs are in adsbdec_amd_diag.h.  The
- * reference has no plugin/FFI interface: one prototype (adsbdec.h:5) plus extern C functions with file-scope state.  Each
- * entry point names the reference seam it stands behind (file:line); INTEGRATION.md shows the change in air.c / output.c that binds them.
+ * reference has no plugin/FFI interface: one prototype (adsbdec.h:5) plus extern C functions with file-scope state (SURVEY.md 8b).  Each entry point names the reference seam it stands behind (file:line); INTEGRATION.md shows the change in air.c / output.c that binds them.
  * Conventions follow the reference: int 0 / -1 with a message from adsb_last_error() (air.c:113-118 prints to stderr); one producer thread
- * per handle (decodeiq is not re-entrant: air.c:33-34,49-50, demod.c:86); plain pointers and sizes.  HIP is the only implementation: no
- * CPU fallback; adsb_create() fails loudly when no gfx950 device is usable.
+ * per handle (decodeiq is not re-entrant: air.c:33-34,49-50, demod.c:86); plain pointers and sizes.  HIP is the only implementation: no CPU fallback; adsb_create() fails loudly when no gfx950 device is usable.
  * Input domain.  uint16 samples carrying the Airspy's 12-bit ADC code centred on 2048 (air.c:64).  Bit-identical to the reference for every
  * code in [0, 4095] and up to |x-2048| <= ~23 000; beyond, the reference's `int p1 = float + float` (demod.c:102-105) overflows while this
- * library compares un-wrapped values: accepted, no parity claimed.  Streams end below 2^32 samples (the reference's `fidx` wraps
- * there, SURVEY Q13: a push that would reach it fails) unless adsb_set_long_stream is on: any length, decoded as the reference does. */
+ * library compares un-wrapped values: accepted, no parity claimed (SURVEY Q1).  Streams end below 2^32 samples (the reference's `fidx` wraps there, SURVEY Q13: a push that would reach it fails) unless adsb_set_long_stream is on: any length, decoded as the reference does (DESIGN.md). */
 #ifndef ADSBDEC_AMD_H
 #define ADSBDEC_AMD_H
 #include <stddef.h>
@@ -109,26 +106,22 @@ long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *
  *   s0 = w0 >> 20,  s1 = (w0 >> 8) & 0xfff,  s2 = (w0 & 0xff) << 4 | w1 >> 28,  s3 = (w1 >> 16) & 0xfff,  s4 = (w1 >> 4) & 0xfff,
  *   s5 = (w1 & 0xf) << 8 | w2 >> 24,  s6 = (w2 >> 12) & 0xfff,  s7 = w2 & 0xfff.
  * n counts SAMPLES: n % 8 == 0, ADSB_PACKED12_BYTES(n) bytes are read, at a stream position that is a multiple of 8 (uint16 and packed pushes mix
- * there); device pointers 4-byte aligned.  Otherwise -1, handle unchanged.  Frames, ts, Try/Ok, counters and contracts: the uint16 calls'.  Extra device
- * memory the handle keeps (grown on demand): host pushes, two landing buffers of 1.5 B x stage_samples; device pushes, a scratch of 2 B x n. */
+ * there); device pointers 4-byte aligned.  Otherwise -1, handle unchanged.  Frames, ts, Try/Ok, counters and contracts: the uint16 calls'.  Extra device memory the handle keeps (grown on demand): host pushes, two landing buffers of 1.5 B x stage_samples; device pushes, a scratch of 2 B x n. */
 #define ADSB_PACKED12_BYTES(n) ((n) / 8 * 12)
 int adsb_push_packed(adsb_decoder *d, const void *packed, size_t n); int adsb_push_packed_async(adsb_decoder *d, const void *packed, size_t n);
 int adsb_push_device_packed(adsb_decoder *d, const void *device_packed, size_t n); int adsb_push_device_packed_final(adsb_decoder *d, const void *device_packed, size_t n);
 long adsb_decode_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_frame **frames);
 /* adsb_decode_batch_device / _host for packed captures (n[i] counts samples): results, first / stats and the handle's state as theirs, capture i
- * decoded as its unpacked twin alone.  Refused by capture index, handle unchanged: n[i] % 8 != 0, a _device pointer not 4-byte aligned, NULL with
- * n[i] > 0, n[i] >= 2^32.  Extra device memory: a scratch of 2 B x sum n (captures at 128-byte boundaries), ONE launch; _host: + 1.5 B x sum n. */
+ * decoded as its unpacked twin alone.  Refused by capture index, handle unchanged: n[i] % 8 != 0, a _device pointer not 4-byte aligned, NULL with n[i] > 0, n[i] >= 2^32.  Extra device memory: a scratch of 2 B x sum n (captures at 128-byte boundaries), ONE launch; _host: + 1.5 B x sum n. */
 long adsb_decode_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n,
                                      const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const void *const *packed, const size_t *n,
                                    const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 /* Other REAL sample formats, converted to the uint16 code on the GPU; fmt is the airspy_rx -t number (from the definitions below, not checked against
  * libairspy).  3 INT16_REAL: int16 x = (code - 2048) << 4; code = (x >> 4) + 2048; inexact iff x & 15.  1 FLOAT32_REAL: x = (code - 2048) / 2048;
- * r = rint(2048 x), code = r + 2048 clamped to [0, 4095] -- clamped: outside, +-Inf, NaN (-> 2048); else inexact iff (code - 2048) / 2048 is not x
- * (every denormal is, -0.0 is not).  4 UINT16_REAL, 5 RAW: the uint16 call of the same kind and its rules.  0, 2 (IQ: no raw twin), anything else: -1.
+ * r = rint(2048 x), code = r + 2048 clamped to [0, 4095] -- clamped: outside, +-Inf, NaN (-> 2048); else inexact iff (code - 2048) / 2048 is not x (every denormal is, -0.0 is not).  4 UINT16_REAL, 5 RAW: the uint16 call of the same kind and its rules.  0, 2 (IQ: no raw twin), anything else: -1.
  * Any n at any stream position, mixing with the other pushes; device pointers aligned to the element, else -1, handle unchanged.  Frames, ts, Try/Ok
- * and contracts: the uint16 calls'.  Extra device memory, kept as for packed input: host pushes, two landing buffers of (2 or 4) B x stage_samples;
- * device pushes and batches, the packed calls' scratch (2 B x n; ONE conversion launch per batch); _batch_host: + (2 or 4) B x sum n. */
+ * and contracts: the uint16 calls'.  Extra device memory, kept as for packed input: host pushes, two landing buffers of (2 or 4) B x stage_samples; device pushes and batches, the packed calls' scratch (2 B x n; ONE conversion launch per batch); _batch_host: + (2 or 4) B x sum n. */
 enum { ADSB_FMT_FLOAT32_REAL = 1, ADSB_FMT_INT16_REAL = 3, ADSB_FMT_UINT16_REAL = 4, ADSB_FMT_RAW = 5 }; size_t adsb_format_bytes(int fmt, size_t n); /* bytes of n samples (0: a format that is refused) */
 int adsb_push_as(adsb_decoder *d, int fmt, const void *samples, size_t n); int adsb_push_async_as(adsb_decoder *d, int fmt, const void *samples, size_t n);
 int adsb_push_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n); int adsb_push_device_final_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n);
@@ -144,11 +137,9 @@ int adsb_get_format_report(const adsb_decoder *d, adsb_format_report *out);
  * twin (the _as calls refuse 0 and 2), but they ARE where demod.c works: power sample a[m] = |sample m|^2, everything behind it the reference's code on that array.
  * INT16_IQ: little-endian int16 (I, Q); i = I / 16, q = Q / 16, a = fl(fl(i i) + fl(q q)), binary32, nothing fused.  The / 16 puts I, Q in ADC-code units like
  * (float)r - 2048: demod.c:102-105's int truncation acts at its granularity; pw and the Beast level are on a COMPARABLE scale, not a calibrated one (nobody here
- * has measured libairspy's filter gain).  FLOAT32_IQ: binary32 (I, Q), nominal [-1, 1); each scalar r = rint(32768 x), ties to even, clamped to [-32768, 32767]
- * (NaN -> 0, +-Inf clamped), then as INT16_IQ: 1/16 ADC LSB.  libairspy's float path need not sit on that grid: expect adsb_get_format_report's inexact (per
+ * has measured libairspy's filter gain).  FLOAT32_IQ: binary32 (I, Q), nominal [-1, 1); each scalar r = rint(32768 x), ties to even, clamped to [-32768, 32767] (NaN -> 0, +-Inf clamped), then as INT16_IQ: 1/16 ADC LSB.  libairspy's float path need not sit on that grid: expect adsb_get_format_report's inexact (per
  * scalar) to be non-zero for real -t 0 files.  Power samples enter in twos (air.c:94-99): a trailing odd sample at adsb_finish is never seen.  n counts COMPLEX
- * samples.  A stream's kind, real or IQ, is fixed by its first push with samples after adsb_create / adsb_reset; the other kind then returns -1.  Also refused,
- * handle unchanged: fmt not 0 / 2, NULL with n > 0, a device pointer not 4-byte aligned, a stream reaching 2^31 complex samples, an adsb_set_long_stream handle.
+ * samples.  A stream's kind, real or IQ, is fixed by its first push with samples after adsb_create / adsb_reset; the other kind then returns -1.  Also refused, handle unchanged: fmt not 0 / 2, NULL with n > 0, a device pointer not 4-byte aligned, a stream reaching 2^31 complex samples, an adsb_set_long_stream handle.
  * fmt 2 device pointers: in place when 16-byte aligned at a multiple of 4 complex samples, else staged; fmt 0: converted on the GPU (FLOAT32_REAL's buffers). */
 enum { ADSB_FMT_FLOAT32_IQ = 0, ADSB_FMT_INT16_IQ = 2 }; size_t adsb_iq_bytes(int fmt, size_t n); /* bytes of n complex samples: 8 n, 4 n; 0 for anything else */
 int adsb_push_iq(adsb_decoder *d, int fmt, const void *samples, size_t n); int adsb_push_iq_async(adsb_decoder *d, int fmt, const void *samples, size_t n);
@@ -158,12 +149,23 @@ long adsb_decode_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, co
                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
                                const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
+/* float32 POWER samples at 10 MS/s: a[0:n] IS the reference's ampbuff stream (adsbdec.h:5 deqframe(const float *ampbuff, const int len)), from any front end -- another SDR, a filter of
+ * the caller's, a tensor computed in HBM.  Decoded exactly as the _iq calls decode a[] behind their squaring step: samples enter in twos (air.c:94-99), a trailing odd one at adsb_finish
+ * is never seen, the EOF horizon is the reference's with M = n - (n & 1); pw = ((int)(a[g] + a[g+10]) + (int)(a[g+35] + a[g+45])) / 4 (demod.c:102-105,127,133); a sample outside the
+ * buffer reads as +0.  INPUT DOMAIN: every sample finite, sign bit clear, below 2^29 (no negatives, -0.0, NaN, Inf) -- every sum the reference converts to int, and p1 + p2, then stays
+ * below 2^31; subnormals are inside (kept, not flushed).  Outside it the reference itself is undefined behaviour: no guarantee here, nothing detected or counted.  n counts power samples.
+ * A third stream kind beside real and IQ (fixed by the first push with samples; another kind then returns -1).  Also refused, handle unchanged: NULL with n > 0, a device pointer not
+ * 4-byte aligned, a stream reaching 2^31 power samples, an adsb_set_long_stream handle.  Device pointers: in place when 16-byte aligned at a multiple of 4 samples, else staged. */
+int adsb_push_power(adsb_decoder *d, const float *samples, size_t n); int adsb_push_power_async(adsb_decoder *d, const float *samples, size_t n);
+int adsb_push_device_power(adsb_decoder *d, const void *device_samples, size_t n); int adsb_push_device_power_final(adsb_decoder *d, const void *device_samples, size_t n);
+long adsb_decode_device_power(adsb_decoder *d, const void *device_samples, size_t n, const adsb_frame **frames);
+long adsb_decode_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
+long adsb_decode_batch_host_power(adsb_decoder *d, size_t n_captures, const float *const *samples, const size_t *n, const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 /* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
  * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. */
 int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
 int adsb_finish(adsb_decoder *d); /* end of input (EOF, air.c:241-244): the remaining offsets and the end-of-file horizon (SURVEY Q10) */
-/* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.  adsb_host_alloc_on binds the
- * memory to the NUMA node of `device` (best effort).  adsb_host_register page-locks memory the caller already owns.  0 / -1. */
+/* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.  adsb_host_alloc_on binds the memory to the NUMA node of `device` (best effort).  adsb_host_register page-locks memory the caller already owns.  0 / -1. */
 void *adsb_host_alloc(size_t bytes); void *adsb_host_alloc_on(size_t bytes, int device);
 void adsb_host_free(void *p); int adsb_host_register(void *p, size_t bytes); int adsb_host_unregister(void *p);
 /* Frame egress: what the reference hands to netout() (output.c:159), in its order.  adsb_drain copies (returns the number, <= cap, or -1);
@@ -204,8 +206,7 @@ typedef struct adsb_multi_info { /* of the last adsb_multi_decode_* call */
 adsb_multi *adsb_multi_create(const adsb_config *cfg, int n_devices, const int *devices);
 void adsb_multi_destroy(adsb_multi *m); int adsb_multi_devices(const adsb_multi *m);
 /* configs[4]: ONE capture, time-sharded over as many devices as it is worth (>= 128 Ki offsets per shard); each worker feeds its halo'd slice in
- * 32 MiB pieces and resolves its shard while its kernels run; the calling thread stitches and the workers gather.  Returns the number of frames, in
- * the reference's order, *frames valid until the next call on m; -1 on failure (after a worker was given up -- adsb_multi_last_error says so -- the
+ * 32 MiB pieces and resolves its shard while its kernels run; the calling thread stitches and the workers gather.  Returns the number of frames, in the reference's order, *frames valid until the next call on m; -1 on failure (after a worker was given up -- adsb_multi_last_error says so -- the
  * handle only answers -1, and that call's SOURCE buffers must stay alive).  _host: the capture lies in host memory (page-lock it); _file: every worker
  * reads its own slice of a regular file; _device: slice i is resident in the HBM of worker i's device and holds the samples adsb_multi_plan says. */
 long adsb_multi_decode_host(adsb_multi *m, const uint16_t *samples, size_t n, const adsb_frame **frames); long adsb_multi_decode_file(adsb_multi *m, const char *path, const adsb_frame **frames);

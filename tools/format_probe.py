@@ -4,6 +4,7 @@ comparison interleaved.
 
     python tools/format_probe.py [--reps 20] [--out profiles/r11_formats.txt]
     python tools/format_probe.py --iq [--reps 20] [--out profiles/r14_iq.txt]      # complex captures: see iq_probe()
+    python tools/format_probe.py --power [--reps 20] [--out profiles/r15_power.txt] [--ab parent=path/to/libadsbdec_amd.so]   # power_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
     (with counters, and without: a kernel that does not classify its samples at all) and adsb_unpack_packed12 at the same n
@@ -269,15 +270,140 @@ def iq_probe(L, reps, lines):
         d.close()
 
 
+def power_probe(L, reps, lines):
+    """float32 power samples (the _power calls), every comparison interleaved in this one process:
+    (a) the scan kernel's own time (cfg.profile: adsb_profile.big_ms / big_launches) and the call's wall time of
+        adsb_decode_device_power on 128 Mi power samples against adsb_decode_device_iq (fmt 2) on the int16 capture those samples
+        are iq_power of -- 512 MiB each, the same frames;
+    (b) one adsb_decode_batch_device_power of 256 captures of 512 Ki power samples against the loop of 256 single calls."""
+    from tools.gen_signal import make_iq_workload
+    NC = 1 << 27
+    block, truth = make_iq_workload(1 << 22, seed=1)
+    iq = torch.from_numpy(block.reshape(-1)).cuda().repeat(NC >> 22)
+    s = iq.view(-1, 2).to(torch.float32) * 0.0625
+    ii, qq = s[:, 0] * s[:, 0], s[:, 1] * s[:, 1]          # (one rounded operation per line: sample_formats.iq_power)
+    pw = (ii + qq).contiguous()
+    del s, ii, qq
+    torch.cuda.synchronize()
+    from adsbdec_amd.sample_formats import iq_power
+    assert torch.equal(pw[: 1 << 22].cpu(), torch.from_numpy(iq_power(block))), "torch's power samples are not iq_power's"
+    d_iq, d_pw = (capi.Decoder(df18=False, profile=True) for _ in range(2))
+    out = C.POINTER(capi.Frame)()
+
+    def kernel_ms(d):
+        p = d.profile()
+        return p["big_ms"], p["big_launches"]
+
+    sides = {
+        "IQ     adsb_decode_device_iq 2   128 Mi complex int16": (d_iq, lambda: L.adsb_decode_device_iq(d_iq._h, 2, iq.data_ptr(), NC, C.byref(out))),
+        "power  adsb_decode_device_power  128 Mi float32 power": (d_pw, lambda: L.adsb_decode_device_power(d_pw._h, pw.data_ptr(), NC, C.byref(out))),
+    }
+    frames = {}
+    for name, (d, fn) in sides.items():
+        for _ in range(3):
+            frames[name] = fn()
+        assert frames[name] > 0, (name, L.adsb_last_error(d._h))
+    names = list(sides)
+    assert frames[names[0]] == frames[names[1]], frames
+    kms, wall = {k: [] for k in sides}, {k: [] for k in sides}
+    steps = 5
+    for r in range(reps):
+        order = names[r % 2:] + names[:r % 2]
+        for name in order:
+            d, fn = sides[name]
+            m0, l0 = kernel_ms(d)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+            m1, l1 = kernel_ms(d)
+            kms[name].append((m1 - m0) / max(1, l1 - l0))
+    lines += ["# (a) scan kernel on its own clock (cfg.profile, ms per launch) and the call's wall time; 512 MiB on both sides, the power samples",
+              f"#     iq_power of the int16 capture; {reps} rounds x {steps} calls per side, the sides in rotation; medians (quartiles)",
+              "#   side                                                    frames   kernel ms (q1 .. q3)            call ms   kernel / IQ (median of rounds)   call / IQ"]
+    base, wbase = kms[names[0]], wall[names[0]]
+    for name in names:
+        q = statistics.quantiles(kms[name], n=4)
+        ratio = med([a / b for a, b in zip(kms[name], base)])
+        wratio = med([a / b for a, b in zip(wall[name], wbase)])
+        lines.append(f"    {name:55s} {frames[name]:7d}   {med(kms[name]):.5f} ({q[0]:.5f} .. {q[2]:.5f})   {med(wall[name]):8.4f}   {ratio:.4f}   {wratio:.4f}")
+        print(lines[-1], flush=True)
+
+    B, n = 256, 1 << 19
+    nn = (C.c_size_t * B)(*([n] * B))
+    first = (C.c_uint64 * (B + 1))()
+    d_batch, d_loop = capi.Decoder(df18=False), capi.Decoder(df18=False)
+    ptrs = [pw.data_ptr() + 4 * n * i for i in range(B)]
+    p = (C.c_void_p * B)(*ptrs)
+
+    def batch():
+        t0 = time.perf_counter()
+        k = L.adsb_decode_batch_device_power(d_batch._h, B, p, nn, C.byref(out), first, None)
+        dt = time.perf_counter() - t0
+        assert k >= 0, L.adsb_last_error(d_batch._h)
+        return dt, [int(first[i + 1] - first[i]) for i in range(B)]
+
+    def loop():
+        per = []
+        t0 = time.perf_counter()
+        for i in range(B):
+            per.append(L.adsb_decode_device_power(d_loop._h, ptrs[i], n, d_loop._out_ref))
+        return time.perf_counter() - t0, per
+
+    (_, fb), (_, fl) = batch(), loop()
+    assert fb == fl, "frames per capture differ"
+    tb, tl = [], []
+    for _ in range(reps):
+        tb.append(batch()[0])
+        tl.append(loop()[0])
+    lines += ["#", "# (b) one adsb_decode_batch_device_power of 256 captures of 512 Ki power samples (slices of the same buffer) against the loop of",
+              "#     256 adsb_decode_device_power calls; frames per capture equal; wall time, medians",
+              "#   batch ms    loop ms   loop/batch   frames",
+              f"    {med(tb) * 1e3:9.3f}  {med(tl) * 1e3:9.3f}  {med(tl) / med(tb):10.2f}  {sum(fb):7d}"]
+    print(lines[-1], flush=True)
+    for d in (d_iq, d_pw, d_batch, d_loop):
+        d.close()
+    del iq, pw
+    torch.cuda.empty_cache()
+
+
+def real_kernel_ab(builds, rounds, lines):
+    """(c) the existing real-sample kernel across the change: tools/ab_interleaved.py in a process of its own (it dlopens every build
+    side by side), the first build listed twice for the A/A."""
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "tools", "ab_interleaved.py"), "--rounds", str(rounds), "--steps", "10"] + builds
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
+    if r.returncode != 0:
+        raise SystemExit(f"ab_interleaved.py failed:\n{r.stdout}\n{r.stderr}")
+    lines += ["#", "# (c) the existing real-sample kernel (scan_kernel.hip, adsb_decode_device on the sparse 256 Mi-sample workload) across the change:",
+              "#     tools/ab_interleaved.py " + " ".join(cmd[2:6]) + " parent=<--ab> parent2=<--ab> tree=<this tree's library>", "#     parent = the library of the parent commit, parent2 = the same file again (the A/A), tree = this tree"]
+    lines += ["    " + ln for ln in r.stdout.splitlines()]
+    print(r.stdout, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--iq", action="store_true", help="complex captures (the _iq calls) instead: profiles/r14_iq.txt")
+    ap.add_argument("--power", action="store_true", help="float32 power samples (the _power calls) instead: profiles/r15_power.txt")
+    ap.add_argument("--ab", default=None, metavar="PARENT_LIB", help="with --power: the parent commit's libadsbdec_amd.so, for the A/B of the real kernel")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "r14_iq.txt" if a.iq else "r11_formats.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r15_power.txt" if a.power else "r14_iq.txt" if a.iq else "r11_formats.txt")
     torch.cuda.set_device(0)
     L = capi.load()
+    if a.power:
+        lines = ["# tools/format_probe.py --power: float32 power samples (scan_power_kernel.hip, the _power calls) beside the IQ kernel, one process,",
+                 f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
+                 "# The IQ capture is one 4 Mi-sample block of tools/gen_signal.py make_iq_workload (seed 1) repeated 32 times.", "#"]
+        power_probe(L, a.reps, lines)
+        if a.ab:
+            real_kernel_ab([f"parent={a.ab}", f"parent2={a.ab}", f"tree={capi.LIB_PATH}"], 2 * a.reps, lines)
+        else:
+            lines += ["#", "# (c) not measured in this run: no --ab parent library given"]
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.iq:
         lines = ["# tools/format_probe.py --iq: complex captures (scan_iq_kernel.hip, the _iq calls) beside the real-sample kernel, one process,",
                  f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
