@@ -19,10 +19,11 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libadsbdec_amd.so")
 CLI = os.path.join(LIBDIR, "adsbdec_amd_cli")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+ROCM = os.environ.get("ROCM", "/opt/rocm")  # the HIP runtime's headers and library for the host program, as the Makefile's ROCM
 
 HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip", "scan_power_kernel.hip", "seam_kernel.hip", "decoder.hip", "decoder_collect.hip",
                "decoder_lifecycle.hip", "decoder_batch.hip", "decoder_shard.hip", "unpack12.hip", "unpack12_batch.hip",
-               "convert_samples.hip"]
+               "convert_samples.hip", "power_export_kernel.hip", "decoder_export.hip"]
 C_SOURCES = ["format.c"]
 # host-only C++ (no HIP): the multi-GPU driver over the C-ABI, and the part of the C-ABI that needs no device
 CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]
@@ -106,8 +107,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
     sink_src = os.path.join(CSRC, "cli", "sink.c")
     if os.path.exists(cli_src) and (force or _newer(CLI, [cli_src, sink_src, os.path.join(CSRC, "cli", "sink.h"), LIB,
                                                            os.path.join(ROOT, "include", "adsbdec_amd.h")])):
-        _run(["gcc", "-O2", "-Wall", "-o", CLI, cli_src, sink_src, "-I", os.path.join(ROOT, "include"),
-              "-L", LIBDIR, "-ladsbdec_amd", "-lpthread", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"])
+        # (the HIP runtime's C API: the device buffer of the program's own that -W -q exports through)
+        _run(["gcc", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__", "-o", CLI, cli_src, sink_src, "-I", os.path.join(ROOT, "include"),
+              "-I", os.path.join(ROCM, "include"), "-L", LIBDIR, "-ladsbdec_amd", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-lpthread",
+              "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ROCM, "lib")])
     return LIB
 
 

@@ -202,6 +202,12 @@ SYMBOLS = {
                                                   C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     "adsb_decode_batch_host_power": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                 C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    "adsb_power_window": (C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t]),
+    "adsb_power_window_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t]),
+    "adsb_power_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "adsb_power_device_as": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "adsb_power_device_packed": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "adsb_power_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -854,6 +860,43 @@ class Decoder:
         if self._L.adsb_decode_batch_host_power(self._h, k, p, n, self._out_ref, first, st) < 0:
             self._check(-1, "adsb_decode_batch_host_power")
         return self._batch_result(self._out, first, st, k, stats)
+
+    # ---- the export calls (include/adsbdec_amd.h: adsb_power_*): the front end's float32 power samples into an array of the caller's
+    def _power_call(self, name, *args):
+        k = getattr(self._L, name)(self._h, *args)
+        if k < 0:
+            self._check(-1, name)
+        return int(k)
+
+    def power_window(self, ptr: int, first_sample: int, n: int, m_begin: int, m_end: int, out_ptr: int, cap: int) -> int:
+        """adsb_power_window: the uint16 samples [first_sample, first_sample + n) in HBM -> power samples [m_begin, m_end) at out_ptr."""
+        return self._power_call("adsb_power_window", ptr, first_sample, n, m_begin, m_end, out_ptr, cap)
+
+    def power_window_host(self, x: np.ndarray, first_sample: int, m_begin: int, m_end: int) -> np.ndarray:
+        """adsb_power_window_host: x holds the stream's samples from first_sample on -> float32 array of power samples [m_begin, m_end)."""
+        x = np.ascontiguousarray(x, dtype=np.uint16)
+        out = np.empty(max(0, m_end - m_begin), dtype=np.float32)
+        k = self._power_call("adsb_power_window_host", x.ctypes.data, first_sample, x.size, m_begin, m_end, out.ctypes.data, out.size)
+        return out[:k]
+
+    def power_device(self, ptr: int, n: int, out_ptr: int, cap: int) -> int:
+        """adsb_power_device: a capture of n uint16 samples in HBM as a fresh stream -> its 2 (n // 4) power samples at out_ptr."""
+        return self._power_call("adsb_power_device", ptr, n, out_ptr, cap)
+
+    def power_device_as(self, fmt: int, ptr: int, n: int, out_ptr: int, cap: int) -> int:
+        return self._power_call("adsb_power_device_as", fmt, ptr, n, out_ptr, cap)
+
+    def power_device_packed(self, ptr: int, n: int, out_ptr: int, cap: int) -> int:
+        return self._power_call("adsb_power_device_packed", ptr, n, out_ptr, cap)
+
+    def power_device_iq(self, fmt: int, ptr: int, n: int, out_ptr: int, cap: int) -> int:
+        """adsb_power_device_iq: n complex samples in HBM -> n power samples at out_ptr."""
+        return self._power_call("adsb_power_device_iq", fmt, ptr, n, out_ptr, cap)
+
+    def power(self, x: np.ndarray) -> np.ndarray:
+        """The power samples of a capture in host memory: power_window_host from the stream's start, 2 (n // 4) floats."""
+        x = np.ascontiguousarray(x, dtype=np.uint16).reshape(-1)
+        return self.power_window_host(x, 0, 0, 2 * (x.size // 4))
 
     def format_report(self):
         """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""

@@ -28,6 +28,14 @@
  *                   clear, below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); outside it nothing is promised or detected.
  *                   Trailing bytes that do not make a sample are not decoded and stderr says how many.  Not with -t, -q, -p, -G or
  *                   -B; a file below 2^31 samples.
+ *     -W out.pw     EXTENSION: EXPORT instead of decoding: write the float32 power samples of the file of -f -- the reference's ampbuff
+ *                   (air.c:54-91), what -w reads -- to out.pw, little-endian, and print nothing.  A uint16 file is read in pieces of about
+ *                   4 Mi samples, each with 16 samples of overlap in front, through adsb_power_window_host: bounded memory, any length
+ *                   below 2^32 samples; a trailing n % 4 samples give no output.  With -q 2 | 0 the file is IQ: one power sample per
+ *                   complex sample, pieces without overlap through a device buffer of this program's and adsb_power_device_iq: any
+ *                   length.  out.pw is created once the GPU is open; a signal between two pieces ends the program with status 1 and a
+ *                   message (out.pw then holds the pieces so far).  Not with -w, -t (python -m adsbdec_amd.sample_formats converts
+ *                   such files), -p, -G, -B, -s, -l or several -f.
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -65,6 +73,8 @@
 #include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
+
+#include <hip/hip_runtime_api.h> /* -W -q: a device buffer of this program's own (three calls) */
 
 #include "adsbdec_amd.h"
 #include "sink.h"
@@ -172,7 +182,8 @@ static void usage(void)
 {
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
     printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-q type] [-w] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
-    printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n\n");
+    printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n");
+    printf("        adsbdec_amd_cli [-q type] [-d gpu] -W out.pw -f filename\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
     printf("\t-b : output binary beast format\n");
@@ -187,6 +198,8 @@ static void usage(void)
     printf("\t     default), 0 float32 IQ (quantised to the int16 grid on the GPU); not with -t, -p, -G or -B\n");
     printf("\t-w : (extension) the file holds float32 POWER samples at 10 MS/s (little-endian), the demodulator's own input; every sample finite,\n");
     printf("\t     sign bit clear and below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); not with -t, -q, -p, -G or -B\n");
+    printf("\t-W out.pw : (extension) export, do not decode: write the float32 power samples of the file (what -w reads) to out.pw; with -q the\n");
+    printf("\t     file is IQ (any length; a real file: below 2^32 samples); not with -w, -t, -p, -G, -B, -s, -l or several -f\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
@@ -498,9 +511,128 @@ static int run_batch_list(const adsb_config *cfg, int *devs, int ndev, char **pa
     _exit(rc); /* (no teardown: see the end of main) */
 }
 
+/* read() until `want` bytes are in or the file ends */
+static size_t read_full(int fd, void *buf, size_t want)
+{
+    size_t got = 0;
+    while (got < want) {
+        const ssize_t k = read(fd, (char *)buf + got, want - got);
+        if (k <= 0)
+            break;
+        got += (size_t)k;
+    }
+    return got;
+}
+
+/* -W: the file's power samples into `outpath`; nothing is decoded.  A piece of a uint16 file is EXPORT_PIECE power samples (a
+ * multiple of 28: about 4 Mi samples) behind the last 16 samples of the piece before it; an IQ piece is EXPORT_PIECE complex samples. */
+#define EXPORT_PIECE ((uint64_t)28 * 74898)
+#define EXPORT_OVERLAP 16
+static int run_export(const char *filename, const char *outpath, int device, int iq, int qtype)
+{
+    const int fd = open(filename, O_RDONLY);
+    if (fd < 0) {
+        fprintf(stderr, "%s: cannot read: %s\n", filename, strerror(errno));
+        return 255;
+    }
+    adsb_config cfg;
+    adsb_config_default(&cfg);
+    cfg.device = device;
+    adsb_decoder *dec = adsb_create(&cfg);
+    if (!dec) {
+        fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
+        return 255;
+    }
+    FILE *out = fopen(outpath, "wb"); /* (behind adsb_create: no empty file is left where no GPU is) */
+    if (!out) {
+        fprintf(stderr, "%s: cannot write: %s\n", outpath, strerror(errno));
+        return 255;
+    }
+    int rc = 0;
+    float *pw = (float *)malloc(EXPORT_PIECE * sizeof(float));
+    if (!iq) {
+        uint16_t *buf = (uint16_t *)malloc((EXPORT_OVERLAP + 2 * EXPORT_PIECE) * sizeof(uint16_t));
+        if (!buf || !pw) {
+            fprintf(stderr, "out of memory for the export buffers\n");
+            return 255;
+        }
+        for (uint64_t k = 0; rc == 0 && !stop_requested; k++) {
+            const size_t bytes = read_full(fd, buf + EXPORT_OVERLAP, 2 * EXPORT_PIECE * sizeof(uint16_t));
+            const size_t have = bytes / 2; /* (a trailing odd byte is dropped, as decodeiq(iqbuff, n / 2) drops it, air.c:239) */
+            const size_t lead = k ? EXPORT_OVERLAP : 0;
+            const uint64_t m_begin = k * EXPORT_PIECE, m_end = m_begin + 2 * (have / 4);
+            const long got = adsb_power_window_host(dec, buf + EXPORT_OVERLAP - lead, 2 * m_begin - lead, have + lead, m_begin, m_end, pw, EXPORT_PIECE);
+            if (got < 0) {
+                fprintf(stderr, "adsb_power_window_host() failed: %s\n", adsb_last_error(dec));
+                rc = 255;
+            } else if (fwrite(pw, sizeof(float), (size_t)got, out) != (size_t)got) {
+                fprintf(stderr, "%s: cannot write\n", outpath);
+                rc = 1;
+            }
+            if (have < 2 * EXPORT_PIECE) {
+                if (rc == 0 && (have % 4 || bytes % 2))
+                    fprintf(stderr, "%zu trailing bytes ignored (the reference reads four samples at a time)\n", (have % 4) * 2 + bytes % 2);
+                break;
+            }
+            memcpy(buf, buf + 2 * EXPORT_PIECE, EXPORT_OVERLAP * sizeof(uint16_t)); /* the next piece's overlap */
+        }
+    } else {
+        const size_t elem = adsb_iq_bytes(qtype, 1);
+        void *buf = malloc(EXPORT_PIECE * elem), *d_in = NULL, *d_out = NULL;
+        if (!buf || !pw) {
+            fprintf(stderr, "out of memory for the export buffers\n");
+            return 255;
+        }
+        if (hipSetDevice(device < 0 ? 0 : device) != hipSuccess || hipMalloc(&d_in, EXPORT_PIECE * elem) != hipSuccess ||
+            hipMalloc(&d_out, EXPORT_PIECE * sizeof(float)) != hipSuccess) {
+            fprintf(stderr, "cannot allocate the device buffers of the export\n");
+            return 255;
+        }
+        while (rc == 0 && !stop_requested) { /* (every piece a call of its own, no stream position: any length) */
+            const size_t bytes = read_full(fd, buf, EXPORT_PIECE * elem);
+            const size_t have = bytes / elem;
+            long got = 0;
+            if (have && hipMemcpy(d_in, buf, have * elem, hipMemcpyHostToDevice) != hipSuccess) {
+                fprintf(stderr, "copying a piece to the device failed\n");
+                rc = 255;
+            } else if (have && (got = adsb_power_device_iq(dec, qtype, d_in, have, (float *)d_out, EXPORT_PIECE)) < 0) {
+                fprintf(stderr, "adsb_power_device_iq() failed: %s\n", adsb_last_error(dec));
+                rc = 255;
+            } else if (got && hipMemcpy(pw, d_out, (size_t)got * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+                fprintf(stderr, "copying a piece from the device failed\n");
+                rc = 255;
+            } else if (fwrite(pw, sizeof(float), (size_t)got, out) != (size_t)got) {
+                fprintf(stderr, "%s: cannot write\n", outpath);
+                rc = 1;
+            }
+            if (bytes < EXPORT_PIECE * elem) {
+                if (rc == 0 && bytes % elem)
+                    fprintf(stderr, "%zu trailing bytes ignored (not a whole %zu-byte sample)\n", bytes % elem, elem);
+                break;
+            }
+        }
+        adsb_format_report rep;
+        if (rc == 0 && qtype == ADSB_FMT_FLOAT32_IQ && adsb_get_format_report(dec, &rep) == 0 && rep.inexact + rep.clamped > 0)
+            fprintf(stderr, "%llu of %llu float scalars were rounded to the int16 grid (%llu clamped): expected of a float32 IQ capture\n",
+                    (unsigned long long)(rep.inexact + rep.clamped), (unsigned long long)rep.converted, (unsigned long long)rep.clamped);
+    }
+    if (fclose(out) != 0 && rc == 0) {
+        fprintf(stderr, "%s: cannot write\n", outpath);
+        rc = 1;
+    }
+    if (stop_requested && rc == 0) { /* (a signal ended the loop between two pieces) */
+        fprintf(stderr, "%s: interrupted: the file holds the pieces written so far, not the whole export\n", outpath);
+        rc = 1;
+    }
+    fflush(stderr);
+    if (getenv("ADSB_CLI_CLEAN_EXIT"))
+        exit(rc);
+    _exit(rc); /* (no teardown: see the end of main) */
+}
+
 int main(int argc, char **argv)
 {
-    const char *filename = NULL, *listfile = NULL;
+    const char *filename = NULL, *listfile = NULL, *export_path = NULL;
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
     int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, c;
@@ -511,7 +643,7 @@ int main(int argc, char **argv)
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -569,6 +701,9 @@ int main(int argc, char **argv)
         case 'w':
             power = 1;
             break;
+        case 'W':
+            export_path = optarg;
+            break;
         case 't': {
             char *end;
             stype = strtol(optarg, &end, 10);
@@ -589,6 +724,18 @@ int main(int argc, char **argv)
             usage();
             return 1;
         }
+    }
+    if (export_path && (power || stype_arg || packed || ndev || listfile || outmode != SINK_STDOUT || nfiles > 1)) {
+        /* -W writes power samples and decodes nothing: refused before any GPU call */
+        fprintf(stderr, "-W is not supported with %s: %s\n",
+                power ? "-w" : stype_arg ? "-t" : packed ? "-p" : ndev ? "-G" : listfile ? "-B" : outmode == SINK_CONNECT ? "-s" : outmode == SINK_LISTEN ? "-l" : "several -f",
+                power                    ? "a file of power samples is already what -W writes"
+                : stype_arg              ? "the export reads uint16 codes (or IQ samples with -q); python -m adsbdec_amd.sample_formats converts other real types"
+                : packed                 ? "the export reads uint16 codes (or IQ samples with -q); python -m adsbdec_amd.packed12 unpacks"
+                : ndev || listfile       ? "the export runs on one GPU (-d), one file at a time"
+                : outmode != SINK_STDOUT ? "power samples go to the file named, not to a peer"
+                                         : "the export writes one file");
+        return 1;
     }
     const int converted = stype == ADSB_FMT_FLOAT32_REAL || stype == ADSB_FMT_INT16_REAL;
     if (stype_arg && !converted && stype != ADSB_FMT_UINT16_REAL && stype != ADSB_FMT_RAW) {
@@ -651,6 +798,16 @@ int main(int argc, char **argv)
     if (!filename || (nfiles > 1 && (ndev == 0 || outmode != SINK_STDOUT)) || (ndev && device >= 0)) {
         usage();
         return 1;
+    }
+    if (export_path) {
+        install_signals();
+        if (device >= 0) {
+            restrict_visible_devices(&device, 1);
+        } else if (!getenv("ROCR_VISIBLE_DEVICES") && !getenv("HIP_VISIBLE_DEVICES") && !getenv("ADSB_CLI_ALL_DEVICES")) {
+            int first = 0;
+            restrict_visible_devices(&first, 1);
+        }
+        return run_export(filename, export_path, device, iq, (int)qtype);
     }
     if (packed && ndev) {
         fprintf(stderr, "-p (packed 12-bit input) is not supported with -G: the multi-GPU driver reads uint16 files only\n");

@@ -5,6 +5,7 @@
 //   decoder_lifecycle.hip  create, destroy, reset; the device, NUMA and pinned-memory helpers
 //   decoder_batch.hip      a batch of independent captures (adsb_decode_batch_*)
 //   decoder_shard.hip      the shard calls of the multi-GPU driver (adsb_scan_shard*, adsb_shard_begin / _end)
+//   decoder_export.hip     the export calls (adsb_power_*): the front end's power samples into an array of the caller's
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
 
@@ -299,7 +300,8 @@ struct adsb_decoder {
     std::vector<size_t> batch_unpacked_at;   // the last packed batch: every capture's first sample in batch_unpacked, then the end
     bool batch_stats_on = false; // the last call was a batch: adsb_get_stats answers batch_stats, the sum over its captures
     adsb_stats batch_stats{};
-    adsb::Buf<uint16_t> win_buf; // adsb_scan_shard_host: device copy of the caller's window
+    adsb::Buf<uint16_t> win_buf; // adsb_scan_shard_host, adsb_power_window_host: device copy of the caller's window
+    adsb::Buf<float> pow_buf;    // adsb_power_window_host: the window's power samples, copied back from here
 
     int fail(const char *fmt, ...)
     {

@@ -13,8 +13,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* Bumped when an entry point or struct member changes meaning or place; within one version adsb_config and adsb_profile grow at their END
- * only (adsb_create reads cfg->struct_size bytes).  5: adsb_config carries `abi` (any other value is refused); debug_* knobs: diag header. */
+/* Bumped when an entry point or struct member changes meaning or place; within one version adsb_config and adsb_profile grow at their END only. */
 #define ADSB_ABI_VERSION 5
 #define ADSB_PULSEW 5 /* constants of the path (adsbdec.h:1-3, air.c:32,47) */
 #define ADSB_DECOFFSET 1200
@@ -46,12 +45,9 @@ typedef struct adsb_config {
     void *stream;           /* hipStream_t to launch on; NULL = a stream owned by the handle                      */
     int32_t all_candidates; /* 1: the device reports EVERY CRC-valid offset; 0 (default): not those the greedy scan can never visit (same frames) */
     int32_t fix_1bit;       /* EXTENSION (SURVEY Q8), off by default: repair DF17/18 frames whose CRC residual is the syndrome of one bit in [5,112) */
-    int32_t push_overlap;   /* 1: adsb_push() returns once `samples` is COPIED to the device, the scan in flight; a call's frames become
-                               drainable during the NEXT push / finish / sync (same frames, same order).  0 (default): when the call returns */
-    int32_t host_threads;   /* Threads that consume the device's hand-off stream.  1: the calling thread alone, ALWAYS.  2: + a thread of the
-                               handle's own that reads large launches' stream; N >= 3 (<= 17): + N - 2 that decide batches of tiles ahead and
-                               write frames.  0 (default): 1, until a launch hands over a record per 2 048 offsets; then 6, or 2 below 12 CPUs
-                               (INTEGRATION.md).  adsb_profile.host_threads_running says what exists; same frames, order and counters always. */
+    int32_t push_overlap;   /* 1: adsb_push() returns once `samples` is COPIED, the scan in flight; its frames drain one call later (INTEGRATION.md) */
+    int32_t host_threads;   /* Threads that consume the hand-off stream.  1: the caller alone, ALWAYS.  2: + a reader thread; N >= 3 (<= 17): + N - 2 that
+                               decide tiles ahead.  0 (default): 1, then 6 (2 below 12 CPUs) under dense traffic (INTEGRATION.md).  Same frames always. */
     int32_t wait_timeout_s; /* no wait for the device lasts longer (0 = default, 120 s): then -1, adsb_last_error() names what was waited for */
     int32_t warm_start;     /* 1: adsb_create also pays the runtime's first-use costs of copying (7-9 ms each): for a one-shot process */
     const void *debug;      /* NULL, or an adsb_debug_config (adsbdec_amd_diag.h: test knobs); copied by adsb_create */
@@ -85,18 +81,15 @@ void adsb_destroy(adsb_decoder *d); int adsb_reset(adsb_decoder *d);
 /* Sample ingress; replaces `decodeiq(const unsigned short *r, const int len)` (air.c:54), called from fileInput (air.c:239) / rx_callback
  * (air.c:175).  `samples` is borrowed for the call.  Any n: the stream is the concatenation of all pushes (the reference needs n % 4 == 0). */
 int adsb_push(adsb_decoder *d, const uint16_t *samples, size_t n);
-/* The same from a double-buffered read loop: returns once copy and scan of this chunk are ENQUEUED, then collects the PREVIOUS chunk's frames.
- * `samples` stays borrowed until the next push / finish / sync returns; frames become drainable one call later, in order.  adsb_sync waits for all. */
+/* From a double-buffered read loop (INTEGRATION.md): returns once copy and scan are ENQUEUED; `samples` stays borrowed until the next push / finish / sync; adsb_sync waits for all. */
 int adsb_push_async(adsb_decoder *d, const uint16_t *samples, size_t n); int adsb_sync(adsb_decoder *d);
-/* Samples already resident in HBM (no reference counterpart).  A 16-byte aligned pointer at a stream position that is a
- * multiple of 8 samples is scanned in place.  _final = push of the LAST piece + adsb_finish in one pass. */
+/* Samples already in HBM: scanned in place when 16-byte aligned at a stream position that is a multiple of 8 samples.  _final = push of the LAST piece + adsb_finish. */
 int adsb_push_device(adsb_decoder *d, const void *device_samples, size_t n); int adsb_push_device_final(adsb_decoder *d, const void *device_samples, size_t n);
 /* `adsbdec -f` for ONE capture in HBM: adsb_reset + adsb_push_device_final + adsb_take.  The number of frames (*frames as adsb_take) or -1. */
 long adsb_decode_device(adsb_decoder *d, const void *device_samples, size_t n, const adsb_frame **frames);
-/* n_captures INDEPENDENT captures in as few launches as they fit, each decoded exactly as adsb_decode_device(d, p[i], n[i]) would
- * decode it alone (g and ts from 0).  Capture i's frames are (*frames)[first[i] .. first[i+1]) (first: n_captures + 1 entries), valid as
- * adsb_take's; stats: NULL, or n_captures tables (try_ with cfg.collect_stats).  Leaves the handle as adsb_decode_device does: reset, then
- * finished.  Returns all frames' number, or -1; refused with the handle unchanged: a _device pointer not 16-byte aligned, n[i] >= 2^32. */
+/* n_captures INDEPENDENT captures in as few launches as they fit, each decoded as adsb_decode_device(d, p[i], n[i]) would decode it alone, and
+ * the handle left as by that call.  Capture i's frames are (*frames)[first[i] .. first[i+1]) (first: n_captures + 1 entries), valid as adsb_take's;
+ * stats: NULL, or n_captures tables.  Returns all frames' number, or -1, handle unchanged: a _device pointer not 16-byte aligned, n[i] >= 2^32. */
 long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
                               const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n,
@@ -149,11 +142,10 @@ long adsb_decode_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, co
                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
                                const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
-/* float32 POWER samples at 10 MS/s: a[0:n] IS the reference's ampbuff stream (adsbdec.h:5 deqframe(const float *ampbuff, const int len)), from any front end -- another SDR, a filter of
- * the caller's, a tensor computed in HBM.  Decoded exactly as the _iq calls decode a[] behind their squaring step: samples enter in twos (air.c:94-99), a trailing odd one at adsb_finish
- * is never seen, the EOF horizon is the reference's with M = n - (n & 1); pw = ((int)(a[g] + a[g+10]) + (int)(a[g+35] + a[g+45])) / 4 (demod.c:102-105,127,133); a sample outside the
- * buffer reads as +0.  INPUT DOMAIN: every sample finite, sign bit clear, below 2^29 (no negatives, -0.0, NaN, Inf) -- every sum the reference converts to int, and p1 + p2, then stays
- * below 2^31; subnormals are inside (kept, not flushed).  Outside it the reference itself is undefined behaviour: no guarantee here, nothing detected or counted.  n counts power samples.
+/* float32 POWER samples at 10 MS/s: a[0:n] IS the reference's ampbuff stream (adsbdec.h:5 deqframe(const float *ampbuff, const int len)), from any front end.  Decoded exactly as
+ * the _iq calls decode a[] behind their squaring step: samples enter in twos (air.c:94-99), a trailing odd one at adsb_finish is never seen, the EOF horizon is the reference's with
+ * M = n - (n & 1); pw = ((int)(a[g] + a[g+10]) + (int)(a[g+35] + a[g+45])) / 4 (demod.c:102-105,127,133); a sample outside the buffer reads as +0.  INPUT DOMAIN: every sample finite,
+ * sign bit clear, below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are inside): the reference's int sums then stay below 2^31.  Outside it nothing is promised or detected.  n counts power samples.
  * A third stream kind beside real and IQ (fixed by the first push with samples; another kind then returns -1).  Also refused, handle unchanged: NULL with n > 0, a device pointer not
  * 4-byte aligned, a stream reaching 2^31 power samples, an adsb_set_long_stream handle.  Device pointers: in place when 16-byte aligned at a multiple of 4 samples, else staged. */
 int adsb_push_power(adsb_decoder *d, const float *samples, size_t n); int adsb_push_power_async(adsb_decoder *d, const float *samples, size_t n);
@@ -161,6 +153,20 @@ int adsb_push_device_power(adsb_decoder *d, const void *device_samples, size_t n
 long adsb_decode_device_power(adsb_decoder *d, const void *device_samples, size_t n, const adsb_frame **frames);
 long adsb_decode_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_decode_batch_host_power(adsb_decoder *d, size_t n_captures, const float *const *samples, const size_t *n, const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
+/* The way OUT at that boundary: the reference's ampbuff (air.c:54-91), bit for bit, in an array of the caller's.  adsb_power_window: the buffer holds uint16 samples
+ * [first_sample, first_sample + n) of a stream; power[i] = power sample m_begin + i.  RULES (one by one in INTEGRATION.md); one broken: -1, a message, nothing written.
+ *   1. first_sample % 8 == 0; device_samples and device_power 16-byte aligned; m_begin % 28 == 0; m_begin <= m_end; power_cap >= m_end - m_begin.
+ *   2. Every sample's OWN pair is held: 2 m_begin >= first_sample, 2 m_end <= first_sample + n.  The six OLDER pairs read as silence (0x800) if not held.
+ *   3. first_sample + n < 2^32, on adsb_set_long_stream handles too.  4. Returns m_end - m_begin, every float written; an empty window launches nothing.
+ *   5. The handle's stream and resolver stay untouched: callable between pushes.  6. _as and _iq (fmt 0) add to adsb_get_format_report.
+ * _host: through buffers the handle keeps.  adsb_power_device: the window (0, n, 0, 2 (n / 4)).  _as (fmt 1 | 3) / _packed: through the scratch of
+ * adsb_decode_device_as / _packed, shared with them.  _iq (fmt 2 | 0): n COMPLEX samples -> n power samples. */
+long adsb_power_window(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *device_power, size_t power_cap);
+long adsb_power_window_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *power, size_t power_cap);
+long adsb_power_device(adsb_decoder *d, const void *device_samples, size_t n, float *device_power, size_t power_cap);
+long adsb_power_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap);
+long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t n, float *device_power, size_t power_cap);
+long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap);
 /* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
  * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. */
 int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
@@ -173,20 +179,17 @@ void adsb_host_free(void *p); int adsb_host_register(void *p, size_t bytes); int
 long adsb_drain(adsb_decoder *d, adsb_frame *out, size_t cap); long adsb_take(adsb_decoder *d, const adsb_frame **frames); size_t adsb_pending(const adsb_decoder *d);
 /* print_stats() counters (valid.c:84-100); try_ needs collect_stats=1 (counted on the device, fetched by this call). */
 int adsb_get_stats(const adsb_decoder *d, adsb_stats *out);
-/* Fills the first `size` bytes of *out (the macro passes the caller's sizeof: adsb_profile grows at its end). */
-int adsb_get_profile_sized(const adsb_decoder *d, adsb_profile *out, size_t size);
+int adsb_get_profile_sized(const adsb_decoder *d, adsb_profile *out, size_t size); /* fills the first `size` bytes of *out: the macro passes the caller's sizeof */
 #define adsb_get_profile(d, out) adsb_get_profile_sized((d), (out), sizeof(adsb_profile))
 const char *adsb_last_error(const adsb_decoder *d); /* last error text of a handle, or of the last failed adsb_create() when d == NULL */
 /* formatpkt() (output.c:204-262, WITH_AIR).  outformat 0 = AVR "*hex;\n", 1 = AVR-MLAT "@ts48hex;\n", 2 = Beast; pkt holds 256 bytes.  The length. */
 int adsb_format_frame(const adsb_frame *f, int outformat, char *pkt);
-/* The CPUs local to HIP device `device` (local_cpulist, e.g. "0-63,128-191") and its NUMA node: the thread that feeds a handle polls memory the
- * device writes, 2.5-3 x slower from the far socket.  The string's length, 0 when the platform does not say, -1 on error / node or -1. */
+/* The CPUs local to HIP device `device` (local_cpulist, e.g. "0-63,128-191") and its NUMA node (INTEGRATION.md, Deployment note).  The string's length, 0 if unknown, -1 / node or -1. */
 int adsb_device_cpulist(int device, char *out, size_t cap); int adsb_device_numa_node(int device);
 /* Splits the offsets [0, power_samples - ADSB_WINDOW] of one stream over n_shards owners (SURVEY.md 8e).  Shard i owns [g_begin[i], g_end[i])
  * (g_begin % 28 == 0) and needs the samples [first_sample[i], + n_samples[i]): 2 408 of halo.  Returns the shards used (<= n_shards). */
 int adsb_plan_shards(uint64_t total_samples, int n_shards, uint64_t *g_begin, uint64_t *g_end, uint64_t *first_sample, uint64_t *n_samples);
-/* ---- ONE process, several GPUs (csrc/multi.cpp): the host of BASELINE configs[3] / configs[4].  A worker thread and a decoder handle per device; no
- * collective on the data path.  Stands where fileInput's loop (air.c:217-246) feeds decodeiq and netout (output.c:159-182) takes frames. */
+/* ---- ONE process, several GPUs (csrc/multi.cpp; INTEGRATION.md "One process, several GPUs"): a worker thread and a decoder handle per device. */
 typedef struct adsb_multi adsb_multi;
 typedef struct adsb_multi_info { /* of the last adsb_multi_decode_* call */
     int32_t shards;         /* shards the capture was cut into (streams decoded side by side, for the stream calls)  */
@@ -205,10 +208,9 @@ typedef struct adsb_multi_info { /* of the last adsb_multi_decode_* call */
  * on a one-GPU box).  cfg as for adsb_create (device and stream are ignored).  NULL on failure (adsb_multi_last_error(NULL)). */
 adsb_multi *adsb_multi_create(const adsb_config *cfg, int n_devices, const int *devices);
 void adsb_multi_destroy(adsb_multi *m); int adsb_multi_devices(const adsb_multi *m);
-/* configs[4]: ONE capture, time-sharded over as many devices as it is worth (>= 128 Ki offsets per shard); each worker feeds its halo'd slice in
- * 32 MiB pieces and resolves its shard while its kernels run; the calling thread stitches and the workers gather.  Returns the number of frames, in the reference's order, *frames valid until the next call on m; -1 on failure (after a worker was given up -- adsb_multi_last_error says so -- the
- * handle only answers -1, and that call's SOURCE buffers must stay alive).  _host: the capture lies in host memory (page-lock it); _file: every worker
- * reads its own slice of a regular file; _device: slice i is resident in the HBM of worker i's device and holds the samples adsb_multi_plan says. */
+/* ONE capture, time-sharded over as many devices as it is worth.  Returns the number of frames, in the reference's order, *frames valid until the
+ * next call on m; -1 on failure (after a worker was given up the handle only answers -1, and that call's SOURCE buffers must stay alive).  _host: host
+ * memory (page-lock it); _file: every worker reads its slice of a regular file; _device: slice i in worker i's HBM holds what adsb_multi_plan says. */
 long adsb_multi_decode_host(adsb_multi *m, const uint16_t *samples, size_t n, const adsb_frame **frames); long adsb_multi_decode_file(adsb_multi *m, const char *path, const adsb_frame **frames);
 long adsb_multi_decode_device(adsb_multi *m, uint64_t total_samples, const void *const *slices, int n_slices, const adsb_frame **frames);
 int adsb_multi_plan(const adsb_multi *m, uint64_t total_samples, uint64_t *g_begin, uint64_t *g_end,
@@ -220,11 +222,9 @@ int adsb_multi_set_long_streams(adsb_multi *m, int on); /* adsb_set_long_stream 
 int adsb_multi_decode_streams_host(adsb_multi *m, int n_streams, const uint16_t *const *samples, const size_t *n); int adsb_multi_decode_streams_file(adsb_multi *m, int n_streams, const char *const *paths);
 long adsb_multi_stream_frames(const adsb_multi *m, int stream, const adsb_frame **frames); int adsb_multi_stream_stats(const adsb_multi *m, int stream, adsb_stats *out);
 int adsb_multi_get_info(const adsb_multi *m, adsb_multi_info *out);
-/* n_captures INDEPENDENT captures over the devices: each worker decodes a contiguous range of them (balanced by the offsets to scan) in sub-batches
- * of at most batch_bytes of sample data (default 256 MiB; diag header: adsb_multi_set_batch_bytes), one adsb_decode_batch_host[_packed] each.
- * packed != 0: Airspy packed 12-bit.  Results as adsb_decode_batch_host's, in capture order, valid until the next call on m; adsb_multi_get_stats: the
- * sum.  _files: capture i is the regular file paths[i] (uint16: size / 2 samples; packed: its whole 12-byte groups).  -1, no partial result: a worker
- * failed, or a file is unreadable (the message names index and path). */
+/* n_captures INDEPENDENT captures over the devices, a contiguous range per worker in sub-batches (INTEGRATION.md).  packed != 0: Airspy packed 12-bit.
+ * Results as adsb_decode_batch_host's, in capture order, valid until the next call on m; adsb_multi_get_stats: the sum.  _files: capture i is the regular
+ * file paths[i] (uint16: size / 2 samples; packed: its whole 12-byte groups).  -1, no partial result: a worker failed or a file is unreadable. */
 long adsb_multi_decode_batch_host(adsb_multi *m, size_t n_captures, const void *const *samples, const size_t *n, int packed,
                                   const adsb_frame **frames, uint64_t *first, adsb_stats *stats);
 long adsb_multi_decode_batch_files(adsb_multi *m, size_t n_captures, const char *const *paths, int packed,

@@ -5,6 +5,7 @@ comparison interleaved.
     python tools/format_probe.py [--reps 20] [--out profiles/r11_formats.txt]
     python tools/format_probe.py --iq [--reps 20] [--out profiles/r14_iq.txt]      # complex captures: see iq_probe()
     python tools/format_probe.py --power [--reps 20] [--out profiles/r15_power.txt] [--ab parent=path/to/libadsbdec_amd.so]   # power_probe()
+    python tools/format_probe.py --export [--reps 20] [--out profiles/r17_power_export.txt] [--layout name=path/to/libadsbdec_amd.so ...]   # export_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
     (with counters, and without: a kernel that does not classify its samples at all) and adsb_unpack_packed12 at the same n
@@ -367,6 +368,136 @@ def power_probe(L, reps, lines):
     torch.cuda.empty_cache()
 
 
+def export_probe(L, reps, lines, layouts):
+    """The power export (power_export_kernel.hip, the adsb_power_* calls), every comparison interleaved in this one process:
+    (a) adsb_power_device on the 256 Mi-sample benchmark workload (512 MiB in, 512 MiB out; the call waits for its kernel, so its wall
+        time is launch + kernel + wait) twice over -- the A/A -- beside adsb_decode_device on the same capture (wall, and the scan
+        kernel on its own clock), and beside every other build given with --layout name=path: measurement builds of the library
+        whose power_export_kernel.hip was compiled with another store layout (-DADSB_EXPORT_STORE=0: seven plain 16-byte stores
+        per lane; =1: the same, non-temporal; =3: the tree's transposition through LDS with non-temporal stores);
+    (b) adsb_power_device_iq (fmt 2) on 128 Mi complex samples; (c) adsb_power_window_host on 16 Mi samples, host memory both ways."""
+    import numpy as np
+    t, _ = make_workload(torch, N, seed=1)
+    M = N // 2
+    out = torch.empty(M, dtype=torch.float32, device="cuda")
+    d_dec = capi.Decoder(df18=False, profile=True)
+    fr = C.POINTER(capi.Frame)()
+
+    def bind(path):
+        B = C.CDLL(path)
+        B.adsb_create.restype = C.c_void_p
+        B.adsb_create.argtypes = [C.c_void_p]
+        B.adsb_power_device.restype = C.c_long
+        B.adsb_power_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        cfg = capi.make_config()
+        h = B.adsb_create(C.byref(cfg))
+        assert h, path
+        return B, h
+
+    d_tree = capi.Decoder()
+    tree = (L, d_tree._h)
+    builds = {"tree (transposed through LDS)": tree, "tree again (the A/A)": tree}
+    for spec in layouts:
+        name, _, path = spec.partition("=")
+        builds[name] = bind(path)
+    ref = None
+    for name, (B, h) in builds.items():                    # warm-up, and every layout writes the same floats
+        for _ in range(3):
+            assert B.adsb_power_device(h, t.data_ptr(), N, out.data_ptr(), M) == M, name
+        if ref is None:
+            ref = out.clone()
+            from oracle import oracle as O
+            O.build()
+            # the oracle's power samples: the head, and a slice from each later trip of the grid (the phase of a stream has a period
+            # of 28 samples: oracle.power(x[f:])[6:] == oracle.power(x)[f // 2 + 6:] for f a multiple of 28)
+            for f in [0] + [28 * (j * (N >> 3) // 28) for j in range(1, 8)] + [28 * ((N - (1 << 20)) // 28)]:
+                piece = t[f: f + (1 << 20)].cpu().numpy().view(np.uint16)
+                want = O.power(piece)[: 2 * (piece.size // 4)].view(np.uint32)
+                got = out[f // 2: f // 2 + want.size].cpu().numpy().view(np.uint32)
+                lead = 6 if f else 0
+                assert np.array_equal(got[lead:], want[lead:]), f"not the oracle's power samples at sample {f}"
+        else:
+            assert torch.equal(out.view(torch.int32), ref.view(torch.int32)), f"{name}: other floats"
+        out.zero_()
+    del ref
+    for _ in range(3):
+        frames = L.adsb_decode_device(d_dec._h, t.data_ptr(), N, C.byref(fr))
+    assert frames > 0
+
+    def kernel_ms():
+        p = d_dec.profile()
+        return p["big_ms"], p["big_launches"]
+
+    steps = 5
+    wall = {k: [] for k in builds}
+    dec_wall, dec_k = [], []
+    names = list(builds)
+    for r in range(reps):
+        order = names[r % len(names):] + names[:r % len(names)]
+        for name in order:
+            B, h = builds[name]
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                B.adsb_power_device(h, t.data_ptr(), N, out.data_ptr(), M)
+            wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        m0, l0 = kernel_ms()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            L.adsb_decode_device(d_dec._h, t.data_ptr(), N, C.byref(fr))
+        dec_wall.append((time.perf_counter() - t0) * 1e3 / steps)
+        m1, l1 = kernel_ms()
+        dec_k.append((m1 - m0) / max(1, l1 - l0))
+    lines += [f"# (a) adsb_power_device, 256 Mi uint16 samples -> 128 Mi float32 power samples (512 MiB in, 512 MiB out); {reps} rounds x {steps} calls per side,",
+              "#     the sides in rotation; wall time of the call (launch + kernel + the wait for it), medians (quartiles); traffic = 1 GiB / median",
+              "#   side                                        call ms (q1 .. q3)              TB/s    / tree (median of rounds)"]
+    base = wall[names[0]]
+    for name in names:
+        q = statistics.quantiles(wall[name], n=4)
+        ratio = med([a / b for a, b in zip(wall[name], base)])
+        lines.append(f"    {name:42s} {med(wall[name]):.4f} ({q[0]:.4f} .. {q[2]:.4f})   {2 * 2 * N / (med(wall[name]) * 1e-3) * 1e-12:6.3f}   {ratio:.4f}")
+        print(lines[-1], flush=True)
+    q = statistics.quantiles(dec_k, n=4)
+    lines += [f"    adsb_decode_device on the same capture: call {med(dec_wall):.4f} ms, its scan kernel {med(dec_k):.5f} ms per launch ({q[0]:.5f} .. {q[2]:.5f}), {frames} frames",
+              "#   (the scan kernel has the same loads and FIR, everything else of the decoder, and no stores; DESIGN.md section 7's Stage A floors:",
+              "#    0.098 ms loads, 0.098 ms arithmetic, 0.118 ms both)"]
+    print(lines[-2], flush=True)
+    del out
+
+    NC = 1 << 27
+    iq = t.view(torch.int16)[: 2 * NC]                      # (any int16 pairs: the kernel's time does not depend on the values)
+    out = torch.empty(NC, dtype=torch.float32, device="cuda")
+    d = capi.Decoder()
+    ms = []
+    for r in range(-3, reps):
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            assert L.adsb_power_device_iq(d._h, 2, iq.data_ptr(), NC, out.data_ptr(), NC) == NC
+        if r >= 0:
+            ms.append((time.perf_counter() - t0) * 1e3 / steps)
+    from adsbdec_amd.sample_formats import iq_power
+    for f in (0, NC // 2 + 4, NC - (1 << 20)):                # the head and two later trips of the grid
+        assert np.array_equal(out[f: f + (1 << 20)].cpu().numpy().view(np.uint32),
+                              iq_power(iq[2 * f: 2 * f + (1 << 21)].cpu().numpy().reshape(-1, 2)).view(np.uint32)), f
+    q = statistics.quantiles(ms, n=4)
+    lines += ["#", "# (b) adsb_power_device_iq (fmt 2), 128 Mi complex int16 samples -> 128 Mi power samples (512 MiB in, 512 MiB out); wall time of the call",
+              f"    call {med(ms):.4f} ms ({q[0]:.4f} .. {q[2]:.4f})   {2 * 4 * NC / (med(ms) * 1e-3) * 1e-12:.3f} TB/s"]
+    print(lines[-1], flush=True)
+    del out, iq
+
+    NH = 1 << 24
+    x = t[:NH].cpu().numpy().view(np.uint16)
+    ms = []
+    for r in range(-2, max(5, reps // 2)):
+        t0 = time.perf_counter()
+        a = d.power_window_host(x, 0, 0, NH // 2)
+        if r >= 0:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    assert len(a) == NH // 2
+    lines += ["#", "# (c) adsb_power_window_host, 16 Mi samples (32 MiB in from pageable host memory, 32 MiB out to it); wall time of the call",
+              f"    call {med(ms):.3f} ms (min {min(ms):.3f}, max {max(ms):.3f})   {NH / (med(ms) * 1e-3) * 1e-9:.2f} GS/s"]
+    print(lines[-1], flush=True)
+
+
 def real_kernel_ab(builds, rounds, lines):
     """(c) the existing real-sample kernel across the change: tools/ab_interleaved.py in a process of its own (it dlopens every build
     side by side), the first build listed twice for the A/A."""
@@ -387,11 +518,27 @@ def main():
     ap.add_argument("--iq", action="store_true", help="complex captures (the _iq calls) instead: profiles/r14_iq.txt")
     ap.add_argument("--power", action="store_true", help="float32 power samples (the _power calls) instead: profiles/r15_power.txt")
     ap.add_argument("--ab", default=None, metavar="PARENT_LIB", help="with --power: the parent commit's libadsbdec_amd.so, for the A/B of the real kernel")
+    ap.add_argument("--export", action="store_true", help="the power export (the adsb_power_* calls) instead: profiles/r17_power_export.txt")
+    ap.add_argument("--layout", action="append", default=[], metavar="NAME=LIB", help="with --export: a build of the library with another store layout, measured beside the tree's")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "r15_power.txt" if a.power else "r14_iq.txt" if a.iq else "r11_formats.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r17_power_export.txt" if a.export else "r15_power.txt" if a.power else "r14_iq.txt" if a.iq else "r11_formats.txt")
     torch.cuda.set_device(0)
     L = capi.load()
+    if a.export:
+        lines = ["# tools/format_probe.py --export: the power export (power_export_kernel.hip, the adsb_power_* calls), one process,",
+                 f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
+                 "# The capture is the benchmark's: tools/gen_signal.py make_workload, 256 Mi samples, seed 1.",
+                 "# Sides named with --layout are builds of the library that differ in power_export_kernel.hip alone (-DADSB_EXPORT_STORE=k; a lane's",
+                 "# 28 floats are 112 contiguous bytes of the output), loaded beside the tree's in this process; every build writes the same floats:",
+                 "#   tree     k = 2: a wave's 1792 samples turned through 7 KiB of LDS of its own; each of seven stores writes 1 KiB of contiguous lines",
+                 "#   plain    k = 0: seven 16-byte stores per lane, 112 bytes apart by lane, as Stage A's loads are",
+                 "#   nt       k = 1: plain's stores, non-temporal",
+                 "#   lds-nt   k = 3: the tree's stores, non-temporal", "#"]
+        export_probe(L, a.reps, lines, a.layout)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.power:
         lines = ["# tools/format_probe.py --power: float32 power samples (scan_power_kernel.hip, the _power calls) beside the IQ kernel, one process,",
                  f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
