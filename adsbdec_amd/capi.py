@@ -602,8 +602,10 @@ class Decoder:
         return out, t, [_struct_dict(segs[i]) for i in range(ns.value)], [_struct_dict(launches[i]) for i in range(nl.value)]
 
     def batch_unpacked(self, capture: int, n: int):
-        """adsb_batch_unpacked_copy: the first n unpacked samples of capture `capture` of the last decode_batch*_packed call, as
-        the batch unpack kernel left them (n may reach into the pad behind the capture, up to its 128-byte-rounded slot)."""
+        """adsb_batch_unpacked_copy: the first n samples of capture `capture` of the last packed or converted batch call
+        (decode_batch*_packed, decode_batch*_as with a converted format, decode_batch*_iq with fmt 0), as the batch unpack or
+        conversion kernel left them (n may reach into the pad behind the capture, up to its 128-byte-rounded slot).  For a
+        converted IQ batch n counts int16 scalars, returned as their 16 bits.  Refused after a batch call that fills no scratch."""
         out = np.empty(n, dtype=np.uint16)
         self._check(self._L.adsb_batch_unpacked_copy(self._h, capture, out.ctypes.data, n), "adsb_batch_unpacked_copy")
         return out

@@ -349,6 +349,7 @@ long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
         if (batch_convert(d, what, adsb::kConvFloat32Iq, n_captures, src, scalars.data(), at))
             return -1;
     } else {
+        d->batch_unpacked_at.clear(); // (adsb_batch_unpacked_copy: no table of this call's; the copies below rewrite the scratch)
         size_t bytes = 0;
         for (size_t i = 0; i < n_captures; i++)
             if ((uintptr_t)src[i] % 16 != 0)
@@ -549,6 +550,7 @@ long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *co
     if (adsb_reset(d) != 0)
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
+    d->batch_unpacked_at.clear(); // (adsb_batch_unpacked_copy: this call unpacks and converts nothing)
     return decode_batch(d, n_captures, device_samples, n, frames, first, stats);
 }
 
@@ -569,6 +571,7 @@ long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *
         off[i] = bytes;
         bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
     }
+    d->batch_unpacked_at.clear(); // (as adsb_decode_batch_device)
     if (batch_grow(d, "adsb_decode_batch_host", "the captures", d->batch_in, bytes))
         return -1;
     std::vector<const void *> at(n_captures);
@@ -706,9 +709,10 @@ int adsb_batch_unpacked_copy(adsb_decoder *d, size_t capture, uint16_t *dst_u16,
 {
     if (!d)
         return -1;
-    // batch_unpacked_at: where every capture of the last packed batch starts in the scratch (samples), and where the last one's slot ends
+    // batch_unpacked_at: where every capture of the last packed or converted batch call starts in the scratch (samples), and where
+    // the last one's slot ends; empty behind a batch call that fills no such table
     if (capture + 1 >= d->batch_unpacked_at.size())
-        return d->fail("adsb_batch_unpacked_copy: the last packed batch call had no capture %zu", capture);
+        return d->fail("adsb_batch_unpacked_copy: the last packed or converted batch call had no capture %zu", capture);
     const size_t at = d->batch_unpacked_at[capture], slot = d->batch_unpacked_at[capture + 1] - at;
     if (n > slot)
         return d->fail("adsb_batch_unpacked_copy: capture %zu has a slot of %zu samples, %zu were asked for", capture, slot, n);

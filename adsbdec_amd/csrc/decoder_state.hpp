@@ -297,7 +297,9 @@ struct adsb_decoder {
     adsb::Table batch_tab, unpack_tab;
     adsb::Buf<uint8_t> batch_in, batch_land; // .cap bytes
     adsb::Buf<uint16_t> batch_unpacked;      // .cap samples
-    std::vector<size_t> batch_unpacked_at;   // the last packed batch: every capture's first sample in batch_unpacked, then the end
+    // the last packed or converted batch call: every capture's first sample in batch_unpacked, then the end (for a converted IQ
+    // batch a sample is an int16 scalar); empty behind a batch call that fills no such table
+    std::vector<size_t> batch_unpacked_at;
     bool batch_stats_on = false; // the last call was a batch: adsb_get_stats answers batch_stats, the sum over its captures
     adsb_stats batch_stats{};
     adsb::Buf<uint16_t> win_buf; // adsb_scan_shard_host, adsb_power_window_host: device copy of the caller's window

@@ -323,11 +323,14 @@ long adsb_batch_resolve_ex(size_t n_captures, const size_t *n, int cus, int pass
  * outside every segment).  Any of the pointers may be NULL.  0, or -1 (no handle). */
 int adsb_batch_records(adsb_decoder *d, const adsb_candidate **cands, size_t *n_cands, const uint64_t **tries, size_t *n_tries,
                        const adsb_batch_segment **segs, size_t *n_segs, const adsb_batch_launch **launches, size_t *n_launches);
-/* The first n unpacked samples of capture `capture` of the last adsb_decode_batch_*_packed call on d, as the batch unpack kernel
- * (csrc/unpack12_batch.hip) left them in the handle's scratch -> dst_u16 (host memory), by a copy on the handle's stream that is
- * waited for.  n may reach past the capture's samples to the end of its slot (every capture starts at a 128-byte boundary of the
- * scratch: up to 63 samples of pad, which no kernel writes).  -1 (with a message) for a capture index that call did not have or
- * an n beyond that capture's slot. */
+/* The first n samples of capture `capture` of the last packed or converted batch call on d -- adsb_decode_batch_*_packed,
+ * adsb_decode_batch_*_as with a converted format (1, 3), adsb_decode_batch_*_iq with fmt 0 -- as the batch unpack kernel
+ * (csrc/unpack12_batch.hip) or the batch conversion kernel (csrc/convert_samples.hip) left them in the handle's scratch -> dst_u16
+ * (host memory), by a copy on the handle's stream that is waited for.  For a converted IQ batch a sample is one int16 scalar (its
+ * 16 bits; two per complex sample) and n counts scalars.  n may reach past the capture's samples to the end of its slot (every
+ * capture starts at a 128-byte boundary of the scratch: up to 63 samples of pad, which no kernel writes).  -1 (with a message) for
+ * a capture index that call did not have, an n beyond that capture's slot, or when the last batch call on d was one that fills no
+ * such scratch (the uint16 batch calls, IQ fmt 2, the power batches). */
 int adsb_batch_unpacked_copy(adsb_decoder *d, size_t capture, uint16_t *dst_u16, size_t n);
 
 /* ---- a batch over the devices of adsb_multi (adsb_multi_decode_batch_*; csrc/multi.cpp), without a device ------------------------
