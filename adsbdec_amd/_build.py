@@ -21,7 +21,7 @@ CLI = os.path.join(LIBDIR, "adsbdec_amd_cli")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ROCM = os.environ.get("ROCM", "/opt/rocm")  # the HIP runtime's headers and library for the host program, as the Makefile's ROCM
 
-HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip", "scan_power_kernel.hip", "seam_kernel.hip", "decoder.hip", "decoder_collect.hip",
+HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip", "scan_iq8_kernel.hip", "scan_power_kernel.hip", "seam_kernel.hip", "decoder.hip", "decoder_collect.hip",
                "decoder_lifecycle.hip", "decoder_batch.hip", "decoder_shard.hip", "unpack12.hip", "unpack12_batch.hip",
                "convert_samples.hip", "power_export_kernel.hip", "decoder_export.hip"]
 C_SOURCES = ["format.c"]

@@ -112,8 +112,9 @@ class FormatReport(C.Structure):
 # fmt of the _as calls: the airspy_rx -t numbers (include/adsbdec_amd.h)
 FMT_FLOAT32_REAL, FMT_INT16_REAL, FMT_UINT16_REAL, FMT_RAW = 1, 3, 4, 5
 # fmt of the _iq calls (complex captures): arrays of shape (n, 2) = (I, Q), or flat ones of 2 n scalars
-FMT_FLOAT32_IQ, FMT_INT16_IQ = 0, 2
-IQ_DTYPES = {FMT_FLOAT32_IQ: np.dtype("<f4"), FMT_INT16_IQ: np.dtype("<i2")}
+# (8 INT8_IQ is the library's own number, not an airspy_rx -t one: interleaved signed bytes, HackRF cs8 / bladeRF and USRP sc8)
+FMT_FLOAT32_IQ, FMT_INT16_IQ, FMT_INT8_IQ = 0, 2, 8
+IQ_DTYPES = {FMT_FLOAT32_IQ: np.dtype("<f4"), FMT_INT16_IQ: np.dtype("<i2"), FMT_INT8_IQ: np.dtype("i1")}
 FMT_DTYPES = {FMT_FLOAT32_REAL: np.dtype("<f4"), FMT_INT16_REAL: np.dtype("<i2"), FMT_UINT16_REAL: np.dtype("<u2"), FMT_RAW: np.dtype("<u2")}
 
 
@@ -701,7 +702,7 @@ class Decoder:
             self._check(-1, "adsb_decode_batch_host_as")
         return self._batch_result(self._out, first, st, k, stats)
 
-    # ---- complex captures (include/adsbdec_amd.h: the _iq calls; fmt 0 FLOAT32_IQ, 2 INT16_IQ); n counts COMPLEX samples
+    # ---- complex captures (include/adsbdec_amd.h: the _iq calls; fmt 0 FLOAT32_IQ, 2 INT16_IQ, 8 INT8_IQ); n counts COMPLEX samples
     @staticmethod
     def _iq_arg(fmt, x):
         if isinstance(x, tuple):

@@ -23,6 +23,9 @@
  *                   how many: the sign of a wrong -t.  -t 1 and -t 3 not with -p, -G or -B.
  *     -q type       EXTENSION: the file holds COMPLEX samples at 10 MS/s, numbered as airspy_rx -t numbers them: 2 INT16_IQ (its
  *                   default), 0 FLOAT32_IQ (adsbdec_amd.h: the _iq calls).  Not with -t, -p, -G or -B; a file below 2^31 samples.
+ *                   -q 8 is NOT an airspy_rx number: INT8_IQ, interleaved signed bytes I, Q as hackrf_transfer -r writes them (cs8;
+ *                   bladeRF and USRP sc8 are the same bytes), decoded as the int16 capture (I << 8, Q << 8) is.  Not with -w or -W
+ *                   either.
  *     -w            EXTENSION: the file holds float32 POWER samples at 10 MS/s, little-endian: the reference's ampbuff stream itself
  *                   (adsbdec.h:5), from any front end (adsbdec_amd.h: the _power calls).  Input domain: every sample finite, sign bit
  *                   clear, below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); outside it nothing is promised or detected.
@@ -196,6 +199,7 @@ static void usage(void)
     printf("\t     converted on the GPU, 4 and 5 are the uint16 code (the default); not 0 or 2 (IQ); 1 and 3 not with -p, -G or -B\n");
     printf("\t-q type : (extension) the file holds COMPLEX samples at 10 MS/s, as airspy_rx -t numbers them: 2 signed 16 bits IQ (airspy_rx's\n");
     printf("\t     default), 0 float32 IQ (quantised to the int16 grid on the GPU); not with -t, -p, -G or -B\n");
+    printf("\t     -q 8 (not an airspy_rx number): signed 8 bits IQ, as hackrf_transfer -r writes (cs8 / sc8); not with -w or -W either\n");
     printf("\t-w : (extension) the file holds float32 POWER samples at 10 MS/s (little-endian), the demodulator's own input; every sample finite,\n");
     printf("\t     sign bit clear and below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); not with -t, -q, -p, -G or -B\n");
     printf("\t-W out.pw : (extension) export, do not decode: write the float32 power samples of the file (what -w reads) to out.pw; with -q the\n");
@@ -638,7 +642,7 @@ int main(int argc, char **argv)
     int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, c;
     long stype = 5; /* -t: ADSB_FMT_RAW */
     const char *stype_arg = NULL;
-    long qtype = -1; /* -q: ADSB_FMT_INT16_IQ / ADSB_FMT_FLOAT32_IQ */
+    long qtype = -1; /* -q: ADSB_FMT_INT16_IQ / ADSB_FMT_FLOAT32_IQ / ADSB_FMT_INT8_IQ */
     const char *qtype_arg = NULL;
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
@@ -725,6 +729,16 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    if (qtype_arg && qtype == ADSB_FMT_INT8_IQ && (stype_arg || packed || ndev || listfile || power || export_path)) {
+        /* int8 IQ is decoded from one file on one GPU and nothing else: refused before any GPU call */
+        fprintf(stderr, "-q 8 is not supported with %s: %s\n", stype_arg ? "-t" : packed ? "-p" : ndev ? "-G" : listfile ? "-B" : power ? "-w" : "-W",
+                stype_arg ? "a file holds real samples (-t) or IQ samples (-q), not both"
+                : packed  ? "a file is packed 12-bit real or IQ, not both"
+                : power   ? "a file holds IQ samples (-q) or power samples (-w), not both"
+                : export_path ? "the export reads uint16 codes, int16 IQ (-q 2) or float32 IQ (-q 0); an int8 sample's power is 256 (I^2 + Q^2)"
+                          : "the multi-GPU driver reads uint16 and packed files only");
+        return 1;
+    }
     if (export_path && (power || stype_arg || packed || ndev || listfile || outmode != SINK_STDOUT || nfiles > 1)) {
         /* -W writes power samples and decodes nothing: refused before any GPU call */
         fprintf(stderr, "-W is not supported with %s: %s\n",
@@ -752,8 +766,8 @@ int main(int argc, char **argv)
                 packed ? "a file is packed 12-bit or of that type, not both" : "the multi-GPU driver reads uint16 and packed files only");
         return 1;
     }
-    if (qtype_arg && qtype != ADSB_FMT_INT16_IQ && qtype != ADSB_FMT_FLOAT32_IQ) {
-        fprintf(stderr, "-q %s: not an IQ sample type; -q takes 2 (int16 IQ) or 0 (float32 IQ), real samples go with -t\n", qtype_arg);
+    if (qtype_arg && qtype != ADSB_FMT_INT16_IQ && qtype != ADSB_FMT_FLOAT32_IQ && qtype != ADSB_FMT_INT8_IQ) {
+        fprintf(stderr, "-q %s: not an IQ sample type; -q takes 2 (int16 IQ), 0 (float32 IQ) or 8 (int8 IQ), real samples go with -t\n", qtype_arg);
         return 1;
     }
     if (qtype_arg && (stype_arg || packed || ndev || listfile)) {

@@ -25,6 +25,13 @@ static uint64_t chunk_offsets(bool streaming)
     return 28ull * ((mi << 20) / 28);
 }
 
+// Where unit `unit` of staging buffer `buf` lies: the buffers are arrays of 16-bit units for every kind but an int8 IQ stream's,
+// whose units are bytes (decoder_state.hpp kind_unit_bytes).
+static inline uint16_t *stage_at(adsb_decoder *d, int buf, uint64_t unit)
+{
+    return reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(d->stage[buf].p) + unit * adsb::kind_unit_bytes(d->kind));
+}
+
 // One past the last offset that can be scanned once `n_samples` samples of the stream are in: the whole 1196-sample
 // window of an offset must have been produced.  A stream produces power samples in twos (air.c:59-92); a shard's samples
 // end where its last owned window does (adsb_plan_shards), which need not be a whole quad, and its scan never goes
@@ -226,6 +233,8 @@ int slot_launch(adsb_decoder *d, ScanSlot &s)
         HIP_TRY(d, adsb::launch_scan(ka, stats, ls));
     } else if (d->kind == adsb::kKindIq && !d->sink.cands) { // (a stateless shard scan on a handle that holds an IQ stream is a real one)
         HIP_TRY(d, adsb::launch_scan_iq(s.args, stats, ls));
+    } else if (d->kind == adsb::kKindIq8 && !d->sink.cands) {
+        HIP_TRY(d, adsb::launch_scan_iq8(s.args, stats, ls));
     } else if (d->kind == adsb::kKindPower && !d->sink.cands) {
         HIP_TRY(d, adsb::launch_scan_power(s.args, stats, ls));
     } else {
@@ -537,7 +546,7 @@ int scan_submit(adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, uint64
         a.g_begin = g_begin;
         a.g_end = g_stop;
         fill_scan_args(d, a);
-        // (choose_passes's table was measured with the real kernel; IQ launches use it as it is: nobody has measured theirs)
+        // (choose_passes's table was measured with the real kernel; IQ and int8 IQ launches use it as it is: nobody has measured theirs)
         a.passes = (d->dbg.passes >= 2 && d->dbg.passes <= adsb::kMaxPasses) ? d->dbg.passes
                                                                                          : adsb::choose_passes(n_off, d->n_cus, last_launch_was_dense(d));
         a.big_tiles = adsb::choose_big_tiles(n_off, a.passes, d->n_cus, d->dbg.big_tiles);
@@ -623,7 +632,8 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight)
             // that has already completed costs nothing).
             if (aside && d->piece > 1)
                 HIP_TRY(d, hipStreamWaitEvent(ts, d->ev_copy[(d->piece - 1) % adsb_decoder::kCopyStreams], 0));
-            HIP_TRY(d, adsb::launch_copy_samples(d->stage[d->cur ^ 1], d->stage[d->cur] + skip, left, ts)); // (the library's own kernel:
+            // (an int8 IQ stream's units are bytes, an even number of them: left / 2 16-bit words from byte `skip` on)
+            HIP_TRY(d, adsb::launch_copy_samples(d->stage[d->cur ^ 1], stage_at(d, d->cur, skip), (left * adsb::kind_unit_bytes(d->kind) + 1) / 2, ts)); // (the library's own kernel:
             //                                the runtime's first device-to-device copy of a process costs 7 ms, scan_kernel.hip)
             // Behind EVERY tail copy, the one of a synchronous push on the scan stream included: a following
             // adsb_push_async copies right behind this tail on a copy stream that nothing else orders against it.
@@ -658,7 +668,7 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight)
 // land[] like packed ones and the conversion kernel stands where the unpack does.  Any n, any stage_fill.
 static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind kind, bool async = false, bool packed = false, int conv = 0)
 {
-    const size_t elem = adsb::convert_element_bytes(conv);
+    const size_t elem = adsb::convert_element_bytes(conv), unit = adsb::kind_unit_bytes(d->kind);
     const char *p = static_cast<const char *>(src);
     while (n) {
         uint64_t room = d->stage_cap - kStageSlack - d->stage_fill;
@@ -667,7 +677,7 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
         if (room == 0)
             return d->fail("staging buffer exhausted (stage_samples too small)");
         const size_t take = (size_t)std::min<uint64_t>(room, n);
-        const size_t bytes = packed ? take / adsb::kPackedGroupSamples * adsb::kPackedGroupBytes : conv ? take * elem : take * sizeof(uint16_t);
+        const size_t bytes = packed ? take / adsb::kPackedGroupSamples * adsb::kPackedGroupBytes : conv ? take * elem : take * unit;
         if (async) {
             d->piece++;
             const int cs = (int)(d->piece % adsb_decoder::kCopyStreams);
@@ -675,16 +685,16 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
             // Same rule as for the tail copy in process_stage: two writers that are not ordered never share a
             // cache line.  A piece that starts inside a 128-byte line (pushes of odd sizes) waits for the copy of
             // the piece before it, which ends in that line.
-            if (d->piece > 1 && (d->stage_fill * sizeof(uint16_t)) % 128 != 0 && d->dbg_async != 2)
+            if (d->piece > 1 && (d->stage_fill * unit) % 128 != 0 && d->dbg_async != 2)
                 HIP_TRY(d, hipStreamWaitEvent(cstream, d->ev_copy[cs ^ 1], 0));
             if (packed) {
                 HIP_TRY(d, hipMemcpyAsync(d->land[cs], p, bytes, kind, cstream));
-                HIP_TRY(d, adsb::launch_unpack12(d->stage[d->cur] + d->stage_fill, d->land[cs], take / adsb::kPackedGroupSamples, cstream));
+                HIP_TRY(d, adsb::launch_unpack12(stage_at(d, d->cur, d->stage_fill), d->land[cs], take / adsb::kPackedGroupSamples, cstream));
             } else if (conv) {
                 HIP_TRY(d, hipMemcpyAsync(d->land[cs], p, bytes, kind, cstream));
-                HIP_TRY(d, adsb::launch_convert(conv, d->stage[d->cur] + d->stage_fill, d->land[cs], take, d->d_fmt, cstream));
+                HIP_TRY(d, adsb::launch_convert(conv, stage_at(d, d->cur, d->stage_fill), d->land[cs], take, d->d_fmt, cstream));
             } else {
-                HIP_TRY(d, hipMemcpyAsync(d->stage[d->cur] + d->stage_fill, p, bytes, kind, cstream));
+                HIP_TRY(d, hipMemcpyAsync(stage_at(d, d->cur, d->stage_fill), p, bytes, kind, cstream));
             }
             HIP_TRY(d, hipEventRecord(d->ev_copy[cs], cstream));
             if (d->dbg_async != 2)
@@ -696,12 +706,12 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
             // synchronous push was complete when it returned)
             if (packed) {
                 HIP_TRY(d, hipMemcpyAsync(d->land[0], p, bytes, kind, d->stream));
-                HIP_TRY(d, adsb::launch_unpack12(d->stage[d->cur] + d->stage_fill, d->land[0], take / adsb::kPackedGroupSamples, d->stream));
+                HIP_TRY(d, adsb::launch_unpack12(stage_at(d, d->cur, d->stage_fill), d->land[0], take / adsb::kPackedGroupSamples, d->stream));
             } else if (conv) {
                 HIP_TRY(d, hipMemcpyAsync(d->land[0], p, bytes, kind, d->stream));
-                HIP_TRY(d, adsb::launch_convert(conv, d->stage[d->cur] + d->stage_fill, d->land[0], take, d->d_fmt, d->stream));
+                HIP_TRY(d, adsb::launch_convert(conv, stage_at(d, d->cur, d->stage_fill), d->land[0], take, d->d_fmt, d->stream));
             } else {
-                HIP_TRY(d, hipMemcpyAsync(d->stage[d->cur] + d->stage_fill, p, bytes, kind, d->stream));
+                HIP_TRY(d, hipMemcpyAsync(stage_at(d, d->cur, d->stage_fill), p, bytes, kind, d->stream));
             }
             d->copy_unconfirmed = true;
         }
@@ -794,10 +804,10 @@ int format_dispatch(adsb_decoder *d, const char *what, int fmt, size_t *elem)
 // The stream's kind is fixed by its first push with samples; a push of another kind is refused, the handle as it was.
 int kind_refusal(adsb_decoder *d, const char *what, int kind)
 {
-    static const char *const names[] = {"", "real", "IQ", "power"};
+    static const char *const names[] = {"", "real", "IQ (fmt 0 / 2)", "power", "int8 IQ (fmt 8)"};
     if (adsb::kind_in_twos(kind) && d->long_stream)
         return d->fail("%s: a long-stream handle (adsb_set_long_stream) takes real samples only, not %s ones: the counter wrap it follows is "
-                       "the FIR ring's (air.c:34) and %s stream has no ring", what, names[kind], kind == adsb::kKindIq ? "an IQ" : "a power");
+                       "the FIR ring's (air.c:34) and %s stream has no ring", what, names[kind], kind == adsb::kKindPower ? "a power" : "an IQ");
     if (d->kind != adsb::kKindNone && d->kind != kind)
         return d->fail("%s: the stream holds %s samples (its first push fixed that) and %s samples cannot follow them: adsb_reset starts a "
                        "fresh stream", what, names[d->kind], names[kind]);
@@ -806,6 +816,7 @@ int kind_refusal(adsb_decoder *d, const char *what, int kind)
 
 // adsb_push, adsb_push_async and their packed forms: samples in host memory (`packed`: whole groups of 12-bit samples).
 // kind: kKindIq from the _iq calls, whose n counts 16-bit units (fmt 2) or float scalars (fmt 0): two per complex sample;
+// kKindIq8 from the _iq calls with fmt 8, whose n counts BYTES: two per complex sample (kind_unit_bytes);
 // kKindPower from the _power calls, whose n counts 16-bit units too: two per power sample.
 static int push_host(adsb_decoder *d, const void *samples, size_t n, bool async, bool packed, const char *what, int conv = 0,
                      int kind = adsb::kKindReal)
@@ -871,7 +882,9 @@ static int push_device_impl(adsb_decoder *d, const void *device_samples, size_t 
     if (n)
         d->kind = kind;
     HIP_TRY(d, hipSetDevice(d->device));
+    // p[0] is unit d->n_samples of the stream; a unit is 16 bits, or a byte of an int8 IQ stream (kind_unit_bytes)
     const uint16_t *p = static_cast<const uint16_t *>(device_samples);
+    const size_t unit = adsb::kind_unit_bytes(kind);
     const bool aligned = (d->n_samples % 8 == 0) && ((uintptr_t)p % 16 == 0);
     if (!aligned || n < kInPlaceMinSamples) {
         if (n && push_copy(d, p, n, hipMemcpyDeviceToDevice))
@@ -940,7 +953,8 @@ static int push_device_impl(adsb_decoder *d, const void *device_samples, size_t 
     if (left > d->stage_cap - kStageSlack)
         return d->fail("in-place tail (%llu samples) exceeds the staging buffer", (unsigned long long)left);
     d->cur ^= 1; // the seam scan above may still be reading the other buffer
-    HIP_TRY(d, adsb::launch_copy_samples(d->stage[d->cur], p + (keep_first - first), left, d->stream));
+    HIP_TRY(d, adsb::launch_copy_samples(d->stage[d->cur], reinterpret_cast<const uint16_t *>(static_cast<const char *>(device_samples) + (keep_first - first) * unit),
+                                         (left * unit + 1) / 2, d->stream));
     d->stage_first = keep_first;
     d->stage_fill = left;
     if (g_end > d->g_scanned) {
@@ -1044,20 +1058,25 @@ static int push_device_as_impl(adsb_decoder *d, int fmt, const void *p, size_t n
 
 // ---- complex samples (the _iq calls; include/adsbdec_amd.h) ----
 // What every _iq call checks before anything of the handle changes.  n counts complex samples; the stream counts 16-bit units
-// (two per complex sample), so everything behind these checks is the uint16 machinery with 2 n.
+// (two per complex sample), so everything behind these checks is the uint16 machinery with 2 n.  An int8 stream (fmt 8) counts
+// bytes, two per complex sample as well: the same machinery with the same 2 n, and a unit of one byte where it copies.
 int iq_refusal(adsb_decoder *d, const char *what, int fmt, const void *p, size_t n, bool device, uint64_t at_units)
 {
-    if (fmt != 0 && fmt != 2)
-        return d->fail("%s: format %d is not an IQ format (0 FLOAT32_IQ, 2 INT16_IQ; real samples go through the _as calls)", what, fmt);
+    const size_t align = fmt == adsb::kFmtInt8Iq ? 2 : 4;
+    if (!adsb::iq_sample_bytes(fmt))
+        return d->fail("%s: format %d is not an IQ format (0 FLOAT32_IQ, 2 INT16_IQ, 8 INT8_IQ; real samples go through the _as calls)", what, fmt);
     if ((uint64_t)n >= (1ull << 31) || at_units + 2 * (uint64_t)n >= (1ull << 32))
         return d->fail("%s: the stream would reach 2^31 complex samples (%llu + %zu): IQ streams end below", what,
                        (unsigned long long)(at_units / 2), n);
     if (n && !p)
         return d->fail("%s: NULL samples", what);
-    if (device && (uintptr_t)p % 4 != 0)
-        return d->fail("%s: device pointer %p is not 4-byte aligned", what, p);
+    if (device && (uintptr_t)p % align != 0)
+        return d->fail("%s: device pointer %p is not %zu-byte aligned", what, p, align);
     return 0;
 }
+
+// the stream kind an _iq format makes: fmt 0 is converted to fmt 2's int16 pairs; fmt 8 is a kind of its own, its units bytes
+static inline int iq_kind(int fmt) { return fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq; }
 
 static int push_host_iq(adsb_decoder *d, int fmt, const void *samples, size_t n, bool async, const char *what)
 {
@@ -1065,10 +1084,11 @@ static int push_host_iq(adsb_decoder *d, int fmt, const void *samples, size_t n,
         return -1;
     if (iq_refusal(d, what, fmt, samples, n, false, d->n_samples))
         return -1;
-    return push_host(d, samples, 2 * n, async, false, what, fmt == 0 ? adsb::kConvFloat32Iq : 0, adsb::kKindIq);
+    return push_host(d, samples, 2 * n, async, false, what, fmt == 0 ? adsb::kConvFloat32Iq : 0, iq_kind(fmt));
 }
 
-// fmt 2 is scanned where it lies under the uint16 rule (16-byte aligned, at a multiple of 4 complex samples; else staged);
+// fmt 2 is scanned where it lies under the uint16 rule (16-byte aligned, at a multiple of 4 complex samples; else staged), and so
+// is fmt 8 (scan_iq8_kernel.hip's lanes are then 8-byte aligned; its typed 4-byte loads ask for less);
 // fmt 0 is converted into the scratch of the other converted device pushes first.
 static int push_device_iq(adsb_decoder *d, int fmt, const void *p, size_t n, bool final, const char *what, bool checked = false)
 {
@@ -1078,13 +1098,13 @@ static int push_device_iq(adsb_decoder *d, int fmt, const void *p, size_t n, boo
         return -1;
     if (d->finished)
         return d->fail("%s after adsb_finish", what);
-    if (kind_refusal(d, what, adsb::kKindIq))
+    if (kind_refusal(d, what, iq_kind(fmt)))
         return -1;
     if (n == 0 && !final)
         return 0;
     if (fmt == 0)
         return push_device_as_impl(d, adsb::kConvFloat32Iq, p, 2 * n, final, what, adsb::kKindIq);
-    return push_device_impl(d, p, 2 * n, final, adsb::kKindIq);
+    return push_device_impl(d, p, 2 * n, final, iq_kind(fmt));
 }
 
 // ---- float32 power samples (the _power calls; include/adsbdec_amd.h) ----
@@ -1167,7 +1187,7 @@ long adsb_decode_device_power(adsb_decoder *d, const void *device_samples, size_
 
 size_t adsb_iq_bytes(int fmt, size_t n)
 {
-    return fmt == 2 ? 4 * n : fmt == 0 ? 8 * n : 0;
+    return adsb::iq_sample_bytes(fmt) * n;
 }
 
 int adsb_push_iq(adsb_decoder *d, int fmt, const void *samples, size_t n)
@@ -1196,7 +1216,7 @@ long adsb_decode_device_iq(adsb_decoder *d, int fmt, const void *device_samples,
     if (!d || !frames)
         return -1;
     // refused before the reset, at the position the reset will set: a refused call leaves the handle as it was
-    if (iq_refusal(d, what, fmt, device_samples, n, true, 0) || (d->long_stream && kind_refusal(d, what, adsb::kKindIq)))
+    if (iq_refusal(d, what, fmt, device_samples, n, true, 0) || (d->long_stream && kind_refusal(d, what, iq_kind(fmt))))
         return -1;
     if (adsb_reset(d) != 0 || push_device_iq(d, fmt, device_samples, n, true, what, true) != 0)
         return -1;

@@ -115,6 +115,8 @@ int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void
         s.busy = true; // (a failure from here on leaves a launch in flight: adsb_reset waits for it)
         if (d->kind == adsb::kKindIq)
             HIP_TRY(d, adsb::launch_scan_batch_iq(a, seg_d, tile_d, L.tiles, stats, ls));
+        else if (d->kind == adsb::kKindIq8)
+            HIP_TRY(d, adsb::launch_scan_batch_iq8(a, seg_d, tile_d, L.tiles, stats, ls));
         else if (d->kind == adsb::kKindPower)
             HIP_TRY(d, adsb::launch_scan_batch_power(a, seg_d, tile_d, L.tiles, stats, ls));
         else
@@ -319,10 +321,10 @@ int batch_refusal_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
 {
     if (n_captures && (!p || !n))
         return d->fail("%s: NULL capture arrays", what);
-    if (fmt != 0 && fmt != 2)
+    if (!adsb::iq_sample_bytes(fmt))
         return iq_refusal(d, what, fmt, nullptr, 0, device, 0);
     if (d->long_stream)
-        return kind_refusal(d, what, adsb::kKindIq);
+        return kind_refusal(d, what, fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq);
     char who[96];
     for (size_t i = 0; i < n_captures; i++) {
         snprintf(who, sizeof who, "%s: capture %zu", what, i);
@@ -335,6 +337,9 @@ int batch_refusal_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
 // The captures in device memory at src[] (fmt 2: int16 pairs, 4-byte aligned; fmt 0: float pairs) -> frames.  Whatever is not
 // 16-byte aligned int16 goes through scratch first: fmt 0 by the batch conversion launch, a misaligned fmt-2 capture by a copy.
 // kind = kKindPower (fmt 2): the captures are float32 power samples, n[] counts them -- the same 4-byte units on the same road.
+// kind = kKindIq8 (fmt 8): int8 pairs, 2-byte aligned.  The layout is asked at the number the widened twin is asked at, 4 (n / 2),
+// so segments, tiles and launches are the twin's; a unit is a BYTE there (decoder_state.hpp kind_unit_bytes), which only the
+// scratch copies of the captures that are not 16-byte aligned see -- the segment table counts complex samples either way.
 long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
                      const adsb_frame **frames, uint64_t *first, adsb_stats *stats, int kind = adsb::kKindIq)
 {
@@ -344,6 +349,7 @@ long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
         scalars[i] = 2 * n[i];
     }
     std::vector<const void *> at(src, src + n_captures);
+    const size_t unit = adsb::kind_unit_bytes(kind);
     d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
     if (fmt == 0) {
         if (batch_convert(d, what, adsb::kConvFloat32Iq, n_captures, src, scalars.data(), at))
@@ -353,7 +359,7 @@ long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
         size_t bytes = 0;
         for (size_t i = 0; i < n_captures; i++)
             if ((uintptr_t)src[i] % 16 != 0)
-                bytes += (units[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+                bytes += (units[i] * unit + 127) & ~(size_t)127;
         if (bytes && batch_grow(d, what, "the captures that are not 16-byte aligned", d->batch_unpacked, bytes))
             return -1;
         size_t off = 0;
@@ -362,8 +368,8 @@ long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
                 continue;
             at[i] = reinterpret_cast<const char *>(d->batch_unpacked.p) + off;
             if (units[i])
-                HIP_TRY(d, hipMemcpyAsync(const_cast<void *>(at[i]), src[i], units[i] * sizeof(uint16_t), hipMemcpyDeviceToDevice, d->stream));
-            off += (units[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
+                HIP_TRY(d, hipMemcpyAsync(const_cast<void *>(at[i]), src[i], units[i] * unit, hipMemcpyDeviceToDevice, d->stream));
+            off += (units[i] * unit + 127) & ~(size_t)127;
         }
     }
     d->kind = kind; // (behind the reset: the batch launches are scan_iq_batch_kernel's or scan_power_batch_kernel's)
@@ -448,7 +454,7 @@ long adsb_decode_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, co
     if (adsb_reset(d) != 0)
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
-    return decode_batch_iq(d, what, fmt, n_captures, device_samples, n, frames, first, stats);
+    return decode_batch_iq(d, what, fmt, n_captures, device_samples, n, frames, first, stats, fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq);
 }
 
 long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
@@ -463,7 +469,7 @@ long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, cons
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     // every capture as it is at a 128-byte boundary of the landing buffer the other host batches use
-    const size_t elem = fmt == 0 ? 8 : 4;
+    const size_t elem = adsb::iq_sample_bytes(fmt);
     size_t bytes = 0;
     for (size_t i = 0; i < n_captures; i++)
         bytes += (n[i] * elem + 127) & ~(size_t)127;
@@ -480,7 +486,7 @@ long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, cons
     }
     for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again)
         WAIT_STREAM(d, cs, "a copy stream");
-    return decode_batch_iq(d, what, fmt, n_captures, land.data(), n, frames, first, stats);
+    return decode_batch_iq(d, what, fmt, n_captures, land.data(), n, frames, first, stats, fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq);
 }
 
 long adsb_decode_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,

@@ -183,6 +183,8 @@ long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, 
     const char *what = "adsb_power_device_iq";
     if (!d)
         return -1;
+    if (fmt == kFmtInt8Iq) // (decoded, not exported: an int8 sample's power is 256 (I^2 + Q^2), which a caller has in one line)
+        return d->fail("%s: format 8 (INT8_IQ) is not exported: the power export takes fmt 0 FLOAT32_IQ and 2 INT16_IQ only", what);
     if (iq_refusal(d, what, fmt, device_samples, n, true, 0))
         return -1;
     if ((uintptr_t)device_power % 16)

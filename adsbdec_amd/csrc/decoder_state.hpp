@@ -50,10 +50,15 @@ inline const char *tuning_env(const char *) { return nullptr; }
 constexpr uint64_t kDefaultStageSamples = 32ull << 20; // 64 MiB per staging buffer
 constexpr uint64_t kStageSlack = 4096;                 // samples kept free for alignment padding
 constexpr size_t kInPlaceMinSamples = 1u << 16;
-constexpr int kKindNone = 0, kKindReal = 1, kKindIq = 2, kKindPower = 3; // adsb_decoder::kind
-// the stream's 32-bit units ARE its power samples (complex int16 samples, float32 power samples): no FIR ring, no quads, and
-// the power samples enter the demodulator two at a time (air.c:94-99)
-constexpr bool kind_in_twos(int kind) { return kind == kKindIq || kind == kKindPower; }
+constexpr int kKindNone = 0, kKindReal = 1, kKindIq = 2, kKindPower = 3, kKindIq8 = 4; // adsb_decoder::kind
+// a PAIR of the stream's units IS a power sample (complex int16 samples, float32 power samples, complex int8 samples): no FIR
+// ring, no quads, and the power samples enter the demodulator two at a time (air.c:94-99)
+constexpr bool kind_in_twos(int kind) { return kind == kKindIq || kind == kKindPower || kind == kKindIq8; }
+// Bytes of one unit of the stream -- what n_samples, stage_first and stage_fill count.  Every kind counts TWO units per pair /
+// power sample, so the index arithmetic of the stream machinery (pairs, the carry in twos, compaction, the in-place rule at a
+// multiple of 8 units, the EOF horizon) is one for all of them; a unit is 16 bits everywhere except in an int8 IQ stream, whose
+// unit is ONE BYTE (I or Q).  Only where the machinery turns units into addresses and byte counts does the kind matter.
+constexpr size_t kind_unit_bytes(int kind) { return kind == kKindIq8 ? 1 : 2; }
 constexpr size_t kSeamSamples = 4096; // > 2*(28+8+1196): enough for the first in-place tile's pre-halo
 constexpr int kSlots = 4;
 constexpr size_t kTryStateBytes = 4 * sizeof(unsigned long long) + 4 * sizeof(uint32_t); // d_try_acc + d_carry_n
@@ -131,6 +136,7 @@ struct ScanSink { // where collected records go: a caller's vectors, or (null) t
 //              the other buffer -- when the buffer is half full).  stage_first is a multiple of
 //              8 samples so that pair index/4 alignment and 16-byte loads line up with the stream.
 //              adsb_push_async copies into it on two copy streams of its own (push_copy).
+//              (An int8 IQ stream's units are bytes: stage_first, stage_fill and stage_cap count them, and the buffers are half used.)
 //              Ordering rule of the copies into it: two writers that are not ordered never share a
 //              cache line (process_stage, push_copy).
 //   slots[]    the record buffers of the launches in flight (ScanSlot)
@@ -181,7 +187,7 @@ struct adsb_decoder {
     bool finished = false;
     // What the stream holds, fixed by its first push with samples after adsb_create / adsb_reset: real samples (the uint16,
     // packed and _as calls: the FIR front end), complex ones (the _iq calls: scan_iq_kernel.hip) or float32 power samples (the
-    // _power calls: scan_power_kernel.hip).  They never mix.
+    // _power calls: scan_power_kernel.hip), or complex int8 ones (the _iq calls with fmt 8: scan_iq8_kernel.hip).  They never mix.
     int kind = adsb::kKindNone;
     // Long streams (adsb_set_long_stream): no refusal at 2^32 samples; launches are cut at every wrap of the reference's
     // sample counter and the offsets around it go through the seam kernel (scan_submit, seam_kernel.h)

@@ -32,6 +32,23 @@ constexpr int kFmtFloat32Real = 1, kFmtInt16Real = 3, kFmtUint16Real = 4, kFmtRa
 // airspy_rx -t number -- that one is 0, which the _as calls refuse -- and no _as call accepts it (format_element_bytes: 0).
 constexpr int kConvFloat32Iq = 8;
 
+// fmt values of the _iq calls (include/adsbdec_amd.h).  kFmtInt8Iq is the PUBLIC number 8 and has nothing to do with kConvFloat32Iq,
+// which happens to be 8 too: an int8 capture is never converted (scan_iq8_kernel.hip reads it as it is), so the public number
+// never reaches a conversion -- the _iq calls map it to the stream kind kKindIq8 (decoder_state.hpp) at the boundary, conv = 0.
+constexpr int kFmtFloat32Iq = 0, kFmtInt16Iq = 2, kFmtInt8Iq = 8;
+
+// bytes of one complex sample of an _iq format (0: not one)
+ADSB_HD constexpr size_t iq_sample_bytes(int fmt) { return fmt == kFmtInt8Iq ? 2 : fmt == kFmtInt16Iq ? 4 : fmt == kFmtFloat32Iq ? 8 : 0; }
+
+// The power sample of ONE int8 IQ sample d = (I, Q), two signed bytes in the low 16 bits: the INT16_IQ power sample of the widened
+// twin (I << 8, Q << 8) -- i = 16 I, q = 16 Q, a = fl(fl(i i) + fl(q q)) = 256 (I^2 + Q^2), an integer of at most 2^23: every product
+// and the sum are exact in binary32, so nothing here rounds and a fused form would give the same bits.
+ADSB_HD inline float iq8_power(uint32_t d)
+{
+    const float i = (float)(16 * (int)(int8_t)(uint8_t)(d & 0xFFu)), q = (float)(16 * (int)(int8_t)(uint8_t)((d >> 8) & 0xFFu));
+    return i * i + q * q;
+}
+
 constexpr uint32_t kSampleExact = 0, kSampleInexact = 1, kSampleClamped = 2;
 
 // bytes per sample of a converted format (0: not one)

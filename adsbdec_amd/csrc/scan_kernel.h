@@ -199,6 +199,11 @@ hipError_t launch_scan_batch(const ScanArgs &args, const BatchSeg *segs, const u
 hipError_t launch_scan_iq(const ScanArgs &args, bool stats, hipStream_t stream);
 hipError_t launch_scan_batch_iq(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
                                 hipStream_t stream);
+// ... for a stream of complex int8 samples (scan_iq8_kernel.hip): x is addressed in complex samples of TWO bytes, (I, Q) signed
+// bytes, its first sample 8-byte aligned and pbuf0 a multiple of 4; pbuf0 / p_lo / p_hi / g count complex samples as above.
+hipError_t launch_scan_iq8(const ScanArgs &args, bool stats, hipStream_t stream);
+hipError_t launch_scan_batch_iq8(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
+                                 hipStream_t stream);
 // ... and for a stream of float32 power samples (scan_power_kernel.hip): x holds ONE binary32 power sample per word, the
 // reference's ampbuff; pbuf0 / p_lo / p_hi / g count power samples.
 hipError_t launch_scan_power(const ScanArgs &args, bool stats, hipStream_t stream);

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "power_ordered.h" // taps, power_ordered<>, columns_to_bytes: shared with seam_kernel.hip
+#include "sample_format.h" // iq8_power: the power sample of one int8 IQ sample, shared with a CPU test
 #include "scan_kernel.h"
 #include "slicer_bits.h"
 #include "scan_stamps.h" // ADSB_STAMP / ADSB_COUNT: nothing in the shipped build (a measurement build's per-phase tile clocks)
@@ -254,6 +255,25 @@ __device__ __noinline__ uint32_t pw_at_iq(const uint32_t *__restrict__ x, int64_
     return (uint32_t)((p1 + p2) / 4);
 }
 
+// ---- the int8 IQ front end's slow path (scan_iq8_kernel.hip) ----
+// pw of the offset g of a stream of complex int8 samples (demod.c:102-105,127,133): x is addressed in complex samples of TWO
+// bytes, so the four samples at g + {0, 10, 35, 45} are four 2-byte loads; a sample outside the buffer reads as (0, 0).  The power
+// sample of one is sample_format.h's iq8_power.
+__device__ __noinline__ uint32_t pw_at_iq8(const uint32_t *__restrict__ x, int64_t pbuf0, int64_t p_lo, int64_t p_hi, int64_t g)
+{
+    const uint16_t *__restrict__ x16 = reinterpret_cast<const uint16_t *>(x);
+    const int off[4] = {0, 10, 35, 45};
+    float a[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int64_t pi = g + off[k];
+        a[k] = iq8_power((pi >= p_lo && pi < p_hi) ? (uint32_t)x16[pi - pbuf0] : 0u);
+    }
+    const int p1 = __float2int_rz(a[0] + a[1]);
+    const int p2 = __float2int_rz(a[2] + a[3]);
+    return (uint32_t)((p1 + p2) / 4);
+}
+
 // ---- the power front end's slow path (scan_power_kernel.hip) ----
 // pw of the offset g of a stream of float32 power samples (demod.c:102-105,127,133): the stream IS the reference's ampbuff, so
 // the four samples at g + {0, 10, 35, 45} are four loads; a sample outside the buffer reads as +0.
@@ -272,7 +292,7 @@ __device__ __noinline__ uint32_t pw_at_power(const uint32_t *__restrict__ x, int
 }
 
 // The front end of the kernel the stages are built into: what Stage A reads and how pw is formed
-constexpr int kFrontReal = 0, kFrontIq = 1, kFrontPower = 2;
+constexpr int kFrontReal = 0, kFrontIq = 1, kFrontPower = 2, kFrontIq8 = 3;
 
 // pw of offset g by that front end
 template <int kFront>
@@ -282,6 +302,8 @@ __device__ __forceinline__ uint32_t pw_of(const uint32_t *__restrict__ x, int64_
         return pw_at_iq(x, pbuf0, p_lo, p_hi, g);
     else if constexpr (kFront == kFrontPower)
         return pw_at_power(x, pbuf0, p_lo, p_hi, g);
+    else if constexpr (kFront == kFrontIq8)
+        return pw_at_iq8(x, pbuf0, p_lo, p_hi, g);
     else
         return pw_at(x, pbuf0, p_lo, p_hi, g);
 }
@@ -573,6 +595,152 @@ __device__ __forceinline__ void stage_a_iq(const uint32_t *__restrict__ xin, con
             const f32x2 ii = {tl[k].x, tl[k].y}, qq = {tl[k].z, tl[k].w};
             const f32x2 scale = {0.00390625f, 0.00390625f}; // 2^-8: (I / 16)^2 + (Q / 16)^2
             f32x2 s = (ii * ii + qq * qq) * scale;
+            asm volatile("" : "+v"(s)); // (the 28 samples first, in this order, then the planes: 96 registers hold either, not a mix)
+            a[2 * k] = s.x;
+            a[2 * k + 1] = s.y;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            a[28 + k] = from_next_lane(a[k]);
+
+        // demod.c:102-105: every preamble sum is c[k] = (int)(a[k] + a[k+10]).  The
+        // truncated value is kept as a float (v_trunc_f32 == the C conversion for the
+        // magnitudes in the input domain); the integer comparisons `c > 2 c'` are
+        // decided by the SIGN of 2 c' - c, which one fused multiply-add gives exactly
+        // (a single rounding cannot change the sign of a non-zero difference and an
+        // exact zero stays zero).
+        //
+        // Packing: every operation here combines index k with k + 5 or k + 10, so the
+        // usual (k, k+1) register pairs cannot feed v_pk_* on both sides (5 is odd).
+        // Pairs (k, k+2) for k mod 5 in {0, 1} can -- the partner set is closed under
+        // +5 -- and leave k mod 5 == 4 as scalar operations: 4 of 5 values are packed.
+        float c[34], dv[28], e1v[28], e2v[28];
+#pragma unroll
+        for (int k = 0; k < 33; k++) {
+            if (k % 5 < 2) {
+                const f32x2 lo = {a[k], a[k + 2]}, hi = {a[k + 10], a[k + 12]};
+                const f32x2 sum = lo + hi;
+                c[k] = __builtin_truncf(sum.x);
+                c[k + 2] = __builtin_truncf(sum.y);
+            } else if (k % 5 == 4) {
+                c[k] = __builtin_truncf(a[k] + a[k + 10]);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < 28; m++) {
+            if (m % 5 < 2 && m + 2 < 28) {
+                const f32x2 am = {a[m], a[m + 2]}, an = {a[m + 5], a[m + 7]};
+                const f32x2 cm = {c[m], c[m + 2]}, cn = {c[m + 5], c[m + 7]};
+                const f32x2 two = {2.0f, 2.0f};
+                const f32x2 dd = an - am;
+                const f32x2 x1 = __builtin_elementwise_fma(cn, two, -cm);
+                const f32x2 x2 = __builtin_elementwise_fma(cm, two, -cn);
+                dv[m] = dd.x, dv[m + 2] = dd.y;
+                e1v[m] = x1.x, e1v[m + 2] = x1.y;
+                e2v[m] = x2.x, e2v[m + 2] = x2.y;
+            } else if (m % 5 == 4 || (m % 5 < 2 && m + 2 >= 28)) {
+                dv[m] = a[m + 5] - a[m];
+                e1v[m] = __builtin_fmaf(c[m + 5], 2.0f, -c[m]);
+                e2v[m] = __builtin_fmaf(c[m], 2.0f, -c[m + 5]);
+            }
+        }
+
+        uint32_t d = 0, e1 = 0, e2 = 0;
+#pragma unroll
+        for (int m = 27; m >= 0; m--) { // bit m of each word <-> sample m of the run
+            d = push_sign(d, __float_as_uint(dv[m]));    // a[m+5] - a[m] < 0:  a[m] > a[m+5]   (demod.c:34)
+            e1 = push_sign(e1, __float_as_uint(e1v[m])); // 2 c[m+5] - c[m] < 0: c[m] > 2 c[m+5] (SN = 2, demod.c:83)
+            e2 = push_sign(e2, __float_as_uint(e2v[m])); // 2 c[m] - c[m+5] < 0: c[m+5] > 2 c[m]
+        }
+        asm volatile("" : "+v"(d), "+v"(e1), "+v"(e2)); // (the words are made by every lane: the arithmetic is not to sink under the branch)
+        if (lane < kWaveRuns) { // lane 63 only feeds lane 62
+            pl_d[v] = d;
+            pl_e1[v] = e1;
+            pl_e2[v] = e2;
+        }
+    }
+}
+
+// ------------------------------ Stage A, int8 IQ front end ------------------------------
+// The same tile, the same passes and lanes for a stream of complex int8 samples (scan_iq8_kernel.hip): xin is addressed in complex
+// samples of TWO bytes, so a lane's run of 28 is 56 bytes and a wave's window 3 584.  wlo is a multiple of 28 samples and the buffer's
+// first sample a multiple of 4 (the handle's in-place rule and its staging buffers), so a lane's address is 8-byte aligned and no
+// more.  The loads are stage_a_iq's typed ones one size down: fourteen of 4 bytes, data format 8_8_8_8, the SIGNED scaled number
+// format (the load path converts int8 to f32, exactly), destination select x z y w, so that a load leaves (I0, I1) and (Q0, Q1) in
+// two register pairs and the squares and the sum of two samples are three packed operations.
+//
+// What the planes are made from here is n = I^2 + Q^2, NOT the power sample a = 256 n (i = 16 I: the widened twin's I / 16).  Every
+// plane bit is a sign: of a[m+5] - a[m], and of 2 c' - c with c = trunc(a[k] + a[k+10]).  n is an integer of at most 2^15 and every
+// sum of two at most 2^16, so with n in a's place every operation is exact, trunc is the identity, and each result is the power
+// samples' result times 2^-8 -- exact too (256 n <= 2^23), with the same sign and the same zeros.  The 28 multiplications by 256
+// would change no bit of the planes; pw, where the scale does matter, is pw_at_iq8's.  No float operation here is fused, none
+// rounds.  (Measured against seven untyped 8-byte loads with I^2 + Q^2 as a signed byte dot product, v_dot4c_i32_i8, and one
+// conversion per sample, with and without the scale: profiles/r19_iq8.txt, the typed loads are 9.5 % faster on the kernel's clock.)
+__device__ __forceinline__ void stage_a_iq8(const uint32_t *__restrict__ xin, const int64_t pbuf0, const int64_t p_lo,
+                                            const int64_t p_hi, const int64_t t0, const int K, const int wave, const int lane,
+                                            uint32_t *pl_d, uint32_t *pl_e1, uint32_t *pl_e2)
+{
+    auto first_run = [&](int ps) { return kWaveRuns * (kWaves * ps + wave); };
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    const uint16_t *__restrict__ x16 = reinterpret_cast<const uint16_t *>(xin);
+#pragma unroll 1
+    for (int pass = 0; pass < K; pass++) {
+        const int v0 = first_run(pass); // first run of this wave in this pass
+        const int v = v0 + lane;
+        const int64_t wlo = t0 + (int64_t)kRun * v0; // lane 0's first sample: a multiple of 28, so of 4 (8 bytes)
+        // wave-uniform: every sample this wave loads lies inside the buffer
+        const bool interior = (wlo >= p_lo) && (wlo + kRun * 64 <= p_hi);
+        f32x4 tl[14]; // tl[k] = (I, I', Q, Q') of samples 2k, 2k+1 of the run
+        if (interior) {
+            const uint64_t wbase = (uint64_t)(x16 + (wlo - pbuf0));
+            i32x4 rs;
+            rs.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)wbase);
+            rs.y = __builtin_amdgcn_readfirstlane((int)((uint32_t)(wbase >> 32) & 0xFFFFu)); // stride 0: raw buffer
+            rs.z = 64 * kRun * 2;                                                             // bytes
+            rs.w = (int)(4u | 6u << 3 | 5u << 6 | 7u << 9 /* dst_sel xzyw */ | 3u << 12 /* SSCALED */ | 10u << 15 /* 8_8_8_8 */);
+            const int voff = lane * (kRun * 2);
+            asm volatile("buffer_load_format_xyzw %0, %14, %15, 0 offen\n\t"
+                         "buffer_load_format_xyzw %1, %14, %15, 0 offen offset:4\n\t"
+                         "buffer_load_format_xyzw %2, %14, %15, 0 offen offset:8\n\t"
+                         "buffer_load_format_xyzw %3, %14, %15, 0 offen offset:12\n\t"
+                         "buffer_load_format_xyzw %4, %14, %15, 0 offen offset:16\n\t"
+                         "buffer_load_format_xyzw %5, %14, %15, 0 offen offset:20\n\t"
+                         "buffer_load_format_xyzw %6, %14, %15, 0 offen offset:24\n\t"
+                         "buffer_load_format_xyzw %7, %14, %15, 0 offen offset:28\n\t"
+                         "buffer_load_format_xyzw %8, %14, %15, 0 offen offset:32\n\t"
+                         "buffer_load_format_xyzw %9, %14, %15, 0 offen offset:36\n\t"
+                         "buffer_load_format_xyzw %10, %14, %15, 0 offen offset:40\n\t"
+                         "buffer_load_format_xyzw %11, %14, %15, 0 offen offset:44\n\t"
+                         "buffer_load_format_xyzw %12, %14, %15, 0 offen offset:48\n\t"
+                         "buffer_load_format_xyzw %13, %14, %15, 0 offen offset:52"
+                         "\n\ts_waitcnt vmcnt(0)"
+                         : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]), "=&v"(tl[4]), "=&v"(tl[5]), "=&v"(tl[6]),
+                           "=&v"(tl[7]), "=&v"(tl[8]), "=&v"(tl[9]), "=&v"(tl[10]), "=&v"(tl[11]), "=&v"(tl[12]),
+                           "=&v"(tl[13])
+                         : "v"(voff), "s"(rs)
+                         : "memory");
+        } else {
+            // the ragged end of a buffer (and whatever lies below its first sample): plain 2-byte loads, converted here; a missing
+            // sample is (0, 0)
+            int lane_here = lane;
+            asm volatile("" : "+v"(lane_here)); // (opaque, as in stage_a: nothing of this rare path is precomputed per tile and spilled)
+            const int64_t pr0 = wlo + (int64_t)(kRun * lane_here);
+#pragma unroll
+            for (int k = 0; k < 14; k++) {
+                const int64_t pa = pr0 + 2 * k, pb = pa + 1;
+                const uint32_t d0 = (pa >= p_lo && pa < p_hi) ? (uint32_t)x16[pa - pbuf0] : 0u;
+                const uint32_t d1 = (pb >= p_lo && pb < p_hi) ? (uint32_t)x16[pb - pbuf0] : 0u;
+                tl[k] = f32x4{(float)(int)(int8_t)(uint8_t)(d0 & 0xFFu), (float)(int)(int8_t)(uint8_t)(d1 & 0xFFu),
+                              (float)(int)(int8_t)(uint8_t)(d0 >> 8), (float)(int)(int8_t)(uint8_t)(d1 >> 8)};
+            }
+        }
+        // a[0..27]: this run, as I^2 + Q^2 (the head of this function); a[28..43]: the first 16 samples of the next run (next lane)
+        float a[44];
+#pragma unroll
+        for (int k = 0; k < 14; k++) {
+            const f32x2 ii = {tl[k].x, tl[k].y}, qq = {tl[k].z, tl[k].w};
+            f32x2 s = ii * ii + qq * qq;
             asm volatile("" : "+v"(s)); // (the 28 samples first, in this order, then the planes: 96 registers hold either, not a mix)
             a[2 * k] = s.x;
             a[2 * k + 1] = s.y;

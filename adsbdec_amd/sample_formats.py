@@ -23,6 +23,15 @@ and float32 POWER samples (the library's _power calls: the reference's ampbuff s
 numpy statement of their input domain (power_domain_ok) and a converter that writes the power file of an IQ capture:
 
     python -m adsbdec_amd.sample_formats -t 2 --power in.s16iq out.pw   # iq_power of an int16 IQ capture (-t 0: of a float32 one)
+
+and complex int8 captures (the _iq calls' fmt 8 -- the library's own number, not one of airspy_rx: hackrf_transfer's cs8, bladeRF and
+USRP sc8), which are decoded as their widened int16 twin is:
+
+    INT8_IQ       int8 (I, Q);  twin = (I << 8, Q << 8) as INT16_IQ;  power sample a = 256 (I^2 + Q^2), an exact integer <= 2^23
+
+    python -m adsbdec_amd.sample_formats -t 8 in.s16iq out.cs8          # int16 IQ capture -> int8 (x >> 8); stderr counts low bits lost
+    python -m adsbdec_amd.sample_formats -t 8 --back in.cs8 out.s16iq   # the widened twin (exact)
+    python -m adsbdec_amd.sample_formats -t 8 --power in.cs8 out.pw     # its power samples
 """
 from __future__ import annotations
 
@@ -32,10 +41,10 @@ import sys
 import numpy as np
 
 FLOAT32_REAL, INT16_REAL = 1, 3
-FLOAT32_IQ, INT16_IQ = 0, 2
+FLOAT32_IQ, INT16_IQ, INT8_IQ = 0, 2, 8
 DTYPES = {FLOAT32_REAL: np.dtype("<f4"), INT16_REAL: np.dtype("<i2")}
-IQ_DTYPES = {FLOAT32_IQ: np.dtype("<f4"), INT16_IQ: np.dtype("<i2")}
-NAMES = {FLOAT32_REAL: "FLOAT32_REAL", INT16_REAL: "INT16_REAL", FLOAT32_IQ: "FLOAT32_IQ", INT16_IQ: "INT16_IQ"}
+IQ_DTYPES = {FLOAT32_IQ: np.dtype("<f4"), INT16_IQ: np.dtype("<i2"), INT8_IQ: np.dtype("i1")}
+NAMES = {FLOAT32_REAL: "FLOAT32_REAL", INT16_REAL: "INT16_REAL", FLOAT32_IQ: "FLOAT32_IQ", INT16_IQ: "INT16_IQ", INT8_IQ: "INT8_IQ"}
 
 
 def _codes(x) -> np.ndarray:
@@ -120,11 +129,25 @@ def to_int16_iq(x):
     return r, int(inexact.sum()), int(clamped.sum())
 
 
+def widen_int8_iq(x8) -> np.ndarray:
+    """int8 IQ scalars -> the int16 IQ scalars of the widened twin (x << 8: exact), same shape."""
+    return (np.asarray(x8, dtype=np.int8).astype(np.int16) * np.int16(256)).astype("<i2")
+
+
+def to_int8_iq(x16):
+    """int16 IQ scalars -> (int8 scalars, inexact): x >> 8, an arithmetic shift; inexact counts the scalars whose low 8 bits are
+    not all zero (what the shift drops)."""
+    x = np.asarray(x16, dtype=np.int16)
+    return (x >> 8).astype(np.int8), int(np.count_nonzero(x & 0xFF))
+
+
 def iq_power(x, fmt: int = INT16_IQ) -> np.ndarray:
     """The power samples of a complex capture (scalars I, Q, I, Q, ...: any shape with an even number of them) as the library
     defines them: strict binary32, two rounded products and a rounded sum, one power sample per complex sample."""
     if fmt == FLOAT32_IQ:
         x = flags_float32_iq(x)[0]
+    elif fmt == INT8_IQ:                                        # the widened twin's samples: 256 (I^2 + Q^2), exact
+        x = widen_int8_iq(x)
     elif fmt != INT16_IQ:
         raise ValueError(f"format {fmt} is not an IQ format")
     s = np.asarray(x, dtype=np.int16).reshape(-1, 2).astype(np.float32) * np.float32(0.0625)
@@ -154,6 +177,23 @@ def _main_power(a) -> int:
     return 0
 
 
+def _main_iq8(a) -> int:
+    dt = IQ_DTYPES[INT8_IQ] if a.back else IQ_DTYPES[INT16_IQ]
+    b = np.fromfile(a.src, dtype=np.uint8)
+    cut = b.size % (2 * dt.itemsize)
+    if cut:
+        sys.stderr.write(f"{a.src}: {cut} trailing bytes (a partial sample) ignored\n")
+    x = b[: b.size - cut].view(dt)
+    if a.back:
+        widen_int8_iq(x).tofile(a.dst)
+    else:
+        r, inexact = to_int8_iq(x)
+        if inexact:
+            sys.stderr.write(f"{a.src}: {inexact} of {x.size} scalars are not on the int8 grid (low bits dropped)\n")
+        r.tofile(a.dst)
+    return 0
+
+
 def _main_iq(a) -> int:
     dt = IQ_DTYPES[FLOAT32_IQ] if a.back else IQ_DTYPES[INT16_IQ]
     b = np.fromfile(a.src, dtype=np.uint8)
@@ -173,8 +213,9 @@ def _main_iq(a) -> int:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m adsbdec_amd.sample_formats", description=__doc__.split("\n\n")[0])
-    ap.add_argument("-t", type=int, choices=sorted(DTYPES) + [FLOAT32_IQ, INT16_IQ], required=True,
-                    help="1 = FLOAT32_REAL, 3 = INT16_REAL (as airspy_rx -t); 0 = between INT16_IQ and FLOAT32_IQ; with --power: 2 / 0, the format of src")
+    ap.add_argument("-t", type=int, choices=sorted(DTYPES) + [FLOAT32_IQ, INT16_IQ, INT8_IQ], required=True,
+                    help="1 = FLOAT32_REAL, 3 = INT16_REAL (as airspy_rx -t); 0 = between INT16_IQ and FLOAT32_IQ; 8 = between INT16_IQ and INT8_IQ; "
+                         "with --power: 2 / 0 / 8, the format of src")
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--back", action="store_true", help="the format -> uint16 codes instead of uint16 codes -> the format")
@@ -182,12 +223,14 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.power:
         if a.t not in IQ_DTYPES or a.back:
-            ap.error("--power takes -t 2 or -t 0 and no --back")
+            ap.error("--power takes -t 2, -t 0 or -t 8 and no --back")
         return _main_power(a)
     if a.t == INT16_IQ:
         ap.error("-t 2 goes with --power only (the converter between the IQ formats is -t 0)")
     if a.t == FLOAT32_IQ:
         return _main_iq(a)
+    if a.t == INT8_IQ:
+        return _main_iq8(a)
     dt = DTYPES[a.t] if a.back else np.dtype("<u2")
     b = np.fromfile(a.src, dtype=np.uint8)
     cut = b.size % dt.itemsize

@@ -133,8 +133,8 @@ int adsb_get_format_report(const adsb_decoder *d, adsb_format_report *out);
  * has measured libairspy's filter gain).  FLOAT32_IQ: binary32 (I, Q), nominal [-1, 1); each scalar r = rint(32768 x), ties to even, clamped to [-32768, 32767] (NaN -> 0, +-Inf clamped), then as INT16_IQ: 1/16 ADC LSB.  libairspy's float path need not sit on that grid: expect adsb_get_format_report's inexact (per
  * scalar) to be non-zero for real -t 0 files.  Power samples enter in twos (air.c:94-99): a trailing odd sample at adsb_finish is never seen.  n counts COMPLEX
  * samples.  A stream's kind, real or IQ, is fixed by its first push with samples after adsb_create / adsb_reset; the other kind then returns -1.  Also refused, handle unchanged: fmt not 0 / 2, NULL with n > 0, a device pointer not 4-byte aligned, a stream reaching 2^31 complex samples, an adsb_set_long_stream handle.
- * fmt 2 device pointers: in place when 16-byte aligned at a multiple of 4 complex samples, else staged; fmt 0: converted on the GPU (FLOAT32_REAL's buffers). */
-enum { ADSB_FMT_FLOAT32_IQ = 0, ADSB_FMT_INT16_IQ = 2 }; size_t adsb_iq_bytes(int fmt, size_t n); /* bytes of n complex samples: 8 n, 4 n; 0 for anything else */
+ * fmt 2 device pointers: in place when 16-byte aligned at a multiple of 4 complex samples, else staged; fmt 0: converted on the GPU (FLOAT32_REAL's buffers).  INT8_IQ = 8 is NOT an airspy_rx -t number (the name means "8 bits"): interleaved signed bytes I, Q, two per complex sample at 10 MS/s -- hackrf_transfer's cs8, bladeRF / USRP sc8.  Decoded exactly as fmt 2 decodes the widened twin (I << 8, Q << 8): a[m] = 256 (I^2 + Q^2), an integer <= 2^23, exact in binary32; never converted, so adsb_get_format_report says (0, 0, 0).  A stream kind of its own: fmt 8 does not mix with fmt 0 / 2, real or power pushes (-1, both named).  Refused like fmt 2, but the device pointer must be 2-byte aligned; in place under fmt 2's rule (16-byte aligned at a multiple of 4 complex samples: the kernel's lanes are then 8-byte aligned, its 4-byte loads ask for less), anything else staged.  Not exported (adsb_power_device_iq), not sharded. */
+enum { ADSB_FMT_FLOAT32_IQ = 0, ADSB_FMT_INT16_IQ = 2, ADSB_FMT_INT8_IQ = 8 }; size_t adsb_iq_bytes(int fmt, size_t n); /* bytes of n complex samples: 8 n, 4 n, 2 n; 0 for anything else */
 int adsb_push_iq(adsb_decoder *d, int fmt, const void *samples, size_t n); int adsb_push_iq_async(adsb_decoder *d, int fmt, const void *samples, size_t n);
 int adsb_push_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n); int adsb_push_device_iq_final(adsb_decoder *d, int fmt, const void *device_samples, size_t n);
 long adsb_decode_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_frame **frames);

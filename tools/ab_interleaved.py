@@ -2,6 +2,7 @@
 """A/B of several builds of the library IN ONE PROCESS, launches interleaved.
 
     python tools/ab_interleaved.py [--dense10] [--rounds 40] [--steps 10] name=path/to/libadsbdec_amd.so ...
+    python tools/ab_interleaved.py --iq8 ...    # adsb_decode_device_iq fmt 8 on 128 Mi complex int8 samples (scan_iq8_kernel.hip)
 
 Separate processes on the same box differ by 2-3 % from run to run (clock governor, which CUs a process gets first): more
 than most of the changes round 6 tried.  Here every build is dlopen'ed side by side (they share the one HIP runtime), each
@@ -25,7 +26,7 @@ from bench import make_dense, make_dense10, make_gate_storm, make_workload  # no
 
 def bind(path):
     L = C.CDLL(path)
-    for name in ("adsb_config_init", "adsb_create", "adsb_destroy", "adsb_decode_device", "adsb_get_profile_sized", "adsb_last_error"):
+    for name in ("adsb_config_init", "adsb_create", "adsb_destroy", "adsb_decode_device", "adsb_decode_device_iq", "adsb_get_profile_sized", "adsb_last_error"):
         res, args = capi.SYMBOLS[name]
         try:
             fn = getattr(L, name)
@@ -43,6 +44,7 @@ def main():
     storm = "--gate-storm" in args
     noise = "--dense" in args
     stats = "--stats" in args
+    iq8 = "--iq8" in args  # complex int8 samples through adsb_decode_device_iq fmt 8: make_iq_workload quantised with >> 8
     rounds = int(args[args.index("--rounds") + 1]) if "--rounds" in args else 40
     steps = int(args[args.index("--steps") + 1]) if "--steps" in args else 10
     builds = []  # name=path[@passes=N[,big_tiles=M]]: the same library under several adsb_debug_config settings
@@ -53,7 +55,14 @@ def main():
             builds.append((name, path, dict(kv.split("=") for kv in knobs.split(",") if kv)))
     n = int(args[args.index("--samples") + 1]) if "--samples" in args else 256 << 20
     n -= n % 28
-    x = make_dense10(torch, n, 101) if dense10 else make_gate_storm(torch, n, 102) if storm else make_dense(torch, n, 100) if noise else make_workload(torch, n, seed=1)[0]
+    if iq8:
+        from adsbdec_amd.sample_formats import to_int8_iq
+        from tools.gen_signal import make_iq_workload
+        block = to_int8_iq(make_iq_workload(1 << 22, seed=1)[0])[0]
+        x = torch.from_numpy(block.reshape(-1)).cuda().repeat(32)
+        n = x.numel() // 2
+    else:
+        x = make_dense10(torch, n, 101) if dense10 else make_gate_storm(torch, n, 102) if storm else make_dense(torch, n, 100) if noise else make_workload(torch, n, seed=1)[0]
     torch.cuda.synchronize()
     hs = []
     keep = []
@@ -89,10 +98,15 @@ def main():
         L.adsb_get_profile_sized(h, C.byref(p), C.sizeof(p))
         return p.big_ms, p.big_launches
 
+    def decode(L, h):
+        if iq8:
+            return L.adsb_decode_device_iq(h, 8, x.data_ptr(), n, C.byref(out))
+        return L.adsb_decode_device(h, x.data_ptr(), x.numel(), C.byref(out))
+
     frames = {}
     for name, L, h in hs:  # warm-up, and every build must find the same frames
         for _ in range(5):
-            frames[name] = L.adsb_decode_device(h, x.data_ptr(), x.numel(), C.byref(out))
+            frames[name] = decode(L, h)
     if len(set(frames.values())) != 1:
         raise SystemExit(f"the builds disagree: {frames}")
     per = {name: [] for name, _, _ in hs}
@@ -103,12 +117,12 @@ def main():
             m0, l0 = kernel_ms(L, h)
             t0 = time.perf_counter()
             for _ in range(steps):
-                L.adsb_decode_device(h, x.data_ptr(), x.numel(), C.byref(out))
+                decode(L, h)
             wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
             m1, l1 = kernel_ms(L, h)
             per[name].append((m1 - m0) / max(1, l1 - l0))
     base = per[hs[0][0]]
-    print(f"{n} samples; workload {'dense10' if dense10 else 'gate_storm' if storm else 'noise 7 %' if noise else 'sparse'}{' +stats' if stats else ''}, {frames[hs[0][0]]} frames, "
+    print(f"{n} samples; workload {'int8 IQ (fmt 8)' if iq8 else 'dense10' if dense10 else 'gate_storm' if storm else 'noise 7 %' if noise else 'sparse'}{' +stats' if stats else ''}, {frames[hs[0][0]]} frames, "
           f"{rounds} rounds x {steps} launches per build, kernel clock, ms per launch")
     for name, _, _ in hs:
         v = sorted(per[name])

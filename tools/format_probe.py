@@ -368,6 +368,117 @@ def power_probe(L, reps, lines):
     torch.cuda.empty_cache()
 
 
+def iq8_probe(L, reps, lines):
+    """Complex int8 captures (fmt 8 of the _iq calls, scan_iq8_kernel.hip), every comparison interleaved in this one process and the
+    A/A spread of the same run -- the same side measured twice, in rotation with the others -- beside every ratio:
+    (a) the scan kernel's own time (cfg.profile) and the call's wall time of adsb_decode_device_iq fmt 8 on 128 Mi complex int8
+        samples (256 MiB) against fmt 2 on the widened twin (512 MiB; scan_iq_kernel.hip, unchanged), the same frames;
+    (b) the fmt 8 call against what a user could do before: widen on the device with torch (x.to(int16) << 8, then a device
+        synchronisation: the library's stream is its own) and adsb_decode_device_iq fmt 2.  GATED: the old route moves five times
+        the bytes, so it has to be slower by more than the A/A spread;
+    (c) one adsb_decode_batch_device_iq fmt 8 of 256 captures of 512 Ki samples against the loop of 256 single calls."""
+    from tools.gen_signal import make_iq_workload
+    from adsbdec_amd.sample_formats import to_int8_iq
+    NC = 1 << 27
+    block16, truth = make_iq_workload(1 << 22, seed=1)
+    block = to_int8_iq(block16)[0]
+    x8 = torch.from_numpy(block.reshape(-1)).cuda().repeat(NC >> 22)
+    widen = lambda: x8.to(torch.int16) << 8
+    tw = widen().contiguous()
+    torch.cuda.synchronize()
+    assert torch.equal(tw[: 1 << 12].cpu(), torch.from_numpy(block.reshape(-1)[: 1 << 12].astype("int16") * 256))
+    decs = {k: capi.Decoder(df18=False, profile=True) for k in ("i16", "i16'", "i8", "i8'", "old")}
+    out = C.POINTER(capi.Frame)()
+
+    def old_route():
+        w = widen()
+        torch.cuda.synchronize()
+        return L.adsb_decode_device_iq(decs["old"]._h, 2, w.data_ptr(), NC, C.byref(out))
+
+    sides = {
+        "int16  adsb_decode_device_iq 2 on the widened twin    ": ("i16", lambda: L.adsb_decode_device_iq(decs["i16"]._h, 2, tw.data_ptr(), NC, C.byref(out))),
+        "int16' the same side again (A/A)                      ": ("i16'", lambda: L.adsb_decode_device_iq(decs["i16'"]._h, 2, tw.data_ptr(), NC, C.byref(out))),
+        "int8   adsb_decode_device_iq 8, 128 Mi complex int8   ": ("i8", lambda: L.adsb_decode_device_iq(decs["i8"]._h, 8, x8.data_ptr(), NC, C.byref(out))),
+        "int8'  the same side again (A/A)                      ": ("i8'", lambda: L.adsb_decode_device_iq(decs["i8'"]._h, 8, x8.data_ptr(), NC, C.byref(out))),
+        "old    torch widening + synchronize + fmt 2           ": ("old", old_route),
+    }
+    frames = {}
+    for name, (k, fn) in sides.items():
+        for _ in range(3):
+            frames[name] = fn()
+        assert frames[name] > 0, (name, L.adsb_last_error(decs[k]._h))
+    names = list(sides)
+    assert len(set(frames.values())) == 1, frames
+    kms, wall = {k: [] for k in sides}, {k: [] for k in sides}
+    steps = 5
+    for r in range(reps):
+        order = names[r % len(names):] + names[:r % len(names)]
+        for name in order:
+            k, fn = sides[name]
+            p0 = decs[k].profile()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+            p1 = decs[k].profile()
+            kms[name].append((p1["big_ms"] - p0["big_ms"]) / max(1, p1["big_launches"] - p0["big_launches"]))
+    n16, n16b, n8, n8b, nold = names
+    ratio = lambda v, a, b: med([x / y for x, y in zip(v[a], v[b])])
+    lines += ["# (a), (b): scan kernel on its own clock (cfg.profile, ms per launch) and the call's wall time; 128 Mi complex samples on every side,",
+              f"#     the same frames; {reps} rounds x {steps} calls per side, the sides in rotation; medians (quartiles of the kernel time)",
+              "#   side                                                    frames   kernel ms (q1 .. q3)            call ms"]
+    for name in names:
+        q = statistics.quantiles(kms[name], n=4)
+        lines.append(f"    {name:55s} {frames[name]:7d}   {med(kms[name]):.5f} ({q[0]:.5f} .. {q[2]:.5f})   {med(wall[name]):8.4f}")
+        print(lines[-1], flush=True)
+    aa_k = max(abs(ratio(kms, n16b, n16) - 1), abs(ratio(kms, n8b, n8) - 1))
+    aa_w = max(abs(ratio(wall, n16b, n16) - 1), abs(ratio(wall, n8b, n8) - 1))
+    lines += ["#   ratios (median over the rounds of the per-round ratio); A/A = the larger |ratio - 1| of the two sides measured twice",
+              f"    (a) int8 / int16   kernel {ratio(kms, n8, n16):.4f} (A/A {aa_k:.4f})   call {ratio(wall, n8, n16):.4f} (A/A {aa_w:.4f})",
+              f"    (b) old / int8     call {ratio(wall, nold, n8):.4f} (A/A {aa_w:.4f})   [the old route's scan kernel / int8's: {ratio(kms, nold, n8):.4f}]"]
+    print("\n".join(lines[-2:]), flush=True)
+    gate_ok = ratio(wall, nold, n8) > 1 + aa_w
+    lines.append(f"    (b) gate: the old route is slower than the fmt 8 call by more than the A/A spread: {'PASS' if gate_ok else 'FAIL'}")
+
+    B, n = 256, 1 << 19
+    nn = (C.c_size_t * B)(*([n] * B))
+    first = (C.c_uint64 * (B + 1))()
+    d_batch, d_loop = capi.Decoder(df18=False), capi.Decoder(df18=False)
+    ptrs = [x8.data_ptr() + 2 * n * i for i in range(B)]
+    p = (C.c_void_p * B)(*ptrs)
+
+    def batch():
+        t0 = time.perf_counter()
+        k = L.adsb_decode_batch_device_iq(d_batch._h, 8, B, p, nn, C.byref(out), first, None)
+        dt = time.perf_counter() - t0
+        assert k >= 0, L.adsb_last_error(d_batch._h)
+        return dt, [int(first[i + 1] - first[i]) for i in range(B)]
+
+    def loop():
+        per = []
+        t0 = time.perf_counter()
+        for i in range(B):
+            per.append(L.adsb_decode_device_iq(d_loop._h, 8, ptrs[i], n, d_loop._out_ref))
+        return time.perf_counter() - t0, per
+
+    (_, fb), (_, fl) = batch(), loop()
+    assert fb == fl, "frames per capture differ"
+    tb, tl = [], []
+    for _ in range(reps):
+        tb.append(batch()[0])
+        tl.append(loop()[0])
+    lines += ["#", "# (c) one adsb_decode_batch_device_iq fmt 8 of 256 captures of 512 Ki complex samples (slices of the same buffer) against the loop",
+              "#     of 256 adsb_decode_device_iq fmt 8 calls; frames per capture equal; wall time, medians (reported, not gated)",
+              "#   batch ms    loop ms   loop/batch   frames",
+              f"    {med(tb) * 1e3:9.3f}  {med(tl) * 1e3:9.3f}  {med(tl) / med(tb):10.2f}  {sum(fb):7d}"]
+    print(lines[-1], flush=True)
+    for d in list(decs.values()) + [d_batch, d_loop]:
+        d.close()
+    del x8, tw
+    torch.cuda.empty_cache()
+    return gate_ok
+
+
 def export_probe(L, reps, lines, layouts):
     """The power export (power_export_kernel.hip, the adsb_power_* calls), every comparison interleaved in this one process:
     (a) adsb_power_device on the 256 Mi-sample benchmark workload (512 MiB in, 512 MiB out; the call waits for its kernel, so its wall
@@ -517,12 +628,13 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--iq", action="store_true", help="complex captures (the _iq calls) instead: profiles/r14_iq.txt")
     ap.add_argument("--power", action="store_true", help="float32 power samples (the _power calls) instead: profiles/r15_power.txt")
-    ap.add_argument("--ab", default=None, metavar="PARENT_LIB", help="with --power: the parent commit's libadsbdec_amd.so, for the A/B of the real kernel")
+    ap.add_argument("--iq8", action="store_true", help="complex int8 captures (fmt 8 of the _iq calls) instead: profiles/r19_iq8.txt")
+    ap.add_argument("--ab", default=None, metavar="PARENT_LIB", help="with --power or --iq8: the parent commit's libadsbdec_amd.so, for the A/B of the real kernel")
     ap.add_argument("--export", action="store_true", help="the power export (the adsb_power_* calls) instead: profiles/r17_power_export.txt")
     ap.add_argument("--layout", action="append", default=[], metavar="NAME=LIB", help="with --export: a build of the library with another store layout, measured beside the tree's")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "r17_power_export.txt" if a.export else "r15_power.txt" if a.power else "r14_iq.txt" if a.iq else "r11_formats.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r17_power_export.txt" if a.export else "r19_iq8.txt" if a.iq8 else "r15_power.txt" if a.power else "r14_iq.txt" if a.iq else "r11_formats.txt")
     torch.cuda.set_device(0)
     L = capi.load()
     if a.export:
@@ -538,6 +650,22 @@ def main():
         export_probe(L, a.reps, lines, a.layout)
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+        return
+    if a.iq8:
+        lines = ["# tools/format_probe.py --iq8: complex int8 captures (scan_iq8_kernel.hip, fmt 8 of the _iq calls) beside the int16 IQ kernel, one",
+                 f"# process, {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
+                 "# The capture is one 4 Mi-sample block of tools/gen_signal.py make_iq_workload (seed 1) quantised with >> 8 and repeated 32 times.", "#"]
+        gate_ok = iq8_probe(L, a.reps, lines)
+        if a.ab:
+            real_kernel_ab([f"parent={a.ab}", f"parent2={a.ab}", f"tree={capi.LIB_PATH}"], 2 * a.reps, lines)
+            lines[lines.index("# (c) the existing real-sample kernel (scan_kernel.hip, adsb_decode_device on the sparse 256 Mi-sample workload) across the change:")] = \
+                "# (d) the existing real-sample kernel (scan_kernel.hip, adsb_decode_device on the sparse 256 Mi-sample workload) across the change:"
+        else:
+            lines += ["#", "# (d) not measured in this run: no --ab parent library given"]
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        if not gate_ok:
+            raise SystemExit("(b): the fmt 8 call is not faster than torch widening + fmt 2 by more than the A/A spread")
         return
     if a.power:
         lines = ["# tools/format_probe.py --power: float32 power samples (scan_power_kernel.hip, the _power calls) beside the IQ kernel, one process,",
