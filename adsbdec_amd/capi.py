@@ -209,6 +209,11 @@ SYMBOLS = {
     "adsb_power_device_as": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "adsb_power_device_packed": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "adsb_power_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "adsb_power_batch_device": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_power_batch_device_as": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_power_batch_device_packed": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_power_batch_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_power_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -900,6 +905,39 @@ class Decoder:
         """The power samples of a capture in host memory: power_window_host from the stream's start, 2 (n // 4) floats."""
         x = np.ascontiguousarray(x, dtype=np.uint16).reshape(-1)
         return self.power_window_host(x, 0, 0, 2 * (x.size // 4))
+
+    # ---- the export of a batch of captures in one launch (include/adsbdec_amd.h: adsb_power_batch_*)
+    @staticmethod
+    def _power_batch_args(ptrs, ns, out_ptrs, caps):
+        k = len(ns)
+        assert len(ptrs) == len(out_ptrs) == len(caps) == k
+        arr = lambda t, vals: (t * max(1, k))(*vals)
+        return (k, arr(C.c_void_p, [int(v) if v else None for v in ptrs]), arr(C.c_size_t, [int(v) for v in ns]),
+                arr(C.c_void_p, [int(v) if v else None for v in out_ptrs]), arr(C.c_size_t, [int(v) for v in caps]))
+
+    def power_batch_device(self, ptrs, ns, out_ptrs, caps) -> int:
+        """adsb_power_batch_device: capture i (ns[i] uint16 samples in HBM at ptrs[i]) -> its 2 (ns[i] // 4) power samples at
+        out_ptrs[i], as power_device writes them for it alone; one launch for all.  Returns the floats written in all."""
+        return self._power_call("adsb_power_batch_device", *self._power_batch_args(ptrs, ns, out_ptrs, caps))
+
+    def power_batch_device_as(self, fmt: int, ptrs, ns, out_ptrs, caps) -> int:
+        return self._power_call("adsb_power_batch_device_as", fmt, *self._power_batch_args(ptrs, ns, out_ptrs, caps))
+
+    def power_batch_device_packed(self, ptrs, ns, out_ptrs, caps) -> int:
+        return self._power_call("adsb_power_batch_device_packed", *self._power_batch_args(ptrs, ns, out_ptrs, caps))
+
+    def power_batch_device_iq(self, fmt: int, ptrs, ns, out_ptrs, caps) -> int:
+        """adsb_power_batch_device_iq: ns[i] complex samples -> ns[i] power samples at out_ptrs[i]."""
+        return self._power_call("adsb_power_batch_device_iq", fmt, *self._power_batch_args(ptrs, ns, out_ptrs, caps))
+
+    def power_batch(self, arrays) -> list:
+        """The power samples of uint16 captures in host memory, a float32 array of 2 (n // 4) each: adsb_power_batch_host."""
+        arrays = [np.ascontiguousarray(a, dtype=np.uint16).reshape(-1) for a in arrays]
+        outs = [np.empty(2 * (a.size // 4), dtype=np.float32) for a in arrays]
+        args = self._power_batch_args([a.ctypes.data if a.size else None for a in arrays], [a.size for a in arrays],
+                                      [o.ctypes.data if o.size else None for o in outs], [o.size for o in outs])
+        assert self._power_call("adsb_power_batch_host", *args) == sum(o.size for o in outs)
+        return outs
 
     def format_report(self):
         """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""

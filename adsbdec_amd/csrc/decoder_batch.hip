@@ -396,6 +396,19 @@ int batch_refusal_power(adsb_decoder *d, const char *what, size_t n_captures, co
 
 } // namespace
 
+// decoder_export_batch.hip: the batch exports unpack and convert into the same scratch, by the same one launch
+int adsb::batch_unpack_to_scratch(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n,
+                                  std::vector<const void *> &at)
+{
+    return batch_unpack(d, what, n_captures, src, n, at);
+}
+
+int adsb::batch_convert_to_scratch(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
+                                   std::vector<const void *> &at)
+{
+    return batch_convert(d, what, fmt, n_captures, src, n, at);
+}
+
 extern "C" {
 
 long adsb_decode_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,

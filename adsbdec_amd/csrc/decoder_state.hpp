@@ -6,6 +6,7 @@
 //   decoder_batch.hip      a batch of independent captures (adsb_decode_batch_*)
 //   decoder_shard.hip      the shard calls of the multi-GPU driver (adsb_scan_shard*, adsb_shard_begin / _end)
 //   decoder_export.hip     the export calls (adsb_power_*): the front end's power samples into an array of the caller's
+//   decoder_export_batch.hip  ... of a batch of captures in one launch (adsb_power_batch_*)
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
 
@@ -301,6 +302,7 @@ struct adsb_decoder {
     std::vector<uint64_t> batch_tries, batch_tbuf;
     std::vector<adsb_stats> batch_per;
     adsb::Table batch_tab, unpack_tab;
+    adsb::Table export_tab; // adsb_power_batch_*: the export launch's table, a row per capture that has power samples (power_export_batch.hpp)
     adsb::Buf<uint8_t> batch_in, batch_land; // .cap bytes
     adsb::Buf<uint16_t> batch_unpacked;      // .cap samples
     // the last packed or converted batch call: every capture's first sample in batch_unpacked, then the end (for a converted IQ
@@ -459,6 +461,12 @@ void book_launch(adsb_decoder *d, ScanSlot &s, uint64_t offsets);
 int regrow_if_overflowed(adsb_decoder *d, ScanSlot &s, int attempt);
 void start_reader(adsb_decoder *d);
 void start_gang(adsb_decoder *d, int helpers);
+// decoder_batch.hip: the packed captures / the captures of format fmt at src[] -> uint16 samples in batch_unpacked by ONE launch on
+// the scan stream, capture i from at[i] on (a 128-byte boundary); not waited for
+int batch_unpack_to_scratch(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n,
+                            std::vector<const void *> &at);
+int batch_convert_to_scratch(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
+                             std::vector<const void *> &at);
 // decoder_lifecycle.hip
 void set_create_error(const char *why); // what adsb_last_error(NULL) shows: a call without a handle has failed
 

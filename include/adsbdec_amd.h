@@ -160,13 +160,13 @@ long adsb_decode_batch_host_power(adsb_decoder *d, size_t n_captures, const floa
  *   3. first_sample + n < 2^32, on adsb_set_long_stream handles too.  4. Returns m_end - m_begin, every float written; an empty window launches nothing.
  *   5. The handle's stream and resolver stay untouched: callable between pushes.  6. _as and _iq (fmt 0) add to adsb_get_format_report.
  * _host: through buffers the handle keeps.  adsb_power_device: the window (0, n, 0, 2 (n / 4)).  _as (fmt 1 | 3) / _packed: through the scratch of
- * adsb_decode_device_as / _packed, shared with them.  _iq (fmt 2 | 0): n COMPLEX samples -> n power samples. */
+ * adsb_decode_device_as / _packed, shared with them.  _iq (fmt 2 | 0): n COMPLEX samples -> n power samples.  adsb_power_batch_*: a BATCH of captures, capture i exactly as the single call of the same flavour exports it alone (the same floats from device_power[i][0] on; a fresh stream each: the six pairs before its first sample read as silence, never as a neighbour's samples), in ONE export launch behind at most one unpack (_packed) or conversion (_as fmt 1 | 3, _iq fmt 0) launch into the scratch of adsb_decode_batch_device_packed / _as; returns the floats written in all; rules 5 and 6 hold.  Refused (-1, the message names the capture, nothing launched, written or counted): what the single call refuses of a capture, n[i] >= 2^32 (IQ: 2^31), power_cap[i] below its count, n_captures >= 2^32 - 1.  A capture without power samples (n[i] < 4; IQ: 0) may have NULL pointers and costs nothing. */
 long adsb_power_window(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *device_power, size_t power_cap);
-long adsb_power_window_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *power, size_t power_cap);
-long adsb_power_device(adsb_decoder *d, const void *device_samples, size_t n, float *device_power, size_t power_cap);
-long adsb_power_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap);
-long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t n, float *device_power, size_t power_cap);
-long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap);
+long adsb_power_window_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *power, size_t power_cap); long adsb_power_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, float *const *power, const size_t *power_cap);
+long adsb_power_device(adsb_decoder *d, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
+long adsb_power_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
+long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, float *const *device_power, const size_t *power_cap);
+long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
 /* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
  * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. */
 int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);

@@ -6,6 +6,7 @@ comparison interleaved.
     python tools/format_probe.py --iq [--reps 20] [--out profiles/r14_iq.txt]      # complex captures: see iq_probe()
     python tools/format_probe.py --power [--reps 20] [--out profiles/r15_power.txt] [--ab parent=path/to/libadsbdec_amd.so]   # power_probe()
     python tools/format_probe.py --export [--reps 20] [--out profiles/r17_power_export.txt] [--layout name=path/to/libadsbdec_amd.so ...]   # export_probe()
+    python tools/format_probe.py --export-batch [--reps 20] [--out profiles/r20_export_batch.txt] [--ab path/to/parent/libadsbdec_amd.so]   # export_batch_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
     (with counters, and without: a kernel that does not classify its samples at all) and adsb_unpack_packed12 at the same n
@@ -609,6 +610,133 @@ def export_probe(L, reps, lines, layouts):
     print(lines[-1], flush=True)
 
 
+def export_batch_probe(L, reps, lines, parent):
+    """The batch power export (power_export_batch_kernel.hip, the adsb_power_batch_* calls) against the loop of single calls, every
+    comparison interleaved in this one process, wall time of the calls (each waits for its kernels; the ctypes arrays are built once):
+    (a) 256 captures of 1 Mi uint16 samples; (b) the same for _packed, _as fmt 3 and fmt 1, _iq fmt 2 and fmt 0 (512 Ki complex samples
+    each); (c) ONE capture of 256 Mi samples as a batch of one beside adsb_power_device -- the tree's, the tree's again (the A/A) and
+    the parent commit's (--ab), loaded into this process; (d) 4096 captures of 2048 samples, every pass a plain-load pass."""
+    import numpy as np
+    from adsbdec_amd.packed12 import pack12
+    t, _ = make_workload(torch, N, seed=1)
+    d = capi.Decoder()
+    h = d._h
+    out = torch.empty(N // 2, dtype=torch.float32, device="cuda")
+    out2 = torch.empty(N // 2, dtype=torch.float32, device="cuda")
+
+    def arrays(base, stride_bytes, ns, obase, counts):
+        k = len(ns)
+        oat = np.concatenate([[0], np.cumsum(counts)[:-1]]) * 4
+        return (k, (C.c_void_p * k)(*[base + i * stride_bytes for i in range(k)]), (C.c_size_t * k)(*ns),
+                (C.c_void_p * k)(*[obase + int(o) for o in oat]), (C.c_size_t * k)(*counts))
+
+    def leg(title, batch_fn, single_fn, src, elem_bytes, k, n, count, steps):
+        """k captures of n units (elem_bytes each) from src, count floats each: batch, batch again, loop -- in rotation."""
+        A = arrays(src.data_ptr(), int(n * elem_bytes), [n] * k, out.data_ptr(), [count] * k)
+        A2 = arrays(src.data_ptr(), int(n * elem_bytes), [n] * k, out2.data_ptr(), [count] * k)
+
+        def batch():
+            assert batch_fn(*A) == k * count
+
+        def loop(B=A2):
+            for i in range(k):
+                single_fn(B[1][i], n, B[3][i], count)
+        for _ in range(2):
+            batch()
+            loop()
+        torch.cuda.synchronize()
+        assert torch.equal(out[: k * count].view(torch.int32), out2[: k * count].view(torch.int32)), title + ": the batch and the loop write other floats"
+        sides = {"batch": batch, "batch again (the A/A)": batch, "loop of single calls": loop}
+        wall = {s_: [] for s_ in sides}
+        names = list(sides)
+        for r in range(reps):
+            for name in names[r % 3:] + names[:r % 3]:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    sides[name]()
+                wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        aa = [b / a_ for a_, b in zip(wall[names[0]], wall[names[1]])]
+        ratio = [b / a_ for a_, b in zip(wall[names[0]], wall[names[2]])]
+        qa, qr = statistics.quantiles(aa, n=4), statistics.quantiles(ratio, n=4)
+        lines.append(f"    {title:34s} batch {med(wall[names[0]]):9.4f} ms   loop {med(wall[names[2]]):9.4f} ms   loop / batch {med(ratio):7.3f} ({qr[0]:.3f} .. {qr[2]:.3f})"
+                     f"   A/A {med(aa):.4f} ({qa[0]:.4f} .. {qa[2]:.4f})")
+        print(lines[-1], flush=True)
+        return med(ratio), med(aa)
+
+    K, N1 = 256, 1 << 20
+    lines += [f"# (a), (b) {K} captures side by side in one allocation; {reps} rounds x 3 calls per side, the sides in rotation; medians of the rounds (quartiles);",
+              "#     every leg: the batch and the loop write the same floats (compared on the device) before anything is timed",
+              "#   leg                                  one batch call        256 single calls     ratio of the rounds                    batch / batch"]
+    S1 = lambda name: (lambda p, n, o, c: getattr(L, name)(h, p, n, o, c))
+    S2 = lambda name, fmt: (lambda p, n, o, c: getattr(L, name)(h, fmt, p, n, o, c))
+    B1 = lambda name: (lambda k, p, n, o, c: getattr(L, name)(h, k, p, n, o, c))
+    B2 = lambda name, fmt: (lambda k, p, n, o, c: getattr(L, name)(h, fmt, k, p, n, o, c))
+    leg("(a) uint16, 1 Mi samples each", B1("adsb_power_batch_device"), S1("adsb_power_device"), t, 2, K, N1, N1 // 2, 3)
+    packed = torch.from_numpy(pack12(t[:N1].cpu().numpy().view(np.uint16))).cuda().repeat(K)
+    leg("(b) _packed", B1("adsb_power_batch_device_packed"), S1("adsb_power_device_packed"), packed, 1.5, K, N1, N1 // 2, 3)
+    del packed
+    s16 = ((t.to(torch.int32) - 2048) * 16).to(torch.int16)
+    leg("(b) _as fmt 3 INT16_REAL", B2("adsb_power_batch_device_as", S16), S2("adsb_power_device_as", S16), s16, 2, K, N1, N1 // 2, 3)
+    del s16
+    f32 = (t.to(torch.float32) - 2048.0) / 2048.0
+    leg("(b) _as fmt 1 FLOAT32_REAL", B2("adsb_power_batch_device_as", F32), S2("adsb_power_device_as", F32), f32, 4, K, N1, N1 // 2, 3)
+    del f32
+    iq = t.view(torch.int16)
+    leg("(b) _iq fmt 2, 512 Ki complex each", B2("adsb_power_batch_device_iq", 2), S2("adsb_power_device_iq", 2), iq, 4, K, N1 // 2, N1 // 2, 3)
+    fiq = iq.to(torch.float32) / 32768.0
+    leg("(b) _iq fmt 0, 512 Ki complex each", B2("adsb_power_batch_device_iq", 0), S2("adsb_power_device_iq", 0), fiq, 8, K, N1 // 2, N1 // 2, 3)
+    del fiq, iq
+    lines += ["#", "# (d) 4096 captures of 2048 samples: every pass takes the plain-load road (a capture's first pass always does)"]
+    leg("(d) uint16, 2048 samples each", B1("adsb_power_batch_device"), S1("adsb_power_device"), t, 2, 4096, 2048, 1024, 1)
+
+    # (c) one large capture: the batch of one beside the single call, the tree's and the parent's
+    M = N // 2
+    one = arrays(t.data_ptr(), 0, [N], out.data_ptr(), [M])
+    sides = {"adsb_power_device (tree)": lambda: L.adsb_power_device(h, t.data_ptr(), N, out.data_ptr(), M),
+             "adsb_power_device (tree again: the A/A)": lambda: L.adsb_power_device(h, t.data_ptr(), N, out.data_ptr(), M)}
+    if parent:
+        P = C.CDLL(parent)
+        P.adsb_create.restype = C.c_void_p
+        P.adsb_create.argtypes = [C.c_void_p]
+        P.adsb_power_device.restype = C.c_long
+        P.adsb_power_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        cfg = capi.make_config()
+        ph = P.adsb_create(C.byref(cfg))
+        assert ph, parent
+        sides["adsb_power_device (parent commit)"] = lambda: P.adsb_power_device(ph, t.data_ptr(), N, out.data_ptr(), M)
+    sides["adsb_power_batch_device, n_captures = 1"] = lambda: L.adsb_power_batch_device(h, *one)
+    ref = None
+    for name, fn in sides.items():
+        for _ in range(3):
+            assert fn() == M, name
+        if ref is None:
+            ref = out.clone()
+        else:
+            assert torch.equal(out.view(torch.int32), ref.view(torch.int32)), name + ": other floats"
+        out.zero_()
+    del ref
+    names, steps = list(sides), 5
+    wall = {k_: [] for k_ in names}
+    for r in range(reps):
+        for name in names[r % len(names):] + names[:r % len(names)]:
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                sides[name]()
+            wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+    lines += ["#", f"# (c) ONE capture of 256 Mi samples (512 MiB in, 512 MiB out); {reps} rounds x {steps} calls per side, the sides in rotation; wall time of the call;",
+              "#     every side writes the same floats",
+              "#   side                                        call ms (q1 .. q3)              TB/s    / tree (median of rounds, q1 .. q3)"]
+    base = wall[names[0]]
+    for name in names:
+        q = statistics.quantiles(wall[name], n=4)
+        rr = [a_ / b for a_, b in zip(wall[name], base)]
+        qr = statistics.quantiles(rr, n=4)
+        lines.append(f"    {name:42s} {med(wall[name]):.4f} ({q[0]:.4f} .. {q[2]:.4f})   {2 * 2 * N / (med(wall[name]) * 1e-3) * 1e-12:6.3f}   {med(rr):.4f} ({qr[0]:.4f} .. {qr[2]:.4f})")
+        print(lines[-1], flush=True)
+    if not parent:
+        lines += ["#   (the parent commit's library was not given with --ab: its side was not measured in this run)"]
+
+
 def real_kernel_ab(builds, rounds, lines):
     """(c) the existing real-sample kernel across the change: tools/ab_interleaved.py in a process of its own (it dlopens every build
     side by side), the first build listed twice for the A/A."""
@@ -632,8 +760,21 @@ def main():
     ap.add_argument("--ab", default=None, metavar="PARENT_LIB", help="with --power or --iq8: the parent commit's libadsbdec_amd.so, for the A/B of the real kernel")
     ap.add_argument("--export", action="store_true", help="the power export (the adsb_power_* calls) instead: profiles/r17_power_export.txt")
     ap.add_argument("--layout", action="append", default=[], metavar="NAME=LIB", help="with --export: a build of the library with another store layout, measured beside the tree's")
+    ap.add_argument("--export-batch", action="store_true", help="the batch power export (the adsb_power_batch_* calls) against the loop of single calls instead: profiles/r20_export_batch.txt; --ab: the parent commit's library, for (c)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.export_batch:
+        a.out = a.out or os.path.join(ROOT, "profiles", "r20_export_batch.txt")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --export-batch: the batch power export (power_export_batch_kernel.hip, the adsb_power_batch_* calls) beside",
+                 f"# the loop of single calls, one process, {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
+                 "# The samples are the benchmark's: tools/gen_signal.py make_workload, 256 Mi samples, seed 1, cut into captures (and converted on the device",
+                 "# into each format; the packed leg repeats the first capture's packed bytes).  Wall time of the C calls through ctypes; every call waits for",
+                 "# its kernels, so a loop pays one launch-and-wait round trip per capture (two launches for the flavours that unpack or convert).", "#"]
+        export_batch_probe(capi.load(), a.reps, lines, a.ab)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     a.out = a.out or os.path.join(ROOT, "profiles", "r17_power_export.txt" if a.export else "r19_iq8.txt" if a.iq8 else "r15_power.txt" if a.power else "r14_iq.txt" if a.iq else "r11_formats.txt")
     torch.cuda.set_device(0)
     L = capi.load()
