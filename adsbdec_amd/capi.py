@@ -118,6 +118,15 @@ IQ_DTYPES = {FMT_FLOAT32_IQ: np.dtype("<f4"), FMT_INT16_IQ: np.dtype("<i2"), FMT
 FMT_DTYPES = {FMT_FLOAT32_REAL: np.dtype("<f4"), FMT_INT16_REAL: np.dtype("<i2"), FMT_UINT16_REAL: np.dtype("<u2"), FMT_RAW: np.dtype("<u2")}
 
 
+class TryFrame(C.Structure):
+    """adsb_try_frame (include/adsbdec_amd_diag.h): an accepted frame as the try-count kernel reads it, 16 bytes."""
+    _fields_ = [("g", C.c_uint64), ("span", C.c_uint32), ("pad", C.c_uint32)]
+
+
+TRY_FRAME_DTYPE = np.dtype([("g", "<u8"), ("span", "<u4"), ("pad", "<u4")])   # the same record for numpy arrays
+TRY_REGION = 4096                                                             # try words per tile region (csrc/scan_kernel.h kTryRegion)
+
+
 class Profile(C.Structure):
     _fields_ = [("launches", C.c_uint64), ("relaunches", C.c_uint64), ("offsets", C.c_uint64),
                 ("kernel_ms", C.c_double), ("last_kernel_ms", C.c_double), ("last_offsets", C.c_uint64),
@@ -217,6 +226,9 @@ SYMBOLS = {
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "adsb_count_tries_alone": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adsb_multi_decode_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int,
                                                 C.POINTER(C.POINTER(Frame)), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     "adsb_multi_decode_batch_files": (C.c_long, [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_int,

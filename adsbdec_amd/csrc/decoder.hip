@@ -1451,6 +1451,61 @@ int adsb_convert_samples(void *dst_u16, const void *src, int fmt, size_t n, uint
     return -1;
 }
 
+int adsb_count_tries_alone(const uint32_t *tries, uint32_t n_tries, const uint32_t *regions, const uint32_t *region_counts,
+                           uint32_t n_tiles, int passes, uint32_t big_tiles, uint64_t g_base, const uint64_t *carry_in,
+                           const uint32_t *n_carry, const adsb_try_frame *frames, uint32_t n_frames, uint64_t hi, int final,
+                           uint64_t *carry_out, uint32_t carry_cap, uint32_t *n_carry_out, uint32_t *n_carry_next, uint64_t *acc,
+                           void *stream)
+{
+    static_assert(sizeof(adsb_try_frame) == sizeof(adsb::TryFrame) && offsetof(adsb_try_frame, span) == offsetof(adsb::TryFrame, span),
+                  "adsb_try_frame is TryFrame");
+    char why[240] = "";
+    const bool have_regions = regions || region_counts;
+    auto off = [](const void *p, size_t a) { return (uintptr_t)p % a != 0; };
+    if (!n_carry || !n_carry_out || !n_carry_next || !acc)
+        snprintf(why, sizeof why, "adsb_count_tries_alone: NULL n_carry, n_carry_out, n_carry_next or acc");
+    else if ((n_tries && !tries) || (n_frames && !frames) || (carry_cap && (!carry_in || !carry_out)) ||
+             (have_regions && (!regions || !region_counts)) || (n_tiles && !have_regions))
+        snprintf(why, sizeof why, "adsb_count_tries_alone: NULL buffer with a non-zero count (tries %u, tiles %u, frames %u, carry_cap %u)",
+                 n_tries, n_tiles, n_frames, carry_cap);
+    else if (off(tries, 4) || off(regions, 4) || off(region_counts, 4) || off(n_carry, 4) || off(n_carry_out, 4) || off(n_carry_next, 4) ||
+             off(carry_in, 8) || off(carry_out, 8) || off(frames, 8) || off(acc, 8))
+        snprintf(why, sizeof why, "adsb_count_tries_alone: the 32-bit arrays must be 4-byte, the 64-bit arrays and the frames 8-byte aligned");
+    else if (passes < 2 || passes > adsb::kMaxPasses)
+        snprintf(why, sizeof why, "adsb_count_tries_alone: passes = %d is outside 2..%d", passes, adsb::kMaxPasses);
+    else if (carry_cap == 0 && !final)
+        snprintf(why, sizeof why, "adsb_count_tries_alone: carry_cap == 0 needs final (undecided tries have nowhere to go)");
+    else {
+        adsb::TryCountArgs a{};
+        a.tries = tries;
+        a.n_tries = n_tries;
+        a.regions = have_regions ? regions : nullptr;
+        a.region_counts = have_regions ? region_counts : nullptr;
+        a.n_tiles = have_regions ? n_tiles : 0;
+        a.passes = passes;
+        a.big_tiles = big_tiles;
+        a.g_base = g_base;
+        a.carry_in = carry_in;
+        a.n_carry = n_carry;
+        a.frames = reinterpret_cast<const adsb::TryFrame *>(frames);
+        a.n_frames = n_frames;
+        a.hi = hi;
+        a.final = final ? 1 : 0;
+        a.carry_out = carry_out;
+        a.carry_cap = carry_cap;
+        a.n_carry_out = n_carry_out;
+        a.n_carry_next = n_carry_next;
+        a.acc = reinterpret_cast<unsigned long long *>(acc);
+        const hipError_t e = adsb::launch_count_tries(a, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess)
+            snprintf(why, sizeof why, "adsb_count_tries_alone: launch failed: %s", hipGetErrorString(e));
+    }
+    if (!why[0])
+        return 0;
+    set_create_error(why);
+    return -1;
+}
+
 int adsb_finish(adsb_decoder *d)
 {
     if (!d)

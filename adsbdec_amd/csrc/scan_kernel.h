@@ -138,6 +138,24 @@ constexpr int kTryRegion = 4 * kQueueCap; // try words per tile region: 8.5 % of
 // greedy scan jumped over it -- and three device-side counters accumulate.  Tries at or
 // beyond `hi` are not decided yet and are carried to the next pass.  Nothing comes back to
 // the host until statistics are asked for: a pass is enqueued and forgotten.
+//
+// The contract of a pass (tests/try_count_cases.py restates it in numpy; tests/test_gpu_try_count.py holds the kernel to it try
+// by try through adsb_count_tries_alone).  Given
+//   frames    (g_f, span_f), ascending and NOT overlapping: g_{f+1} >= g_f + span_f, with 1 <= span_f <= ADSB_DECOFFSET_K;
+//   tries     from three sources: tile t's region, the words (g - g_base) << 2 | code at regions[t * kTryRegion ..
+//             + min(region_counts[t], kTryRegion)), EVERY g of them inside tile t's offsets [t0, t1) of the launch geometry
+//             (passes, big_tiles); the launch-wide list, same words, any g >= g_base; the carry-in, (g << 2) | code in 64 bits,
+//             its first min(*n_carry, carry_cap) entries;
+// every try is decided once:
+//   1. g >= hi: appended to the carry-out (final == 0) or dropped (final == 1).  The order of the carry-out is unspecified; only
+//      the first carry_cap appended entries are stored, *n_carry_out counts all of them, and acc[3] becomes non-zero iff more
+//      than carry_cap were appended.
+//   2. otherwise it is SHADOWED iff some frame has g_f < g < g_f + span_f -- both strict: a frame's own offset is a visited Try,
+//      the offset behind its span is where the scan goes on -- and not counted;
+//   3. otherwise acc[min(code, 2)] += 1.
+// *n_carry_next is zero afterwards; acc[0..2] are 64-bit and accumulate over the passes.  The kernel relies on the three
+// conditions in capitals: the region path looks only at frames that start in [t0 - (ADSB_DECOFFSET_K - 1), t1), in 32-bit
+// arithmetic relative to that window, and the binary search tests one frame, the last that starts below the try.
 struct TryFrame { // an accepted frame as the count kernel needs it (one upload per pass)
     uint64_t g;
     uint32_t span, pad;

@@ -379,6 +379,31 @@ int adsb_convert_samples(void *dst_u16, const void *src, int fmt, size_t n, uint
 /* The same for the scalars of FLOAT32_IQ (the _iq calls, fmt 0): n_scalars float32 at src -> n_scalars int16 at dst_i16 (adsbdec_amd.h: r = rint(32768 x)). */
 int adsb_convert_iq_float32(void *dst_i16, const void *src, size_t n_scalars, uint64_t *device_counters2, void *stream);
 
+/* ---- the try-count pass of a statistics run on its own (csrc/scan_kernel.h TryCountArgs: the contract; valid.c:46,68) -----------
+ * ONE launch of the count kernel, by the launcher the decoder uses (its grid is the shipped one), over arrays in device memory;
+ * no handle, no state.  An accepted frame is an adsb_try_frame; a try word of the list and of the regions is (g - g_base) << 2 |
+ * code, one of the carry lists (g << 2) | code.
+ *   tries / n_tries           the launch-wide list
+ *   regions, region_counts    NULL (both), or n_tiles regions of 4096 words each and their n_tiles counts: tile t's tries, all of
+ *                             them inside tile t's offsets of the geometry (passes 2..32, big_tiles) from g_base on
+ *   frames / n_frames         ascending, not overlapping, span 1..1200
+ *   carry_in, n_carry         tries left by an earlier pass: the first min(*n_carry, carry_cap) entries are read
+ *   hi, final                 tries at or beyond hi go to carry_out (final == 0: carry_cap > 0) or are dropped (final != 0)
+ *   carry_out [carry_cap], n_carry_out (zero before the call), n_carry_next (zeroed by the call), acc (four uint64: [0..2] are
+ *                             ADDED to, [3] is set when more than carry_cap entries were appended)
+ * Enqueued on `stream` (a hipStream_t; NULL: the null stream): the caller synchronizes.  0, or -1 with the reason in
+ * adsb_last_error(NULL) and nothing launched: NULL where a count is non-zero (n_carry, n_carry_out, n_carry_next and acc are
+ * always needed), a pointer not aligned to its element, passes outside 2..32, carry_cap == 0 without final. */
+typedef struct adsb_try_frame {
+    uint64_t g;
+    uint32_t span, pad;
+} adsb_try_frame;
+int adsb_count_tries_alone(const uint32_t *tries, uint32_t n_tries, const uint32_t *regions, const uint32_t *region_counts,
+                           uint32_t n_tiles, int passes, uint32_t big_tiles, uint64_t g_base, const uint64_t *carry_in,
+                           const uint32_t *n_carry, const adsb_try_frame *frames, uint32_t n_frames, uint64_t hi, int final,
+                           uint64_t *carry_out, uint32_t carry_cap, uint32_t *n_carry_out, uint32_t *n_carry_next, uint64_t *acc,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,7 +190,8 @@ def greedy(full, tries, m):
     """The reference's decode of m power samples (m even) from the per-offset lists: air.c:94-99's accumulate / carry around
     demod.c:84-144 -- a deqframe call whenever 40 980 samples or more are buffered, which visits the buffered offsets up to 1 200
     from its end, accepts the first candidate it meets and jumps behind it -- with ts counting the visited offsets and the Try
-    row the try words at visited offsets.  `full`: (g, pw, frame, reserved), ascending.  -> (frames, stats with "fixed").
+    row the try words at visited offsets.  `full`: (g, pw, frame, reserved), ascending.  -> (frames, stats with "fixed", the end of
+    the last visited range: the position the decode stops at, 0 when it visits nothing).
     cases() holds it to oracle.demod_power on every capture; it is what says which frames a list WITH repaired records gives."""
     gs = [c[0] for c in full]
     frames, seen = [], []
@@ -227,7 +228,7 @@ def greedy(full, tries, m):
         vis = (k >= 0) & (tg < hi[np.maximum(k, 0)])
         for code, df in enumerate((11, 17, 18)):
             stats["try"][df] = int(np.count_nonzero(vis & ((tries & np.uint64(3)) == code)))
-    return frames, stats
+    return frames, stats, (seen[-1][1] if seen else 0)
 
 
 def _records(frames):
@@ -236,7 +237,8 @@ def _records(frames):
 
 class Case:
     """One capture: x (what is pushed), a (its power samples), n, n_off, ev[df18] = (candidates with reserved = 0, tries) of every
-    offset, dec[(df18, fix1)] = (frames, stats) of the greedy decode, fixed = the records fix_1bit adds (df18 on)."""
+    offset, dec[(df18, fix1)] = (frames, stats) of the greedy decode, end[df18] = where that decode's last visited range ends, fixed =
+    the records fix_1bit adds (df18 on)."""
 
 
 @functools.lru_cache(maxsize=None)
@@ -256,17 +258,17 @@ def cases(front):
         c.n_off = n_offsets(c.n)
         assert c.a.dtype == np.float32 and c.a.size == c.n and power_domain_ok(c.a), name
         assert c.n_off == 0 or c.n_off - 1 + 1195 < c.n
-        c.ev, c.dec = {}, {}
+        c.ev, c.dec, c.end = {}, {}, {}
         m = c.n - (c.n & 1)
         for df18 in (False, True):
             cands, tries = O.scan_all(c.a, 0, c.n_off, df18)
             c.ev[df18] = ([r + (0,) for r in cands], tries)
             frames, stats = O.demod_power(c.a, df18=df18)
             c.dec[(df18, False)] = (frames, stats)
-            mf, ms = greedy(c.ev[df18][0], tries, m)
+            mf, ms, c.end[df18] = greedy(c.ev[df18][0], tries, m)
             assert _records(mf) == _records(frames) and (ms["try"], ms["ok"], ms["fixed"]) == (stats["try"], stats["ok"], 0), (front, name, df18)
         c.fixed = repairable(O, c.a, *c.ev[True]) if c.n_off else []
-        c.dec[(True, True)] = greedy(sorted(c.ev[True][0] + c.fixed), c.ev[True][1], m)
+        c.dec[(True, True)] = greedy(sorted(c.ev[True][0] + c.fixed), c.ev[True][1], m)[:2]
         out[name] = c
         if name in EDGES:
             gs = [r[0] for r in c.ev[True][0]]

@@ -67,10 +67,10 @@ def cases():
             c.ev[df18] = ([r + (0,) for r in cands], tries)
             frames, stats = O.demod_power(c.a, df18=df18)
             c.dec[(df18, False)] = (frames, stats)
-            mf, ms = F.greedy(c.ev[df18][0], tries, m)
+            mf, ms, _ = F.greedy(c.ev[df18][0], tries, m)
             assert F._records(mf) == F._records(frames) and (ms["try"], ms["ok"], ms["fixed"]) == (stats["try"], stats["ok"], 0), (name, df18)
         c.fixed = F.repairable(O, c.a, *c.ev[True]) if c.n_off else []
-        c.dec[(True, True)] = F.greedy(sorted(c.ev[True][0] + c.fixed), c.ev[True][1], m)
+        c.dec[(True, True)] = F.greedy(sorted(c.ev[True][0] + c.fixed), c.ev[True][1], m)[:2]
         out[name] = c
     assert out["short"].n_off == 0 and [n for n in out if n not in EDGES and n != "short"] == list(KINDS)
     SECONDS["iq8"] = time.perf_counter() - t0
