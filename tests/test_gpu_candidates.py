@@ -89,11 +89,12 @@ def _window(ev, gb, ge):
     return [c + (0,) for c in cands if gb <= c[0] < ge], tries[(g >= gb) & (g < ge)]
 
 
-def _scan(capi, dec, cap, host, fs, n, gb, ge):
-    """adsb_scan_shard (or adsb_scan_shard_host from a pageable copy) -> (candidates as tuples, tries)."""
+def _scan(capi, dec, cap, host, fs, n, gb, ge, **caps):
+    """adsb_scan_shard (or adsb_scan_shard_host from a pageable copy) -> (candidates as tuples, tries).  caps: cand_cap and
+    try_cap of Decoder.scan_shard, for callers whose lists are short (its defaults allocate 8 MB a call)."""
     x, t, _ = cap
     if not host:
-        cands, nc, tries = dec.scan_shard(t.data_ptr() + 2 * fs, fs, n, gb, ge)
+        cands, nc, tries = dec.scan_shard(t.data_ptr() + 2 * fs, fs, n, gb, ge, **caps)
     else:
         L = capi.load()
         buf = np.ascontiguousarray(x[fs:fs + n])
@@ -103,7 +104,21 @@ def _scan(capi, dec, cap, host, fs, n, gb, ge):
                                     tries.ctypes.data_as(C.POINTER(C.c_uint64)), tries.size, C.byref(ntv))
         assert rc == 0, (L.adsb_last_error(dec._h) or b"").decode()
         nc, tries = ncv.value, tries[: ntv.value].copy()
-    return [(int(c.g), int(c.pw), bytes(c.frame[: c.len]), int(c.reserved)) for c in cands[:nc]], tries
+    return _tuples(capi, cands, nc), tries
+
+
+def _tuples(capi, cands, nc):
+    """The first nc records of a capi.Candidate array as (g, pw, bytes, reserved), read through one numpy view of the array."""
+    if not nc:
+        return []
+    size = C.sizeof(capi.Candidate)
+    raw = np.frombuffer(cands, dtype=np.uint8, count=nc * size).reshape(nc, size)
+    at = {name: getattr(capi.Candidate, name).offset for name in ("g", "pw", "len", "frame", "reserved")}
+    g = raw[:, at["g"]:at["g"] + 8].copy().view(np.uint64)[:, 0].tolist()
+    pw = raw[:, at["pw"]:at["pw"] + 4].copy().view(np.uint32)[:, 0].tolist()
+    ln, res = raw[:, at["len"]].tolist(), raw[:, at["reserved"]].tolist()
+    fr = raw[:, at["frame"]:at["frame"] + 14].tobytes()
+    return [(g[i], pw[i], fr[14 * i:14 * i + ln[i]], res[i]) for i in range(nc)]
 
 
 @pytest.mark.limit(120)
