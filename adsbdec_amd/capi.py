@@ -109,6 +109,11 @@ class FormatReport(C.Structure):
     _fields_ = [("converted", C.c_uint64), ("inexact", C.c_uint64), ("clamped", C.c_uint64)]
 
 
+class LevelReport(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("negative", C.c_uint64), ("rail_lo", C.c_uint64), ("rail_hi", C.c_uint64), ("over", C.c_uint64),
+                ("hist", C.c_uint64 * 2048)]
+
+
 # fmt of the _as calls: the airspy_rx -t numbers (include/adsbdec_amd.h)
 FMT_FLOAT32_REAL, FMT_INT16_REAL, FMT_UINT16_REAL, FMT_RAW = 1, 3, 4, 5
 # fmt of the _iq calls (complex captures): arrays of shape (n, 2) = (I, Q), or flat ones of 2 n scalars
@@ -223,6 +228,12 @@ SYMBOLS = {
     "adsb_power_batch_device_packed": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adsb_power_batch_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adsb_power_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_level_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_level_device_as": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_level_device_packed": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_level_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_level_device_power": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_level_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -950,6 +961,52 @@ class Decoder:
                                       [o.ctypes.data if o.size else None for o in outs], [o.size for o in outs])
         assert self._power_call("adsb_power_batch_host", *args) == sum(o.size for o in outs)
         return outs
+
+    # ---- the level calls (include/adsbdec_amd.h: adsb_level_*): the power samples the export of the same flavour writes, reduced to a
+    # report (counters and a 2048-bin histogram of the floats' bit patterns) and an envelope of one float per 28 power samples
+    @staticmethod
+    def level_dict(r: "LevelReport", env=None) -> dict:
+        """A LevelReport as the dict adsbdec_amd.levels.level_report returns (env: None, or the float32 array that goes with it)."""
+        out = {k: int(getattr(r, k)) for k in ("samples", "negative", "rail_lo", "rail_hi", "over")}
+        out["hist"] = np.ctypeslib.as_array(r.hist).astype(np.uint64)
+        if env is not None:
+            out["env"] = env
+        return out
+
+    def _level_call(self, name, *args, out=None, env_ptr=0, env_cap=0):
+        """-> the report as a dict (no "env": the envelope, if any, is on the device at env_ptr).  out: a LevelReport to fill instead of a new one."""
+        r = LevelReport() if out is None else out
+        if getattr(self._L, name)(self._h, *args, C.byref(r), env_ptr or None, env_cap) < 0:
+            self._check(-1, name)
+        return self.level_dict(r)
+
+    def level_device(self, ptr: int, n: int, env_ptr: int = 0, env_cap: int = 0, out=None) -> dict:
+        """adsb_level_device: a capture of n uint16 samples in HBM as a fresh stream -> the report of its 2 (n // 4) power samples."""
+        return self._level_call("adsb_level_device", ptr, n, out=out, env_ptr=env_ptr, env_cap=env_cap)
+
+    def level_device_as(self, fmt: int, ptr: int, n: int, env_ptr: int = 0, env_cap: int = 0, out=None) -> dict:
+        return self._level_call("adsb_level_device_as", fmt, ptr, n, out=out, env_ptr=env_ptr, env_cap=env_cap)
+
+    def level_device_packed(self, ptr: int, n: int, env_ptr: int = 0, env_cap: int = 0, out=None) -> dict:
+        return self._level_call("adsb_level_device_packed", ptr, n, out=out, env_ptr=env_ptr, env_cap=env_cap)
+
+    def level_device_iq(self, fmt: int, ptr: int, n: int, env_ptr: int = 0, env_cap: int = 0, out=None) -> dict:
+        """adsb_level_device_iq: n complex samples in HBM (fmt 0, 2 or 8) -> the report of their n power samples."""
+        return self._level_call("adsb_level_device_iq", fmt, ptr, n, out=out, env_ptr=env_ptr, env_cap=env_cap)
+
+    def level_device_power(self, ptr: int, n: int, env_ptr: int = 0, env_cap: int = 0, out=None) -> dict:
+        """adsb_level_device_power: n float32 power samples in HBM -> their report (the domain holds iff negative == 0 and hist[1248:] is empty)."""
+        return self._level_call("adsb_level_device_power", ptr, n, out=out, env_ptr=env_ptr, env_cap=env_cap)
+
+    def level(self, x: np.ndarray, env: bool = True) -> dict:
+        """The report of a uint16 capture in host memory, adsb_level_host: the counters, "hist" (np.uint64, 2048) and "env" (np.float32,
+        one per 28 power samples)."""
+        x = np.ascontiguousarray(x, dtype=np.uint16).reshape(-1)
+        e = np.empty(-(-(2 * (x.size // 4)) // 28) if env else 0, dtype=np.float32)
+        r = LevelReport()
+        if self._L.adsb_level_host(self._h, x.ctypes.data if x.size else None, x.size, C.byref(r), e.ctypes.data if e.size else None, e.size) < 0:
+            self._check(-1, "adsb_level_host")
+        return self.level_dict(r, e)
 
     def format_report(self):
         """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""

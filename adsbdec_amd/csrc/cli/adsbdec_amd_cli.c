@@ -28,7 +28,7 @@
  *                   either.
  *     -w            EXTENSION: the file holds float32 POWER samples at 10 MS/s, little-endian: the reference's ampbuff stream itself
  *                   (adsbdec.h:5), from any front end (adsbdec_amd.h: the _power calls).  Input domain: every sample finite, sign bit
- *                   clear, below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); outside it nothing is promised or detected.
+ *                   clear, below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); outside it nothing is promised (-L -w detects it).
  *                   Trailing bytes that do not make a sample are not decoded and stderr says how many.  Not with -t, -q, -p, -G or
  *                   -B; a file below 2^31 samples.
  *     -W out.pw     EXTENSION: EXPORT instead of decoding: write the float32 power samples of the file of -f -- the reference's ampbuff
@@ -39,6 +39,12 @@
  *                   length.  out.pw is created once the GPU is open; a signal between two pieces ends the program with status 1 and a
  *                   message (out.pw then holds the pieces so far).  Not with -w, -t (python -m adsbdec_amd.sample_formats converts
  *                   such files), -p, -G, -B, -s, -l or several -f.
+ *     -L            EXTENSION: REPORT THE LEVELS instead of decoding (adsbdec_amd.h: the adsb_level_* calls): of the power samples -W would
+ *                   write -- or, with -p, -t 1 | 3, -q 2 | 0 | 8 or -w, of that input's -- print `samples M negative N rail_lo A rail_hi B
+ *                   over C`, a line `bin K lower_edge COUNT` per non-empty bin of the histogram (1/8 octave, 0.75 dB), and the median, the
+ *                   99.9th percentile and the peak bin in dB of raw power units (not dBFS: nobody has measured the front end's gain).  The
+ *                   whole file is one capture in one call: a real file below 2^32 samples, IQ and power below 2^31.  Not with -G, -B,
+ *                   -W, -s, -l or several -f.
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -186,7 +192,8 @@ static void usage(void)
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
     printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-q type] [-w] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
     printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n");
-    printf("        adsbdec_amd_cli [-q type] [-d gpu] -W out.pw -f filename\n\n");
+    printf("        adsbdec_amd_cli [-q type] [-d gpu] -W out.pw -f filename\n");
+    printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -f filename\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
     printf("\t-b : output binary beast format\n");
@@ -204,6 +211,10 @@ static void usage(void)
     printf("\t     sign bit clear and below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are fine); not with -t, -q, -p, -G or -B\n");
     printf("\t-W out.pw : (extension) export, do not decode: write the float32 power samples of the file (what -w reads) to out.pw; with -q the\n");
     printf("\t     file is IQ (any length; a real file: below 2^32 samples); not with -w, -t, -p, -G, -B, -s, -l or several -f\n");
+    printf("\t-L : (extension) report the levels, do not decode: the file's power samples (what -W writes; with -w the file's own floats) as\n");
+    printf("\t     counters (samples, negative, codes on the ADC's rails and above 4095), a histogram in bins of 1/8 octave (0.75 dB) and its\n");
+    printf("\t     median, 99.9th percentile and peak in dB of raw power units; input as -p, -t, -q (8 too) or -w say; the whole file in one\n");
+    printf("\t     call (a real file: below 2^32 samples, IQ and power: below 2^31); not with -G, -B, -W, -s, -l or several -f\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
@@ -634,12 +645,138 @@ static int run_export(const char *filename, const char *outpath, int device, int
     _exit(rc); /* (no teardown: see the end of main) */
 }
 
+/* -L: the level report of the file's power samples on stdout; nothing is decoded.  The whole file is ONE capture in ONE call (the
+ * report of a real capture needs every pair's six predecessors, and no level call takes a window): kind 0 uint16 (adsb_level_host,
+ * through the handle's buffers), 1 -t 1 | 3, 2 -p, 3 -q, 4 -w (a device buffer of the program's own). */
+static double bin_db(unsigned k, int *zero)
+{
+    /* the lower edge of bin k = (e, f) is 2^(e - 127) (1 + f / 8), a subnormal bin's 2^-126 f / 8: 10 log10 of it */
+    static const double m_db[8] = {0.0, 0.51152522447381288, 0.96910013008056415, 1.3830269816628146, 1.7609125905568124,
+                                   2.1085336531489318, 2.4303804868629444, 2.7300127206373764};
+    static const double f_db[8] = {0.0, -9.0308998699194358, -6.0205999132796242, -4.2596873227228116, -3.0102999566398121,
+                                   -2.0411998265592479, -1.2493873660829995, -0.57991946977686754};
+    const int e = (int)(k >> 3), f = (int)(k & 7);
+    *zero = k == 0;
+    return e ? 3.0102999566398121 * (e - 127) + m_db[f] : 3.0102999566398121 * -126 + f_db[f];
+}
+
+static unsigned bin_of_quantile(const adsb_level_report *r, double q)
+{
+    uint64_t total = 0, run = 0;
+    for (unsigned k = 0; k < 2048; k++)
+        total += r->hist[k];
+    const double t = q * (double)total;
+    uint64_t need = (uint64_t)t;
+    if ((double)need < t)
+        need++;
+    if (need == 0)
+        need = 1;
+    for (unsigned k = 0; k < 2048; k++)
+        if ((run += r->hist[k]) >= need)
+            return k;
+    return 0;
+}
+
+static void print_db(const char *name, unsigned k, const char *end)
+{
+    int zero;
+    const double db = bin_db(k, &zero);
+    if (zero)
+        printf("%s -inf dB%s", name, end);
+    else if (k >= 2040)
+        printf("%s %s%s", name, k == 2040 ? "inf dB" : "nan", end);
+    else
+        printf("%s %.2f dB%s", name, db, end);
+}
+
+static int run_level(const char *filename, int device, int kind, int fmt)
+{
+    const int fd = open(filename, O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        fprintf(stderr, "%s: cannot read as a regular file: %s\n", filename, fd < 0 ? strerror(errno) : "-L takes the whole file in one call");
+        return 255;
+    }
+    adsb_config cfg;
+    adsb_config_default(&cfg);
+    cfg.device = device;
+    adsb_decoder *dec = adsb_create(&cfg);
+    if (!dec) {
+        fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
+        return 255;
+    }
+    const size_t elem = kind == 0 ? 2 : kind == 1 ? adsb_format_bytes(fmt, 1) : kind == 3 ? adsb_iq_bytes(fmt, 1) : kind == 4 ? sizeof(float) : 0;
+    void *buf = malloc((size_t)sb.st_size + 16), *d_in = NULL;
+    adsb_level_report *rep = (adsb_level_report *)malloc(sizeof *rep);
+    if (!buf || !rep) {
+        fprintf(stderr, "out of memory for the file's %lld bytes\n", (long long)sb.st_size);
+        return 255;
+    }
+    const size_t bytes = read_full(fd, buf, (size_t)sb.st_size);
+    const size_t n = kind == 2 ? bytes / 12 * 8 : bytes / elem, used = kind == 2 ? bytes / 12 * 12 : n * elem;
+    const size_t real_tail = kind <= 1 ? (n % 4) * elem : 0; /* (the reference reads four samples at a time) */
+    if (bytes - used + real_tail)
+        fprintf(stderr, "%zu trailing bytes ignored (%s)\n", bytes - used + real_tail,
+                kind == 2 ? "not a whole 12-byte group of packed samples" : kind <= 1 ? "the reference reads four samples at a time" : "not a whole sample");
+    long got;
+    const char *call = "adsb_level_host";
+    if (kind == 0) {
+        got = adsb_level_host(dec, (const uint16_t *)buf, n, rep, NULL, 0);
+    } else {
+        if (hipSetDevice(device < 0 ? 0 : device) != hipSuccess || (used && hipMalloc(&d_in, used) != hipSuccess) ||
+            (used && hipMemcpy(d_in, buf, used, hipMemcpyHostToDevice) != hipSuccess)) {
+            fprintf(stderr, "cannot bring the file's %zu bytes to the device\n", used);
+            return 255;
+        }
+        if (kind == 1)
+            call = "adsb_level_device_as", got = adsb_level_device_as(dec, fmt, d_in, n, rep, NULL, 0);
+        else if (kind == 2)
+            call = "adsb_level_device_packed", got = adsb_level_device_packed(dec, d_in, n, rep, NULL, 0);
+        else if (kind == 3)
+            call = "adsb_level_device_iq", got = adsb_level_device_iq(dec, fmt, d_in, n, rep, NULL, 0);
+        else
+            call = "adsb_level_device_power", got = adsb_level_device_power(dec, d_in, n, rep, NULL, 0);
+    }
+    if (got < 0) {
+        fprintf(stderr, "%s() failed: %s\n", call, adsb_last_error(dec));
+        return 255;
+    }
+    printf("samples %llu negative %llu rail_lo %llu rail_hi %llu over %llu\n", (unsigned long long)rep->samples, (unsigned long long)rep->negative,
+           (unsigned long long)rep->rail_lo, (unsigned long long)rep->rail_hi, (unsigned long long)rep->over);
+    unsigned peak = 0;
+    uint64_t counted = 0;
+    for (unsigned k = 0; k < 2048; k++) {
+        if (!rep->hist[k])
+            continue;
+        union { uint32_t u; float f; } edge;
+        edge.u = k << 20;
+        if (k < 2040)
+            printf("bin %u %.9g %llu\n", k, (double)edge.f, (unsigned long long)rep->hist[k]);
+        else
+            printf("bin %u %s %llu\n", k, k == 2040 ? "inf" : "nan", (unsigned long long)rep->hist[k]);
+        peak = k;
+        counted += rep->hist[k];
+    }
+    if (counted) { /* (dB of raw power units, not dBFS: nobody has measured the front end's gain) */
+        print_db("median", bin_of_quantile(rep, 0.5), " ");
+        print_db("p99.9", bin_of_quantile(rep, 0.999), " ");
+        print_db("peak", peak, "\n");
+    } else {
+        printf("median none p99.9 none peak none\n");
+    }
+    fflush(stdout);
+    fflush(stderr);
+    if (getenv("ADSB_CLI_CLEAN_EXIT"))
+        exit(0);
+    _exit(0); /* (no teardown: see the end of main) */
+}
+
 int main(int argc, char **argv)
 {
     const char *filename = NULL, *listfile = NULL, *export_path = NULL;
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
-    int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, c;
+    int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, level = 0, c;
     long stype = 5; /* -t: ADSB_FMT_RAW */
     const char *stype_arg = NULL;
     long qtype = -1; /* -q: ADSB_FMT_INT16_IQ / ADSB_FMT_FLOAT32_IQ / ADSB_FMT_INT8_IQ */
@@ -647,7 +784,7 @@ int main(int argc, char **argv)
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:L")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -708,6 +845,9 @@ int main(int argc, char **argv)
         case 'W':
             export_path = optarg;
             break;
+        case 'L':
+            level = 1;
+            break;
         case 't': {
             char *end;
             stype = strtol(optarg, &end, 10);
@@ -728,6 +868,16 @@ int main(int argc, char **argv)
             usage();
             return 1;
         }
+    }
+    if (level && (ndev || listfile || export_path || outmode != SINK_STDOUT || nfiles > 1)) {
+        /* -L reports the levels of one file in one call and decodes nothing: refused before any GPU call */
+        fprintf(stderr, "-L is not supported with %s: %s\n",
+                ndev ? "-G" : listfile ? "-B" : export_path ? "-W" : outmode == SINK_CONNECT ? "-s" : outmode == SINK_LISTEN ? "-l" : "several -f",
+                ndev || listfile         ? "the level report runs on one GPU (-d), one file at a time: no batch and no multi-GPU form"
+                : export_path            ? "a run writes the power samples or reports their levels, not both"
+                : outmode != SINK_STDOUT ? "the report is text on stdout, not packets for a peer"
+                                         : "the report is of one file");
+        return 1;
     }
     if (qtype_arg && qtype == ADSB_FMT_INT8_IQ && (stype_arg || packed || ndev || listfile || power || export_path)) {
         /* int8 IQ is decoded from one file on one GPU and nothing else: refused before any GPU call */
@@ -812,6 +962,15 @@ int main(int argc, char **argv)
     if (!filename || (nfiles > 1 && (ndev == 0 || outmode != SINK_STDOUT)) || (ndev && device >= 0)) {
         usage();
         return 1;
+    }
+    if (level) {
+        if (device >= 0) {
+            restrict_visible_devices(&device, 1);
+        } else if (!getenv("ROCR_VISIBLE_DEVICES") && !getenv("HIP_VISIBLE_DEVICES") && !getenv("ADSB_CLI_ALL_DEVICES")) {
+            int first = 0;
+            restrict_visible_devices(&first, 1);
+        }
+        return run_level(filename, device, converted ? 1 : packed ? 2 : iq ? 3 : power ? 4 : 0, iq ? (int)qtype : (int)stype);
     }
     if (export_path) {
         install_signals();

@@ -7,6 +7,7 @@
 //   decoder_shard.hip      the shard calls of the multi-GPU driver (adsb_scan_shard*, adsb_shard_begin / _end)
 //   decoder_export.hip     the export calls (adsb_power_*): the front end's power samples into an array of the caller's
 //   decoder_export_batch.hip  ... of a batch of captures in one launch (adsb_power_batch_*)
+//   decoder_level.hip      the level calls (adsb_level_*): a capture's power samples reduced to a report and an envelope
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
 
@@ -312,6 +313,10 @@ struct adsb_decoder {
     adsb_stats batch_stats{};
     adsb::Buf<uint16_t> win_buf; // adsb_scan_shard_host, adsb_power_window_host: device copy of the caller's window
     adsb::Buf<float> pow_buf;    // adsb_power_window_host: the window's power samples, copied back from here
+    // the level calls (adsb_level_*, decoder_level.hip): the report's words as the kernels add to them (level.h kLevelWords), zeroed on
+    // the scan stream at the start of a call and copied to the pinned half before it returns; measurement builds: a row per workgroup
+    adsb::Totals<unsigned long long> level;
+    adsb::Buf<uint32_t> level_rows;
 
     int fail(const char *fmt, ...)
     {

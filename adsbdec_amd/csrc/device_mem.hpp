@@ -1,5 +1,5 @@
-// device_mem.hpp -- owners of the HIP resources the host side holds (internal, host-only): a buffer that only grows, an
-// event, a stream.  Each frees what it holds when it goes, so a handle is torn down by `delete` (adsb_destroy only has
+// device_mem.hpp -- owners of the HIP resources the host side holds (internal, host-only): a buffer that only grows (alone, or paired with
+// its pinned twin: Table, Totals), an event, a stream.  Each frees what it holds when it goes, so a handle is torn down by `delete` (adsb_destroy only has
 // to quiesce the streams first) and a failed allocation half-way through a regrow leaks nothing.  Move-only; each
 // converts to the raw pointer or handle it owns, so the HIP calls and the kernels' argument structs take them as they are.
 #pragma once
@@ -72,6 +72,18 @@ struct Table {
         const size_t want = bytes + bytes / 4 + 4096;
         const hipError_t e = dev.reserve(want);
         return e != hipSuccess ? e : host.reserve(want);
+    }
+};
+
+// Totals a kernel adds to on the device and the pinned array the host reads them from: `words` each, allocated together; zeroed
+// and copied back by whoever launches (decoder_level.hip).
+template <class T> struct Totals {
+    Buf<T, Mem::Device> dev;
+    Buf<T, Mem::Pinned> host;
+    hipError_t reserve(size_t words)
+    {
+        const hipError_t e = dev.reserve(words);
+        return e != hipSuccess ? e : host.reserve(words);
     }
 };
 

@@ -1,0 +1,460 @@
+// level_kernel.hip -- the level report of a capture's power samples (include/adsbdec_amd.h: the adsb_level_* calls): a histogram of
+// their bit patterns in 2048 bins (bits >> 20: 8 bins per octave), the maximum of every run of 28 (the envelope), the samples with
+// the sign bit set, and the input's codes on its rails.  Every quantity is a count or an unsigned maximum, so any order of
+// reduction gives the same bits (adsbdec_amd/levels.py level_report is the definition).
+//
+// level_kernel is power_export_kernel (power_export_kernel.hip) up to the end of its FIR: the same pass structure (a wave covers
+// 64 runs of 28 power samples, grid-stride), the same 17 typed buffer loads of a lane's 34 pairs, the same plain-load road where
+// the window leaves the buffer, the same constants written per pass, the same power_run<0> -- and then, instead of the export's
+// stores, the reduction tail.  The load block, the constants and the FIR are a COPY: a function shared with stage_a moved the
+// existing units' code (DESIGN.md section 4 "IQ captures"), and those units compile to the instructions they had.
+// level_units_kernel is the same tail behind an element-wise front end: a lane takes 28 complex int16 samples, complex int8
+// samples or float32 power samples (seven 16-byte loads where the array is 16-byte aligned, as scan_power_kernel's; unit by unit
+// where it is not, and in the capture's last run).
+//
+// The tail, per lane and pass: the run's 28 bit patterns -> one unsigned maximum (a float per lane, 256 contiguous bytes per wave);
+// 28 increments of a histogram in LDS; the codes the lane OWNS -> the rail counters.  A lane's window overlaps its neighbour's by
+// six pairs: the counters look at slots 6 .. 33 only.  Counters are counted per wave on the scalar side: a compare into a lane mask,
+// its population count, a scalar add.
+//
+// Accumulation (DESIGN.md section 4 "Level report" has the measurements; ADSB_LEVEL_HIST picks in a measurement build, the
+// shipped one defines nothing).  The build runs with the compiler's atomic optimizer off, so an LDS add is one per lane; 32-bit
+// counts cannot overflow (a capture has fewer than 2^32 power samples).
+//   bit 0: 0 one histogram per workgroup (8 KiB), 1 one per wave (32 KiB)
+//   bit 1: the wave-uniform shortcut -- when every counting lane of an increment hits the same bin, ONE lane adds their number.
+//          Silence puts all 64 x 28 increments of a pass on bin 0.
+//   bit 2: the run-uniform shortcut instead -- a lane whose 28 samples fall in one bin adds their number at once.  It costs a
+//          minimum beside the envelope's maximum and one compare per run, where bit 1 costs two lane masks per increment.
+// Shipped: 5, a histogram per wave with the run-uniform shortcut.
+// The flush (ADSB_LEVEL_FLUSH): 0 the workgroup adds its non-zero bins to the 64-bit totals with vector atomics, eight
+// wave-instructions of 512 contiguous bytes; 1 it writes a row of 32-bit counts and level_reduce_kernel sums the rows.
+// ADSB_LEVEL_BLOCKS caps the grid: fewer workgroups, fewer adds on the same words.
+#include "scan_stages.h"
+
+#include <algorithm>
+
+#include "level.h"
+
+#ifndef ADSB_LEVEL_HIST
+#define ADSB_LEVEL_HIST 5
+#endif
+#ifndef ADSB_LEVEL_FLUSH
+#define ADSB_LEVEL_FLUSH 0
+#endif
+#ifndef ADSB_LEVEL_BLOCKS
+#define ADSB_LEVEL_BLOCKS 2048
+#endif
+
+namespace adsb {
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kLevelWave = 64 * kRun; // power samples of a wave's pass
+constexpr int kHistCopies = (ADSB_LEVEL_HIST & 1) ? kWaves : 1;
+constexpr int kRowsSlices = 16;       // level_reduce_kernel: the rows are summed in this many interleaved slices
+
+// lanes of the wave for which p holds (wave-uniform: the scalar side counts)
+__device__ __forceinline__ uint32_t lanes(bool p) { return (uint32_t)__builtin_popcountll(__ballot(p)); }
+
+struct Counts { // wave-uniform, over the wave's passes
+    uint32_t negative = 0, rail_lo = 0, rail_hi = 0, over = 0;
+};
+
+// one increment per lane with `on`
+__device__ __forceinline__ void hist_add(uint32_t *hist, const uint32_t bin, const bool on, const int lane)
+{
+#if ADSB_LEVEL_HIST & 2
+    const unsigned long long act = __ballot(on);
+    if (act == 0)
+        return;
+    const int first = __builtin_ctzll(act);
+    const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, first);
+    if (__ballot(on && bin == b0) == act) { // (wave-uniform)
+        if (lane == first)
+            atomicAdd(&hist[b0], (uint32_t)__builtin_popcountll(act));
+        return;
+    }
+#endif
+    if (on)
+        atomicAdd(&hist[bin], 1u);
+}
+
+// The reduction tail of one run: b[k] is the bit pattern of the lane's power sample k, of which the first `left` exist (kFull: all
+// 28, in every lane of the wave).  kSigned: a sample may have its sign bit set (never behind a front end that squares and adds).
+// Returns the run's envelope bits.
+template <bool kFull, bool kSigned>
+__device__ __forceinline__ uint32_t level_tail(const uint32_t (&b)[kRun], const int left, uint32_t *hist, Counts &c, const int lane)
+{
+    uint32_t mx = 0;
+#if ADSB_LEVEL_HIST & 4
+    uint32_t mn = 0xFFFFFFFFu, n_on = (kFull && !kSigned) ? kRun : 0;
+#endif
+#pragma unroll
+    for (int k = 0; k < kRun; k++) {
+        const bool have = kFull || k < left;
+        const bool minus = kSigned && (int32_t)b[k] < 0;
+        if (kSigned)
+            c.negative += lanes(have && minus);
+        const bool on = have && !minus;
+        mx = max(mx, on ? b[k] : 0u);
+#if ADSB_LEVEL_HIST & 4
+        mn = min(mn, on ? b[k] : 0xFFFFFFFFu);
+        if (!(kFull && !kSigned))
+            n_on += on;
+#else
+        hist_add(hist, b[k] >> 20, on, lane);
+#endif
+    }
+#if ADSB_LEVEL_HIST & 4
+    // the run-uniform shortcut: smallest and largest counted pattern in one bin (no counted sample: 4095 against 0) -> one add
+    if ((mn >> 20) == (mx >> 20)) {
+        atomicAdd(&hist[mx >> 20], n_on);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kRun; k++)
+            if ((kFull || k < left) && !(kSigned && (int32_t)b[k] < 0))
+                atomicAdd(&hist[b[k] >> 20], 1u);
+    }
+#endif
+    return mx;
+}
+
+// The codes of the pairs a lane owns (slots 6 .. 33 of its window) as the typed loads hand them over -- integers 0 .. 65535, exact
+// in binary32 -- on the ADC's rails and beyond them.  First the lane's smallest and largest code (as bit patterns: floats that are
+// not negative order as their words do); a pass in which no lane has a 0 or a code from 4095 up -- most passes of most captures --
+// counts nothing.
+template <bool kFull> __device__ __forceinline__ void rails_real(const f32x2 (&vv)[34], const int left, Counts &c)
+{
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+#pragma unroll
+    for (int k = 0; k < kRun; k++) {
+        const float fx = vv[6 + k].x, fy = vv[6 + k].y; // (copies: a bit cast of the vector's element itself reads element 0 for both)
+        const uint32_t x = __builtin_bit_cast(uint32_t, fx), y = __builtin_bit_cast(uint32_t, fy);
+        lo = min(min(lo, x), y); // (a ragged run's codes behind `left` too: they can only send the pass to the counting below)
+        hi = max(max(hi, x), y);
+    }
+    if (__ballot(lo == 0u || hi >= __builtin_bit_cast(uint32_t, 4095.0f)) == 0) // (wave-uniform)
+        return;
+#pragma unroll
+    for (int k = 0; k < kRun; k++) {
+        const bool have = kFull || k < left;
+        const f32x2 v = vv[6 + k];
+        c.rail_lo += lanes(have && v.x == 0.0f) + lanes(have && v.y == 0.0f);
+        c.rail_hi += lanes(have && v.x == 4095.0f) + lanes(have && v.y == 4095.0f);
+        c.over += lanes(have && v.x > 4095.0f) + lanes(have && v.y > 4095.0f);
+    }
+}
+
+// ... of complex samples: u[k] = (I, Q) as two int16 (kKind == kLevelIq16) or two int8 in the low half (kLevelIq8), on the format's
+// minimum and maximum.  The same pre-check with packed 16-bit minima and maxima (int8: of the widened twin, I << 8 and Q << 8).
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+template <int kKind, bool kFull> __device__ __forceinline__ void rails_iq(const uint32_t (&u)[kRun], const int left, Counts &c)
+{
+    constexpr uint32_t kMask = kKind == kLevelIq8 ? 0xFFu : 0xFFFFu, kLo = kKind == kLevelIq8 ? 0x80u : 0x8000u, kHi = kLo - 1;
+    constexpr int kShift = kKind == kLevelIq8 ? 8 : 16;
+    s16x2 lo = {32767, 32767}, hi = {-32768, -32768};
+#pragma unroll
+    for (int k = 0; k < kRun; k++) {
+        const uint32_t w = kKind == kLevelIq8 ? __builtin_amdgcn_perm(0u, u[k], 0x010C000Cu) : u[k]; // bytes (0, I, 0, Q)
+        const s16x2 v = __builtin_bit_cast(s16x2, w);
+        lo = __builtin_elementwise_min(lo, v);
+        hi = __builtin_elementwise_max(hi, v);
+    }
+    constexpr short kTop = kKind == kLevelIq8 ? 0x7F00 : 0x7FFF;
+    if (__ballot(lo.x == -32768 || lo.y == -32768 || hi.x == kTop || hi.y == kTop) == 0) // (wave-uniform)
+        return;
+#pragma unroll
+    for (int k = 0; k < kRun; k++) {
+        const bool have = kFull || k < left;
+        const uint32_t i = u[k] & kMask, q = (u[k] >> kShift) & kMask;
+        c.rail_lo += lanes(have && i == kLo) + lanes(have && q == kLo);
+        c.rail_hi += lanes(have && i == kHi) + lanes(have && q == kHi);
+    }
+}
+
+// ---- what a workgroup does before its first pass and behind its last ----
+__device__ __forceinline__ void block_begin(uint32_t (*hist)[kLevelBins], uint32_t *cnt)
+{
+    uint32_t *flat = &hist[0][0];
+    for (int i = threadIdx.x; i < kHistCopies * kLevelBins; i += kThreads)
+        flat[i] = 0;
+    if (threadIdx.x < 4)
+        cnt[threadIdx.x] = 0;
+    __syncthreads();
+}
+
+__device__ __forceinline__ void block_end(uint32_t (*hist)[kLevelBins], uint32_t *cnt, const Counts &c, const int lane,
+                                          unsigned long long *__restrict__ totals, uint32_t *__restrict__ rows)
+{
+    if (lane == 0) { // the waves' counters meet in LDS: one add per workgroup and counter leaves it
+        if (c.negative)
+            atomicAdd(&cnt[0], c.negative);
+        if (c.rail_lo)
+            atomicAdd(&cnt[1], c.rail_lo);
+        if (c.rail_hi)
+            atomicAdd(&cnt[2], c.rail_hi);
+        if (c.over)
+            atomicAdd(&cnt[3], c.over);
+    }
+    __syncthreads();
+#if ADSB_LEVEL_FLUSH == 1
+    uint32_t *row = rows + (size_t)blockIdx.x * kLevelRowWords;
+    if (threadIdx.x < 4)
+        row[threadIdx.x] = cnt[threadIdx.x];
+#else
+    if (threadIdx.x < 4 && cnt[threadIdx.x])
+        atomicAdd(&totals[1 + threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+#endif
+#pragma unroll
+    for (int j = 0; j < kLevelBins / kThreads; j++) {
+        const int bin = j * kThreads + threadIdx.x;
+        uint32_t v = 0;
+#pragma unroll
+        for (int w = 0; w < kHistCopies; w++)
+            v += hist[w][bin];
+#if ADSB_LEVEL_FLUSH == 1
+        row[4 + bin] = v;
+#else
+        if (v)
+            atomicAdd(&totals[5 + bin], (unsigned long long)v);
+#endif
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void level_kernel(const uint32_t *__restrict__ xin, const int64_t p_hi, const int64_t m_end,
+                                                         unsigned long long *__restrict__ totals, float *__restrict__ env,
+                                                         uint32_t *__restrict__ rows)
+{
+    __shared__ uint32_t hist[kHistCopies][kLevelBins];
+    __shared__ uint32_t cnt[4];
+    const int lane = threadIdx.x & 63;
+    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t *my_hist = hist[(ADSB_LEVEL_HIST & 1) ? wave_in_block : 0];
+    block_begin(hist, cnt);
+    Counts c;
+    const int64_t n_passes = (m_end + kLevelWave - 1) / kLevelWave; // a pass: one wave, 64 runs
+    const int64_t stride = (int64_t)gridDim.x * kWaves;
+#pragma unroll 1
+    for (int64_t pass = (int64_t)blockIdx.x * kWaves + wave_in_block; pass < n_passes; pass += stride) {
+        // the FIR's constants, written per pass as stage_a writes them (fir_product)
+        FirConsts kc = {{{0, 0}, {0, 0}, {0, 0}, {0, 0}}, {{tap<12>(), tap<13>()}, {tap<10>(), tap<11>()}, {tap<8>(), tap<9>()}, {tap<6>(), tap<7>()}}};
+#define ADSB_KC(b, T0, T1)                                                                                                          \
+    asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"                                                                            \
+                 : "=v"(kc.c2048[b].x), "=v"(kc.c2048[b].y)                                                                         \
+                 : "i"(__builtin_bit_cast(uint32_t, 2048.0f * tap<T0>())), "i"(__builtin_bit_cast(uint32_t, 2048.0f * tap<T1>())))
+        ADSB_KC(0, 12, 13);
+        ADSB_KC(1, 10, 11);
+        ADSB_KC(2, 8, 9);
+        ADSB_KC(3, 6, 7);
+#undef ADSB_KC
+#pragma unroll
+        for (int b = 0; b < 4; b++)
+            asm volatile("" : "+s"(kc.taps[b]));
+        const int64_t w0 = pass * kLevelWave; // the wave's first power sample = lane 0's first pair: a multiple of 28
+        const int64_t wlo = w0 - 8;           // lane 0's window starts 8 pairs below (two of them are never read)
+        // wave-uniform: every pair this wave loads lies inside the buffer
+        const bool interior = (wlo >= 0) && (wlo + kRun * 64 + 8 <= p_hi);
+        f32x4 tl[17]; // tl[k]: pairs 2k+2, 2k+3 of the lane's 36 = slots 2k, 2k+1
+        if (interior) {
+            const uint64_t wbase = (uint64_t)(xin + wlo);
+            i32x4 rs;
+            rs.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)wbase);
+            rs.y = __builtin_amdgcn_readfirstlane((int)((uint32_t)(wbase >> 32) & 0xFFFFu)); // stride 0: raw buffer
+            rs.z = 64 * kRun * 4 + 64;                                                        // bytes
+            rs.w = (int)(4u | 5u << 3 | 6u << 6 | 7u << 9 /* dst_sel xyzw */ | 2u << 12 /* USCALED */ | 12u << 15 /* 16_16_16_16 */);
+            const int voff = lane * (kRun * 4);
+            asm volatile("buffer_load_format_xyzw %0, %17, %18, 0 offen offset:8\n\t"
+                         "buffer_load_format_xyzw %1, %17, %18, 0 offen offset:16\n\t"
+                         "buffer_load_format_xyzw %2, %17, %18, 0 offen offset:24\n\t"
+                         "buffer_load_format_xyzw %3, %17, %18, 0 offen offset:32\n\t"
+                         "buffer_load_format_xyzw %4, %17, %18, 0 offen offset:40\n\t"
+                         "buffer_load_format_xyzw %5, %17, %18, 0 offen offset:48\n\t"
+                         "buffer_load_format_xyzw %6, %17, %18, 0 offen offset:56\n\t"
+                         "buffer_load_format_xyzw %7, %17, %18, 0 offen offset:64\n\t"
+                         "buffer_load_format_xyzw %8, %17, %18, 0 offen offset:72\n\t"
+                         "buffer_load_format_xyzw %9, %17, %18, 0 offen offset:80\n\t"
+                         "buffer_load_format_xyzw %10, %17, %18, 0 offen offset:88\n\t"
+                         "buffer_load_format_xyzw %11, %17, %18, 0 offen offset:96\n\t"
+                         "buffer_load_format_xyzw %12, %17, %18, 0 offen offset:104\n\t"
+                         "buffer_load_format_xyzw %13, %17, %18, 0 offen offset:112\n\t"
+                         "buffer_load_format_xyzw %14, %17, %18, 0 offen offset:120\n\t"
+                         "buffer_load_format_xyzw %15, %17, %18, 0 offen offset:128\n\t"
+                         "buffer_load_format_xyzw %16, %17, %18, 0 offen offset:136"
+                         "\n\ts_waitcnt vmcnt(0)"
+                         : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]), "=&v"(tl[4]), "=&v"(tl[5]), "=&v"(tl[6]),
+                           "=&v"(tl[7]), "=&v"(tl[8]), "=&v"(tl[9]), "=&v"(tl[10]), "=&v"(tl[11]), "=&v"(tl[12]),
+                           "=&v"(tl[13]), "=&v"(tl[14]), "=&v"(tl[15]), "=&v"(tl[16])
+                         : "v"(voff), "s"(rs)
+                         : "memory");
+        } else {
+            // The start of the capture -- the reference's zero-initialised ring (air.c:33: a missing pair is 0x0800,0x0800 -> v = 0)
+            // -- and its ragged end: plain loads, converted here
+            int64_t pr0 = wlo + (int64_t)kRun * lane;
+            asm volatile("" : "+v"(pr0)); // (opaque, as in stage_a: the 34 pair indices of this rare path are not precomputed and spilled)
+#pragma unroll
+            for (int k = 0; k < 17; k++) {
+                const int64_t pa = pr0 + 2 * k + 2, pb = pa + 1;
+                const uint32_t d0 = (pa >= 0 && pa < p_hi) ? xin[pa] : 0x08000800u;
+                const uint32_t d1 = (pb >= 0 && pb < p_hi) ? xin[pb] : 0x08000800u;
+                tl[k] = f32x4{(float)(d0 & 0xFFFFu), (float)(d0 >> 16), (float)(d1 & 0xFFFFu), (float)(d1 >> 16)};
+            }
+        }
+        // the run's pairs as (I, Q), slot s <-> pair s - 6 of the run (the - 2048 and the fs/4 sign are inside the FIR's products)
+        f32x2 vv[34];
+#pragma unroll
+        for (int s = 0; s < 34; s++) {
+            const f32x4 q = tl[s >> 1];
+            vv[s] = (s & 1) ? f32x2{q.z, q.w} : f32x2{q.x, q.y};
+        }
+        float a[kRun];
+        power_run<0>(vv, a, kc);
+
+        // the lane's run is power samples [m0, m0 + 28), of which those below m_end exist; the lane owns their pairs, slots 6 .. 33
+        const int64_t m0 = w0 + (int64_t)kRun * lane;
+        const int left = (int)std::min<int64_t>(kRun, std::max<int64_t>(0, m_end - m0));
+        const bool full = w0 + kLevelWave <= m_end; // (wave-uniform)
+        uint32_t b[kRun];
+#pragma unroll
+        for (int k = 0; k < kRun; k++)
+            b[k] = __builtin_bit_cast(uint32_t, a[k]);
+        // (a sum of two squares of finite floats: the sign bit is never set)
+        const uint32_t mx = full ? level_tail<true, false>(b, kRun, my_hist, c, lane) : level_tail<false, false>(b, left, my_hist, c, lane);
+        if (full)
+            rails_real<true>(vv, kRun, c);
+        else
+            rails_real<false>(vv, left, c);
+        if (env && left > 0)
+            env[pass * 64 + lane] = __builtin_bit_cast(float, mx);
+    }
+    block_end(hist, cnt, c, lane, totals, rows);
+}
+
+// The bit pattern of unit u's power sample, and its scalars on the rails: int16 -32768 / 32767, int8 -128 / 127.
+template <int kKind> __device__ __forceinline__ uint32_t unit_bits(const uint32_t u)
+{
+    return kKind == kLevelIq16 ? __builtin_bit_cast(uint32_t, iq_power(u)) : kKind == kLevelIq8 ? __builtin_bit_cast(uint32_t, iq8_power(u)) : u;
+}
+
+template <int kKind>
+__global__ __launch_bounds__(kThreads) void level_units_kernel(const void *__restrict__ xin, const size_t n, unsigned long long *__restrict__ totals,
+                                                               float *__restrict__ env, uint32_t *__restrict__ rows)
+{
+    __shared__ uint32_t hist[kHistCopies][kLevelBins];
+    __shared__ uint32_t cnt[4];
+    const int lane = threadIdx.x & 63;
+    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t *my_hist = hist[(ADSB_LEVEL_HIST & 1) ? wave_in_block : 0];
+    block_begin(hist, cnt);
+    Counts c;
+    const size_t n_passes = (n + kLevelWave - 1) / kLevelWave;
+    const size_t stride = (size_t)gridDim.x * kWaves;
+    constexpr size_t kUnit = kKind == kLevelIq8 ? 2 : 4;
+    const bool aligned = (uintptr_t)xin % (4 * kUnit) == 0; // (a run is 28 units: every lane's is then aligned as the array is)
+#pragma unroll 1
+    for (size_t pass = (size_t)blockIdx.x * kWaves + wave_in_block; pass < n_passes; pass += stride) {
+        const size_t w0 = pass * kLevelWave, m0 = w0 + (size_t)kRun * lane;
+        const bool full = w0 + kLevelWave <= n; // (wave-uniform)
+        const int left = m0 >= n ? 0 : (int)std::min<size_t>(kRun, n - m0);
+        uint32_t u[kRun];
+        if (full && aligned) {
+            if constexpr (kKind == kLevelIq8) {
+                const u32x2 *p = reinterpret_cast<const u32x2 *>(static_cast<const uint16_t *>(xin) + m0);
+#pragma unroll
+                for (int k = 0; k < kRun / 4; k++) {
+                    const u32x2 q = p[k];
+                    u[4 * k] = q.x & 0xFFFFu, u[4 * k + 1] = q.x >> 16, u[4 * k + 2] = q.y & 0xFFFFu, u[4 * k + 3] = q.y >> 16;
+                }
+            } else {
+                const u32x4 *p = reinterpret_cast<const u32x4 *>(static_cast<const uint32_t *>(xin) + m0);
+#pragma unroll
+                for (int k = 0; k < kRun / 4; k++) {
+                    const u32x4 q = p[k];
+                    u[4 * k] = q.x, u[4 * k + 1] = q.y, u[4 * k + 2] = q.z, u[4 * k + 3] = q.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kRun; k++) {
+                u[k] = 0;
+                if (k < left)
+                    u[k] = kKind == kLevelIq8 ? (uint32_t) static_cast<const uint16_t *>(xin)[m0 + k] : static_cast<const uint32_t *>(xin)[m0 + k];
+            }
+        }
+        uint32_t b[kRun];
+#pragma unroll
+        for (int k = 0; k < kRun; k++)
+            b[k] = unit_bits<kKind>(u[k]);
+        constexpr bool kSigned = kKind == kLevelPower;
+        const uint32_t mx = full ? level_tail<true, kSigned>(b, kRun, my_hist, c, lane) : level_tail<false, kSigned>(b, left, my_hist, c, lane);
+        if constexpr (kKind != kLevelPower) {
+            if (full)
+                rails_iq<kKind, true>(u, kRun, c);
+            else
+                rails_iq<kKind, false>(u, left, c);
+        }
+        if (env && left > 0)
+            env[pass * 64 + lane] = __builtin_bit_cast(float, mx);
+    }
+    block_end(hist, cnt, c, lane, totals, rows);
+}
+
+// ADSB_LEVEL_FLUSH == 1: column `col` of the rows of `blocks` workgroups, every kRowsSlices-th from blockIdx.y on, added to the totals
+__global__ __launch_bounds__(256) void level_reduce_kernel(const uint32_t *__restrict__ rows, const unsigned blocks,
+                                                           unsigned long long *__restrict__ totals)
+{
+    const unsigned col = blockIdx.x * 256 + threadIdx.x;
+    if (col >= (unsigned)kLevelRowWords)
+        return;
+    unsigned long long v = 0;
+    for (unsigned r = blockIdx.y; r < blocks; r += kRowsSlices)
+        v += rows[(size_t)r * kLevelRowWords + col];
+    if (v)
+        atomicAdd(&totals[1 + col], v);
+}
+
+hipError_t reduce_rows(const uint32_t *rows, unsigned blocks, unsigned long long *totals, hipStream_t stream)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !level_uses_rows())
+        return e;
+    hipLaunchKernelGGL(level_reduce_kernel, dim3((kLevelRowWords + 255) / 256, kRowsSlices), dim3(256), 0, stream, rows, blocks, totals);
+    return hipGetLastError();
+}
+
+} // namespace
+
+unsigned level_max_blocks() { return ADSB_LEVEL_BLOCKS; }
+bool level_uses_rows() { return ADSB_LEVEL_FLUSH == 1; }
+
+hipError_t launch_level(const uint32_t *x, int64_t p_hi, int64_t m_end, unsigned long long *totals, float *env, uint32_t *rows,
+                        hipStream_t stream)
+{
+    if (m_end <= 0)
+        return hipSuccess;
+    const uint64_t passes = ((uint64_t)m_end + kLevelWave - 1) / kLevelWave;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(level_max_blocks(), (passes + kWaves - 1) / kWaves);
+    hipLaunchKernelGGL(level_kernel, dim3(blocks), dim3(kThreads), 0, stream, x, p_hi, m_end, totals, env, rows);
+    return reduce_rows(rows, blocks, totals, stream);
+}
+
+hipError_t launch_level_units(int kind, const void *x, size_t n, unsigned long long *totals, float *env, uint32_t *rows, hipStream_t stream)
+{
+    if (n == 0)
+        return hipSuccess;
+    const uint64_t passes = ((uint64_t)n + kLevelWave - 1) / kLevelWave;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(level_max_blocks(), (passes + kWaves - 1) / kWaves);
+    if (kind == kLevelIq16)
+        hipLaunchKernelGGL(level_units_kernel<kLevelIq16>, dim3(blocks), dim3(kThreads), 0, stream, x, n, totals, env, rows);
+    else if (kind == kLevelIq8)
+        hipLaunchKernelGGL(level_units_kernel<kLevelIq8>, dim3(blocks), dim3(kThreads), 0, stream, x, n, totals, env, rows);
+    else
+        hipLaunchKernelGGL(level_units_kernel<kLevelPower>, dim3(blocks), dim3(kThreads), 0, stream, x, n, totals, env, rows);
+    return reduce_rows(rows, blocks, totals, stream);
+}
+
+} // namespace adsb

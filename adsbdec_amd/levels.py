@@ -1,0 +1,91 @@
+"""The level report of an array of power samples: the numpy statement that the adsb_level_* calls (include/adsbdec_amd.h,
+csrc/level_kernel.hip) are held to, bit for bit.
+
+`a` is a float32 array of M power samples and b = a.view('<u4') their bit patterns:
+
+    samples    M
+    negative   samples with the sign bit set (-0.0 counts)
+    hist[k]    k in 0 .. 2047, uint64: sign-clear samples with b >> 20 == k -- the exponent and the top three mantissa bits, 8 bins
+               per octave (about 0.75 dB each).  1.0 is bin 1016, 2^29 is bin 1248, Inf and NaN are bins 2040 and up.
+               hist.sum() + negative == M.
+    env[r]     r in 0 .. ceil(M / 28) - 1, float32: the float whose bit pattern is the unsigned maximum over samples
+               [28 r, min(28 r + 28, M)) of (b if the sign is clear, else 0).  For data in the _power calls' domain that is the
+               float maximum of the run; on any data it does not depend on order and is safe with NaN.
+
+Every quantity is an integer or a maximum: any order of reduction gives the same bits.
+
+sample_formats.power_domain_ok(a)  <=>  negative == 0 and hist[1248:].sum() == 0  (domain_ok below; tests/test_level_cpu.py).
+
+The rail counters of a report (rail_lo, rail_hi, over) are counted on the INPUT codes, not on power samples: rails() below.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+BINS = 2048
+RUN = 28                      # power samples per envelope float: a lane's run in the kernels
+BIN_ONE = 1016                # 1.0
+BIN_DOMAIN_END = 1248         # 2^29: the first bin outside the _power calls' domain
+BIN_NONFINITE = 2040          # Inf, and every NaN above it
+
+
+def level_report(a) -> dict:
+    a = np.ascontiguousarray(a)
+    if a.dtype != np.dtype("<f4"):
+        raise ValueError(f"power samples are float32, not {a.dtype}")
+    b = a.reshape(-1).view("<u4")
+    m = b.size
+    minus = (b >> 31).astype(bool)
+    hist = np.bincount((b[~minus] >> 20).astype(np.int64), minlength=BINS).astype(np.uint64)
+    clear = np.where(minus, np.uint32(0), b)
+    runs = -(-m // RUN)
+    padded = np.zeros(runs * RUN, dtype=np.uint32)
+    padded[:m] = clear
+    env = padded.reshape(runs, RUN).max(axis=1).astype("<u4").view("<f4") if runs else np.zeros(0, dtype=np.float32)
+    return dict(samples=m, negative=int(minus.sum()), rail_lo=0, rail_hi=0, over=0, hist=hist, env=env)
+
+
+def bin_lower_edge(k: int) -> float:
+    """The smallest float of bin k (k < 2040: finite)."""
+    return float(np.array([int(k) << 20], dtype="<u4").view("<f4")[0])
+
+
+def percentile(hist, q: float) -> float:
+    """The lower edge of the bin that holds the q-quantile (0 <= q <= 1) of the sign-clear samples: the first bin at which the
+    running count reaches q of the total, and at least one sample."""
+    hist = np.asarray(hist, dtype=np.uint64)
+    if hist.shape != (BINS,):
+        raise ValueError("a histogram has 2048 bins")
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("q lies in [0, 1]")
+    total = int(hist.sum())
+    if total == 0:
+        raise ValueError("an empty histogram has no percentile")
+    need = max(1, int(np.ceil(q * total)))
+    return bin_lower_edge(int(np.searchsorted(np.cumsum(hist), need, side="left")))
+
+
+def domain_ok(report: dict) -> bool:
+    """The verdict sample_formats.power_domain_ok gives on the array, from its report."""
+    return report["negative"] == 0 and int(np.asarray(report["hist"])[BIN_DOMAIN_END:].sum()) == 0
+
+
+def rails(x, kind: str) -> tuple:
+    """(rail_lo, rail_hi, over) of a capture's input codes.  kind "real": x uint16 codes, == 0, == 4095, > 4095, counted over EVERY
+    sample of a capture that has power samples -- the trailing n % 4 codes make no power sample (the reference reads four at a
+    time) but they are samples of the capture all the same; a capture below four samples has no power sample and an all-zero
+    report.  "iq16" / "iq8": x int16 / int8 scalars of complex samples: == the format's minimum, == its maximum; over 0."""
+    x = np.asarray(x).reshape(-1)
+    if kind == "real":
+        if x.size < 4:
+            return 0, 0, 0
+        return int((x == 0).sum()), int((x == 4095).sum()), int((x > 4095).sum())
+    lo, hi = {"iq16": (-32768, 32767), "iq8": (-128, 127)}[kind]
+    return int((x == lo).sum()), int((x == hi).sum()), 0
+
+
+def with_rails(report: dict, x, kind: str) -> dict:
+    """level_report's dict with the input's rail counters filled in: what the call of that flavour reports."""
+    r = dict(report)
+    r["rail_lo"], r["rail_hi"], r["over"] = rails(x, kind)
+    return r

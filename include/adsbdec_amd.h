@@ -145,7 +145,7 @@ long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, cons
 /* float32 POWER samples at 10 MS/s: a[0:n] IS the reference's ampbuff stream (adsbdec.h:5 deqframe(const float *ampbuff, const int len)), from any front end.  Decoded exactly as
  * the _iq calls decode a[] behind their squaring step: samples enter in twos (air.c:94-99), a trailing odd one at adsb_finish is never seen, the EOF horizon is the reference's with
  * M = n - (n & 1); pw = ((int)(a[g] + a[g+10]) + (int)(a[g+35] + a[g+45])) / 4 (demod.c:102-105,127,133); a sample outside the buffer reads as +0.  INPUT DOMAIN: every sample finite,
- * sign bit clear, below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are inside): the reference's int sums then stay below 2^31.  Outside it nothing is promised or detected.  n counts power samples.
+ * sign bit clear, below 2^29 (no negatives, -0.0, NaN, Inf; subnormals are inside): the reference's int sums then stay below 2^31.  Outside it nothing is promised; adsb_level_device_power detects it (negative, hist[1248 ..]).  n counts power samples.
  * A third stream kind beside real and IQ (fixed by the first push with samples; another kind then returns -1).  Also refused, handle unchanged: NULL with n > 0, a device pointer not
  * 4-byte aligned, a stream reaching 2^31 power samples, an adsb_set_long_stream handle.  Device pointers: in place when 16-byte aligned at a multiple of 4 samples, else staged. */
 int adsb_push_power(adsb_decoder *d, const float *samples, size_t n); int adsb_push_power_async(adsb_decoder *d, const float *samples, size_t n);
@@ -160,20 +160,21 @@ long adsb_decode_batch_host_power(adsb_decoder *d, size_t n_captures, const floa
  *   3. first_sample + n < 2^32, on adsb_set_long_stream handles too.  4. Returns m_end - m_begin, every float written; an empty window launches nothing.
  *   5. The handle's stream and resolver stay untouched: callable between pushes.  6. _as and _iq (fmt 0) add to adsb_get_format_report.
  * _host: through buffers the handle keeps.  adsb_power_device: the window (0, n, 0, 2 (n / 4)).  _as (fmt 1 | 3) / _packed: through the scratch of
- * adsb_decode_device_as / _packed, shared with them.  _iq (fmt 2 | 0): n COMPLEX samples -> n power samples.  adsb_power_batch_*: a BATCH of captures, capture i exactly as the single call of the same flavour exports it alone (the same floats from device_power[i][0] on; a fresh stream each: the six pairs before its first sample read as silence, never as a neighbour's samples), in ONE export launch behind at most one unpack (_packed) or conversion (_as fmt 1 | 3, _iq fmt 0) launch into the scratch of adsb_decode_batch_device_packed / _as; returns the floats written in all; rules 5 and 6 hold.  Refused (-1, the message names the capture, nothing launched, written or counted): what the single call refuses of a capture, n[i] >= 2^32 (IQ: 2^31), power_cap[i] below its count, n_captures >= 2^32 - 1.  A capture without power samples (n[i] < 4; IQ: 0) may have NULL pointers and costs nothing. */
+ * adsb_decode_device_as / _packed, shared with them.  _iq (fmt 2 | 0): n COMPLEX samples -> n power samples.  adsb_power_batch_*: a BATCH of captures, capture i exactly as the single call of the same flavour exports it alone (the same floats from device_power[i][0] on; a fresh stream each: the six pairs before its first sample read as silence, never as a neighbour's samples), in ONE export launch behind at most one unpack (_packed) or conversion (_as fmt 1 | 3, _iq fmt 0) launch into the scratch of adsb_decode_batch_device_packed / _as; returns the floats written in all; rules 5 and 6 hold.  Refused (-1, the message names the capture, nothing launched, written or counted; INTEGRATION.md): what the single call refuses of a capture, n[i] >= 2^32 (IQ: 2^31), power_cap[i] below its count, n_captures >= 2^32 - 1.  A capture without power samples (n[i] < 4; IQ: 0) may have NULL pointers and costs nothing.
+ * adsb_level_*: HOW LOUD a capture is, in one pass that stores almost nothing: the report of exactly the M floats a[] that the export call of the same flavour writes (_iq takes fmt 8 too: a = 256 (I^2 + Q^2); _power: the caller's floats), b = their bit patterns.  negative: samples with the sign bit set (-0.0 counts); hist[k]: sign-clear samples with b >> 20 == k (8 bins per octave, 0.75 dB; 1.0 is bin 1016, 2^29 is 1248, Inf / NaN 2040 and up; sum + negative == samples; the _power domain holds iff negative == 0 and hist[1248 ..] == 0); rail_lo / rail_hi / over: input codes == 0 / == 4095 / > 4095 over EVERY sample of the capture, the trailing n % 4 too (real; _as / _packed: of the converted codes), scalars == -32768 / 32767 (IQ fmt 2, and 0 behind its conversion: a clamped float shows) or -128 / 127 (fmt 8), over 0; all 0 for _power.  device_env: NULL with env_cap 0, or env_cap >= ceil(M / 28) floats, 4-byte aligned: env[r] = the float whose bits are the unsigned maximum of (b, sign clear, else 0) over samples [28 r, 28 r + 28) -- in the domain the run's maximum.  Returns M (0: a zeroed report, nothing launched) or -1, nothing written, not the format report either; pointers and lengths as the export call of the flavour (fmt 8: 2-byte aligned, n < 2^31); export rules 5 and 6 hold.  No batch, multi-GPU or stream-window form. */
 long adsb_power_window(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *device_power, size_t power_cap);
 long adsb_power_window_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *power, size_t power_cap); long adsb_power_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, float *const *power, const size_t *power_cap);
 long adsb_power_device(adsb_decoder *d, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
 long adsb_power_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
 long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, float *const *device_power, const size_t *power_cap);
-long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
+long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap); typedef struct adsb_level_report { uint64_t samples, negative, rail_lo, rail_hi, over; uint64_t hist[2048]; } adsb_level_report;
+long adsb_level_device(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_packed(adsb_decoder *d, const void *device_packed, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_power(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_host(adsb_decoder *d, const uint16_t *samples, size_t n, adsb_level_report *out, float *env, size_t env_cap);
 /* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
  * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. */
 int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
 int adsb_finish(adsb_decoder *d); /* end of input (EOF, air.c:241-244): the remaining offsets and the end-of-file horizon (SURVEY Q10) */
 /* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.  adsb_host_alloc_on binds the memory to the NUMA node of `device` (best effort).  adsb_host_register page-locks memory the caller already owns.  0 / -1. */
-void *adsb_host_alloc(size_t bytes); void *adsb_host_alloc_on(size_t bytes, int device);
-void adsb_host_free(void *p); int adsb_host_register(void *p, size_t bytes); int adsb_host_unregister(void *p);
+void *adsb_host_alloc(size_t bytes); void *adsb_host_alloc_on(size_t bytes, int device); void adsb_host_free(void *p); int adsb_host_register(void *p, size_t bytes); int adsb_host_unregister(void *p);
 /* Frame egress: what the reference hands to netout() (output.c:159), in its order.  adsb_drain copies (returns the number, <= cap, or -1);
  * adsb_take hands every pending frame out in place -- valid until the next call that pushes into, finishes, resets or destroys the handle. */
 long adsb_drain(adsb_decoder *d, adsb_frame *out, size_t cap); long adsb_take(adsb_decoder *d, const adsb_frame **frames); size_t adsb_pending(const adsb_decoder *d);
@@ -213,8 +214,7 @@ void adsb_multi_destroy(adsb_multi *m); int adsb_multi_devices(const adsb_multi 
  * memory (page-lock it); _file: every worker reads its slice of a regular file; _device: slice i in worker i's HBM holds what adsb_multi_plan says. */
 long adsb_multi_decode_host(adsb_multi *m, const uint16_t *samples, size_t n, const adsb_frame **frames); long adsb_multi_decode_file(adsb_multi *m, const char *path, const adsb_frame **frames);
 long adsb_multi_decode_device(adsb_multi *m, uint64_t total_samples, const void *const *slices, int n_slices, const adsb_frame **frames);
-int adsb_multi_plan(const adsb_multi *m, uint64_t total_samples, uint64_t *g_begin, uint64_t *g_end,
-                    uint64_t *first_sample, uint64_t *n_samples);
+int adsb_multi_plan(const adsb_multi *m, uint64_t total_samples, uint64_t *g_begin, uint64_t *g_end, uint64_t *first_sample, uint64_t *n_samples);
 int adsb_multi_get_stats(const adsb_multi *m, adsb_stats *out); /* the stream's Try/Ok table (cfg.collect_stats) */
 /* configs[3]: n_streams INDEPENDENT captures, stream s on worker s mod adsb_multi_devices(m), each with its own ts and
  * statistics -- N times what `adsbdec -f` does (main.c:60-89), side by side.  0 / -1; results per stream afterwards. */

@@ -7,6 +7,7 @@ comparison interleaved.
     python tools/format_probe.py --power [--reps 20] [--out profiles/r15_power.txt] [--ab parent=path/to/libadsbdec_amd.so]   # power_probe()
     python tools/format_probe.py --export [--reps 20] [--out profiles/r17_power_export.txt] [--layout name=path/to/libadsbdec_amd.so ...]   # export_probe()
     python tools/format_probe.py --export-batch [--reps 20] [--out profiles/r20_export_batch.txt] [--ab path/to/parent/libadsbdec_amd.so]   # export_batch_probe()
+    python tools/format_probe.py --level [--reps 20] [--out profiles/r23_level.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
     (with counters, and without: a kernel that does not classify its samples at all) and adsb_unpack_packed12 at the same n
@@ -610,6 +611,161 @@ def export_probe(L, reps, lines, layouts):
     print(lines[-1], flush=True)
 
 
+def level_probe(L, reps, lines, variants):
+    """The level report (level_kernel.hip, the adsb_level_* calls), every comparison interleaved in this one process, wall time of the
+    calls (each waits for its kernels):
+    (a) adsb_level_device with an envelope on 256 Mi samples of three contents -- the benchmark workload, clipped Gaussian noise, silence
+        -- twice over (the A/A), beside adsb_power_device and adsb_decode_device on the same capture, and beside every build given with
+        --variant name=path: measurement builds whose level_kernel.hip was compiled with another accumulation (-DADSB_LEVEL_HIST=k),
+        flush (-DADSB_LEVEL_FLUSH=1) or grid cap (-DADSB_LEVEL_BLOCKS=n).  Every build gives the tree's report and envelope;
+    (b) the element-wise flavours on 128 Mi units (fmt 2, fmt 8, power input) beside adsb_power_device_iq (fmt 2)."""
+    import numpy as np
+    from adsbdec_amd import levels
+    M = N // 2
+    work, _ = make_workload(torch, N, seed=1)
+    g = torch.Generator(device="cuda").manual_seed(23)
+    noise = (torch.randn(N, device="cuda", generator=g) * 600.0 + 2048.0).round_().clamp_(0, 4095).to(torch.int16)
+    silence = torch.full((N,), 0x800, dtype=torch.int16, device="cuda")
+    contents = {"workload": work, "noise": noise, "silence": silence}
+    torch.cuda.synchronize()                               # (the library's streams do not wait for torch's)
+    out = torch.empty(M, dtype=torch.float32, device="cuda")
+    KE = -(-M // 28)
+    env = torch.empty(KE, dtype=torch.float32, device="cuda")
+    d_dec = capi.Decoder(df18=False)
+    fr = C.POINTER(capi.Frame)()
+
+    def bind(path):
+        B = C.CDLL(path)
+        B.adsb_create.restype = C.c_void_p
+        B.adsb_create.argtypes = [C.c_void_p]
+        B.adsb_level_device.restype = C.c_long
+        B.adsb_level_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]
+        cfg = capi.make_config()
+        h = B.adsb_create(C.byref(cfg))
+        assert h, path
+        return B, h
+
+    d_tree = capi.Decoder()
+    tree = (L, d_tree._h)
+    builds = {"tree": tree, "tree again (the A/A)": tree}
+    for spec in variants:
+        name, _, path = spec.partition("=")
+        builds[name] = bind(path)
+    rep = capi.LevelReport()
+    steps = 5
+    lines += [f"# (a) adsb_level_device with an envelope, 256 Mi uint16 samples -> the report of 128 Mi power samples (512 MiB in, {KE * 4 / 2 ** 20:.1f} MiB out);",
+              f"#     {reps} rounds x {steps} calls per side, the sides in rotation; wall time of the call (memset + kernel + copy of the totals + the wait), medians (quartiles)"]
+    summary = {}
+    for cname, t in contents.items():
+        ref = None
+        for name, (B, h) in builds.items():                # warm-up, and every build gives the same report and envelope
+            for _ in range(3):
+                env.zero_()
+                assert B.adsb_level_device(h, t.data_ptr(), N, C.byref(rep), env.data_ptr(), KE) == M, (name, cname)
+            got = (capi.Decoder.level_dict(rep), env.clone())
+            assert int(got[0]["hist"].sum()) + got[0]["negative"] == M == got[0]["samples"]
+            if ref is None:
+                ref = got
+                piece = t[: 1 << 22].cpu().numpy().view(np.uint16)  # the head against the definition
+                from oracle import oracle as O
+                O.build()
+                want = levels.level_report(O.power(piece)[: 1 << 21])
+                kf = (1 << 21) // 28                        # (the head's whole runs: its last one is cut short in `want`)
+                assert np.array_equal(ref[1][:kf].cpu().numpy().view(np.uint32), want["env"][:kf].view(np.uint32)), cname
+            else:
+                assert all(got[0][k] == ref[0][k] for k in ("negative", "rail_lo", "rail_hi", "over")) and np.array_equal(got[0]["hist"], ref[0]["hist"]), (name, cname)
+                assert torch.equal(got[1].view(torch.int32), ref[1].view(torch.int32)), (name, cname)
+        h0 = ref[0]["hist"]
+        for _ in range(3):
+            assert L.adsb_power_device(d_tree._h, t.data_ptr(), N, out.data_ptr(), M) == M
+            frames = L.adsb_decode_device(d_dec._h, t.data_ptr(), N, C.byref(fr))
+        names = list(builds)
+        wall = {k: [] for k in names}
+        exp, dec = [], []
+        for r in range(reps):
+            order = names[r % len(names):] + names[:r % len(names)]
+            for name in order:
+                B, h = builds[name]
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    B.adsb_level_device(h, t.data_ptr(), N, C.byref(rep), env.data_ptr(), KE)
+                wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                L.adsb_power_device(d_tree._h, t.data_ptr(), N, out.data_ptr(), M)
+            exp.append((time.perf_counter() - t0) * 1e3 / steps)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                L.adsb_decode_device(d_dec._h, t.data_ptr(), N, C.byref(fr))
+            dec.append((time.perf_counter() - t0) * 1e3 / steps)
+        lines += ["#", f"#   content: {cname} -- {np.count_nonzero(h0)} bins, the fullest holds {100.0 * int(h0.max()) / M:.1f} % of the samples; rail_lo {ref[0]['rail_lo']}, rail_hi {ref[0]['rail_hi']}; {frames} frames",
+                  "#   side                                        call ms (q1 .. q3)          / tree   / adsb_power_device (medians of rounds)"]
+        for name in names:
+            q = statistics.quantiles(wall[name], n=4)
+            lines.append(f"    {name:42s} {med(wall[name]):.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med([a / b for a, b in zip(wall[name], wall['tree'])]):.4f}   {med([a / b for a, b in zip(wall[name], exp)]):.4f}")
+            print(lines[-1], flush=True)
+        for name, v in (("adsb_power_device (512 MiB out)", exp), ("adsb_decode_device", dec)):
+            q = statistics.quantiles(v, n=4)
+            lines.append(f"    {name:42s} {med(v):.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med([a / b for a, b in zip(v, wall['tree'])]):.4f}   {med([a / b for a, b in zip(v, exp)]):.4f}")
+            print(lines[-1], flush=True)
+        summary[cname] = med(wall["tree"])
+    lines += ["#", "#   the tree's call by content: " + ", ".join(f"{k} {v:.4f} ms ({v / summary['workload']:.3f} x the workload's)" for k, v in summary.items())]
+    print(lines[-1], flush=True)
+    del out, noise, silence
+
+    from tools.gen_signal import make_iq_workload
+    from adsbdec_amd.sample_formats import to_int8_iq
+    NC = 1 << 27
+    # the generator is numpy's: one block of 4 Mi complex samples, repeated 32 times (as tools/format_probe.py --iq); its int8 twin
+    # (>> 8); its power samples, one rounded operation per line as sample_formats.iq_power
+    block, _ = make_iq_workload(1 << 22, seed=1)
+    iq = torch.from_numpy(block.reshape(-1)).cuda().repeat(NC >> 22)
+    iq8 = torch.from_numpy(to_int8_iq(block)[0].reshape(-1)).cuda().repeat(NC >> 22)
+    sc = iq.view(-1, 2).to(torch.float32) * 0.0625
+    ii, qq = sc[:, 0] * sc[:, 0], sc[:, 1] * sc[:, 1]
+    pw = (ii + qq).contiguous()
+    del sc, ii, qq
+    torch.cuda.synchronize()                               # (the library's streams do not wait for torch's)
+    # the worst content found: the real workload's codes read as (I, Q) -- a constant offset of 2048 on both, so every power sample
+    # lies in one of TWO neighbouring bins and hardly a run of 28 agrees: all 64 lanes of every increment on two LDS words
+    two = work.view(torch.int16)[: 2 * NC]
+    out = torch.empty(NC, dtype=torch.float32, device="cuda")
+    KC = -(-NC // 28)
+    d = d_tree
+    assert L.adsb_level_device_iq(d._h, 2, two.data_ptr(), NC, C.byref(rep), env.data_ptr(), KC) == NC
+    two_bins = int(np.count_nonzero(np.ctypeslib.as_array(rep.hist)))
+    assert L.adsb_level_device_iq(d._h, 2, iq.data_ptr(), NC, C.byref(rep), env.data_ptr(), KC) == NC
+    h2 = np.ctypeslib.as_array(rep.hist).copy()
+    assert L.adsb_level_device_power(d._h, pw.data_ptr(), NC, C.byref(rep), env.data_ptr(), KC) == NC
+    assert np.array_equal(h2, np.ctypeslib.as_array(rep.hist)), "fmt 2 and its own power samples give different bins"
+    sides = {
+        "adsb_level_device_iq fmt 2 (512 MiB in)": lambda: L.adsb_level_device_iq(d._h, 2, iq.data_ptr(), NC, C.byref(rep), env.data_ptr(), KC),
+        "adsb_level_device_iq fmt 2 again (the A/A)": lambda: L.adsb_level_device_iq(d._h, 2, iq.data_ptr(), NC, C.byref(rep), env.data_ptr(), KC),
+        "adsb_level_device_iq fmt 8 (256 MiB in)": lambda: L.adsb_level_device_iq(d._h, 8, iq8.data_ptr(), NC, C.byref(rep), env.data_ptr(), KC),
+        "adsb_level_device_power (512 MiB in)": lambda: L.adsb_level_device_power(d._h, pw.data_ptr(), NC, C.byref(rep), env.data_ptr(), KC),
+        f"fmt 2, power samples in {two_bins} bins only": lambda: L.adsb_level_device_iq(d._h, 2, two.data_ptr(), NC, C.byref(rep), env.data_ptr(), KC),
+        "adsb_power_device_iq fmt 2 (512 MiB out)": lambda: L.adsb_power_device_iq(d._h, 2, iq.data_ptr(), NC, out.data_ptr(), NC),
+    }
+    ms = {k: [] for k in sides}
+    names = list(sides)
+    for r in range(-2, reps):
+        order = names[r % len(names):] + names[:r % len(names)]
+        for name in order:
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                assert sides[name]() == NC, name
+            if r >= 0:
+                ms[name].append((time.perf_counter() - t0) * 1e3 / steps)
+    lines += ["#", f"# (b) the element-wise flavours, 128 Mi units, with an envelope; wall time of the call, medians (quartiles).  The capture: a 4 Mi-sample block of",
+              f"#     tools/gen_signal.py make_iq_workload (seed 1) repeated 32 times ({np.count_nonzero(h2)} bins, the fullest {100.0 * int(h2.max()) / NC:.1f} % of the samples), its int8 twin, its power samples",
+              "#   side                                        call ms (q1 .. q3)          / adsb_power_device_iq (median of rounds)"]
+    base = ms[names[-1]]
+    for name in names:
+        q = statistics.quantiles(ms[name], n=4)
+        lines.append(f"    {name:42s} {med(ms[name]):.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med([a / b for a, b in zip(ms[name], base)]):.4f}")
+        print(lines[-1], flush=True)
+
+
 def export_batch_probe(L, reps, lines, parent):
     """The batch power export (power_export_batch_kernel.hip, the adsb_power_batch_* calls) against the loop of single calls, every
     comparison interleaved in this one process, wall time of the calls (each waits for its kernels; the ctypes arrays are built once):
@@ -761,8 +917,28 @@ def main():
     ap.add_argument("--export", action="store_true", help="the power export (the adsb_power_* calls) instead: profiles/r17_power_export.txt")
     ap.add_argument("--layout", action="append", default=[], metavar="NAME=LIB", help="with --export: a build of the library with another store layout, measured beside the tree's")
     ap.add_argument("--export-batch", action="store_true", help="the batch power export (the adsb_power_batch_* calls) against the loop of single calls instead: profiles/r20_export_batch.txt; --ab: the parent commit's library, for (c)")
+    ap.add_argument("--level", action="store_true", help="the level report (the adsb_level_* calls) instead: profiles/r23_level.txt")
+    ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB", help="with --level: a build of the library with another accumulation, flush or grid, measured beside the tree's")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.level:
+        a.out = a.out or os.path.join(ROOT, "profiles", "r23_level.txt")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --level: the level report (level_kernel.hip, the adsb_level_* calls), one process,",
+                 f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
+                 "# Contents, 256 Mi samples each: the benchmark's workload (tools/gen_signal.py make_workload, seed 1); Gaussian noise of sigma 600 codes",
+                 "# round 2048, clipped to 0 .. 4095; silence (every code 0x800).",
+                 "# Sides named with --variant are builds of the library that differ in level_kernel.hip alone, loaded beside the tree's in this process:",
+                 "#   -DADSB_LEVEL_HIST=k   bit 0: a histogram per workgroup (0) or per wave (1) in LDS; bit 1: the wave-uniform shortcut (one add when a wave agrees on an increment)",
+                 "#                         bit 2: the run-uniform shortcut instead (one add when a lane's 28 samples agree)",
+                 "#   -DADSB_LEVEL_FLUSH=1  a row of 32-bit counts per workgroup and a second small kernel that sums the rows, instead of 64-bit atomics on the totals",
+                 "#   -DADSB_LEVEL_BLOCKS=n the grid's cap (workgroups of 4 waves)",
+                 "#   the tree is HIST=5 (per wave, run-uniform shortcut), FLUSH=0, BLOCKS=2048; a variant changes the one thing its name says",
+                 "#   (names as built for this record: hK = -DADSB_LEVEL_HIST=K, rows = -DADSB_LEVEL_FLUSH=1, bN = -DADSB_LEVEL_BLOCKS=N)", "#"]
+        level_probe(capi.load(), a.reps, lines, a.variant)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.export_batch:
         a.out = a.out or os.path.join(ROOT, "profiles", "r20_export_batch.txt")
         torch.cuda.set_device(0)
