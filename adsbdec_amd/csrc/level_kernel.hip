@@ -4,10 +4,9 @@
 // reduction gives the same bits (adsbdec_amd/levels.py level_report is the definition).
 //
 // level_kernel is power_export_kernel (power_export_kernel.hip) up to the end of its FIR: the same pass structure (a wave covers
-// 64 runs of 28 power samples, grid-stride), the same 17 typed buffer loads of a lane's 34 pairs, the same plain-load road where
-// the window leaves the buffer, the same constants written per pass, the same power_run<0> -- and then, instead of the export's
-// stores, the reduction tail.  The load block, the constants and the FIR are a COPY: a function shared with stage_a moved the
-// existing units' code (DESIGN.md section 4 "IQ captures"), and those units compile to the instructions they had.
+// 64 runs of 28 power samples, grid-stride) and the same front end -- scan_stages.h real_front, the one definition of the typed
+// loads, the plain-load road, the constants and the FIR that stage_a and the exports call too (profiles/r24_front_shared_isa.txt:
+// each compiles to the instructions it had with lines of its own) -- and then, instead of the export's stores, the reduction tail.
 // level_units_kernel is the same tail behind an element-wise front end: a lane takes 28 complex int16 samples, complex int8
 // samples or float32 power samples (seven 16-byte loads where the array is 16-byte aligned, as scan_power_kernel's; unit by unit
 // where it is not, and in the capture's last run).
@@ -49,12 +48,9 @@ namespace adsb {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kLevelWave = 64 * kRun; // power samples of a wave's pass
 constexpr int kHistCopies = (ADSB_LEVEL_HIST & 1) ? kWaves : 1;
 constexpr int kRowsSlices = 16;       // level_reduce_kernel: the rows are summed in this many interleaved slices
 
@@ -237,87 +233,19 @@ __global__ __launch_bounds__(kThreads) void level_kernel(const uint32_t *__restr
     uint32_t *my_hist = hist[(ADSB_LEVEL_HIST & 1) ? wave_in_block : 0];
     block_begin(hist, cnt);
     Counts c;
-    const int64_t n_passes = (m_end + kLevelWave - 1) / kLevelWave; // a pass: one wave, 64 runs
+    const int64_t n_passes = (m_end + kWavePass - 1) / kWavePass; // a pass: one wave, 64 runs
     const int64_t stride = (int64_t)gridDim.x * kWaves;
 #pragma unroll 1
     for (int64_t pass = (int64_t)blockIdx.x * kWaves + wave_in_block; pass < n_passes; pass += stride) {
-        // the FIR's constants, written per pass as stage_a writes them (fir_product)
-        FirConsts kc = {{{0, 0}, {0, 0}, {0, 0}, {0, 0}}, {{tap<12>(), tap<13>()}, {tap<10>(), tap<11>()}, {tap<8>(), tap<9>()}, {tap<6>(), tap<7>()}}};
-#define ADSB_KC(b, T0, T1)                                                                                                          \
-    asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"                                                                            \
-                 : "=v"(kc.c2048[b].x), "=v"(kc.c2048[b].y)                                                                         \
-                 : "i"(__builtin_bit_cast(uint32_t, 2048.0f * tap<T0>())), "i"(__builtin_bit_cast(uint32_t, 2048.0f * tap<T1>())))
-        ADSB_KC(0, 12, 13);
-        ADSB_KC(1, 10, 11);
-        ADSB_KC(2, 8, 9);
-        ADSB_KC(3, 6, 7);
-#undef ADSB_KC
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-            asm volatile("" : "+s"(kc.taps[b]));
-        const int64_t w0 = pass * kLevelWave; // the wave's first power sample = lane 0's first pair: a multiple of 28
-        const int64_t wlo = w0 - 8;           // lane 0's window starts 8 pairs below (two of them are never read)
-        // wave-uniform: every pair this wave loads lies inside the buffer
-        const bool interior = (wlo >= 0) && (wlo + kRun * 64 + 8 <= p_hi);
-        f32x4 tl[17]; // tl[k]: pairs 2k+2, 2k+3 of the lane's 36 = slots 2k, 2k+1
-        if (interior) {
-            const uint64_t wbase = (uint64_t)(xin + wlo);
-            i32x4 rs;
-            rs.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)wbase);
-            rs.y = __builtin_amdgcn_readfirstlane((int)((uint32_t)(wbase >> 32) & 0xFFFFu)); // stride 0: raw buffer
-            rs.z = 64 * kRun * 4 + 64;                                                        // bytes
-            rs.w = (int)(4u | 5u << 3 | 6u << 6 | 7u << 9 /* dst_sel xyzw */ | 2u << 12 /* USCALED */ | 12u << 15 /* 16_16_16_16 */);
-            const int voff = lane * (kRun * 4);
-            asm volatile("buffer_load_format_xyzw %0, %17, %18, 0 offen offset:8\n\t"
-                         "buffer_load_format_xyzw %1, %17, %18, 0 offen offset:16\n\t"
-                         "buffer_load_format_xyzw %2, %17, %18, 0 offen offset:24\n\t"
-                         "buffer_load_format_xyzw %3, %17, %18, 0 offen offset:32\n\t"
-                         "buffer_load_format_xyzw %4, %17, %18, 0 offen offset:40\n\t"
-                         "buffer_load_format_xyzw %5, %17, %18, 0 offen offset:48\n\t"
-                         "buffer_load_format_xyzw %6, %17, %18, 0 offen offset:56\n\t"
-                         "buffer_load_format_xyzw %7, %17, %18, 0 offen offset:64\n\t"
-                         "buffer_load_format_xyzw %8, %17, %18, 0 offen offset:72\n\t"
-                         "buffer_load_format_xyzw %9, %17, %18, 0 offen offset:80\n\t"
-                         "buffer_load_format_xyzw %10, %17, %18, 0 offen offset:88\n\t"
-                         "buffer_load_format_xyzw %11, %17, %18, 0 offen offset:96\n\t"
-                         "buffer_load_format_xyzw %12, %17, %18, 0 offen offset:104\n\t"
-                         "buffer_load_format_xyzw %13, %17, %18, 0 offen offset:112\n\t"
-                         "buffer_load_format_xyzw %14, %17, %18, 0 offen offset:120\n\t"
-                         "buffer_load_format_xyzw %15, %17, %18, 0 offen offset:128\n\t"
-                         "buffer_load_format_xyzw %16, %17, %18, 0 offen offset:136"
-                         "\n\ts_waitcnt vmcnt(0)"
-                         : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]), "=&v"(tl[4]), "=&v"(tl[5]), "=&v"(tl[6]),
-                           "=&v"(tl[7]), "=&v"(tl[8]), "=&v"(tl[9]), "=&v"(tl[10]), "=&v"(tl[11]), "=&v"(tl[12]),
-                           "=&v"(tl[13]), "=&v"(tl[14]), "=&v"(tl[15]), "=&v"(tl[16])
-                         : "v"(voff), "s"(rs)
-                         : "memory");
-        } else {
-            // The start of the capture -- the reference's zero-initialised ring (air.c:33: a missing pair is 0x0800,0x0800 -> v = 0)
-            // -- and its ragged end: plain loads, converted here
-            int64_t pr0 = wlo + (int64_t)kRun * lane;
-            asm volatile("" : "+v"(pr0)); // (opaque, as in stage_a: the 34 pair indices of this rare path are not precomputed and spilled)
-#pragma unroll
-            for (int k = 0; k < 17; k++) {
-                const int64_t pa = pr0 + 2 * k + 2, pb = pa + 1;
-                const uint32_t d0 = (pa >= 0 && pa < p_hi) ? xin[pa] : 0x08000800u;
-                const uint32_t d1 = (pb >= 0 && pb < p_hi) ? xin[pb] : 0x08000800u;
-                tl[k] = f32x4{(float)(d0 & 0xFFFFu), (float)(d0 >> 16), (float)(d1 & 0xFFFFu), (float)(d1 >> 16)};
-            }
-        }
-        // the run's pairs as (I, Q), slot s <-> pair s - 6 of the run (the - 2048 and the fs/4 sign are inside the FIR's products)
+        const int64_t w0 = pass * kWavePass; // the wave's first power sample = lane 0's first pair: a multiple of 28
         f32x2 vv[34];
-#pragma unroll
-        for (int s = 0; s < 34; s++) {
-            const f32x4 q = tl[s >> 1];
-            vv[s] = (s & 1) ? f32x2{q.z, q.w} : f32x2{q.x, q.y};
-        }
         float a[kRun];
-        power_run<0>(vv, a, kc);
+        real_front<false>(xin, 0, 0, p_hi, w0 - 8, lane, vv, a); // (the wave's window starts 8 pairs below)
 
         // the lane's run is power samples [m0, m0 + 28), of which those below m_end exist; the lane owns their pairs, slots 6 .. 33
         const int64_t m0 = w0 + (int64_t)kRun * lane;
         const int left = (int)std::min<int64_t>(kRun, std::max<int64_t>(0, m_end - m0));
-        const bool full = w0 + kLevelWave <= m_end; // (wave-uniform)
+        const bool full = w0 + kWavePass <= m_end; // (wave-uniform)
         uint32_t b[kRun];
 #pragma unroll
         for (int k = 0; k < kRun; k++)
@@ -351,14 +279,14 @@ __global__ __launch_bounds__(kThreads) void level_units_kernel(const void *__res
     uint32_t *my_hist = hist[(ADSB_LEVEL_HIST & 1) ? wave_in_block : 0];
     block_begin(hist, cnt);
     Counts c;
-    const size_t n_passes = (n + kLevelWave - 1) / kLevelWave;
+    const size_t n_passes = (n + kWavePass - 1) / kWavePass;
     const size_t stride = (size_t)gridDim.x * kWaves;
     constexpr size_t kUnit = kKind == kLevelIq8 ? 2 : 4;
     const bool aligned = (uintptr_t)xin % (4 * kUnit) == 0; // (a run is 28 units: every lane's is then aligned as the array is)
 #pragma unroll 1
     for (size_t pass = (size_t)blockIdx.x * kWaves + wave_in_block; pass < n_passes; pass += stride) {
-        const size_t w0 = pass * kLevelWave, m0 = w0 + (size_t)kRun * lane;
-        const bool full = w0 + kLevelWave <= n; // (wave-uniform)
+        const size_t w0 = pass * kWavePass, m0 = w0 + (size_t)kRun * lane;
+        const bool full = w0 + kWavePass <= n; // (wave-uniform)
         const int left = m0 >= n ? 0 : (int)std::min<size_t>(kRun, n - m0);
         uint32_t u[kRun];
         if (full && aligned) {
@@ -436,7 +364,7 @@ hipError_t launch_level(const uint32_t *x, int64_t p_hi, int64_t m_end, unsigned
 {
     if (m_end <= 0)
         return hipSuccess;
-    const uint64_t passes = ((uint64_t)m_end + kLevelWave - 1) / kLevelWave;
+    const uint64_t passes = ((uint64_t)m_end + kWavePass - 1) / kWavePass;
     const unsigned blocks = (unsigned)std::min<uint64_t>(level_max_blocks(), (passes + kWaves - 1) / kWaves);
     hipLaunchKernelGGL(level_kernel, dim3(blocks), dim3(kThreads), 0, stream, x, p_hi, m_end, totals, env, rows);
     return reduce_rows(rows, blocks, totals, stream);
@@ -446,7 +374,7 @@ hipError_t launch_level_units(int kind, const void *x, size_t n, unsigned long l
 {
     if (n == 0)
         return hipSuccess;
-    const uint64_t passes = ((uint64_t)n + kLevelWave - 1) / kLevelWave;
+    const uint64_t passes = ((uint64_t)n + kWavePass - 1) / kWavePass;
     const unsigned blocks = (unsigned)std::min<uint64_t>(level_max_blocks(), (passes + kWaves - 1) / kWaves);
     if (kind == kLevelIq16)
         hipLaunchKernelGGL(level_units_kernel<kLevelIq16>, dim3(blocks), dim3(kThreads), 0, stream, x, n, totals, env, rows);

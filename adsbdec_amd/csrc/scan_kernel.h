@@ -18,6 +18,7 @@ constexpr int kThreads = 256;   // 4 wavefronts
 constexpr int kWaves = kThreads / 64;
 constexpr int kWaveRuns = 63;   // distinct runs per wave and pass (lane 63 re-computes the next wave's first run)
 constexpr int kPassRuns = kWaves * kWaveRuns;   // 252
+constexpr int kWavePass = 64 * kRun; // power samples of a wave's pass where every lane owns its run (the exports, the level report)
 constexpr int kReachRuns = 44;  // runs of bit planes one long-frame evaluation reaches ahead: ceil((27+1195)/28)
 constexpr int kMaxPasses = 32;
 constexpr int kQueueCap = 4 * kThreads; // survivors compacted per round

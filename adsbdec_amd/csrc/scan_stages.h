@@ -362,6 +362,105 @@ __device__ __forceinline__ uint32_t take28(const uint32_t *w)
     return r & 0x0FFFFFFFu;
 }
 
+// ------------------------------ the real-sample front end ------------------------------
+// One wave's pass over real samples, up to the end of the FIR: a[0..27] = the 28 power samples of the lane's run, vv = the 34
+// pairs (6 of pre-halo + 28) behind them, as the FIR took them.  `wlo` is the first pair of the WAVE's window: lane 0's run
+// starts at pair wlo + 8 (two of the eight are never read), lane L's 28 pairs further per lane.  x[0] is pair pbuf0; a pair
+// outside [p_lo, p_hi) reads as silence.  The ONE definition behind stage_a, power_export_kernel, power_export_batch_kernel and
+// level_kernel: each keeps the instructions its own copy of these lines gave (profiles/r24_front_shared_isa.txt).
+//
+// Input: the 34 pairs a run needs are 17 TYPED buffer loads of 8 bytes per lane (buffer_load_format_xyzw, data format
+// 16_16_16_16, number format USCALED): the load path itself converts the four uint16 to four floats -- exactly, and for free next
+// to 66 v_cvt_f32_u32 per run (4.4 cycles each; kernel -2 .. -4.5 %).  Lanes are 112 bytes apart; the buffer resource is rebuilt
+// per wave and pass around the wave's own 7 KiB window, so no buffer size limit applies.
+// Ptr: const uint32_t * or a pointer to the same words in the global address space.  kNop: s_nop 4 in front of the first load --
+// should a descriptor word reach its register through a v_readfirstlane, the first load is five states behind it (the batch
+// export's descriptor comes from a table row read per pass).
+template <bool kNop, class Ptr>
+__device__ __forceinline__ void real_front(const Ptr xin, const int64_t pbuf0, const int64_t p_lo, const int64_t p_hi, const int64_t wlo,
+                                           const int lane, f32x2 (&vv)[34], float *a)
+{
+    // the FIR's constants (fir_product): the vector ones written here, by instructions the compiler cannot hoist -- eight
+    // registers that live from here to the end of the FIR, not across whatever the caller does behind it (stage_a's plane
+    // arithmetic takes all 96); the scalar ones made opaque INSIDE the caller's loop over passes, so that their exchanged and
+    // negated forms are operand modifiers, not hoisted copies
+    FirConsts kc = {{{0, 0}, {0, 0}, {0, 0}, {0, 0}}, {{tap<12>(), tap<13>()}, {tap<10>(), tap<11>()}, {tap<8>(), tap<9>()}, {tap<6>(), tap<7>()}}};
+#define ADSB_KC(b, T0, T1)                                                                                                          \
+    asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"                                                                            \
+                 : "=v"(kc.c2048[b].x), "=v"(kc.c2048[b].y)                                                                         \
+                 : "i"(__builtin_bit_cast(uint32_t, 2048.0f * tap<T0>())), "i"(__builtin_bit_cast(uint32_t, 2048.0f * tap<T1>())))
+    ADSB_KC(0, 12, 13);
+    ADSB_KC(1, 10, 11);
+    ADSB_KC(2, 8, 9);
+    ADSB_KC(3, 6, 7);
+#undef ADSB_KC
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+        asm volatile("" : "+s"(kc.taps[b]));
+    // wave-uniform: every pair this wave loads lies inside the buffer
+    const bool interior = (wlo >= p_lo) && (wlo + kRun * 64 + 8 <= p_hi);
+    f32x4 tl[17]; // tl[k]: pairs 2k+2, 2k+3 of the lane's 36 = slots 2k, 2k+1
+    if (interior) {
+        const uint64_t wbase = (uint64_t)(xin + (wlo - pbuf0));
+        i32x4 rs;
+        rs.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)wbase);
+        rs.y = __builtin_amdgcn_readfirstlane((int)((uint32_t)(wbase >> 32) & 0xFFFFu)); // stride 0: raw buffer
+        rs.z = 64 * kRun * 4 + 64;                                                        // bytes
+        rs.w = (int)(4u | 5u << 3 | 6u << 6 | 7u << 9 /* dst_sel xyzw */ | 2u << 12 /* USCALED */ | 12u << 15 /* 16_16_16_16 */);
+        const int voff = lane * (kRun * 4);
+#define ADSB_REAL_LOADS(FIRST)                                                                                                      \
+    asm volatile(FIRST "buffer_load_format_xyzw %0, %17, %18, 0 offen offset:8\n\t"                                                 \
+                       "buffer_load_format_xyzw %1, %17, %18, 0 offen offset:16\n\t"                                                \
+                       "buffer_load_format_xyzw %2, %17, %18, 0 offen offset:24\n\t"                                                \
+                       "buffer_load_format_xyzw %3, %17, %18, 0 offen offset:32\n\t"                                                \
+                       "buffer_load_format_xyzw %4, %17, %18, 0 offen offset:40\n\t"                                                \
+                       "buffer_load_format_xyzw %5, %17, %18, 0 offen offset:48\n\t"                                                \
+                       "buffer_load_format_xyzw %6, %17, %18, 0 offen offset:56\n\t"                                                \
+                       "buffer_load_format_xyzw %7, %17, %18, 0 offen offset:64\n\t"                                                \
+                       "buffer_load_format_xyzw %8, %17, %18, 0 offen offset:72\n\t"                                                \
+                       "buffer_load_format_xyzw %9, %17, %18, 0 offen offset:80\n\t"                                                \
+                       "buffer_load_format_xyzw %10, %17, %18, 0 offen offset:88\n\t"                                               \
+                       "buffer_load_format_xyzw %11, %17, %18, 0 offen offset:96\n\t"                                               \
+                       "buffer_load_format_xyzw %12, %17, %18, 0 offen offset:104\n\t"                                              \
+                       "buffer_load_format_xyzw %13, %17, %18, 0 offen offset:112\n\t"                                              \
+                       "buffer_load_format_xyzw %14, %17, %18, 0 offen offset:120\n\t"                                              \
+                       "buffer_load_format_xyzw %15, %17, %18, 0 offen offset:128\n\t"                                              \
+                       "buffer_load_format_xyzw %16, %17, %18, 0 offen offset:136"                                                  \
+                       "\n\ts_waitcnt vmcnt(0)"                                                                                     \
+                 : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]), "=&v"(tl[4]), "=&v"(tl[5]), "=&v"(tl[6]), "=&v"(tl[7]),   \
+                   "=&v"(tl[8]), "=&v"(tl[9]), "=&v"(tl[10]), "=&v"(tl[11]), "=&v"(tl[12]), "=&v"(tl[13]), "=&v"(tl[14]),           \
+                   "=&v"(tl[15]), "=&v"(tl[16])                                                                                     \
+                 : "v"(voff), "s"(rs)                                                                                               \
+                 : "memory")
+        if constexpr (kNop)
+            ADSB_REAL_LOADS("s_nop 4\n\t");
+        else
+            ADSB_REAL_LOADS("");
+#undef ADSB_REAL_LOADS
+    } else {
+        // The start of the buffer -- at a stream's start the reference's zero-initialised ring (air.c:33: a missing pair is
+        // 0x0800,0x0800 -> v = 0), elsewhere the caller's choice (adsbdec_amd.h: the window rule) -- and its ragged end: plain
+        // loads, converted here
+        int64_t pr0 = wlo + (int64_t)kRun * lane;
+        asm volatile("" : "+v"(pr0)); // (opaque: keeps the 34 pair indices of this rare path from being precomputed per tile and spilled)
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+            const int64_t pa = pr0 + 2 * k + 2, pb = pa + 1;
+            const uint32_t d0 = (pa >= p_lo && pa < p_hi) ? xin[pa - pbuf0] : 0x08000800u;
+            const uint32_t d1 = (pb >= p_lo && pb < p_hi) ? xin[pb - pbuf0] : 0x08000800u;
+            tl[k] = f32x4{(float)(d0 & 0xFFFFu), (float)(d0 >> 16), (float)(d1 & 0xFFFFu), (float)(d1 >> 16)};
+        }
+    }
+    // the run's pairs as (I, Q), slot s <-> pair s - 6 of the run: the converted samples as they are -- the - 2048 of
+    // air.c:64-67 and the fs/4 sign of air.c:79-82 are inside the FIR's products (fir_product)
+#pragma unroll
+    for (int s = 0; s < 34; s++) {
+        const f32x4 q = tl[s >> 1];
+        vv[s] = (s & 1) ? f32x2{q.z, q.w} : f32x2{q.x, q.y};
+    }
+    power_run<0>(vv, a, kc);
+}
+
 } // namespace
 
 // ------------------------------ Stage A ------------------------------
@@ -373,94 +472,18 @@ __device__ __forceinline__ void stage_a(const uint32_t *__restrict__ xin, const 
 {
     // first run of wave w in pass ps: a pass of the four waves is 252 consecutive runs
     auto first_run = [&](int ps) { return kWaveRuns * (kWaves * ps + wave); };
-    // Input: the 34 pairs (6 of pre-halo + 28) a run needs are 17 TYPED buffer loads of 8
-    // bytes per lane (buffer_load_format_xyzw, data format 16_16_16_16, number format
-    // USCALED): the load path itself converts the four uint16 to four floats -- exactly, and
-    // for free next to 66 v_cvt_f32_u32 per run (4.4 cycles each; kernel -2 .. -4.5 %).  Lanes are 112 bytes apart; the buffer resource is rebuilt per
-    // wave and pass around the wave's own 7 KiB window, so no buffer size limit applies.
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    auto pass_first_pair = [&](int ps) { return t0 + (int64_t)kRun * first_run(ps) - 8; }; // lane 0's
+    // first pair of the wave's window in pass ps, 8 below lane 0's run (a function of ps, not of the loop's v0: the same value, but
+    // written from v0 an address of the scan kernels moves from the scalar to the vector side, profiles/r24_front_shared_isa.txt)
+    auto pass_first_pair = [&](int ps) { return t0 + (int64_t)kRun * first_run(ps) - 8; };
 #pragma unroll 1
     for (int pass = 0; pass < K; pass++) {
-        // the FIR's constants (fir_product): the vector ones written here, by instructions the compiler cannot hoist -- eight
-        // registers that live from here to the end of the FIR, not across the plane arithmetic behind it; the scalar ones
-        // made opaque INSIDE the loop, so that their exchanged and negated forms are operand modifiers, not hoisted copies
-        FirConsts kc = {{{0, 0}, {0, 0}, {0, 0}, {0, 0}}, {{tap<12>(), tap<13>()}, {tap<10>(), tap<11>()}, {tap<8>(), tap<9>()}, {tap<6>(), tap<7>()}}};
-#define ADSB_KC(b, T0, T1)                                                                                                          \
-    asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"                                                                            \
-                 : "=v"(kc.c2048[b].x), "=v"(kc.c2048[b].y)                                                                         \
-                 : "i"(__builtin_bit_cast(uint32_t, 2048.0f * tap<T0>())), "i"(__builtin_bit_cast(uint32_t, 2048.0f * tap<T1>())))
-        ADSB_KC(0, 12, 13);
-        ADSB_KC(1, 10, 11);
-        ADSB_KC(2, 8, 9);
-        ADSB_KC(3, 6, 7);
-#undef ADSB_KC
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-            asm volatile("" : "+s"(kc.taps[b]));
         const int v0 = first_run(pass); // first run of this wave in this pass
         const int v = v0 + lane;
         const int64_t wlo = pass_first_pair(pass);
-        // wave-uniform: every pair this wave loads lies inside the buffer
-        const bool interior = (wlo >= p_lo) && (wlo + kRun * 64 + 8 <= p_hi);
-        f32x4 tl[17]; // tl[k]: pairs 2k+2, 2k+3 of the lane's 36 = slots 2k, 2k+1
-        if (interior) {
-            const uint64_t wbase = (uint64_t)(xin + (wlo - pbuf0));
-            i32x4 rs;
-            rs.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)wbase);
-            rs.y = __builtin_amdgcn_readfirstlane((int)((uint32_t)(wbase >> 32) & 0xFFFFu)); // stride 0: raw buffer
-            rs.z = 64 * kRun * 4 + 64;                                                        // bytes
-            rs.w = (int)(4u | 5u << 3 | 6u << 6 | 7u << 9 /* dst_sel xyzw */ | 2u << 12 /* USCALED */ | 12u << 15 /* 16_16_16_16 */);
-            const int voff = lane * (kRun * 4);
-            asm volatile("buffer_load_format_xyzw %0, %17, %18, 0 offen offset:8\n\t"
-                         "buffer_load_format_xyzw %1, %17, %18, 0 offen offset:16\n\t"
-                         "buffer_load_format_xyzw %2, %17, %18, 0 offen offset:24\n\t"
-                         "buffer_load_format_xyzw %3, %17, %18, 0 offen offset:32\n\t"
-                         "buffer_load_format_xyzw %4, %17, %18, 0 offen offset:40\n\t"
-                         "buffer_load_format_xyzw %5, %17, %18, 0 offen offset:48\n\t"
-                         "buffer_load_format_xyzw %6, %17, %18, 0 offen offset:56\n\t"
-                         "buffer_load_format_xyzw %7, %17, %18, 0 offen offset:64\n\t"
-                         "buffer_load_format_xyzw %8, %17, %18, 0 offen offset:72\n\t"
-                         "buffer_load_format_xyzw %9, %17, %18, 0 offen offset:80\n\t"
-                         "buffer_load_format_xyzw %10, %17, %18, 0 offen offset:88\n\t"
-                         "buffer_load_format_xyzw %11, %17, %18, 0 offen offset:96\n\t"
-                         "buffer_load_format_xyzw %12, %17, %18, 0 offen offset:104\n\t"
-                         "buffer_load_format_xyzw %13, %17, %18, 0 offen offset:112\n\t"
-                         "buffer_load_format_xyzw %14, %17, %18, 0 offen offset:120\n\t"
-                         "buffer_load_format_xyzw %15, %17, %18, 0 offen offset:128\n\t"
-                         "buffer_load_format_xyzw %16, %17, %18, 0 offen offset:136"
-                         "\n\ts_waitcnt vmcnt(0)"
-                         : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]), "=&v"(tl[4]), "=&v"(tl[5]), "=&v"(tl[6]),
-                           "=&v"(tl[7]), "=&v"(tl[8]), "=&v"(tl[9]), "=&v"(tl[10]), "=&v"(tl[11]), "=&v"(tl[12]),
-                           "=&v"(tl[13]), "=&v"(tl[14]), "=&v"(tl[15]), "=&v"(tl[16])
-                         : "v"(voff), "s"(rs)
-                         : "memory");
-        } else {
-            // Stream start (the ring is zero-initialised, air.c:33: a missing pair is
-            // 0x0800,0x0800 -> v = 0) and the ragged end of a buffer: plain loads, converted here
-            int64_t pr0 = wlo + (int64_t)kRun * lane;
-            asm volatile("" : "+v"(pr0)); // (opaque: keeps the 34 pair indices of this rare path from being precomputed per tile and spilled)
-#pragma unroll
-            for (int k = 0; k < 17; k++) {
-                const int64_t pa = pr0 + 2 * k + 2, pb = pa + 1;
-                const uint32_t d0 = (pa >= p_lo && pa < p_hi) ? xin[pa - pbuf0] : 0x08000800u;
-                const uint32_t d1 = (pb >= p_lo && pb < p_hi) ? xin[pb - pbuf0] : 0x08000800u;
-                tl[k] = f32x4{(float)(d0 & 0xFFFFu), (float)(d0 >> 16), (float)(d1 & 0xFFFFu), (float)(d1 >> 16)};
-            }
-        }
-        // the run's pairs as (I, Q), slot s <-> pair s - 6 of the run: the converted samples as they are -- the - 2048 of
-        // air.c:64-67 and the fs/4 sign of air.c:79-82 are inside the FIR's products (fir_product)
-        f32x2 vv[34];
-#pragma unroll
-        for (int s = 0; s < 34; s++) {
-            const f32x4 q = tl[s >> 1];
-            vv[s] = (s & 1) ? f32x2{q.z, q.w} : f32x2{q.x, q.y};
-        }
-
         // a[0..27]: this run; a[28..43]: the first 16 samples of the next run (next lane)
+        f32x2 vv[34];
         float a[44];
-        power_run<0>(vv, a, kc);
+        real_front<false>(xin, pbuf0, p_lo, p_hi, wlo, lane, vv, a);
 #pragma unroll
         for (int k = 0; k < 16; k++)
             a[28 + k] = from_next_lane(a[k]);
