@@ -24,7 +24,8 @@ ROCM = os.environ.get("ROCM", "/opt/rocm")  # the HIP runtime's headers and libr
 HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip", "scan_iq8_kernel.hip", "scan_power_kernel.hip", "seam_kernel.hip", "decoder.hip", "decoder_collect.hip",
                "decoder_lifecycle.hip", "decoder_batch.hip", "decoder_shard.hip", "unpack12.hip", "unpack12_batch.hip",
                "convert_samples.hip", "power_export_kernel.hip", "decoder_export.hip",
-               "power_export_batch_kernel.hip", "decoder_export_batch.hip", "level_kernel.hip", "decoder_level.hip"]
+               "power_export_batch_kernel.hip", "decoder_export_batch.hip", "level_kernel.hip", "decoder_level.hip",
+               "level_batch_kernel.hip", "decoder_level_batch.hip"]
 C_SOURCES = ["format.c"]
 # host-only C++ (no HIP): the multi-GPU driver over the C-ABI, and the part of the C-ABI that needs no device
 CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]

@@ -234,6 +234,13 @@ SYMBOLS = {
     "adsb_level_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_level_device_power": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_level_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_level_batch_device": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_level_batch_device_as": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_level_batch_device_packed": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_level_batch_device_iq": (C.c_long, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_level_batch_device_power": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_level_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adsb_debug_set_level_batch_blocks": (C.c_int, [C.c_void_p, C.c_int]),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -1007,6 +1014,53 @@ class Decoder:
         if self._L.adsb_level_host(self._h, x.ctypes.data if x.size else None, x.size, C.byref(r), e.ctypes.data if e.size else None, e.size) < 0:
             self._check(-1, "adsb_level_host")
         return self.level_dict(r, e)
+
+    # ---- the level reports of a batch of captures, one launch per 1024 (include/adsbdec_amd.h: adsb_level_batch_*)
+    def _level_batch_call(self, name, *head, ptrs, ns, env_ptrs=None, env_caps=None, out=None) -> list:
+        """-> a list of level_dict dicts, capture by capture.  env_ptrs / env_caps: both None (no envelope at all), or a device pointer
+        (0 / None: none for that capture) and its floats per capture.  out: an array of LevelReport to fill instead of a new one."""
+        k = len(ns)
+        assert len(ptrs) == k and (env_ptrs is None) == (env_caps is None)
+        arr = lambda t, vals: (t * max(1, k))(*vals)
+        r = (LevelReport * max(1, k))() if out is None else out
+        envs = (None, None) if env_ptrs is None else (arr(C.c_void_p, [int(v) if v else None for v in env_ptrs]), arr(C.c_size_t, [int(v) for v in env_caps]))
+        if getattr(self._L, name)(self._h, *head, k, arr(C.c_void_p, [int(v) if v else None for v in ptrs]), arr(C.c_size_t, [int(v) for v in ns]),
+                                  r, *envs) < 0:
+            self._check(-1, name)
+        return [self.level_dict(r[i]) for i in range(k)]
+
+    def level_batch_device(self, ptrs, ns, env_ptrs=None, env_caps=None, out=None) -> list:
+        """adsb_level_batch_device: capture i (ns[i] uint16 samples in HBM at ptrs[i]) -> the report level_device gives for it alone."""
+        return self._level_batch_call("adsb_level_batch_device", ptrs=ptrs, ns=ns, env_ptrs=env_ptrs, env_caps=env_caps, out=out)
+
+    def level_batch_device_as(self, fmt: int, ptrs, ns, env_ptrs=None, env_caps=None, out=None) -> list:
+        return self._level_batch_call("adsb_level_batch_device_as", fmt, ptrs=ptrs, ns=ns, env_ptrs=env_ptrs, env_caps=env_caps, out=out)
+
+    def level_batch_device_packed(self, ptrs, ns, env_ptrs=None, env_caps=None, out=None) -> list:
+        return self._level_batch_call("adsb_level_batch_device_packed", ptrs=ptrs, ns=ns, env_ptrs=env_ptrs, env_caps=env_caps, out=out)
+
+    def level_batch_device_iq(self, fmt: int, ptrs, ns, env_ptrs=None, env_caps=None, out=None) -> list:
+        """adsb_level_batch_device_iq: ns[i] complex samples (fmt 0, 2 or 8) -> the report of their ns[i] power samples."""
+        return self._level_batch_call("adsb_level_batch_device_iq", fmt, ptrs=ptrs, ns=ns, env_ptrs=env_ptrs, env_caps=env_caps, out=out)
+
+    def level_batch_device_power(self, ptrs, ns, env_ptrs=None, env_caps=None, out=None) -> list:
+        return self._level_batch_call("adsb_level_batch_device_power", ptrs=ptrs, ns=ns, env_ptrs=env_ptrs, env_caps=env_caps, out=out)
+
+    def level_batch(self, arrays, env: bool = True) -> list:
+        """The reports of uint16 captures in host memory, adsb_level_batch_host: per capture the dict level() returns ("env" where env)."""
+        arrays = [np.ascontiguousarray(a, dtype=np.uint16).reshape(-1) for a in arrays]
+        es = [np.empty(-(-(2 * (a.size // 4)) // 28) if env else 0, dtype=np.float32) for a in arrays]
+        out = self._level_batch_call("adsb_level_batch_host", ptrs=[a.ctypes.data if a.size else None for a in arrays], ns=[a.size for a in arrays],
+                                     env_ptrs=[e.ctypes.data if e.size else None for e in es] if env else None,
+                                     env_caps=[e.size for e in es] if env else None)
+        if env:
+            for o, e in zip(out, es):
+                o["env"] = e
+        return out
+
+    def set_level_batch_blocks(self, blocks: int) -> None:
+        """adsb_debug_set_level_batch_blocks: cap the workgroups of a batch level launch (0: the default)."""
+        self._check(self._L.adsb_debug_set_level_batch_blocks(self._h, blocks), "adsb_debug_set_level_batch_blocks")
 
     def format_report(self):
         """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""

@@ -8,6 +8,7 @@
 //   decoder_export.hip     the export calls (adsb_power_*): the front end's power samples into an array of the caller's
 //   decoder_export_batch.hip  ... of a batch of captures in one launch (adsb_power_batch_*)
 //   decoder_level.hip      the level calls (adsb_level_*): a capture's power samples reduced to a report and an envelope
+//   decoder_level_batch.hip  the batch level calls (adsb_level_batch_*): the reports of N captures by one launch per sub-batch
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
 
@@ -317,6 +318,12 @@ struct adsb_decoder {
     // the scan stream at the start of a call and copied to the pinned half before it returns; measurement builds: a row per workgroup
     adsb::Totals<unsigned long long> level;
     adsb::Buf<uint32_t> level_rows;
+    // the batch level calls (adsb_level_batch_*, decoder_level_batch.hip): the launch's table, a row per capture that has power samples
+    // (level_batch.hpp), and the totals of a sub-batch, kLevelWords per row -- 16 MiB on the device and as much pinned at
+    // kLevelBatchCaptures rows, grown to the largest sub-batch seen
+    adsb::Table level_tab;
+    adsb::Totals<unsigned long long> level_batch;
+    int level_batch_blocks = 0; // adsb_debug_set_level_batch_blocks: 0, or the most workgroups a batch level launch may have
 
     int fail(const char *fmt, ...)
     {

@@ -76,7 +76,7 @@ struct Table {
 };
 
 // Totals a kernel adds to on the device and the pinned array the host reads them from: `words` each, allocated together; zeroed
-// and copied back by whoever launches (decoder_level.hip).
+// and copied back by whoever launches (decoder_level.hip; decoder_level_batch.hip: kLevelWords per capture of a sub-batch).
 template <class T> struct Totals {
     Buf<T, Mem::Device> dev;
     Buf<T, Mem::Pinned> host;

@@ -332,6 +332,11 @@ int adsb_batch_records(adsb_decoder *d, const adsb_candidate **cands, size_t *n_
  * a capture index that call did not have, an n beyond that capture's slot, or when the last batch call on d was one that fills no
  * such scratch (the uint16 batch calls, IQ fmt 2, the power batches). */
 int adsb_batch_unpacked_copy(adsb_decoder *d, size_t capture, uint16_t *dst_u16, size_t n);
+/* adsb_level_batch_*: the most workgroups a level launch of a batch may have from now on (0: the default, 2048).  With 1, four waves
+ * share a whole sub-batch, and each changes capture -- and flushes its histogram to the totals of the capture it held -- many
+ * times: how a small batch exercises that path.  A call of its own and not a member of adsb_debug_config: the knob can be turned
+ * between two calls on ONE handle, so a test compares both settings on the same device buffers.  0, or -1 (blocks < 0). */
+int adsb_debug_set_level_batch_blocks(adsb_decoder *d, int blocks);
 
 /* ---- a batch over the devices of adsb_multi (adsb_multi_decode_batch_*; csrc/multi.cpp), without a device ------------------------
  * The plan, a pure function: n_captures captures of n[i] samples over n_workers workers.  Worker w gets the captures

@@ -8,6 +8,7 @@ comparison interleaved.
     python tools/format_probe.py --export [--reps 20] [--out profiles/r17_power_export.txt] [--layout name=path/to/libadsbdec_amd.so ...]   # export_probe()
     python tools/format_probe.py --export-batch [--reps 20] [--out profiles/r20_export_batch.txt] [--ab path/to/parent/libadsbdec_amd.so]   # export_batch_probe()
     python tools/format_probe.py --level [--reps 20] [--out profiles/r23_level.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_probe()
+    python tools/format_probe.py --level-batch [--reps 20] [--out profiles/r26_level_batch.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_batch_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
     (with counters, and without: a kernel that does not classify its samples at all) and adsb_unpack_packed12 at the same n
@@ -893,6 +894,176 @@ def export_batch_probe(L, reps, lines, parent):
         lines += ["#   (the parent commit's library was not given with --ab: its side was not measured in this run)"]
 
 
+def level_batch_probe(L, reps, lines, variants):
+    """The batch level report (level_batch_kernel.hip, the adsb_level_batch_* calls) against the loop of single calls, every comparison
+    interleaved in this one process, wall time of the calls (each waits for its kernels; the ctypes arrays are built once):
+    (a) 256 captures of 1 Mi samples, every flavour; (b) 4096 captures of 2048 samples, with and without envelopes; (c) ONE capture of
+    256 Mi samples as a batch of one beside adsb_level_device; (d) leg (a) on noise and on silence; (e) on (a), (b) and (c) every build
+    given with --variant name=path beside the tree's: measurement builds whose level_batch_kernel.hip was compiled with another walk
+    (-DADSB_LEVEL_BATCH_WALK=1) or end (-DADSB_LEVEL_BATCH_MERGE=0).  Every leg: the batch, the loop and every variant give the same reports and envelopes before anything
+    is timed.  Returns whether on (a) and (b) the batch beats the loop by more than the A/A spread."""
+    import numpy as np
+    from adsbdec_amd.packed12 import pack12
+    work, _ = make_workload(torch, N, seed=1)
+    g = torch.Generator(device="cuda").manual_seed(23)
+    noise = (torch.randn(N, device="cuda", generator=g) * 600.0 + 2048.0).round_().clamp_(0, 4095).to(torch.int16)
+    silence = torch.full((N,), 0x800, dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()                               # (the library's streams do not wait for torch's)
+    KE = -(-(N // 2) // 28) + 4096
+    env, env2 = torch.zeros(KE, dtype=torch.float32, device="cuda"), torch.zeros(KE, dtype=torch.float32, device="cuda")
+    d = capi.Decoder()
+    h = d._h
+    SZ = C.sizeof(capi.LevelReport)
+
+    def bind(path):
+        B = C.CDLL(path)
+        for name in ("adsb_create", "adsb_level_batch_device"):
+            fn = getattr(B, name)
+            fn.restype, fn.argtypes = capi.SYMBOLS[name]
+        cfg = capi.make_config()
+        hh = B.adsb_create(C.byref(cfg))
+        assert hh, path
+        return B, hh
+
+    others = {}
+    for spec in variants:
+        name, _, path = spec.partition("=")
+        others[name] = bind(path)
+    gates = []
+
+    def leg(title, bname, sname, fmt, src, elem_bytes, k, n, m, steps, with_env=True, with_variants=False, gated=True):
+        """k captures of n units (elem_bytes each) from src, m power samples each: batch, batch again, loop, variants -- in rotation."""
+        ke = -(-m // 28)
+        pl = [src.data_ptr() + int(i * n * elem_bytes) for i in range(k)]
+        ptrs, ns = (C.c_void_p * k)(*pl), (C.c_size_t * k)(*([n] * k))
+        el = [env2.data_ptr() + 4 * i * ke if with_env else None for i in range(k)]
+        eb = ((C.c_void_p * k)(*[env.data_ptr() + 4 * i * ke for i in range(k)]), (C.c_size_t * k)(*([ke] * k))) if with_env else (None, None)
+        cap = ke if with_env else 0
+        rb, rl = (capi.LevelReport * k)(), (capi.LevelReport * k)()
+        refs = [C.byref(rl, i * SZ) for i in range(k)]
+        head = () if fmt is None else (fmt,)
+        sfn = getattr(L, sname)
+
+        def batch(B=L, hh=h):
+            assert getattr(B, bname)(hh, *head, k, ptrs, ns, rb, *eb) == k * m
+
+        def loop():
+            for i in range(k):
+                sfn(h, *head, pl[i], n, refs[i], el[i], cap)
+        sides = {"batch": batch, "batch again (the A/A)": batch, "loop of single calls": loop}
+        for _ in range(2):
+            loop()
+            batch()
+        torch.cuda.synchronize()
+        assert bytes(rb) == bytes(rl), title + ": the batch and the loop give other reports"
+        assert torch.equal(env[: k * ke].view(torch.int32), env2[: k * ke].view(torch.int32)) or not with_env, title + ": other envelopes"
+        if with_variants:
+            for name, (B, hh) in others.items():
+                C.memset(C.addressof(rb), 0, C.sizeof(rb))
+                env.zero_()
+                torch.cuda.synchronize()
+                for _ in range(2):
+                    batch(B, hh)
+                assert bytes(rb) == bytes(rl), f"{title}: {name} gives other reports"
+                assert torch.equal(env[: k * ke].view(torch.int32), env2[: k * ke].view(torch.int32)) or not with_env, f"{title}: {name}: other envelopes"
+                sides[name] = (lambda B=B, hh=hh: batch(B, hh))
+        wall = {s_: [] for s_ in sides}
+        names = list(sides)
+        for r in range(reps):
+            for name in names[r % len(names):] + names[:r % len(names)]:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    sides[name]()
+                wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        aa = [b / a_ for a_, b in zip(wall[names[0]], wall[names[1]])]
+        ratio = [b / a_ for a_, b in zip(wall[names[0]], wall[names[2]])]
+        qa, qr = statistics.quantiles(aa, n=4), statistics.quantiles(ratio, n=4)
+        lines.append(f"    {title:40s} batch {med(wall[names[0]]):9.4f} ms   loop {med(wall[names[2]]):9.4f} ms   loop / batch {med(ratio):7.3f} ({qr[0]:.3f} .. {qr[2]:.3f})"
+                     f"   A/A {med(aa):.4f} ({qa[0]:.4f} .. {qa[2]:.4f})")
+        print(lines[-1], flush=True)
+        for name in names[3:]:
+            rr = [b / a_ for a_, b in zip(wall[names[0]], wall[name])]
+            q = statistics.quantiles(rr, n=4)
+            lines.append(f"        (e) {name:32s} batch {med(wall[name]):9.4f} ms   / the tree's batch {med(rr):.4f} ({q[0]:.4f} .. {q[2]:.4f})")
+            print(lines[-1], flush=True)
+        if gated:
+            gates.append((title, med(ratio) > 1.0 + max(abs(qa[0] - 1.0), abs(qa[2] - 1.0), abs(med(aa) - 1.0))))
+
+    K, N1 = 256, 1 << 20
+    steps = 5
+    lines += [f"# (a) {K} captures of 1 Mi samples side by side in one allocation, an envelope each; {reps} rounds x {steps} calls per side, the sides in rotation;",
+              "#     medians of the rounds (quartiles); every leg: the batch and the loop give the same reports and envelopes before anything is timed",
+              "#   leg                                        one batch call        256 single calls     ratio of the rounds                    batch / batch"]
+    t = work
+    leg("(a) uint16", "adsb_level_batch_device", "adsb_level_device", None, t, 2, K, N1, N1 // 2, steps, with_variants=True)
+    packed = torch.from_numpy(pack12(t[:N1].cpu().numpy().view(np.uint16))).cuda().repeat(K)
+    leg("(a) _packed", "adsb_level_batch_device_packed", "adsb_level_device_packed", None, packed, 1.5, K, N1, N1 // 2, steps)
+    del packed
+    s16 = ((t.to(torch.int32) - 2048) * 16).to(torch.int16)
+    leg("(a) _as fmt 3 INT16_REAL", "adsb_level_batch_device_as", "adsb_level_device_as", S16, s16, 2, K, N1, N1 // 2, steps)
+    del s16
+    f32 = (t.to(torch.float32) - 2048.0) / 2048.0
+    leg("(a) _as fmt 1 FLOAT32_REAL", "adsb_level_batch_device_as", "adsb_level_device_as", F32, f32, 4, K, N1, N1 // 2, steps)
+    del f32
+    iq = t.view(torch.int16)
+    leg("(a) _iq fmt 2, 512 Ki complex each", "adsb_level_batch_device_iq", "adsb_level_device_iq", 2, iq, 4, K, N1 // 2, N1 // 2, steps)
+    fiq = iq.to(torch.float32) / 32768.0
+    leg("(a) _iq fmt 0, 512 Ki complex each", "adsb_level_batch_device_iq", "adsb_level_device_iq", 0, fiq, 8, K, N1 // 2, N1 // 2, steps)
+    del fiq
+    iq8 = (iq >> 4).to(torch.int8)
+    leg("(a) _iq fmt 8, 512 Ki complex each", "adsb_level_batch_device_iq", "adsb_level_device_iq", 8, iq8, 2, K, N1 // 2, N1 // 2, steps)
+    del iq8
+    pw = iq[: N // 2].to(torch.float32)
+    pw = pw * pw
+    leg("(a) _power, 512 Ki floats each", "adsb_level_batch_device_power", "adsb_level_device_power", None, pw, 4, K, N1 // 2, N1 // 2, steps)
+    del pw, iq
+    lines += ["#", "# (b) 4096 captures of 2048 samples (1024 power samples: one pass each, four sub-batches of 1024 captures)"]
+    leg("(b) uint16, with envelopes", "adsb_level_batch_device", "adsb_level_device", None, t, 2, 4096, 2048, 1024, steps, with_variants=True)
+    leg("(b) uint16, no envelope", "adsb_level_batch_device", "adsb_level_device", None, t, 2, 4096, 2048, 1024, steps, with_env=False, with_variants=True)
+    lines += ["#", "# (d) leg (a), uint16, on other contents: Gaussian noise of sigma 600 codes round 2048, clipped to 0 .. 4095; silence (every code 0x800)"]
+    leg("(d) uint16, noise", "adsb_level_batch_device", "adsb_level_device", None, noise, 2, K, N1, N1 // 2, steps, with_variants=True, gated=False)
+    leg("(d) uint16, silence", "adsb_level_batch_device", "adsb_level_device", None, silence, 2, K, N1, N1 // 2, steps, with_variants=True, gated=False)
+
+    # (c) one large capture: the batch of one beside the single call
+    M = N // 2
+    ke = -(-M // 28)
+    one = (1, (C.c_void_p * 1)(t.data_ptr()), (C.c_size_t * 1)(N), None, (C.c_void_p * 1)(env.data_ptr()), (C.c_size_t * 1)(ke))
+    rep1, repb = capi.LevelReport(), (capi.LevelReport * 1)()
+    sides = {"adsb_level_device (tree)": lambda: L.adsb_level_device(h, t.data_ptr(), N, C.byref(rep1), env2.data_ptr(), ke),
+             "adsb_level_device (tree again: the A/A)": lambda: L.adsb_level_device(h, t.data_ptr(), N, C.byref(rep1), env2.data_ptr(), ke),
+             "adsb_level_batch_device, n_captures = 1": lambda: L.adsb_level_batch_device(h, 1, one[1], one[2], repb, one[4], one[5])}
+    for name, (B, hh) in others.items():
+        sides[f"... n_captures = 1, {name}"] = (lambda B=B, hh=hh: B.adsb_level_batch_device(hh, 1, one[1], one[2], repb, one[4], one[5]))
+    for name, fn in sides.items():
+        C.memset(C.addressof(repb), 0, SZ)
+        for _ in range(3):
+            assert fn() == M, name
+        assert "adsb_level_device" in name or (bytes(repb) == bytes(rep1) and torch.equal(env[:ke].view(torch.int32), env2[:ke].view(torch.int32))), name
+    names = list(sides)
+    wall = {k_: [] for k_ in names}
+    for r in range(reps):
+        for name in names[r % len(names):] + names[:r % len(names)]:
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                sides[name]()
+            wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+    lines += ["#", f"# (c) ONE capture of 256 Mi samples (512 MiB in), with its envelope; {reps} rounds x {steps} calls per side, the sides in rotation; wall time of the call;",
+              "#     every side gives the same report and envelope; recorded, not gated",
+              "#   side                                        call ms (q1 .. q3)          / tree (median of rounds, q1 .. q3)"]
+    base = wall[names[0]]
+    for name in names:
+        q = statistics.quantiles(wall[name], n=4)
+        rr = [a_ / b for a_, b in zip(wall[name], base)]
+        qr = statistics.quantiles(rr, n=4)
+        lines.append(f"    {name:42s} {med(wall[name]):.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med(rr):.4f} ({qr[0]:.4f} .. {qr[2]:.4f})")
+        print(lines[-1], flush=True)
+    lines += ["#", "# gate: on (a) and (b) the batch call beats the loop of single calls by more than the A/A spread of the same leg"]
+    for title, ok in gates:
+        lines.append(f"    {title:40s} {'PASS' if ok else 'FAIL'}")
+    print("\n".join(lines[-len(gates):]), flush=True)
+    return all(ok for _, ok in gates)
+
+
 def real_kernel_ab(builds, rounds, lines):
     """(c) the existing real-sample kernel across the change: tools/ab_interleaved.py in a process of its own (it dlopens every build
     side by side), the first build listed twice for the A/A."""
@@ -918,9 +1089,30 @@ def main():
     ap.add_argument("--layout", action="append", default=[], metavar="NAME=LIB", help="with --export: a build of the library with another store layout, measured beside the tree's")
     ap.add_argument("--export-batch", action="store_true", help="the batch power export (the adsb_power_batch_* calls) against the loop of single calls instead: profiles/r20_export_batch.txt; --ab: the parent commit's library, for (c)")
     ap.add_argument("--level", action="store_true", help="the level report (the adsb_level_* calls) instead: profiles/r23_level.txt")
-    ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB", help="with --level: a build of the library with another accumulation, flush or grid, measured beside the tree's")
+    ap.add_argument("--level-batch", action="store_true", help="the batch level report (the adsb_level_batch_* calls) against the loop of single calls instead: profiles/r26_level_batch.txt")
+    ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB", help="with --level or --level-batch: a build of the library with another accumulation, flush or grid, measured beside the tree's")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.level_batch:
+        a.out = a.out or os.path.join(ROOT, "profiles", "r26_level_batch.txt")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --level-batch: the batch level report (level_batch_kernel.hip, the adsb_level_batch_* calls) beside the loop of",
+                 f"# single calls, one process, {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
+                 "# The samples are the benchmark's: tools/gen_signal.py make_workload, 256 Mi samples, seed 1, cut into captures (and converted on the device",
+                 "# into each format; the packed leg repeats the first capture's packed bytes).  Wall time of the C calls through ctypes; every call waits for",
+                 "# its kernels and its copy of the totals, so a loop pays a memset, a launch, a 16 KiB copy and a wait per capture (two launches for the",
+                 "# flavours that unpack or convert).  Sides named with --variant are builds of the library that differ in level_batch_kernel.hip alone, loaded",
+                 "# beside the tree's in this process:",
+                 "#   -DADSB_LEVEL_BATCH_WALK=1   the passes go to the waves grid-stride, as the single kernel walks, and a wave flushes at every change of",
+                 "#                               capture; the tree (WALK=0) gives every wave a contiguous range of passes",
+                 "#   -DADSB_LEVEL_BATCH_MERGE=0  every wave flushes alone at its end; the tree (MERGE=1) sums the four histograms of a workgroup whose waves",
+                 "#                               end in the same capture and flushes once", "#"]
+        ok = level_batch_probe(capi.load(), a.reps, lines, a.variant)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        if not ok:
+            raise SystemExit("on (a) or (b) the batch call does not beat the loop of single calls by more than the A/A spread")
+        return
     if a.level:
         a.out = a.out or os.path.join(ROOT, "profiles", "r23_level.txt")
         torch.cuda.set_device(0)
