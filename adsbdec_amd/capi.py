@@ -241,6 +241,9 @@ SYMBOLS = {
     "adsb_level_batch_device_power": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adsb_level_batch_host": (C.c_long, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adsb_debug_set_level_batch_blocks": (C.c_int, [C.c_void_p, C.c_int]),
+    "adsb_level_windows": (C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_level_windows_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_level_add": (None, [C.c_void_p, C.c_void_p]),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -1062,6 +1065,32 @@ class Decoder:
         """adsb_debug_set_level_batch_blocks: cap the workgroups of a batch level launch (0: the default)."""
         self._check(self._L.adsb_debug_set_level_batch_blocks(self._h, blocks), "adsb_debug_set_level_batch_blocks")
 
+    # ---- the level reports of K consecutive windows of one stream, one launch per 1024 (include/adsbdec_amd.h: adsb_level_windows)
+    def level_windows(self, ptr: int, first_sample: int, n: int, edges, env_ptr: int = 0, env_cap: int = 0, out=None) -> list:
+        """adsb_level_windows: the uint16 samples [first_sample, first_sample + n) of a stream in HBM -> a list of level_dict dicts,
+        window i of power samples [edges[i], edges[i + 1]) (adsbdec_amd.levels.level_windows is the statement).  The one envelope of
+        all windows, if any, is on the device at env_ptr.  out: an array of LevelReport to fill instead of a new one."""
+        k = len(edges) - 1
+        e = (C.c_uint64 * (k + 1))(*[int(v) for v in edges])
+        r = (LevelReport * max(1, k))() if out is None else out
+        if self._L.adsb_level_windows(self._h, ptr or None, first_sample, n, k, e, r, env_ptr or None, env_cap) < 0:
+            self._check(-1, "adsb_level_windows")
+        return [self.level_dict(r[i]) for i in range(k)]
+
+    def level_windows_host(self, x: np.ndarray, first_sample: int, edges, env: bool = True):
+        """adsb_level_windows_host: x holds the stream's samples from first_sample on -> the list level_windows returns; with env,
+        (that list, the float32 envelope of power samples [edges[0], edges[-1]))."""
+        x = np.ascontiguousarray(x, dtype=np.uint16).reshape(-1)
+        k = len(edges) - 1
+        e = (C.c_uint64 * (k + 1))(*[int(v) for v in edges])
+        ev = np.empty(-(-(int(edges[-1]) - int(edges[0])) // 28) if env else 0, dtype=np.float32)
+        r = (LevelReport * max(1, k))()
+        if self._L.adsb_level_windows_host(self._h, x.ctypes.data if x.size else None, first_sample, x.size, k, e, r,
+                                           ev.ctypes.data if ev.size else None, ev.size) < 0:
+            self._check(-1, "adsb_level_windows_host")
+        reports = [self.level_dict(r[i]) for i in range(k)]
+        return (reports, ev) if env else reports
+
     def format_report(self):
         """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""
         r = FormatReport()
@@ -1365,3 +1394,16 @@ def plan_shards(total_samples: int, n_shards: int):
         raise AdsbError("adsb_plan_shards failed")
     return [dict(g_begin=int(arrs[0][i]), g_end=int(arrs[1][i]), first_sample=int(arrs[2][i]),
                  n_samples=int(arrs[3][i])) for i in range(n_shards)]
+
+
+def level_add(r: dict, s: dict) -> dict:
+    """adsb_level_add on two report dicts (Decoder.level_dict's): what adsbdec_amd.levels.add states, computed by the library."""
+    def struct(d):
+        o = LevelReport()
+        for k in ("samples", "negative", "rail_lo", "rail_hi", "over"):
+            setattr(o, k, int(d[k]))
+        np.ctypeslib.as_array(o.hist)[:] = np.asarray(d["hist"], dtype=np.uint64)
+        return o
+    a, b = struct(r), struct(s)
+    load().adsb_level_add(C.byref(a), C.byref(b))
+    return Decoder.level_dict(a)

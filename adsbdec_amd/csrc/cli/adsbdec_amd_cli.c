@@ -45,6 +45,11 @@
  *                   99.9th percentile and the peak bin in dB of raw power units (not dBFS: nobody has measured the front end's gain).  The
  *                   whole file is one capture in one call: a real file below 2^32 samples, IQ and power below 2^31.  Not with -G, -B,
  *                   -W, -s, -l or several -f.
+ *     -I ms         EXTENSION, with -L on a uint16 file: THE LEVELS OVER TIME (adsb_level_windows_host).  The file, or FIFO, is read in
+ *                   pieces of about 16 Mi samples, each behind the last 16 samples of the piece before it; a line `t START s median ..
+ *                   p99.9 .. peak .. rail_lo A rail_hi B over C` per window of ms milliseconds (10 000 power samples each, rounded down
+ *                   to a multiple of 28), then -L's report of the sum of the windows (a trailing n % 4 samples belong to no window: named
+ *                   on stderr, and not on the rails as plain -L has them).  Not with -t, -p, -q or -w.
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -193,7 +198,8 @@ static void usage(void)
     printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-q type] [-w] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
     printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n");
     printf("        adsbdec_amd_cli [-q type] [-d gpu] -W out.pw -f filename\n");
-    printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -f filename\n\n");
+    printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -f filename\n");
+    printf("        adsbdec_amd_cli [-d gpu] -L -I ms -f filename\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
     printf("\t-b : output binary beast format\n");
@@ -215,6 +221,9 @@ static void usage(void)
     printf("\t     counters (samples, negative, codes on the ADC's rails and above 4095), a histogram in bins of 1/8 octave (0.75 dB) and its\n");
     printf("\t     median, 99.9th percentile and peak in dB of raw power units; input as -p, -t, -q (8 too) or -w say; the whole file in one\n");
     printf("\t     call (a real file: below 2^32 samples, IQ and power: below 2^31); not with -G, -B, -W, -s, -l or several -f\n");
+    printf("\t-I ms : (extension) with -L on a uint16 file: the levels over time.  A line per window of ms milliseconds (10 000 power samples\n");
+    printf("\t     each, rounded down to a multiple of 28): its start in seconds, median, 99.9th percentile and peak, the three rail counters;\n");
+    printf("\t     then -L's report of the whole.  The file is read in pieces of bounded size: a FIFO works; not with -t, -p, -q or -w\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
@@ -646,7 +655,7 @@ static int run_export(const char *filename, const char *outpath, int device, int
 }
 
 /* -L: the level report of the file's power samples on stdout; nothing is decoded.  The whole file is ONE capture in ONE call (the
- * report of a real capture needs every pair's six predecessors, and no level call takes a window): kind 0 uint16 (adsb_level_host,
+ * report of a real capture needs every pair's six predecessors, and only the uint16 flavour has a window call: -I, run_level_windows below): kind 0 uint16 (adsb_level_host,
  * through the handle's buffers), 1 -t 1 | 3, 2 -p, 3 -q, 4 -w (a device buffer of the program's own). */
 static double bin_db(unsigned k, int *zero)
 {
@@ -687,6 +696,34 @@ static void print_db(const char *name, unsigned k, const char *end)
         printf("%s %s%s", name, k == 2040 ? "inf dB" : "nan", end);
     else
         printf("%s %.2f dB%s", name, db, end);
+}
+
+/* the report as -L prints it: the counters, a line per non-empty bin, the summary */
+static void print_level_report(const adsb_level_report *rep)
+{
+    printf("samples %llu negative %llu rail_lo %llu rail_hi %llu over %llu\n", (unsigned long long)rep->samples, (unsigned long long)rep->negative,
+           (unsigned long long)rep->rail_lo, (unsigned long long)rep->rail_hi, (unsigned long long)rep->over);
+    unsigned peak = 0;
+    uint64_t counted = 0;
+    for (unsigned k = 0; k < 2048; k++) {
+        if (!rep->hist[k])
+            continue;
+        union { uint32_t u; float f; } edge;
+        edge.u = k << 20;
+        if (k < 2040)
+            printf("bin %u %.9g %llu\n", k, (double)edge.f, (unsigned long long)rep->hist[k]);
+        else
+            printf("bin %u %s %llu\n", k, k == 2040 ? "inf" : "nan", (unsigned long long)rep->hist[k]);
+        peak = k;
+        counted += rep->hist[k];
+    }
+    if (counted) { /* (dB of raw power units, not dBFS: nobody has measured the front end's gain) */
+        print_db("median", bin_of_quantile(rep, 0.5), " ");
+        print_db("p99.9", bin_of_quantile(rep, 0.999), " ");
+        print_db("peak", peak, "\n");
+    } else {
+        printf("median none p99.9 none peak none\n");
+    }
 }
 
 static int run_level(const char *filename, int device, int kind, int fmt)
@@ -741,29 +778,101 @@ static int run_level(const char *filename, int device, int kind, int fmt)
         fprintf(stderr, "%s() failed: %s\n", call, adsb_last_error(dec));
         return 255;
     }
-    printf("samples %llu negative %llu rail_lo %llu rail_hi %llu over %llu\n", (unsigned long long)rep->samples, (unsigned long long)rep->negative,
-           (unsigned long long)rep->rail_lo, (unsigned long long)rep->rail_hi, (unsigned long long)rep->over);
-    unsigned peak = 0;
-    uint64_t counted = 0;
-    for (unsigned k = 0; k < 2048; k++) {
-        if (!rep->hist[k])
-            continue;
-        union { uint32_t u; float f; } edge;
-        edge.u = k << 20;
-        if (k < 2040)
-            printf("bin %u %.9g %llu\n", k, (double)edge.f, (unsigned long long)rep->hist[k]);
-        else
-            printf("bin %u %s %llu\n", k, k == 2040 ? "inf" : "nan", (unsigned long long)rep->hist[k]);
-        peak = k;
-        counted += rep->hist[k];
+    print_level_report(rep);
+    fflush(stdout);
+    fflush(stderr);
+    if (getenv("ADSB_CLI_CLEAN_EXIT"))
+        exit(0);
+    _exit(0); /* (no teardown: see the end of main) */
+}
+
+/* -L -I ms: the levels over time.  The file -- a FIFO will do -- is read in pieces of LEVEL_PIECE power samples at most, each behind the
+ * last 16 samples of the piece before it, so that every power sample has its six older pairs; a piece is ONE adsb_level_windows_host
+ * call over windows of `ms` milliseconds (10 000 power samples each, rounded down to a multiple of 28).  A line per window, then -L's
+ * own report of their sum (adsb_level_add). */
+#define LEVEL_PIECE ((uint64_t)28 * 299593) /* about 16 Mi samples */
+#define LEVEL_PIECE_WINDOWS 1024            /* one launch (adsbdec_amd.h) */
+#define LEVEL_OVERLAP 16
+static int run_level_windows(const char *filename, int device, double ms)
+{
+    const double per_ms = 10000.0; /* power samples: 20 MS/s real, a power sample per pair */
+    const uint64_t win = ms * per_ms >= (double)LEVEL_PIECE ? LEVEL_PIECE : (uint64_t)(ms * per_ms) / 28 * 28;
+    if (win == 0) {
+        fprintf(stderr, "-I %g: a window holds at least 28 power samples (0.0028 ms)\n", ms);
+        return 1;
     }
-    if (counted) { /* (dB of raw power units, not dBFS: nobody has measured the front end's gain) */
-        print_db("median", bin_of_quantile(rep, 0.5), " ");
-        print_db("p99.9", bin_of_quantile(rep, 0.999), " ");
-        print_db("peak", peak, "\n");
-    } else {
-        printf("median none p99.9 none peak none\n");
+    if (ms * per_ms > (double)LEVEL_PIECE)
+        fprintf(stderr, "-I %g: windows of %llu power samples (%.4f ms), the most this program reads at once\n", ms, (unsigned long long)win,
+                (double)win / per_ms);
+    const int fd = open(filename, O_RDONLY);
+    if (fd < 0) {
+        fprintf(stderr, "%s: cannot read: %s\n", filename, strerror(errno));
+        return 255;
     }
+    adsb_config cfg;
+    adsb_config_default(&cfg);
+    cfg.device = device;
+    adsb_decoder *dec = adsb_create(&cfg);
+    if (!dec) {
+        fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
+        return 255;
+    }
+    uint64_t k_max = LEVEL_PIECE / win;
+    if (k_max > LEVEL_PIECE_WINDOWS)
+        k_max = LEVEL_PIECE_WINDOWS;
+    const char *few = getenv("ADSB_CLI_LEVEL_PIECE"); /* (for tests: the most windows of a piece, so that a small file takes several) */
+    if (few && atoi(few) > 0 && (uint64_t)atoi(few) < k_max)
+        k_max = (uint64_t)atoi(few);
+    const uint64_t piece = k_max * win; /* power samples */
+    uint16_t *buf = (uint16_t *)malloc((LEVEL_OVERLAP + 2 * piece) * sizeof(uint16_t) + 1);
+    uint64_t *edges = (uint64_t *)malloc((k_max + 1) * sizeof(uint64_t));
+    adsb_level_report *rep = (adsb_level_report *)malloc((k_max + 1) * sizeof *rep), *sum = rep ? rep + k_max : NULL;
+    if (!buf || !edges || !rep) {
+        fprintf(stderr, "out of memory for pieces of %llu samples\n", (unsigned long long)(2 * piece));
+        return 255;
+    }
+    memset(sum, 0, sizeof *sum);
+    uint64_t done = 0; /* power samples reported: a multiple of win */
+    for (;;) {
+        const size_t bytes = read_full(fd, buf + LEVEL_OVERLAP, 2 * piece * sizeof(uint16_t));
+        const size_t n_new = bytes / sizeof(uint16_t);
+        const uint64_t m_new = 2 * (uint64_t)(n_new / 4);
+        const int last = bytes < 2 * piece * sizeof(uint16_t);
+        if (last && bytes - 2 * m_new * sizeof(uint16_t))
+            fprintf(stderr, "%zu trailing bytes ignored (the reference reads four samples at a time)\n", bytes - (size_t)(2 * m_new) * sizeof(uint16_t));
+        size_t k = 0;
+        for (edges[0] = done; edges[k] < done + m_new; k++)
+            edges[k + 1] = edges[k] + win < done + m_new ? edges[k] + win : done + m_new;
+        if (k) {
+            const int head = done ? LEVEL_OVERLAP : 0; /* (the stream's start has nothing in front of it) */
+            if (adsb_level_windows_host(dec, buf + LEVEL_OVERLAP - head, 2 * done - head, n_new + head, k, edges, rep, NULL, 0) < 0) {
+                fprintf(stderr, "adsb_level_windows_host() failed: %s\n", adsb_last_error(dec));
+                return 255;
+            }
+        }
+        for (size_t i = 0; i < k; i++) {
+            const adsb_level_report *r = &rep[i];
+            unsigned peak = 0, any = 0;
+            for (unsigned b = 0; b < 2048; b++)
+                if (r->hist[b])
+                    peak = b, any = 1;
+            printf("t %.6f s ", (double)edges[i] / (per_ms * 1000.0));
+            if (any) {
+                print_db("median", bin_of_quantile(r, 0.5), " ");
+                print_db("p99.9", bin_of_quantile(r, 0.999), " ");
+                print_db("peak", peak, " ");
+            } else {
+                printf("median none p99.9 none peak none ");
+            }
+            printf("rail_lo %llu rail_hi %llu over %llu\n", (unsigned long long)r->rail_lo, (unsigned long long)r->rail_hi, (unsigned long long)r->over);
+            adsb_level_add(sum, r);
+        }
+        if (last)
+            break;
+        done += m_new;
+        memcpy(buf, buf + 2 * piece, LEVEL_OVERLAP * sizeof(uint16_t)); /* the piece's last 16 samples, in front of the next */
+    }
+    print_level_report(sum);
     fflush(stdout);
     fflush(stderr);
     if (getenv("ADSB_CLI_CLEAN_EXIT"))
@@ -777,6 +886,8 @@ int main(int argc, char **argv)
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
     int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, level = 0, c;
+    const char *interval_arg = NULL; /* -I: -L's windows, in milliseconds */
+    double interval_ms = 0;
     long stype = 5; /* -t: ADSB_FMT_RAW */
     const char *stype_arg = NULL;
     long qtype = -1; /* -q: ADSB_FMT_INT16_IQ / ADSB_FMT_FLOAT32_IQ / ADSB_FMT_INT8_IQ */
@@ -784,7 +895,7 @@ int main(int argc, char **argv)
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:L")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -848,6 +959,14 @@ int main(int argc, char **argv)
         case 'L':
             level = 1;
             break;
+        case 'I': {
+            char *end;
+            interval_ms = strtod(optarg, &end);
+            if (*end || end == optarg || !(interval_ms > 0) || interval_ms > 1e12)
+                interval_ms = 0;
+            interval_arg = optarg;
+            break;
+        }
         case 't': {
             char *end;
             stype = strtol(optarg, &end, 10);
@@ -877,6 +996,17 @@ int main(int argc, char **argv)
                 : export_path            ? "a run writes the power samples or reports their levels, not both"
                 : outmode != SINK_STDOUT ? "the report is text on stdout, not packets for a peer"
                                          : "the report is of one file");
+        return 1;
+    }
+    if (interval_arg && (!level || stype_arg || packed || qtype_arg || power || interval_ms == 0)) {
+        /* -I cuts -L's report of a uint16 file into windows: refused before any GPU call */
+        if (!level)
+            fprintf(stderr, "-I is not supported without -L: it is the length of the level report's windows\n");
+        else if (stype_arg || packed || qtype_arg || power)
+            fprintf(stderr, "-I is not supported with %s: the windows are of a uint16 file (adsb_level_windows); a slice of an IQ or power file is "
+                            "already exact on its own\n", stype_arg ? "-t" : packed ? "-p" : qtype_arg ? "-q" : "-w");
+        else
+            fprintf(stderr, "-I %s: the windows' length in milliseconds, a number above 0\n", interval_arg);
         return 1;
     }
     if (qtype_arg && qtype == ADSB_FMT_INT8_IQ && (stype_arg || packed || ndev || listfile || power || export_path)) {
@@ -970,6 +1100,8 @@ int main(int argc, char **argv)
             int first = 0;
             restrict_visible_devices(&first, 1);
         }
+        if (interval_arg)
+            return run_level_windows(filename, device, interval_ms);
         return run_level(filename, device, converted ? 1 : packed ? 2 : iq ? 3 : power ? 4 : 0, iq ? (int)qtype : (int)stype);
     }
     if (export_path) {

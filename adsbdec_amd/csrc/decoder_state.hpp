@@ -9,6 +9,7 @@
 //   decoder_export_batch.hip  ... of a batch of captures in one launch (adsb_power_batch_*)
 //   decoder_level.hip      the level calls (adsb_level_*): a capture's power samples reduced to a report and an envelope
 //   decoder_level_batch.hip  the batch level calls (adsb_level_batch_*): the reports of N captures by one launch per sub-batch
+//   decoder_level_windows.hip  the window form (adsb_level_windows*): the reports of K consecutive windows of one stream
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
 

@@ -54,6 +54,18 @@ extern "C" {
 
 int adsb_abi_version(void) { return ADSB_ABI_VERSION; }
 
+// *sum += *part, field by field: every field of a level report is a count, so the reports of the windows of a stream
+// (adsb_level_windows) add up to the report of their union.  NULL: nothing.
+void adsb_level_add(adsb_level_report *sum, const adsb_level_report *part)
+{
+    if (!sum || !part)
+        return;
+    sum->samples += part->samples, sum->negative += part->negative;
+    sum->rail_lo += part->rail_lo, sum->rail_hi += part->rail_hi, sum->over += part->over;
+    for (size_t k = 0; k < sizeof sum->hist / sizeof sum->hist[0]; k++)
+        sum->hist[k] += part->hist[k];
+}
+
 // The host side of the decoder*.hip units is built with -mavx2 (adsbdec_amd/_build.py says why); this file is not.  adsb_create asks here,
 // before anything else, whether the host can run it: a C string to show, or NULL.
 const char *adsb_host_cpu_refusal(void)

@@ -19,7 +19,8 @@
 // workgroup barrier per pass, no counters in LDS.  At the END the four waves of a workgroup meet once (block_finish): where all
 // four hold the same capture -- every workgroup inside a long capture -- their histograms leave as ONE sum, as the single kernel's
 // do; 8192 waves adding the same few hundred words of one capture one after the other is what a batch of one large capture
-// otherwise ends on (ADSB_LEVEL_BATCH_MERGE=0 in a measurement build: every wave flushes alone).  32-bit LDS counts cannot
+// otherwise ends on (ADSB_LEVEL_BATCH_MERGE=0 in a measurement build: every wave flushes alone).  The flush is level_flush.h's,
+// shared with level_windows_kernel.hip.  32-bit LDS counts cannot
 // overflow (a capture has fewer than 2^32 power samples).
 // ADSB_LEVEL_BATCH_WALK picks how the passes go to the waves in a measurement build (the shipped one defines nothing; DESIGN.md
 // section 4 "Batch level report" has the numbers):
@@ -36,13 +37,11 @@
 
 #include "level.h"
 #include "level_tail.h"
+#include "level_flush.h" // wave_begin, wave_flush, block_finish: shared with level_windows_kernel.hip
 #include "level_batch.hpp"
 
 #ifndef ADSB_LEVEL_BATCH_WALK
 #define ADSB_LEVEL_BATCH_WALK 0
-#endif
-#ifndef ADSB_LEVEL_BATCH_MERGE
-#define ADSB_LEVEL_BATCH_MERGE 1
 #endif
 
 namespace adsb {
@@ -58,90 +57,6 @@ typedef __attribute__((address_space(1))) float *global_floats;
 
 static_assert((uint64_t)kWavePass == kLevelPass, "level_batch.hpp restates the pass of scan_kernel.h's run");
 static_assert(ADSB_LEVEL_HIST == 5, "the batch unit is built around a histogram per wave with the run-uniform shortcut");
-constexpr int kBinsPerLane = kLevelBins / 64;
-
-// what the wave has written to its histogram is there for every lane of it to read, and the other way round
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void wave_begin(uint32_t *hist, const int lane)
-{
-#pragma unroll
-    for (int j = 0; j < kBinsPerLane; j++)
-        hist[64 * j + lane] = 0;
-    wave_sync();
-}
-
-// the wave's counters go to the totals of the capture they belong to
-__device__ __forceinline__ void counts_flush(Counts &c, unsigned long long *__restrict__ tot, const int lane)
-{
-    if (lane == 0) {
-        if (c.negative)
-            atomicAdd(&tot[1], (unsigned long long)c.negative);
-        if (c.rail_lo)
-            atomicAdd(&tot[2], (unsigned long long)c.rail_lo);
-        if (c.rail_hi)
-            atomicAdd(&tot[3], (unsigned long long)c.rail_hi);
-        if (c.over)
-            atomicAdd(&tot[4], (unsigned long long)c.over);
-    }
-    c = Counts{};
-}
-
-// The wave's counts go to the totals of the capture they belong to, and the wave holds nothing again.
-__device__ __forceinline__ void wave_flush(uint32_t *hist, Counts &c, unsigned long long *__restrict__ tot, const int lane)
-{
-    wave_sync();
-#pragma unroll 4
-    for (int j = 0; j < kBinsPerLane; j++) {
-        const int bin = 64 * j + lane;
-        const uint32_t v = hist[bin];
-        if (v) {
-            atomicAdd(&tot[5 + bin], (unsigned long long)v);
-            hist[bin] = 0;
-        }
-    }
-    counts_flush(c, tot, lane);
-    wave_sync();
-}
-
-// Behind a wave's last pass: what it still holds (held: of the capture whose totals are number `tot`) leaves.  The workgroup's four
-// waves meet here; where all hold the same capture their histograms are summed first and leave in one add per bin.
-__device__ __forceinline__ void block_finish(uint32_t (*hist)[kLevelBins], uint32_t *who, Counts &c, const bool held, const uint32_t tot,
-                                             unsigned long long *__restrict__ totals, const int lane, const int wave_in_block)
-{
-#if ADSB_LEVEL_BATCH_MERGE
-    if (lane == 0)
-        who[wave_in_block] = held ? tot : 0xFFFFFFFFu; // (never a row: rows are indexed below 2^32 - 1)
-    __syncthreads();
-    const uint32_t t0 = who[0];
-    bool same = t0 != 0xFFFFFFFFu; // (workgroup-uniform)
-#pragma unroll
-    for (int w = 1; w < kWaves; w++)
-        same = same && who[w] == t0;
-    if (same) {
-        unsigned long long *tt = totals + (size_t)t0 * kLevelWords;
-        counts_flush(c, tt, lane);
-#pragma unroll
-        for (int j = 0; j < kLevelBins / kThreads; j++) {
-            const int bin = j * kThreads + threadIdx.x;
-            uint32_t v = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; w++)
-                v += hist[w][bin];
-            if (v)
-                atomicAdd(&tt[5 + bin], (unsigned long long)v);
-        }
-        return;
-    }
-#endif
-    if (held)
-        wave_flush(hist[wave_in_block], c, totals + (size_t)tot * kLevelWords, lane);
-}
 
 // The passes of wave w of n_waves: from *u on, below *end, `step` apart (wave-uniform).
 struct Walk {

@@ -89,3 +89,56 @@ def with_rails(report: dict, x, kind: str) -> dict:
     r = dict(report)
     r["rail_lo"], r["rail_hi"], r["over"] = rails(x, kind)
     return r
+
+
+ZERO = dict(samples=0, negative=0, rail_lo=0, rail_hi=0, over=0)
+
+
+def zero_report() -> dict:
+    """The report of no samples: the identity of add()."""
+    return dict(ZERO, hist=np.zeros(BINS, dtype=np.uint64))
+
+
+def add(r: dict, s: dict) -> dict:
+    """The sum of two reports, field by field (adsb_level_add): every field is a count, so the reports of the windows of a stream
+    add up to the report of their union.  An envelope is not a report's to add: the sum has none."""
+    out = {k: int(r[k]) + int(s[k]) for k in ZERO}
+    out["hist"] = np.asarray(r["hist"], dtype=np.uint64) + np.asarray(s["hist"], dtype=np.uint64)
+    return out
+
+
+def check_edges(edges) -> list:
+    """The edges of K consecutive windows, e[0] <= e[1] <= ... <= e[K]: every edge but the last is a multiple of 28, so a run of 28
+    never spans two windows."""
+    e = [int(v) for v in edges]
+    if not e:
+        raise ValueError("K windows have K + 1 edges")
+    if any(b < a for a, b in zip(e, e[1:])):
+        raise ValueError("the edges must ascend")
+    if any(v % RUN for v in e[:-1]):
+        raise ValueError("every edge but the last is a multiple of 28")
+    return e
+
+
+def level_windows(a, x, edges) -> tuple:
+    """The statement of adsb_level_windows.  `a`: the power samples of a stream of uint16 real samples `x`, indexed from the
+    stream's start (the reference's ampbuff, what adsb_power_window writes; for a buffer that starts at first_sample: the power
+    samples of the stream with x[:first_sample] replaced by 2048).  Window i is power samples [e[i], e[i + 1]).
+
+    -> (reports, env).  reports[i] = level_report(a[e[i]:e[i + 1]]) without its envelope, the rail counters counted on the codes the
+    window owns, x[2 e[i] : 2 e[i + 1]] (== 0, == 4095, > 4095) -- a stream's trailing n % 4 codes belong to no window; an empty
+    window has a zeroed report.  env: ONE envelope for all windows, env[r] over power samples
+    [e[0] + 28 r, min(e[0] + 28 r + 28, e[K])), defined as in level_report -- that of a[e[0]:e[K]]."""
+    e = check_edges(edges)
+    a = np.ascontiguousarray(a).reshape(-1)
+    x = np.asarray(x).reshape(-1)
+    if e[-1] > a.size or 2 * e[-1] > x.size:
+        raise ValueError("the last edge lies beyond the stream")
+    reports = []
+    for lo, hi in zip(e, e[1:]):
+        r = level_report(a[lo:hi])
+        del r["env"]
+        own = x[2 * lo:2 * hi]
+        r["rail_lo"], r["rail_hi"], r["over"] = int((own == 0).sum()), int((own == 4095).sum()), int((own > 4095).sum())
+        reports.append(r)
+    return reports, level_report(a[e[0]:e[-1]])["env"]

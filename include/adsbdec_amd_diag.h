@@ -335,7 +335,8 @@ int adsb_batch_unpacked_copy(adsb_decoder *d, size_t capture, uint16_t *dst_u16,
 /* adsb_level_batch_*: the most workgroups a level launch of a batch may have from now on (0: the default, 2048).  With 1, four waves
  * share a whole sub-batch, and each changes capture -- and flushes its histogram to the totals of the capture it held -- many
  * times: how a small batch exercises that path.  A call of its own and not a member of adsb_debug_config: the knob can be turned
- * between two calls on ONE handle, so a test compares both settings on the same device buffers.  0, or -1 (blocks < 0). */
+ * between two calls on ONE handle, so a test compares both settings on the same device buffers.  The launches of adsb_level_windows
+ * are capped by it too (a wave then crosses many windows).  0, or -1 (blocks < 0). */
 int adsb_debug_set_level_batch_blocks(adsb_decoder *d, int blocks);
 
 /* ---- a batch over the devices of adsb_multi (adsb_multi_decode_batch_*; csrc/multi.cpp), without a device ------------------------

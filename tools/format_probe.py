@@ -8,6 +8,7 @@ comparison interleaved.
     python tools/format_probe.py --export [--reps 20] [--out profiles/r17_power_export.txt] [--layout name=path/to/libadsbdec_amd.so ...]   # export_probe()
     python tools/format_probe.py --export-batch [--reps 20] [--out profiles/r20_export_batch.txt] [--ab path/to/parent/libadsbdec_amd.so]   # export_batch_probe()
     python tools/format_probe.py --level [--reps 20] [--out profiles/r23_level.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_probe()
+    python tools/format_probe.py --level-windows [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/r27_level_windows.txt]   # level_windows_probe()
     python tools/format_probe.py --level-batch [--reps 20] [--out profiles/r26_level_batch.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_batch_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
@@ -1064,6 +1065,123 @@ def level_batch_probe(L, reps, lines, variants):
     return all(ok for _, ok in gates)
 
 
+def level_windows_probe(L, reps, lines, parent):
+    """The window form of the level report (level_windows_kernel.hip, adsb_level_windows) on the benchmark's 256 Mi samples, every
+    comparison interleaved in this one process, wall time of the calls (each waits for its kernel and its copy of the totals):
+    (a) ONE window over the whole buffer beside adsb_level_device on the same buffer; (b) 1024 and 13 000 windows over the same buffer
+    beside the loop of adsb_level_device on the slices -- the route without a window call, inexact at every slice's first six pairs;
+    (c) adsb_level_device of this tree beside the library built from the parent commit (--ab).  Before anything is timed: the window
+    reports add up (adsb_level_add) to adsb_level_device's report, word for word, and the envelopes are equal."""
+    t, _ = make_workload(torch, N, seed=1)
+    torch.cuda.synchronize()                               # (the library's streams do not wait for torch's)
+    M = N // 2
+    ke = -(-M // 28)
+    env, env2 = torch.zeros(ke, dtype=torch.float32, device="cuda"), torch.zeros(ke, dtype=torch.float32, device="cuda")
+    d = capi.Decoder()
+    h = d._h
+    SZ = C.sizeof(capi.LevelReport)
+    rep1 = capi.LevelReport()
+    steps = 5
+
+    def single(B=L, hh=h):
+        assert B.adsb_level_device(hh, t.data_ptr(), N, C.byref(rep1), env2.data_ptr(), ke) == M
+
+    def rotate(sides):
+        names = list(sides)
+        wall = {k_: [] for k_ in names}
+        for r in range(reps):
+            for name in names[r % len(names):] + names[:r % len(names)]:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    sides[name]()
+                wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        return names, wall
+
+    def table(names, wall, base):
+        for name in names:
+            q = statistics.quantiles(wall[name], n=4)
+            rr = [a_ / b for a_, b in zip(wall[name], wall[base])]
+            qr = statistics.quantiles(rr, n=4)
+            lines.append(f"    {name:46s} {med(wall[name]):9.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med(rr):.4f} ({qr[0]:.4f} .. {qr[2]:.4f})")
+            print(lines[-1], flush=True)
+
+    def windows(k):
+        """k windows over [0, M): M / k rounded down to a multiple of 28 each, the last one takes the rest"""
+        win = M // k // 28 * 28
+        e = [i * win for i in range(k)] + [M]
+        return (C.c_uint64 * (k + 1))(*e), e, (capi.LevelReport * k)()
+
+    def check(k, edges, reps_k):
+        for _ in range(2):
+            single()
+        env.zero_()
+        torch.cuda.synchronize()
+        assert L.adsb_level_windows(h, t.data_ptr(), 0, N, k, edges, reps_k, env.data_ptr(), ke) == M
+        total = capi.LevelReport()
+        for i in range(k):
+            L.adsb_level_add(C.byref(total), C.byref(reps_k, i * SZ))
+        assert bytes(total) == bytes(rep1), f"{k} windows do not add up to adsb_level_device's report"
+        assert torch.equal(env.view(torch.int32), env2.view(torch.int32)), f"{k} windows: another envelope"
+
+    # (a)
+    e1, _, r1 = windows(1)
+    check(1, e1, r1)
+    sides = {"adsb_level_device": single, "adsb_level_device again (the A/A)": single,
+             "adsb_level_windows, n_windows = 1": lambda: L.adsb_level_windows(h, t.data_ptr(), 0, N, 1, e1, r1, env.data_ptr(), ke)}
+    names, wall = rotate(sides)
+    lines += [f"# (a) ONE window over 256 Mi samples (512 MiB in) beside adsb_level_device on the same buffer, both with the envelope; {reps} rounds x {steps}",
+              "#     calls per side, the sides in rotation; the same report and envelope from both before anything is timed",
+              "#   side                                              call ms (q1 .. q3)             / adsb_level_device (median of rounds, q1 .. q3)"]
+    table(names, wall, names[0])
+    # (b)
+    lines += ["#", "# (b) K windows over the same buffer in ONE adsb_level_windows call beside K adsb_level_device calls on the slices (each a fresh stream:",
+              "#     its first six pairs see silence, so those reports do not add up to the capture's); no envelope on either side; the window reports",
+              "#     add up to adsb_level_device's report of the whole buffer, word for word",
+              "#   K       window (power samples)   adsb_level_windows ms   again / first (the A/A)      loop of single calls ms   loop / windows (q1 .. q3)"]
+    for k in (1024, 13000):
+        ek, el, rk = windows(k)
+        check(k, ek, rk)
+        ptrs = [t.data_ptr() + 4 * el[i] for i in range(k)]
+        ns = [2 * (el[i + 1] - el[i]) for i in range(k)]
+        one = capi.LevelReport()
+
+        def call(k=k, ek=ek, rk=rk):
+            assert L.adsb_level_windows(h, t.data_ptr(), 0, N, k, ek, rk, None, 0) == M
+
+        def loop(k=k, ptrs=ptrs, ns=ns):
+            for i in range(k):
+                L.adsb_level_device(h, ptrs[i], ns[i], C.byref(one), None, 0)
+        loop()
+        names, wall = rotate({"windows": call, "again": call, "loop": loop})
+        aa = [b / a_ for a_, b in zip(wall["windows"], wall["again"])]
+        rr = [b / a_ for a_, b in zip(wall["windows"], wall["loop"])]
+        qa, qr = statistics.quantiles(aa, n=4), statistics.quantiles(rr, n=4)
+        lines.append(f"    {k:<7d} {el[1]:<24d} {med(wall['windows']):9.4f}               {med(aa):.4f} ({qa[0]:.4f} .. {qa[2]:.4f})     {med(wall['loop']):10.4f}"
+                     f"                {med(rr):8.3f} ({qr[0]:.3f} .. {qr[2]:.3f})")
+        print(lines[-1], flush=True)
+    # (c)
+    lines += ["#", "# (c) adsb_level_device of this tree beside the library built from the parent commit, loaded into this process: the existing call did not move"]
+    if parent:
+        B = C.CDLL(parent)
+        for name in ("adsb_create", "adsb_level_device"):
+            fn = getattr(B, name)
+            fn.restype, fn.argtypes = capi.SYMBOLS[name]
+        assert not hasattr(B, "adsb_level_windows"), "the --ab library is not the parent's: it has the window call"
+        cfg = capi.make_config()
+        hh = B.adsb_create(C.byref(cfg))
+        assert hh, parent
+        single()
+        want = bytes(rep1)
+        single(B, hh)
+        assert bytes(rep1) == want, "the parent's library reports other levels"
+        names, wall = rotate({"adsb_level_device (tree)": single, "adsb_level_device (tree again: the A/A)": single,
+                              "adsb_level_device (parent commit)": lambda: single(B, hh)})
+        lines.append("#   side                                              call ms (q1 .. q3)             / tree (median of rounds, q1 .. q3)")
+        table(names, wall, names[0])
+    else:
+        lines.append("#     not measured in this run: no --ab parent library given")
+
+
 def real_kernel_ab(builds, rounds, lines):
     """(c) the existing real-sample kernel across the change: tools/ab_interleaved.py in a process of its own (it dlopens every build
     side by side), the first build listed twice for the A/A."""
@@ -1090,9 +1208,21 @@ def main():
     ap.add_argument("--export-batch", action="store_true", help="the batch power export (the adsb_power_batch_* calls) against the loop of single calls instead: profiles/r20_export_batch.txt; --ab: the parent commit's library, for (c)")
     ap.add_argument("--level", action="store_true", help="the level report (the adsb_level_* calls) instead: profiles/r23_level.txt")
     ap.add_argument("--level-batch", action="store_true", help="the batch level report (the adsb_level_batch_* calls) against the loop of single calls instead: profiles/r26_level_batch.txt")
+    ap.add_argument("--level-windows", action="store_true", help="the window form of the level report (adsb_level_windows) beside adsb_level_device instead: profiles/r27_level_windows.txt; --ab: the parent commit's library, for (c)")
     ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB", help="with --level or --level-batch: a build of the library with another accumulation, flush or grid, measured beside the tree's")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.level_windows:
+        a.out = a.out or os.path.join(ROOT, "profiles", "r27_level_windows.txt")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --level-windows: the window form of the level report (level_windows_kernel.hip, adsb_level_windows) beside",
+                 f"# adsb_level_device, one process, {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first.",
+                 "# The samples are the benchmark's: tools/gen_signal.py make_workload, 256 Mi samples, seed 1.  Wall time of the C calls through ctypes; every",
+                 "# call waits for its kernel and its copy of the totals (16 KiB a window).", "#"]
+        level_windows_probe(capi.load(), a.reps, lines, a.ab)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.level_batch:
         a.out = a.out or os.path.join(ROOT, "profiles", "r26_level_batch.txt")
         torch.cuda.set_device(0)
