@@ -678,6 +678,15 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
             return d->fail("staging buffer exhausted (stage_samples too small)");
         const size_t take = (size_t)std::min<uint64_t>(room, n);
         const size_t bytes = packed ? take / adsb::kPackedGroupSamples * adsb::kPackedGroupBytes : conv ? take * elem : take * unit;
+        // the piece to stage[cur] + stage_fill on `st`: as it is, or landed in `land` and unpacked or converted from there
+        auto piece_to_stage = [&](uint8_t *land, hipStream_t st) -> int {
+            HIP_TRY(d, hipMemcpyAsync(packed || conv ? (void *)land : (void *)stage_at(d, d->cur, d->stage_fill), p, bytes, kind, st));
+            if (packed)
+                HIP_TRY(d, adsb::launch_unpack12(stage_at(d, d->cur, d->stage_fill), land, take / adsb::kPackedGroupSamples, st));
+            else if (conv)
+                HIP_TRY(d, adsb::launch_convert(conv, stage_at(d, d->cur, d->stage_fill), land, take, d->d_fmt, st));
+            return 0;
+        };
         if (async) {
             d->piece++;
             const int cs = (int)(d->piece % adsb_decoder::kCopyStreams);
@@ -687,15 +696,8 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
             // the piece before it, which ends in that line.
             if (d->piece > 1 && (d->stage_fill * unit) % 128 != 0 && d->dbg_async != 2)
                 HIP_TRY(d, hipStreamWaitEvent(cstream, d->ev_copy[cs ^ 1], 0));
-            if (packed) {
-                HIP_TRY(d, hipMemcpyAsync(d->land[cs], p, bytes, kind, cstream));
-                HIP_TRY(d, adsb::launch_unpack12(stage_at(d, d->cur, d->stage_fill), d->land[cs], take / adsb::kPackedGroupSamples, cstream));
-            } else if (conv) {
-                HIP_TRY(d, hipMemcpyAsync(d->land[cs], p, bytes, kind, cstream));
-                HIP_TRY(d, adsb::launch_convert(conv, stage_at(d, d->cur, d->stage_fill), d->land[cs], take, d->d_fmt, cstream));
-            } else {
-                HIP_TRY(d, hipMemcpyAsync(stage_at(d, d->cur, d->stage_fill), p, bytes, kind, cstream));
-            }
+            if (piece_to_stage(d->land[cs], cstream))
+                return -1;
             HIP_TRY(d, hipEventRecord(d->ev_copy[cs], cstream));
             if (d->dbg_async != 2)
                 HIP_TRY(d, hipStreamWaitEvent(d->stream, d->ev_copy[cs], 0));
@@ -704,15 +706,8 @@ static int push_copy(adsb_decoder *d, const void *src, size_t n, hipMemcpyKind k
         } else {
             // (packed: land[0] -- an earlier asynchronous piece that used it is ordered in front by its event, and an earlier
             // synchronous push was complete when it returned)
-            if (packed) {
-                HIP_TRY(d, hipMemcpyAsync(d->land[0], p, bytes, kind, d->stream));
-                HIP_TRY(d, adsb::launch_unpack12(stage_at(d, d->cur, d->stage_fill), d->land[0], take / adsb::kPackedGroupSamples, d->stream));
-            } else if (conv) {
-                HIP_TRY(d, hipMemcpyAsync(d->land[0], p, bytes, kind, d->stream));
-                HIP_TRY(d, adsb::launch_convert(conv, stage_at(d, d->cur, d->stage_fill), d->land[0], take, d->d_fmt, d->stream));
-            } else {
-                HIP_TRY(d, hipMemcpyAsync(stage_at(d, d->cur, d->stage_fill), p, bytes, kind, d->stream));
-            }
+            if (piece_to_stage(d->land[0], d->stream))
+                return -1;
             d->copy_unconfirmed = true;
         }
         d->stage_fill += take;
@@ -988,6 +983,18 @@ static int packed_device_refusal(adsb_decoder *d, const void *device_packed, siz
     return 0;
 }
 
+// What adsb_push_device_packed* and adsb_push_device_as and their kin do behind their refusals: unpack or convert into the handle's
+// scratch (decoder_stage.hip; conv = 0: unpack), then push that in place -- its launches alternate onto the second scan stream,
+// which waits for the scratch.
+static int push_device_scratch(adsb_decoder *d, int conv, const void *p, size_t n, bool final, const char *what, int kind)
+{
+    if (n == 0)
+        return final ? push_device_impl(d, nullptr, 0, true, kind) : 0;
+    if (adsb::to_scratch(d, what, conv, p, n) || adsb::scratch_before_stream2(d))
+        return -1;
+    return push_device_impl(d, d->unpacked, n, final, kind);
+}
+
 static int push_device_packed_impl(adsb_decoder *d, const void *device_packed, size_t n, bool final, const char *what)
 {
     if (d->finished)
@@ -996,22 +1003,7 @@ static int push_device_packed_impl(adsb_decoder *d, const void *device_packed, s
         return d->fail("a shard stream ends with adsb_shard_end");
     if (kind_refusal(d, what, adsb::kKindReal) || packed_device_refusal(d, device_packed, n, d->n_samples, what) || stream_too_long(d, n))
         return -1;
-    if (n == 0)
-        return final ? push_device_impl(d, nullptr, 0, true) : 0;
-    HIP_TRY(d, hipSetDevice(d->device));
-    if (d->unpacked.reserve(n) != hipSuccess) { // (every earlier push into the scratch has completed: push_device_impl returns behind its reads)
-        (void)hipGetLastError();
-        return d->fail("%s: cannot allocate %zu bytes of device scratch for the unpacked samples (2 bytes per sample)", what,
-                       n * sizeof(uint16_t));
-    }
-    HIP_TRY(d, adsb::launch_unpack12(d->unpacked, device_packed, n / adsb::kPackedGroupSamples, d->stream));
-    if (d->stream2) { // the in-place launches alternate onto the second scan stream, which nothing else orders behind the unpack
-        if (!d->ev_unpack)
-            HIP_TRY(d, d->ev_unpack.create(hipEventDisableTiming));
-        HIP_TRY(d, hipEventRecord(d->ev_unpack, d->stream));
-        HIP_TRY(d, hipStreamWaitEvent(d->stream2, d->ev_unpack, 0));
-    }
-    return push_device_impl(d, d->unpacked, n, final);
+    return push_device_scratch(d, 0, device_packed, n, final, what, adsb::kKindReal);
 }
 
 // adsb_push_device_as and its kin: the checks first (a refused push leaves the handle as it was), at stream position `at`
@@ -1034,26 +1026,7 @@ static int push_device_as_impl(adsb_decoder *d, int fmt, const void *p, size_t n
         return d->fail("a shard stream ends with adsb_shard_end");
     if (kind_refusal(d, what, kind) || device_as_refusal(d, what, p, n, adsb::convert_element_bytes(fmt)) || stream_too_long(d, n))
         return -1;
-    if (n == 0)
-        return final ? push_device_impl(d, nullptr, 0, true, kind) : 0;
-    HIP_TRY(d, hipSetDevice(d->device));
-    if (format_prepare(d, what, 0))
-        return -1;
-    if (d->unpacked.reserve(n) != hipSuccess) { // (every earlier push into the scratch has completed: push_device_impl returns behind its reads)
-        (void)hipGetLastError();
-        return d->fail("%s: cannot allocate %zu bytes of device scratch for the converted samples (2 bytes per sample)", what,
-                       n * sizeof(uint16_t));
-    }
-    HIP_TRY(d, adsb::launch_convert(fmt, d->unpacked, p, n, d->d_fmt, d->stream));
-    d->fmt_converted += n;
-    d->fmt_dirty = true;
-    if (d->stream2) { // as behind a device push's unpack: the second scan stream waits for the conversion
-        if (!d->ev_unpack)
-            HIP_TRY(d, d->ev_unpack.create(hipEventDisableTiming));
-        HIP_TRY(d, hipEventRecord(d->ev_unpack, d->stream));
-        HIP_TRY(d, hipStreamWaitEvent(d->stream2, d->ev_unpack, 0));
-    }
-    return push_device_impl(d, d->unpacked, n, final, kind);
+    return push_device_scratch(d, fmt, p, n, final, what, kind);
 }
 
 // ---- complex samples (the _iq calls; include/adsbdec_amd.h) ----

@@ -196,55 +196,6 @@ long decode_batch(adsb_decoder *d, size_t n_captures, const void *const *p, cons
 }
 
 
-// Room in a device scratch buffer of the handle's.
-template <class T> int batch_grow(adsb_decoder *d, const char *what, const char *of, adsb::Buf<T> &buf, size_t bytes)
-{
-    if (buf.reserve(bytes / sizeof(T)) == hipSuccess)
-        return 0;
-    (void)hipGetLastError();
-    return d->fail("%s: cannot allocate %zu bytes of device scratch for %s", what, bytes, of);
-}
-
-// The packed captures at src[] (device memory, 4-byte aligned) -> uint16 samples in batch_unpacked, capture i from at[i] on (a
-// 128-byte boundary), by ONE launch on the handle's stream: the batch scan that follows on that stream reads behind it.
-int batch_unpack(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n, std::vector<const void *> &at)
-{
-    at.assign(n_captures, nullptr);
-    d->batch_unpacked_at.clear(); // (adsb_batch_unpacked_copy: what this call has)
-    size_t bytes = 0, rows = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
-        rows += n[i] != 0;
-    }
-    if (batch_grow(d, what, "the unpacked samples (2 bytes per sample)", d->batch_unpacked, bytes))
-        return -1;
-    const size_t tab_bytes = (rows + 1) * sizeof(adsb::Unpack12Seg);
-    HIP_TRY(d, d->unpack_tab.reserve(tab_bytes));
-    adsb::Unpack12Seg *tab = reinterpret_cast<adsb::Unpack12Seg *>(d->unpack_tab.host.p);
-    size_t off = 0, row = 0;
-    uint64_t groups = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        at[i] = reinterpret_cast<const char *>(d->batch_unpacked.p) + off;
-        d->batch_unpacked_at.push_back(off / sizeof(uint16_t));
-        if (n[i]) {
-            tab[row].src = (uint64_t)(uintptr_t)src[i];
-            tab[row].dst16 = off / 16;
-            tab[row].g_first = groups;
-            row++;
-            groups += n[i] / adsb::kPackedGroupSamples;
-        }
-        off += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
-    }
-    d->batch_unpacked_at.push_back(off / sizeof(uint16_t));
-    tab[row] = adsb::Unpack12Seg{0, 0, groups}; // behind the last row: where its groups end
-    if (groups == 0)
-        return 0;
-    HIP_TRY(d, hipMemcpyAsync(d->unpack_tab.dev, d->unpack_tab.host, tab_bytes, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(d, adsb::launch_unpack12_batch(d->batch_unpacked, reinterpret_cast<const adsb::Unpack12Seg *>(d->unpack_tab.dev.p), (uint32_t)row, groups,
-                                           d->stream));
-    return 0;
-}
-
 // unpack, decode; and the stream idle behind it whatever the result (a batch without an offset launches no scan that would have
 // been waited for: the table and the scratch are the next call's to rewrite)
 long decode_batch_packed(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n,
@@ -252,52 +203,11 @@ long decode_batch_packed(adsb_decoder *d, const char *what, size_t n_captures, c
 {
     std::vector<const void *> at;
     d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
-    if (batch_unpack(d, what, n_captures, src, n, at))
+    if (batch_to_scratch(d, what, 0, n_captures, src, n, at))
         return -1;
     const long k = decode_batch(d, n_captures, at.data(), n, frames, first, stats);
     WAIT_STREAM(d, d->stream, "the scan stream");
     return k;
-}
-
-// The captures at src[] (device memory, samples of format fmt, each aligned to its element) -> uint16 samples in batch_unpacked,
-// capture i from at[i] on (a 128-byte boundary), by ONE launch on the handle's stream, which adds the batch's off-grid counts.
-int batch_convert(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
-                  std::vector<const void *> &at)
-{
-    at.assign(n_captures, nullptr);
-    d->batch_unpacked_at.clear();
-    size_t bytes = 0, rows = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
-        rows += n[i] != 0;
-    }
-    if (batch_grow(d, what, "the converted samples (2 bytes per sample)", d->batch_unpacked, bytes) || format_prepare(d, what, 0))
-        return -1;
-    const size_t tab_bytes = (rows + 1) * sizeof(adsb::ConvertSeg);
-    HIP_TRY(d, d->unpack_tab.reserve(tab_bytes));
-    adsb::ConvertSeg *tab = reinterpret_cast<adsb::ConvertSeg *>(d->unpack_tab.host.p);
-    size_t off = 0, row = 0;
-    uint64_t groups = 0, samples = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        at[i] = reinterpret_cast<const char *>(d->batch_unpacked.p) + off;
-        d->batch_unpacked_at.push_back(off / sizeof(uint16_t));
-        if (n[i]) {
-            tab[row++] = adsb::ConvertSeg{(uint64_t)(uintptr_t)src[i], off / 16, groups, n[i]};
-            groups += (n[i] + 7) / 8; // (the last group of a capture may be short)
-            samples += n[i];
-        }
-        off += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
-    }
-    d->batch_unpacked_at.push_back(off / sizeof(uint16_t));
-    tab[row] = adsb::ConvertSeg{0, 0, groups, 0}; // behind the last row: where its groups end
-    if (groups == 0)
-        return 0;
-    HIP_TRY(d, hipMemcpyAsync(d->unpack_tab.dev, d->unpack_tab.host, tab_bytes, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(d, adsb::launch_convert_batch(fmt, d->batch_unpacked, reinterpret_cast<const adsb::ConvertSeg *>(d->unpack_tab.dev.p), (uint32_t)row,
-                                          groups, d->d_fmt, d->stream));
-    d->fmt_converted += samples;
-    d->fmt_dirty = true;
-    return 0;
 }
 
 // convert, decode; and the stream idle behind it whatever the result (as decode_batch_packed)
@@ -306,7 +216,7 @@ long decode_batch_as(adsb_decoder *d, const char *what, int fmt, size_t n_captur
 {
     std::vector<const void *> at;
     d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
-    if (batch_convert(d, what, fmt, n_captures, src, n, at))
+    if (batch_to_scratch(d, what, fmt, n_captures, src, n, at))
         return -1;
     const long k = decode_batch(d, n_captures, at.data(), n, frames, first, stats);
     WAIT_STREAM(d, d->stream, "the scan stream");
@@ -352,25 +262,15 @@ long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captur
     const size_t unit = adsb::kind_unit_bytes(kind);
     d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
     if (fmt == 0) {
-        if (batch_convert(d, what, adsb::kConvFloat32Iq, n_captures, src, scalars.data(), at))
+        if (batch_to_scratch(d, what, adsb::kConvFloat32Iq, n_captures, src, scalars.data(), at))
             return -1;
     } else {
-        d->batch_unpacked_at.clear(); // (adsb_batch_unpacked_copy: no table of this call's; the copies below rewrite the scratch)
-        size_t bytes = 0;
+        d->batch_unpacked_at.clear(); // (adsb_batch_unpacked_copy: no table of this call's; the copies rewrite the scratch)
+        std::vector<size_t> bytes(n_captures);
         for (size_t i = 0; i < n_captures; i++)
-            if ((uintptr_t)src[i] % 16 != 0)
-                bytes += (units[i] * unit + 127) & ~(size_t)127;
-        if (bytes && batch_grow(d, what, "the captures that are not 16-byte aligned", d->batch_unpacked, bytes))
+            bytes[i] = units[i] * unit;
+        if (batch_realign(d, what, n_captures, bytes.data(), at))
             return -1;
-        size_t off = 0;
-        for (size_t i = 0; i < n_captures; i++) {
-            if ((uintptr_t)src[i] % 16 == 0)
-                continue;
-            at[i] = reinterpret_cast<const char *>(d->batch_unpacked.p) + off;
-            if (units[i])
-                HIP_TRY(d, hipMemcpyAsync(const_cast<void *>(at[i]), src[i], units[i] * unit, hipMemcpyDeviceToDevice, d->stream));
-            off += (units[i] * unit + 127) & ~(size_t)127;
-        }
     }
     d->kind = kind; // (behind the reset: the batch launches are scan_iq_batch_kernel's or scan_power_batch_kernel's)
     const long k = decode_batch(d, n_captures, at.data(), units.data(), frames, first, stats);
@@ -394,20 +294,19 @@ int batch_refusal_power(adsb_decoder *d, const char *what, size_t n_captures, co
     return 0;
 }
 
+// The host captures of a batch (bytes_of(n[i]) bytes each) into `buf`, each at a multiple of `align` bytes: copied on the copy streams in
+// turn and waited for -- the captures are the caller's again, and the unpack, conversion or scan that reads them needs no event.
+template <class BytesOf>
+int land_batch(adsb_decoder *d, const char *what, adsb::Buf<uint8_t> &buf, const char *of, size_t n_captures, const void *const *src,
+               const size_t *n, BytesOf bytes_of, size_t align, std::vector<const void *> &at)
+{
+    std::vector<size_t> bytes(n_captures);
+    for (size_t i = 0; i < n_captures; i++)
+        bytes[i] = bytes_of(n[i]);
+    return land_captures(d, what, buf, of, n_captures, src, bytes.data(), align, adsb::Land::InTurnWaited, at);
+}
+
 } // namespace
-
-// decoder_export_batch.hip: the batch exports unpack and convert into the same scratch, by the same one launch
-int adsb::batch_unpack_to_scratch(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n,
-                                  std::vector<const void *> &at)
-{
-    return batch_unpack(d, what, n_captures, src, n, at);
-}
-
-int adsb::batch_convert_to_scratch(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
-                                   std::vector<const void *> &at)
-{
-    return batch_convert(d, what, fmt, n_captures, src, n, at);
-}
 
 extern "C" {
 
@@ -437,22 +336,10 @@ long adsb_decode_batch_host_power(adsb_decoder *d, size_t n_captures, const floa
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     // every capture as it is at a 128-byte boundary of the landing buffer the other host batches use
-    size_t bytes = 0;
-    for (size_t i = 0; i < n_captures; i++)
-        bytes += (n[i] * sizeof(float) + 127) & ~(size_t)127;
-    if (batch_grow(d, what, "the captures as they are", d->batch_land, bytes))
+    std::vector<const void *> land;
+    if (land_batch(d, what, d->batch_land, "the captures as they are", n_captures, reinterpret_cast<const void *const *>(samples), n,
+                   [](size_t k) { return k * sizeof(float); }, 128, land))
         return -1;
-    std::vector<const void *> land(n_captures);
-    size_t off = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        land[i] = d->batch_land + off;
-        if (n[i])
-            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, samples[i], n[i] * sizeof(float), hipMemcpyHostToDevice,
-                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
-        off += (n[i] * sizeof(float) + 127) & ~(size_t)127;
-    }
-    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again)
-        WAIT_STREAM(d, cs, "a copy stream");
     return decode_batch_iq(d, what, 2, n_captures, land.data(), n, frames, first, stats, adsb::kKindPower);
 }
 
@@ -482,23 +369,10 @@ long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, cons
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     // every capture as it is at a 128-byte boundary of the landing buffer the other host batches use
+    std::vector<const void *> land;
     const size_t elem = adsb::iq_sample_bytes(fmt);
-    size_t bytes = 0;
-    for (size_t i = 0; i < n_captures; i++)
-        bytes += (n[i] * elem + 127) & ~(size_t)127;
-    if (batch_grow(d, what, "the captures as they are", d->batch_land, bytes))
+    if (land_batch(d, what, d->batch_land, "the captures as they are", n_captures, samples, n, [elem](size_t k) { return k * elem; }, 128, land))
         return -1;
-    std::vector<const void *> land(n_captures);
-    size_t off = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        land[i] = d->batch_land + off;
-        if (n[i])
-            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, samples[i], n[i] * elem, hipMemcpyHostToDevice,
-                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
-        off += (n[i] * elem + 127) & ~(size_t)127;
-    }
-    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again)
-        WAIT_STREAM(d, cs, "a copy stream");
     return decode_batch_iq(d, what, fmt, n_captures, land.data(), n, frames, first, stats, fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq);
 }
 
@@ -540,22 +414,9 @@ long adsb_decode_batch_host_as(adsb_decoder *d, int fmt, size_t n_captures, cons
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     // every capture's samples at a 16-byte boundary of the landing buffer the packed batches use
-    size_t bytes = 0;
-    for (size_t i = 0; i < n_captures; i++)
-        bytes += (n[i] * elem + 15) & ~(size_t)15;
-    if (batch_grow(d, what, "the captures as they are", d->batch_land, bytes))
+    std::vector<const void *> land;
+    if (land_batch(d, what, d->batch_land, "the captures as they are", n_captures, samples, n, [elem](size_t k) { return k * elem; }, 16, land))
         return -1;
-    std::vector<const void *> land(n_captures);
-    size_t off = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        land[i] = d->batch_land + off;
-        if (n[i])
-            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, samples[i], n[i] * elem, hipMemcpyHostToDevice,
-                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
-        off += (n[i] * elem + 15) & ~(size_t)15;
-    }
-    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the conversion needs no event)
-        WAIT_STREAM(d, cs, "a copy stream");
     return decode_batch_as(d, what, fmt, n_captures, land.data(), n, frames, first, stats);
 }
 
@@ -584,25 +445,11 @@ long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     // every capture at a 128-byte boundary of one scratch array of the handle's
-    std::vector<size_t> off(n_captures);
-    size_t bytes = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        off[i] = bytes;
-        bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
-    }
     d->batch_unpacked_at.clear(); // (as adsb_decode_batch_device)
-    if (batch_grow(d, "adsb_decode_batch_host", "the captures", d->batch_in, bytes))
+    std::vector<const void *> at;
+    if (land_batch(d, "adsb_decode_batch_host", d->batch_in, "the captures", n_captures, reinterpret_cast<const void *const *>(samples), n,
+                   [](size_t k) { return k * sizeof(uint16_t); }, 128, at))
         return -1;
-    std::vector<const void *> at(n_captures);
-    for (size_t i = 0; i < n_captures; i++) {
-        uint8_t *dst = d->batch_in + off[i];
-        at[i] = dst;
-        if (n[i])
-            HIP_TRY(d, hipMemcpyAsync(dst, samples[i], n[i] * sizeof(uint16_t), hipMemcpyHostToDevice,
-                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
-    }
-    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the scan needs no event)
-        WAIT_STREAM(d, cs, "a copy stream");
     return decode_batch(d, n_captures, at.data(), n, frames, first, stats);
 }
 
@@ -631,22 +478,10 @@ long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const voi
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     // only the packed bytes cross the link: every capture's at a 16-byte boundary of one landing buffer of the handle's
-    size_t bytes = 0;
-    for (size_t i = 0; i < n_captures; i++)
-        bytes += (ADSB_PACKED12_BYTES(n[i]) + 15) & ~(size_t)15;
-    if (batch_grow(d, what, "the packed captures (1.5 bytes per sample)", d->batch_land, bytes))
+    std::vector<const void *> land;
+    if (land_batch(d, what, d->batch_land, "the packed captures (1.5 bytes per sample)", n_captures, packed, n,
+                   [](size_t k) { return (size_t)ADSB_PACKED12_BYTES(k); }, 16, land))
         return -1;
-    std::vector<const void *> land(n_captures);
-    size_t off = 0;
-    for (size_t i = 0; i < n_captures; i++) {
-        land[i] = d->batch_land + off;
-        if (n[i])
-            HIP_TRY(d, hipMemcpyAsync(d->batch_land + off, packed[i], ADSB_PACKED12_BYTES(n[i]), hipMemcpyHostToDevice,
-                                      d->copy_stream[i % adsb_decoder::kCopyStreams]));
-        off += (ADSB_PACKED12_BYTES(n[i]) + 15) & ~(size_t)15;
-    }
-    for (hipStream_t cs : d->copy_stream) // (copied and waited for: the captures are the caller's again, and the unpack needs no event)
-        WAIT_STREAM(d, cs, "a copy stream");
     return decode_batch_packed(d, what, n_captures, land.data(), n, frames, first, stats);
 }
 

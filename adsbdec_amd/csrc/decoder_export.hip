@@ -65,17 +65,6 @@ long export_capture(adsb_decoder *d, const char *what, const void *device_u16, s
     return export_window(d, device_u16, 0, n, 0, m_end, device_power);
 }
 
-// the scratch of the converted and packed device pushes, grown to n uint16
-int export_scratch(adsb_decoder *d, const char *what, size_t n)
-{
-    HIP_TRY(d, hipSetDevice(d->device));
-    if (d->unpacked.reserve(n) != hipSuccess) { // (every earlier use of the scratch has completed: the calls that use it return behind its reads)
-        (void)hipGetLastError();
-        return d->fail("%s: cannot allocate %zu bytes of device scratch (2 bytes per sample)", what, n * sizeof(uint16_t));
-    }
-    return 0;
-}
-
 } // namespace
 
 extern "C" {
@@ -105,16 +94,9 @@ long adsb_power_window_host(adsb_decoder *d, const uint16_t *samples, uint64_t f
     if (!samples || !power)
         return d->fail("%s: NULL buffer", what);
     const size_t count = (size_t)(m_end - m_begin);
-    HIP_TRY(d, hipSetDevice(d->device));
-    HIP_TRY(d, d->win_buf.reserve((n + 65535) & ~(size_t)65535));
-    HIP_TRY(d, d->pow_buf.reserve((count + 65535) & ~(size_t)65535));
-    // (on a copy stream of the handle's and waited for, as adsb_scan_shard_host copies its window)
-    HIP_TRY(d, hipMemcpyAsync(d->win_buf, samples, n * sizeof(uint16_t), hipMemcpyHostToDevice, d->copy_stream[0]));
-    WAIT_STREAM(d, d->copy_stream[0], "a copy stream");
-    if (export_window(d, d->win_buf, first_sample, n, m_begin, m_end, d->pow_buf) < 0)
+    if (window_in(d, samples, n, count) || export_window(d, d->win_buf, first_sample, n, m_begin, m_end, d->pow_buf) < 0 ||
+        floats_out(d, power, count))
         return -1;
-    HIP_TRY(d, hipMemcpyAsync(power, d->pow_buf, count * sizeof(float), hipMemcpyDeviceToHost, d->copy_stream[0]));
-    WAIT_STREAM(d, d->copy_stream[0], "a copy stream");
     return (long)count;
 }
 
@@ -148,11 +130,8 @@ long adsb_power_device_as(adsb_decoder *d, int fmt, const void *device_samples, 
         return 0;
     if (!device_samples || !device_power)
         return d->fail("%s: NULL buffer", what);
-    if (export_scratch(d, what, n) || format_prepare(d, what, 0))
+    if (to_scratch(d, what, fmt, device_samples, n))
         return -1;
-    HIP_TRY(d, launch_convert(fmt, d->unpacked, device_samples, n, d->d_fmt, d->stream));
-    d->fmt_converted += n;
-    d->fmt_dirty = true;
     return export_window(d, d->unpacked, 0, n, 0, m_end, device_power); // (the same stream: behind the conversion)
 }
 
@@ -172,9 +151,8 @@ long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t
         return 0;
     if (!device_packed || !device_power)
         return d->fail("%s: NULL buffer", what);
-    if (export_scratch(d, what, n))
+    if (to_scratch(d, what, 0, device_packed, n))
         return -1;
-    HIP_TRY(d, launch_unpack12(d->unpacked, device_packed, n / kPackedGroupSamples, d->stream));
     return export_window(d, d->unpacked, 0, n, 0, m_end, device_power); // (the same stream: behind the unpack)
 }
 
@@ -198,11 +176,8 @@ long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, 
     HIP_TRY(d, hipSetDevice(d->device));
     const uint32_t *iq16 = static_cast<const uint32_t *>(device_samples);
     if (fmt == 0) { // FLOAT32_IQ: to the int16 grid first, by the conversion the _iq pushes use (and into their scratch)
-        if (export_scratch(d, what, 2 * n) || format_prepare(d, what, 0))
+        if (to_scratch(d, what, kConvFloat32Iq, device_samples, 2 * n))
             return -1;
-        HIP_TRY(d, launch_convert(kConvFloat32Iq, d->unpacked, device_samples, 2 * n, d->d_fmt, d->stream));
-        d->fmt_converted += 2 * n;
-        d->fmt_dirty = true;
         iq16 = reinterpret_cast<const uint32_t *>(d->unpacked.p);
     }
     HIP_TRY(d, launch_iq_power_export(iq16, n, device_power, d->stream));

@@ -32,15 +32,10 @@ int export_batch_refusal(adsb_decoder *d, const char *what, const ExportBatchRul
     if (n_captures && (!src || !n || !out || !cap))
         return d->fail("%s: NULL capture arrays", what);
     for (size_t i = 0; i < n_captures; i++) {
-        if (!R.iq && (uint64_t)n[i] >= (1ull << 32))
-            return d->fail("%s: capture %zu has %zu samples: 2^32 or more, where the reference's sample counter wraps (air.c:34); "
-                           "a batch has no long-stream mode", what, i, n[i]);
         if (R.iq && (uint64_t)n[i] >= (1ull << 31))
             return d->fail("%s: capture %zu has %zu complex samples: 2^31 or more; IQ streams end below", what, i, n[i]);
-        if (R.packed && n[i] % kPackedGroupSamples != 0)
-            return d->fail("%s: capture %zu: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes)", what, i, n[i]);
-        if (R.in_align && (uintptr_t)src[i] % R.in_align != 0)
-            return d->fail("%s: capture %zu: device pointer %p is not %u-byte aligned", what, i, src[i], R.in_align);
+        if (batch_samples_refusal(d, what, i, src[i], n[i], !R.iq, R.packed, R.in_align))
+            return -1;
         if (R.out_device && (uintptr_t)out[i] % 16 != 0)
             return d->fail("%s: capture %zu: the power array must be 16-byte aligned (%p)", what, i, (const void *)out[i]);
         const uint64_t count = export_count(R, n[i]);
@@ -129,7 +124,7 @@ long adsb_power_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, con
     for (size_t i = 0; i < n_captures; i++)
         converted[i] = power_samples_produced(n[i]) ? n[i] : 0;
     std::vector<const void *> at;
-    if (batch_convert_to_scratch(d, what, fmt, n_captures, device_samples, converted.data(), at)) // (one launch, and the format report's samples)
+    if (batch_to_scratch(d, what, fmt, n_captures, device_samples, converted.data(), at)) // (one launch, and the format report's samples)
         return -1;
     return export_batch(d, kRulesDevice, n_captures, at.data(), n, device_power); // (the same stream: behind the conversion)
 }
@@ -145,7 +140,7 @@ long adsb_power_batch_device_packed(adsb_decoder *d, size_t n_captures, const vo
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     std::vector<const void *> at;
-    if (batch_unpack_to_scratch(d, what, n_captures, device_packed, n, at))
+    if (batch_to_scratch(d, what, 0, n_captures, device_packed, n, at))
         return -1;
     return export_batch(d, kRulesDevice, n_captures, at.data(), n, device_power); // (the same stream: behind the unpack)
 }
@@ -171,7 +166,7 @@ long adsb_power_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, con
     for (size_t i = 0; i < n_captures; i++)
         scalars[i] = 2 * n[i];
     std::vector<const void *> at;
-    if (batch_convert_to_scratch(d, what, kConvFloat32Iq, n_captures, device_samples, scalars.data(), at))
+    if (batch_to_scratch(d, what, kConvFloat32Iq, n_captures, device_samples, scalars.data(), at))
         return -1;
     return export_batch(d, R, n_captures, at.data(), n, device_power);
 }
@@ -189,35 +184,25 @@ long adsb_power_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *c
     HIP_TRY(d, hipSetDevice(d->device));
     // every capture at a 128-byte boundary of the scratch adsb_decode_batch_host lands its captures in, every capture's power
     // samples at a 128-byte boundary of adsb_power_window_host's; copies in, launch and copies out on ONE copy stream, in order
-    std::vector<size_t> in_at(n_captures), out_at(n_captures);
-    size_t in_bytes = 0, out_floats = 0;
+    // (a capture without a power sample takes no room in either)
+    std::vector<size_t> in_bytes(n_captures), floats(n_captures);
+    size_t all = 0;
     for (size_t i = 0; i < n_captures; i++) {
-        in_at[i] = in_bytes;
-        out_at[i] = out_floats;
-        if (power_samples_produced(n[i]) == 0)
-            continue;
-        in_bytes += (n[i] * sizeof(uint16_t) + 127) & ~(size_t)127;
-        out_floats += (power_samples_produced(n[i]) + 31) & ~(uint64_t)31;
+        floats[i] = (size_t)power_samples_produced(n[i]);
+        in_bytes[i] = floats[i] ? n[i] * sizeof(uint16_t) : 0;
+        all += floats[i];
     }
-    if (out_floats == 0)
+    if (all == 0)
         return 0;
     hipStream_t cs = d->copy_stream[0];
-    HIP_TRY(d, d->batch_in.reserve((in_bytes + 65535) & ~(size_t)65535));
-    HIP_TRY(d, d->pow_buf.reserve((out_floats + 65535) & ~(size_t)65535));
-    std::vector<const void *> at(n_captures);
-    std::vector<float *> out(n_captures);
-    for (size_t i = 0; i < n_captures; i++) {
-        at[i] = d->batch_in + in_at[i];
-        out[i] = d->pow_buf + out_at[i];
-        if (power_samples_produced(n[i]))
-            HIP_TRY(d, hipMemcpyAsync(d->batch_in + in_at[i], samples[i], n[i] * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
-    }
-    const long r = export_batch_launch(d, kRulesDevice, n_captures, at.data(), n, out.data(), cs);
-    if (r < 0)
+    std::vector<const void *> at;
+    std::vector<float *> out;
+    if (pow_slots(d, n_captures, floats.data(), out) ||
+        land_captures(d, what, d->batch_in, "the captures", n_captures, src, in_bytes.data(), 128, Land::FirstCopyStream, at))
         return -1;
-    for (size_t i = 0; i < n_captures; i++)
-        if (power_samples_produced(n[i]))
-            HIP_TRY(d, hipMemcpyAsync(power[i], out[i], power_samples_produced(n[i]) * sizeof(float), hipMemcpyDeviceToHost, cs));
+    const long r = export_batch_launch(d, kRulesDevice, n_captures, at.data(), n, out.data(), cs);
+    if (r < 0 || pow_slots_out(d, n_captures, power, out, floats.data(), cs))
+        return -1;
     WAIT_STREAM(d, cs, "a copy stream");
     return r;
 }

@@ -12,8 +12,6 @@ using namespace adsb;
 
 namespace {
 
-size_t env_floats(uint64_t m) { return (size_t)((m + kRun - 1) / kRun); }
-
 // What every level call asks of its report and its envelope, behind the flavour's own checks of the samples.
 int level_out_refusal(adsb_decoder *d, const char *what, uint64_t m, const adsb_level_report *out, const float *env, size_t env_cap)
 {
@@ -94,17 +92,6 @@ long level_units(adsb_decoder *d, const char *what, int kind, const void *p, siz
     return level_end(d, n, out);
 }
 
-// the scratch of the converted and packed device pushes, grown to n uint16: the export's (decoder_export.hip export_scratch)
-int level_scratch(adsb_decoder *d, const char *what, size_t n)
-{
-    HIP_TRY(d, hipSetDevice(d->device));
-    if (d->unpacked.reserve(n) != hipSuccess) { // (every earlier use of the scratch has completed: the calls that use it return behind its reads)
-        (void)hipGetLastError();
-        return d->fail("%s: cannot allocate %zu bytes of device scratch (2 bytes per sample)", what, n * sizeof(uint16_t));
-    }
-    return 0;
-}
-
 } // namespace
 
 extern "C" {
@@ -147,11 +134,8 @@ long adsb_level_device_as(adsb_decoder *d, int fmt, const void *device_samples, 
         return level_empty(out);
     if (!device_samples)
         return d->fail("%s: NULL buffer", what);
-    if (level_scratch(d, what, n) || format_prepare(d, what, 0))
+    if (to_scratch(d, what, fmt, device_samples, n))
         return -1;
-    HIP_TRY(d, launch_convert(fmt, d->unpacked, device_samples, n, d->d_fmt, d->stream));
-    d->fmt_converted += n;
-    d->fmt_dirty = true;
     return level_capture(d, what, d->unpacked, n, out, device_env); // (the same stream: behind the conversion)
 }
 
@@ -171,9 +155,8 @@ long adsb_level_device_packed(adsb_decoder *d, const void *device_packed, size_t
         return level_empty(out);
     if (!device_packed)
         return d->fail("%s: NULL buffer", what);
-    if (level_scratch(d, what, n))
+    if (to_scratch(d, what, 0, device_packed, n))
         return -1;
-    HIP_TRY(d, launch_unpack12(d->unpacked, device_packed, n / kPackedGroupSamples, d->stream));
     return level_capture(d, what, d->unpacked, n, out, device_env); // (the same stream: behind the unpack)
 }
 
@@ -191,11 +174,8 @@ long adsb_level_device_iq(adsb_decoder *d, int fmt, const void *device_samples, 
         return level_units(d, what, kLevelIq8, device_samples, n, out, device_env);
     const void *iq16 = device_samples;
     if (fmt == 0) { // FLOAT32_IQ: to the int16 grid first, by the conversion the _iq pushes and the export use (and into their scratch)
-        if (level_scratch(d, what, 2 * n) || format_prepare(d, what, 0))
+        if (to_scratch(d, what, kConvFloat32Iq, device_samples, 2 * n))
             return -1;
-        HIP_TRY(d, launch_convert(kConvFloat32Iq, d->unpacked, device_samples, 2 * n, d->d_fmt, d->stream));
-        d->fmt_converted += 2 * n;
-        d->fmt_dirty = true;
         iq16 = d->unpacked.p;
     }
     return level_units(d, what, kLevelIq16, iq16, n, out, device_env);
@@ -226,20 +206,9 @@ long adsb_level_host(adsb_decoder *d, const uint16_t *samples, size_t n, adsb_le
     if (!samples)
         return d->fail("%s: NULL buffer", what);
     const size_t ef = env ? env_floats(m) : 0;
-    HIP_TRY(d, hipSetDevice(d->device));
-    HIP_TRY(d, d->win_buf.reserve((n + 65535) & ~(size_t)65535));
-    if (ef)
-        HIP_TRY(d, d->pow_buf.reserve((ef + 65535) & ~(size_t)65535));
-    // (on a copy stream of the handle's and waited for, as adsb_power_window_host copies its window)
-    HIP_TRY(d, hipMemcpyAsync(d->win_buf, samples, n * sizeof(uint16_t), hipMemcpyHostToDevice, d->copy_stream[0]));
-    WAIT_STREAM(d, d->copy_stream[0], "a copy stream");
     adsb_level_report r;
-    if (level_capture(d, what, d->win_buf, n, &r, ef ? d->pow_buf.p : nullptr) < 0)
+    if (window_in(d, samples, n, ef) || level_capture(d, what, d->win_buf, n, &r, ef ? d->pow_buf.p : nullptr) < 0 || (ef && floats_out(d, env, ef)))
         return -1;
-    if (ef) {
-        HIP_TRY(d, hipMemcpyAsync(env, d->pow_buf, ef * sizeof(float), hipMemcpyDeviceToHost, d->copy_stream[0]));
-        WAIT_STREAM(d, d->copy_stream[0], "a copy stream");
-    }
     *out = r;
     return (long)m;
 }

@@ -26,7 +26,6 @@ struct LevelBatchRules {
 };
 
 inline uint64_t level_count(const LevelBatchRules &R, size_t n) { return R.kind == kLevelReal ? power_samples_produced(n) : (uint64_t)n; }
-inline size_t env_floats(uint64_t m) { return (size_t)((m + kRun - 1) / kRun); }
 
 // The refusals of adsb_level_batch_*, by capture, before anything is launched: the batch export's (decoder_export_batch.hip
 // export_batch_refusal) of the samples, the single level call's (decoder_level.hip level_out_refusal) of report and envelope.
@@ -42,16 +41,11 @@ int level_batch_refusal(adsb_decoder *d, const char *what, const LevelBatchRules
     if (!env != !env_cap)
         return d->fail("%s: the envelope arrays are both NULL (no envelope for any capture) or both given", what);
     for (size_t i = 0; i < n_captures; i++) {
-        if (R.kind == kLevelReal && (uint64_t)n[i] >= (1ull << 32))
-            return d->fail("%s: capture %zu has %zu samples: 2^32 or more, where the reference's sample counter wraps (air.c:34); "
-                           "a batch has no long-stream mode", what, i, n[i]);
         if (R.kind != kLevelReal && (uint64_t)n[i] >= (1ull << 31))
             return d->fail("%s: capture %zu has %zu %s samples: 2^31 or more; such streams end below", what, i, n[i],
                            R.kind == kLevelPower ? "power" : "complex");
-        if (R.packed && n[i] % kPackedGroupSamples != 0)
-            return d->fail("%s: capture %zu: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes)", what, i, n[i]);
-        if (R.in_align && (uintptr_t)src[i] % R.in_align != 0)
-            return d->fail("%s: capture %zu: device pointer %p is not %u-byte aligned", what, i, src[i], R.in_align);
+        if (batch_samples_refusal(d, what, i, src[i], n[i], R.kind == kLevelReal, R.packed, R.in_align))
+            return -1;
         const uint64_t m = level_count(R, n[i]);
         if (env) {
             if (!env[i] && env_cap[i])
@@ -141,8 +135,7 @@ long level_batch(adsb_decoder *d, const char *what, const LevelBatchRules &R, Pr
             sized.assign(k, 0);
             for (size_t i = 0; i < k; i++)
                 sized[i] = level_count(R, n[c0 + i]) == 0 ? 0 : prep == Prep::ConvertIq ? 2 * n[c0 + i] : n[c0 + i];
-            if (prep == Prep::Unpack ? batch_unpack_to_scratch(d, what, k, from, sized.data(), at)
-                                     : batch_convert_to_scratch(d, what, fmt, k, from, sized.data(), at))
+            if (batch_to_scratch(d, what, prep == Prep::Unpack ? 0 : fmt, k, from, sized.data(), at))
                 return -1;
             from = at.data();
         }
@@ -254,41 +247,29 @@ long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *c
     std::vector<uint32_t> row_of;
     for (size_t c0 = 0; c0 < n_captures; c0 += kLevelBatchCaptures) {
         const size_t k = std::min(kLevelBatchCaptures, n_captures - c0);
-        std::vector<size_t> in_at(k), env_at(k);
-        size_t in_bytes = 0, env_all = 0;
+        // (a capture without a power sample takes no room in either)
+        std::vector<size_t> in_bytes(k), floats(k);
+        size_t in_all = 0, env_all = 0;
         for (size_t i = 0; i < k; i++) {
             const uint64_t m = power_samples_produced(n[c0 + i]);
-            in_at[i] = in_bytes, env_at[i] = env_all;
-            if (m == 0)
-                continue;
-            in_bytes += (n[c0 + i] * sizeof(uint16_t) + 127) & ~(size_t)127;
-            if (env && env[c0 + i])
-                env_all += (env_floats(m) + 31) & ~(size_t)31;
+            in_bytes[i] = m ? n[c0 + i] * sizeof(uint16_t) : 0;
+            floats[i] = m && env && env[c0 + i] ? env_floats(m) : 0;
+            in_all += in_bytes[i];
+            env_all += floats[i];
         }
-        if (in_bytes == 0) {
+        if (in_all == 0) {
             for (size_t i = 0; i < k; i++)
                 memset(&out[c0 + i], 0, sizeof out[0]);
             continue;
         }
-        HIP_TRY(d, d->batch_in.reserve((in_bytes + 65535) & ~(size_t)65535));
-        if (env_all)
-            HIP_TRY(d, d->pow_buf.reserve((env_all + 65535) & ~(size_t)65535));
-        std::vector<const void *> at(k);
+        std::vector<const void *> at;
         std::vector<float *> env_dev(k, nullptr);
-        for (size_t i = 0; i < k; i++) {
-            at[i] = d->batch_in + in_at[i];
-            if (power_samples_produced(n[c0 + i]) == 0)
-                continue;
-            if (env && env[c0 + i])
-                env_dev[i] = d->pow_buf + env_at[i];
-            HIP_TRY(d, hipMemcpyAsync(d->batch_in + in_at[i], samples[c0 + i], n[c0 + i] * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
-        }
-        if (level_sub_launch(d, what, kRulesDevice, k, at.data(), n + c0, env_all ? env_dev.data() : nullptr, false, cs, row_of))
+        if ((env_all && pow_slots(d, k, floats.data(), env_dev)) ||
+            land_captures(d, what, d->batch_in, "the captures", k, src + c0, in_bytes.data(), 128, Land::FirstCopyStream, at))
             return -1;
-        for (size_t i = 0; i < k; i++)
-            if (env_dev[i])
-                HIP_TRY(d, hipMemcpyAsync(env[c0 + i], env_dev[i], env_floats(power_samples_produced(n[c0 + i])) * sizeof(float),
-                                          hipMemcpyDeviceToHost, cs));
+        if (level_sub_launch(d, what, kRulesDevice, k, at.data(), n + c0, env_all ? env_dev.data() : nullptr, false, cs, row_of) ||
+            (env_all && pow_slots_out(d, k, env + c0, env_dev, floats.data(), cs)))
+            return -1;
         WAIT_STREAM(d, cs, "a copy stream");
         level_sub_reports(d, kRulesDevice, k, n + c0, row_of, out + c0);
         for (size_t i = 0; i < k; i++) {

@@ -15,8 +15,6 @@ using namespace adsb;
 
 namespace {
 
-inline size_t env_floats(uint64_t m) { return (size_t)((m + kRun - 1) / kRun); }
-
 // The refusals of adsb_level_windows*, in one pass: the window call's of the buffer (adsb_power_window's rules 1 to 3), the edges
 // window by window, the single level call's of report and envelope.  in_align: bytes a device input pointer is aligned to (0: host
 // memory, any).
@@ -138,19 +136,9 @@ long adsb_level_windows_host(adsb_decoder *d, const uint16_t *samples, uint64_t 
         return 0;
     }
     const size_t ef = env ? env_floats(m) : 0;
-    HIP_TRY(d, hipSetDevice(d->device));
-    HIP_TRY(d, d->win_buf.reserve((n + 65535) & ~(size_t)65535));
-    if (ef)
-        HIP_TRY(d, d->pow_buf.reserve((ef + 65535) & ~(size_t)65535));
-    // (on a copy stream of the handle's and waited for, as adsb_power_window_host copies its window)
-    HIP_TRY(d, hipMemcpyAsync(d->win_buf, samples, n * sizeof(uint16_t), hipMemcpyHostToDevice, d->copy_stream[0]));
-    WAIT_STREAM(d, d->copy_stream[0], "a copy stream");
-    if (level_windows(d, what, d->win_buf, first_sample, n, n_windows, edges, out, ef ? d->pow_buf.p : nullptr) < 0)
+    if (window_in(d, samples, n, ef) || level_windows(d, what, d->win_buf, first_sample, n, n_windows, edges, out, ef ? d->pow_buf.p : nullptr) < 0 ||
+        (ef && floats_out(d, env, ef)))
         return -1;
-    if (ef) {
-        HIP_TRY(d, hipMemcpyAsync(env, d->pow_buf, ef * sizeof(float), hipMemcpyDeviceToHost, d->copy_stream[0]));
-        WAIT_STREAM(d, d->copy_stream[0], "a copy stream");
-    }
     return (long)m;
 }
 

@@ -185,13 +185,11 @@ int adsb_scan_shard_host(adsb_decoder *d, const uint16_t *host_samples, uint64_t
         return -1;
     if (shard_too_long(d, "adsb_scan_shard_host", first_sample, n, 0))
         return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    HIP_TRY(d, d->win_buf.reserve((n + 65535) & ~(size_t)65535));
     // (copied and waited for: the scan's launches may go to either compute stream, and a window is a few hundred KB.  On a
     // copy stream of the handle's: the synchronous hipMemcpy was seen to cost the process ~1 KB of host memory per call
     // that never came back -- tools/soak_probe.py)
-    HIP_TRY(d, hipMemcpyAsync(d->win_buf, host_samples, n * sizeof(uint16_t), hipMemcpyHostToDevice, d->copy_stream[0]));
-    WAIT_STREAM(d, d->copy_stream[0], "a copy stream");
+    if (window_in(d, host_samples, n, 0))
+        return -1;
     return adsb_scan_shard(d, d->win_buf, first_sample, n, g_begin, g_end, cands, cand_cap, n_cands, tries, try_cap, n_tries);
 }
 

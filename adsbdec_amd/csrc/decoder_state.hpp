@@ -10,6 +10,7 @@
 //   decoder_level.hip      the level calls (adsb_level_*): a capture's power samples reduced to a report and an envelope
 //   decoder_level_batch.hip  the batch level calls (adsb_level_batch_*): the reports of N captures by one launch per sub-batch
 //   decoder_level_windows.hip  the window form (adsb_level_windows*): the reports of K consecutive windows of one stream
+//   decoder_stage.hip      the staging steps every family calls: samples into unpacked, batch_in, batch_land, batch_unpacked, win_buf, pow_buf
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
 
@@ -133,7 +134,8 @@ struct ScanSink { // where collected records go: a caller's vectors, or (null) t
 // The handle.  Its device resources are members that free themselves (device_mem.hpp), declared so that the streams go
 // LAST: behind the buffers and events that were used on them.
 //
-// Data layout in HBM
+// Data layout in HBM (decoder_stage.hip is where land[] of a batch -- batch_land --, unpacked, batch_in, batch_unpacked, win_buf and pow_buf
+// are filled; land[] of a host push is filled by push_copy in decoder.hip, beside the staging buffers it feeds)
 //   stage[2]   uint16 samples; the current one holds stream samples
 //              [stage_first, stage_first+stage_fill): what has not been dropped yet plus the
 //              newest push (pushes are appended; the scanned part is dropped -- the tail moved to
@@ -474,12 +476,20 @@ void book_launch(adsb_decoder *d, ScanSlot &s, uint64_t offsets);
 int regrow_if_overflowed(adsb_decoder *d, ScanSlot &s, int attempt);
 void start_reader(adsb_decoder *d);
 void start_gang(adsb_decoder *d, int helpers);
-// decoder_batch.hip: the packed captures / the captures of format fmt at src[] -> uint16 samples in batch_unpacked by ONE launch on
-// the scan stream, capture i from at[i] on (a 128-byte boundary); not waited for
-int batch_unpack_to_scratch(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n,
-                            std::vector<const void *> &at);
-int batch_convert_to_scratch(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
-                             std::vector<const void *> &at);
+// decoder_stage.hip: the staging steps (conv = 0: packed 12-bit input is unpacked; else the conversion of sample_format.h)
+int to_scratch(adsb_decoder *d, const char *what, int conv, const void *src, size_t n);
+int scratch_before_stream2(adsb_decoder *d);
+enum class Land { InTurnWaited, FirstCopyStream }; // the copy streams in turn, all waited for | copy_stream[0] in order, not waited for
+int land_captures(adsb_decoder *d, const char *what, Buf<uint8_t> &buf, const char *of, size_t n_captures, const void *const *src,
+                  const size_t *bytes, size_t align, Land how, std::vector<const void *> &at);
+int batch_to_scratch(adsb_decoder *d, const char *what, int conv, size_t n_captures, const void *const *src, const size_t *n,
+                     std::vector<const void *> &at);
+int batch_realign(adsb_decoder *d, const char *what, size_t n_captures, const size_t *bytes, std::vector<const void *> &at);
+int window_in(adsb_decoder *d, const uint16_t *samples, size_t n, size_t floats);
+int floats_out(adsb_decoder *d, float *dst, size_t floats);
+int pow_slots(adsb_decoder *d, size_t n_captures, const size_t *floats, std::vector<float *> &at);
+int pow_slots_out(adsb_decoder *d, size_t n_captures, float *const *dst, const std::vector<float *> &at, const size_t *floats, hipStream_t st);
+int batch_samples_refusal(adsb_decoder *d, const char *what, size_t i, const void *src, size_t n, bool real, bool packed, unsigned in_align);
 // decoder_lifecycle.hip
 void set_create_error(const char *why); // what adsb_last_error(NULL) shows: a call without a handle has failed
 

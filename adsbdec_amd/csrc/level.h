@@ -6,11 +6,16 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "scan_kernel.h" // kRun
+
 #pragma GCC visibility push(hidden)
 
 namespace adsb {
 
-constexpr int kLevelBins = 2048;                 // bin = bits >> 20 of a sign-clear float: 8 per octave
+// floats of the envelope of m power samples: one per run (host-only)
+inline size_t env_floats(uint64_t m) { return (size_t)((m + kRun - 1) / kRun); }
+
+constexpr int kLevelBins = 2048;                // bin = bits >> 20 of a sign-clear float: 8 per octave
 constexpr int kLevelWords = 5 + kLevelBins;      // adsb_level_report as uint64 words: samples, negative, rail_lo, rail_hi, over, hist[]
 constexpr int kLevelRowWords = 4 + kLevelBins;   // a workgroup's row of 32-bit counts (measurement builds with ADSB_LEVEL_FLUSH=1)
 // what a launch may be given of the handle's: the workgroups a level launch has at most, and with them the rows

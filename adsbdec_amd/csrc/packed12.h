@@ -62,6 +62,25 @@ ADSB_HD inline uint32_t unpack12_row(const Unpack12Seg *tab, uint32_t lo, uint32
     return lo;
 }
 
+// ---- host-only: building the table ----
+// The table of n_captures packed captures into tab[0 .. rows], rows <= n_captures: capture i has n[i] samples (whole groups), is
+// read at src[i] and written off[i] bytes (a multiple of 16) into the launch's dst.  *groups = the number of all groups.  Returns the
+// rows, the closing one not counted.
+inline uint32_t unpack12_table(size_t n_captures, const void *const *src, const size_t *n, const size_t *off, Unpack12Seg *tab, uint64_t *groups)
+{
+    uint32_t row = 0;
+    uint64_t at = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        if (n[i] == 0)
+            continue;
+        tab[row++] = Unpack12Seg{(uint64_t)(uintptr_t)src[i], off[i] / 16, at};
+        at += n[i] / kPackedGroupSamples;
+    }
+    tab[row] = Unpack12Seg{0, 0, at}; // behind the last row: where its groups end
+    *groups = at;
+    return row;
+}
+
 #ifdef __HIPCC__
 // unpack12.hip: `groups` groups at src (4-byte aligned) -> 8 * groups samples at dst (16-byte aligned), enqueued on `stream`
 hipError_t launch_unpack12(uint16_t *dst, const void *src, size_t groups, hipStream_t stream);

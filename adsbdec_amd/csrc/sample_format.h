@@ -130,6 +130,25 @@ ADSB_HD inline uint32_t convert_row(const ConvertSeg *tab, uint32_t lo, uint32_t
     return lo;
 }
 
+// ---- host-only: building the table ----
+// The table of n_captures captures into tab[0 .. rows], rows <= n_captures: capture i has n[i] samples (its last group may be short),
+// is read at src[i] and written off[i] bytes (a multiple of 16) into the launch's dst.  *groups = the number of all groups.  Returns
+// the rows, the closing one not counted.
+inline uint32_t convert_table(size_t n_captures, const void *const *src, const size_t *n, const size_t *off, ConvertSeg *tab, uint64_t *groups)
+{
+    uint32_t row = 0;
+    uint64_t at = 0;
+    for (size_t i = 0; i < n_captures; i++) {
+        if (n[i] == 0)
+            continue;
+        tab[row++] = ConvertSeg{(uint64_t)(uintptr_t)src[i], off[i] / 16, at, n[i]};
+        at += (n[i] + 7) / 8;
+    }
+    tab[row] = ConvertSeg{0, 0, at, 0}; // behind the last row: where its groups end
+    *groups = at;
+    return row;
+}
+
 #ifdef __HIPCC__
 // n samples of format fmt (kFmtFloat32Real / kFmtInt16Real; kConvFloat32Iq: n scalars -> n int16) at src (aligned to the element) -> n uint16 codes at dst (2-byte
 // aligned), enqueued on `stream`; counters: NULL, or two uint64 in device memory that the samples' inexact and clamped counts are

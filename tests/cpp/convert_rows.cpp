@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../adsbdec_amd/csrc/sample_format.h"
+#include "../../adsbdec_amd/csrc/stage_layout.hpp"
 
 using adsb::ConvertSeg;
 
@@ -73,13 +74,16 @@ int main()
             for (int i = 0; i < 700; i++)
                 len.push_back(1 + rng() % 7);
         }
-        std::vector<ConvertSeg> tab;
+        // the table as the product builds it (convert_table over stage_layout's offsets: decoder_stage.hip)
+        std::vector<size_t> ns(len.begin(), len.end()), bytes, off(len.size());
+        for (size_t l : ns)
+            bytes.push_back(l * sizeof(uint16_t));
+        adsb::stage_layout(len.size(), bytes.data(), 128, off.data());
+        const std::vector<const void *> src(len.size(), nullptr);
+        std::vector<ConvertSeg> tab(len.size() + 1);
         uint64_t g = 0;
-        for (uint64_t l : len) {
-            tab.push_back(ConvertSeg{0, 0, g, l});
-            g += (l + 7) / 8;
-        }
-        tab.push_back(ConvertSeg{0, 0, g, 0});
+        if (adsb::convert_table(len.size(), src.data(), ns.data(), off.data(), tab.data(), &g) != len.size())
+            return 1;
         tables++;
         // every group within a chunk and a half of every capture boundary, in rising order (each once: the windows of short
         // captures overlap), so that ONE scan of the table, which only ever moves forward, names every group's row; and random ones

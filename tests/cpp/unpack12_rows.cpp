@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../adsbdec_amd/csrc/packed12.h"
+#include "../../adsbdec_amd/csrc/stage_layout.hpp"
 
 using adsb::Unpack12Seg;
 
@@ -42,13 +43,18 @@ int main()
         }
         if (t == 0)
             len = {1, 1ull << 29, 1, 1, (1ull << 29) - 1, 255, 1, 256, 257};
-        std::vector<Unpack12Seg> tab;
-        uint64_t g = 0;
+        // the table as the product builds it (unpack12_table over stage_layout's offsets: decoder_stage.hip)
+        std::vector<size_t> ns, bytes, off(len.size());
         for (uint64_t l : len) {
-            tab.push_back(Unpack12Seg{0, 0, g});
-            g += l;
+            ns.push_back((size_t)l * adsb::kPackedGroupSamples);
+            bytes.push_back(ns.back() * sizeof(uint16_t));
         }
-        tab.push_back(Unpack12Seg{0, 0, g});
+        adsb::stage_layout(len.size(), bytes.data(), 128, off.data());
+        const std::vector<const void *> src(len.size(), nullptr);
+        std::vector<Unpack12Seg> tab(len.size() + 1);
+        uint64_t g = 0;
+        if (adsb::unpack12_table(len.size(), src.data(), ns.data(), off.data(), tab.data(), &g) != len.size())
+            return 1;
         tables++;
         // every group within a chunk and a half of every capture boundary, and random ones
         for (size_t r = 0; r + 1 < tab.size(); r++)

@@ -411,3 +411,85 @@ def inside_loud(payload, guard_front, guard_back):
     """guard | payload | guard as bytes -> (bytes, byte offset of the payload)."""
     f, p, b = (np.ascontiguousarray(v).view(np.uint8).reshape(-1) for v in (guard_front, payload, guard_back))
     return np.concatenate([f, p, b]), f.size
+
+
+# ---------------------------------------------------------------- section 3, batches: a loud batch, then the targets
+N_AROUND = 70_000                              # the targets of section 3 are captures of about this many samples
+# road: (family of stale_cases, the form the call takes, fmt, device call?).  The families: "real" (the n % 4 = 1 edge capture and
+# 70 000 .. 70 007 samples), "packed" (the three of whole groups), "iq" (the five complex ones); every target batch has an empty capture
+# in the middle, and the loud batch in front of it is the loud capture three times, each cut to a different length.
+BATCH_ROADS = {
+    "decode_batch": ("real", "u16", None, False),
+    "decode_batch_as3": ("real", "s16", 3, False),
+    "decode_batch_as1": ("real", "f32", 1, False),
+    "decode_batch_packed": ("packed", "packed", None, False),
+    "decode_batch_iq0": ("iq", "iqf32", 0, False),
+    "decode_batch_iq2_one_pointer_4_mod_16": ("iq", "iq16", 2, False),
+    "decode_batch_power": ("iq", "power", None, False),
+    "decode_batch_device_packed": ("packed", "packed", None, True),
+    "decode_batch_device_as3": ("real", "s16", 3, True),
+    "decode_batch_device_iq2_one_pointer_4_mod_16": ("iq", "iq16", 2, True),   # (the scratch copy of misaligned captures: device pointers only)
+    "power_batch": ("real", "u16", None, False),
+    "power_batch_device_packed": ("packed", "packed", None, True),
+    "power_batch_device_as1": ("real", "f32", 1, True),
+    "power_batch_device_iq0": ("iq", "iqf32", 0, True),
+    "level_batch": ("real", "u16", None, False),
+    "level_batch_device_packed": ("packed", "packed", None, True),
+    "level_batch_device_as3": ("real", "s16", 3, True),
+    "level_batch_device_iq0": ("iq", "iqf32", 0, True),
+}
+
+
+def batch_form(form, x):
+    """A capture as the oracle knows it (codes, or int16 (I, Q) rows) -> the array a call of this form is given."""
+    from adsbdec_amd import sample_formats as S
+    from adsbdec_amd.packed12 import pack12
+    if form == "packed":
+        return pack12(x) if x.size else np.empty(0, np.uint8)
+    if form == "power":
+        return np.ascontiguousarray(S.iq_power(x), dtype="<f4")
+    return np.ascontiguousarray({"s16": S.to_int16_real, "f32": S.to_float32_real, "iqf32": S.to_float32_iq}.get(form, lambda v: v)(x))
+
+
+LOUD_CUTS = (0, 1, 2)                          # groups of 8 elements cut from the end of the loud capture: three lengths, all of them
+                                               # four times a target of N_AROUND samples and, to within 16 elements, the edge capture
+
+
+def loud_batch(loud):
+    """The loud capture three times, each cut to a different length (whole groups of 8 elements: packed input comes in them)."""
+    n = len(loud)
+    return [np.ascontiguousarray(loud[:n - 8 * k]) for k in LOUD_CUTS]
+
+
+def with_an_empty_capture(targets):
+    """The targets in order with an empty capture in the middle -> (captures, index of the empty one)."""
+    mid = len(targets) // 2
+    return list(targets[:mid]) + [targets[0][:0]] + list(targets[mid:]), mid
+
+
+def slots(n_bytes, align):
+    """Where a batch's captures lie in one of the handle's batch buffers: capture i at the sum of the sizes before it, each rounded
+    up to `align` bytes -> (offsets, total).  The plain statement of csrc/stage_layout.hpp."""
+    at, cur = [], 0
+    for b in n_bytes:
+        at.append(cur)
+        cur += -(-int(b) // align) * align
+    return at, cur
+
+
+def check_stale_batch_shows(loud, targets, align):
+    """loud, targets: the arrays two batches put into one buffer, captures at multiples of `align` bytes.  Every target of the batch
+    that follows the loud one lies wholly inside bytes the loud batch wrote, the buffer shrinks in use, and what the loud batch left
+    at the target's place is not the target: a call that read its buffer's past would read other samples."""
+    la, lt = slots([np.asarray(x).nbytes for x in loud], align)
+    ta, tt = slots([np.asarray(x).nbytes for x in targets], align)
+    assert tt < lt and len({np.asarray(x).nbytes for x in loud}) == len(loud) == 3
+    flat = np.zeros(lt, np.uint8)                             # (the pad between two captures is nobody's: zeros here)
+    for x, a in zip(loud, la):
+        b = np.ascontiguousarray(x).reshape(-1).view(np.uint8)
+        flat[a:a + b.size] = b
+    assert all(a % align == 0 for a in la + ta)
+    for x, a in zip(targets, ta):
+        b = np.ascontiguousarray(x).reshape(-1).view(np.uint8)
+        assert b.size == 0 or not np.array_equal(flat[a:a + b.size], b)
+    return True

@@ -5,7 +5,8 @@ kernel or a launch bound that read a few pairs outside [p, p + n) would read the
 1. pieces of one stream, each in a tensor of its own between 8192 units of ANOTHER frame-carrying capture, with frames planted
    across and directly behind every cut (tests/guarded_cases.py), in place and staged, through all eight fronts and two handles;
 2. the edge captures of the neighbouring modules (a frame from sample 0 on), decoded as a stream from their loud buffers;
-3. a handle whose scratch, staging and landing buffers hold a louder, four times longer capture when the target arrives;
+3. a handle whose scratch, staging and landing buffers hold a louder, four times longer capture when the target arrives -- and
+   whose batch buffers, tables and totals hold a loud batch when a batch of targets arrives;
 4. whole-capture exports and level reports of captures that lie inside loud memory with both rails planted in the guards.
 
 Every comparison is equality with the oracle.  tests/test_guarded_cpu.py proves without a device that each guard can be seen.
@@ -226,7 +227,7 @@ def test_edge_captures_of_the_other_fronts_behind_a_loud_guard(capi, torch_cuda,
 
 
 # ---------------------------------------------------------------- 3. a handle whose buffers hold a louder, longer capture
-N_AROUND = 70_000                                 # the lengths n .. n + 7 of the packed and quad classes: above the in-place minimum
+N_AROUND = G.N_AROUND                             # 70 000: the lengths n .. n + 7 of the packed and quad classes: above the in-place minimum
 _stale = {}
 
 
@@ -406,6 +407,146 @@ def test_host_calls_from_windows_that_held_a_loud_capture(capi, oracle, torch_cu
             assert np.array_equal(got["env"].view(np.uint32), want["env"].view(np.uint32)), ("level", j)
     finally:
         d.close()
+
+
+# ---------------------------------------------------------------- 3b. batches into buffers that held a loud batch
+BATCH_ROADS, batch_form = G.BATCH_ROADS, G.batch_form    # (tests/guarded_cases.py: shared with the CPU proof)
+_batch_want = {}
+
+
+def batch_cases(oracle, family):
+    """-> (the loud batch, the target batch with an empty capture in the middle, that capture's index, the targets' oracle answers
+    with None for the empty one), all as the oracle knows them."""
+    c = stale_cases(oracle)
+    loud = G.loud_batch(G.loud_iq(2, len(c["loud_iq"]), 8401) if family == "iq" else c["loud"])
+    targets, mid = G.with_an_empty_capture([x for x, _, _ in c[family]])
+    answers = list(c[family])
+    answers.insert(mid, None)
+    return loud, targets, mid, answers
+
+
+def _host_at_4_mod_16(a):
+    """A copy of the array whose first byte lies at an address that is 4 mod 16."""
+    raw = np.empty(a.nbytes + 32, np.uint8)
+    lead = (4 - raw.ctypes.data) % 16
+    out = raw[lead:lead + a.nbytes].view(a.dtype).reshape(a.shape)
+    out[...] = a
+    assert out.ctypes.data % 16 == 4
+    return out
+
+
+def _count(form, a):
+    """What the calls are given as n: samples, complex samples or power samples."""
+    return a.size // 12 * 8 if form == "packed" else a.size // 2 if form in ("iq16", "iqf32") else a.size
+
+
+def _run_batch(capi, torch, d, road, caps, skew_one, floats=None):
+    """One batch call of a road -> what it gave, in a form that compares with ==: decodes ([records], [stats]); exports [the floats'
+    bytes] (checked: nothing behind cap; device calls with `floats`: check_out against them); levels ([(counters, bins' bytes,
+    envelope's bytes)], the reports with "env"), nothing behind an envelope."""
+    from test_gpu_power_export import GUARD as OUT_GUARD, SENT
+    family, form, fmt, on_device = BATCH_ROADS[road]
+    arrs = [batch_form(form, x) for x in caps]
+    biggest = max(range(len(arrs)), key=lambda i: arrs[i].size)
+    ns = [_count(form, a) for a in arrs]
+    keep, ptrs = [], []
+    if on_device:
+        for i, a in enumerate(arrs):
+            if skew_one and i == biggest:                         # one complex sample of loud memory in front: 4 mod 16
+                t, p = to_dev(torch, np.concatenate([np.full(4, 0x7F, np.uint8), a.reshape(-1).view(np.uint8)]), 4)
+            else:
+                t, p = to_dev(torch, a, 0) if a.size else (None, 0)
+            keep.append(t)
+            ptrs.append(p)
+    elif skew_one:
+        arrs[biggest] = _host_at_4_mod_16(arrs[biggest])
+    # the power samples a capture gives: two per four real samples, one per complex sample
+    ks = [len(x) if family == "iq" else 2 * (len(x) // 4) for x in caps]
+    if road.startswith("decode"):
+        if on_device:
+            call = {"packed": lambda: d.decode_batch_device_packed(ptrs, ns, stats=True), "s16": lambda: d.decode_batch_device_as(fmt, ptrs, ns, stats=True),
+                    "iq16": lambda: d.decode_batch_device_iq(fmt, ptrs, ns, stats=True)}[form]
+        else:
+            call = {"u16": lambda: d.decode_batch(arrs, stats=True), "s16": lambda: d.decode_batch_as(fmt, arrs, stats=True),
+                    "f32": lambda: d.decode_batch_as(fmt, arrs, stats=True), "packed": lambda: d.decode_batch_packed(arrs, stats=True),
+                    "iq16": lambda: d.decode_batch_iq(fmt, arrs, stats=True), "iqf32": lambda: d.decode_batch_iq(fmt, arrs, stats=True),
+                    "power": lambda: d.decode_batch_power(arrs, stats=True)}[form]
+        frames, st = call()
+        return [records(f) for f in frames], st
+    if road.startswith("power"):
+        if on_device:
+            outs = [dev_out(torch, k) for k in ks]
+            args = d._power_batch_args(ptrs, ns, [p if k else 0 for (_, p), k in zip(outs, ks)], ks)
+            name = {"packed": "adsb_power_batch_device_packed", "f32": "adsb_power_batch_device_as", "iqf32": "adsb_power_batch_device_iq"}[form]
+            assert d._power_call(name, *(() if form == "packed" else (fmt,)), *args) == sum(ks)
+            for j, (t, _) in enumerate(outs):
+                if floats is not None and floats[j] is not None:
+                    check_out(t, floats[j][:ks[j]], (road, j))
+            got = [t.cpu().numpy().view(np.uint32) for t, _ in outs]
+        else:
+            got = [np.full(k + OUT_GUARD, SENT, np.uint32) for k in ks]
+            args = d._power_batch_args([a.ctypes.data if a.size else None for a in arrs], ns, [o.ctypes.data if k else None for o, k in zip(got, ks)], ks)
+            assert d._power_call("adsb_power_batch_host", *args) == sum(ks)
+        assert all((o[k:] == SENT).all() for o, k in zip(got, ks)), (road, "floats behind cap")
+        return [o[:k].tobytes() for o, k in zip(got, ks)]
+    if on_device:
+        envs = [dev_env(torch, k) if k else (None, 0, 0) for k in ks]
+        call = {"packed": lambda **kw: d.level_batch_device_packed(ptrs, ns, **kw), "s16": lambda **kw: d.level_batch_device_as(fmt, ptrs, ns, **kw),
+                "iqf32": lambda **kw: d.level_batch_device_iq(fmt, ptrs, ns, **kw)}[form]
+        out = call(env_ptrs=[p for _, p, _ in envs], env_caps=[k for _, _, k in envs])
+        for r, (t, _, k) in zip(out, envs):
+            e = t.cpu().numpy().view(np.uint32) if t is not None else np.empty(0, np.uint32)
+            assert (e[k:] == SENT).all(), (road, "floats behind the envelope")
+            r["env"] = e[:k].view(np.float32).copy()
+    else:
+        out = d.level_batch(arrs, env=True)
+    return [({k: v for k, v in r.items() if k not in ("hist", "env")}, r["hist"].tobytes(), r["env"].view(np.uint32).tobytes()) for r in out], out
+
+
+@pytest.mark.limit(60)
+@pytest.mark.parametrize("road", list(BATCH_ROADS))
+def test_batches_into_buffers_that_held_a_loud_batch(capi, oracle, torch_cuda, road):
+    """batch_in, batch_land and batch_unpacked, the unpack, export and level tables and the level totals of a handle whose first batch
+    call was the loud capture three times, each cut to a different length: the targets of stale_cases with an empty capture in the
+    middle then give the oracle's answers -- records and Ok/Try, floats bit for bit with nothing behind cap, reports and envelopes
+    word for word -- and what a fresh handle gives."""
+    family, form, fmt, on_device = BATCH_ROADS[road]
+    loud, targets, mid, answers = batch_cases(oracle, family)
+    skew_one = "4_mod_16" in road
+    kw = dict(df18=True, collect_stats=True)
+    floats = [None if w is None else w[2] for w in answers]
+    used, fresh = capi.Decoder(**kw), capi.Decoder(**kw)
+    try:
+        _run_batch(capi, torch_cuda, used, road, loud, skew_one)              # the loud batch goes through the call first and is discarded
+        got = _run_batch(capi, torch_cuda, used, road, targets, skew_one, floats)
+        again = _run_batch(capi, torch_cuda, fresh, road, targets, skew_one)
+    finally:
+        used.close()
+        fresh.close()
+    if road.startswith("decode"):
+        assert got[0][mid] == [] and not any(got[1][mid]["ok"].values()) and not any(got[1][mid]["try"].values()), (road, "the empty capture")
+        for j, w in enumerate(answers):
+            if w is not None:
+                assert got[0][j] == records(w[1][0]), (road, j, "behind the loud batch")
+                check_stats(got[1][j], w[1][1], True, (road, j))
+        assert again == got, (road, "a fresh handle")
+    elif road.startswith("power"):
+        assert got[mid] == b"", (road, "the empty capture")
+        for j, w in enumerate(answers):
+            if w is not None:
+                k = len(got[j]) // 4
+                assert k > 0 and got[j] == np.ascontiguousarray(w[2][:k], dtype=np.float32).tobytes(), (road, j, "behind the loud batch")
+        assert again == got, (road, "a fresh handle")
+    else:
+        assert got[1][mid]["samples"] == 0 and not got[1][mid]["hist"].any() and got[1][mid]["env"].size == 0, (road, "the empty capture")
+        for j, w in enumerate(answers):
+            if w is not None:
+                if (family, j) not in _batch_want:
+                    _batch_want[family, j] = want_iq(S().to_float32_iq(w[0]), 0) if family == "iq" else want_real(oracle, w[0], w[2])
+                want = _batch_want[family, j]
+                check_level(got[1][j], None, want, (road, j))
+                assert np.array_equal(got[1][j]["env"].view(np.uint32), want["env"].view(np.uint32)), (road, j, "the envelope")
+        assert again[0] == got[0], (road, "a fresh handle")
 
 
 # ---------------------------------------------------------------- 4. whole-capture exports and level reports inside loud memory

@@ -135,6 +135,41 @@ def test_the_loud_captures_are_longer_and_never_silence():
     assert not G.never_silence(np.array([1, 0x800], np.uint16)) and not G.never_silence(np.array([1.0, 0.0], np.float32))
 
 
+@pytest.mark.parametrize("road", list(G.BATCH_ROADS))
+def test_a_batch_behind_the_loud_batch_lies_in_what_it_wrote(road):
+    """Per road of test_batches_into_buffers_that_held_a_loud_batch and per buffer the road fills -- what the call is given, landed at
+    16 bytes (the _as and packed host batches) or 128, and the 16-bit samples a packed or converted batch leaves in batch_unpacked at
+    128: the loud batch is three captures of three lengths, none of them silence; the target batch is shorter in all, so each of its
+    captures lies in bytes the loud batch wrote, and those bytes are not its own; the empty capture in the middle takes no room.  A
+    loud batch of one length only, or one shorter than the targets, fails the check."""
+    family, form, _, on_device = G.BATCH_ROADS[road]
+    if family == "iq":
+        loud = G.loud_batch(G.loud_iq(2, 4 * len(F._iq_edge(1)), 8401))
+        targets = [F._iq_edge(1)] + [np.ascontiguousarray(F._iq_edge(2)[:G.N_AROUND // 2 + j]) for j in range(4)]
+    else:
+        edge, base = _edge_capture(1), _edge_capture(2)
+        loud = G.loud_batch(G.loud_codes(4 * edge.size + 8 - (4 * edge.size) % 8, 8400))
+        targets = [edge] + [np.ascontiguousarray(base[:G.N_AROUND + j]) for j in range(8)]
+        if family == "packed":
+            from test_gpu_batch_packed import packable
+            targets = [packable(edge), np.ascontiguousarray(base[:G.N_AROUND]), np.ascontiguousarray(base[:G.N_AROUND + 8])]
+    targets, mid = G.with_an_empty_capture(targets)
+    assert 0 < mid < len(targets) - 1 and len(targets[mid]) == 0 and all(len(x) for i, x in enumerate(targets) if i != mid)
+    assert all(len(x) >= 4 * G.N_AROUND // (2 if family == "iq" else 1) for x in loud) and all(G.never_silence(x) for x in loud)
+    given = lambda caps: [G.batch_form(form, x) for x in caps]
+    assert form == "packed" or all(G.never_silence(a) for a in given(loud))      # (packed bytes: a zero byte is no silence)
+    if not on_device:                                                            # the landing buffer: batch_in or batch_land
+        assert G.check_stale_batch_shows(given(loud), given(targets), 16 if form in ("s16", "f32", "packed") else 128)
+    if form in ("s16", "f32", "packed", "iqf32"):                                # batch_unpacked: codes, or int16 scalars
+        assert G.check_stale_batch_shows(loud, targets, 128)
+    at, _ = G.slots([np.asarray(x).nbytes for x in targets], 128)
+    assert at[mid] == at[mid + 1]
+    with pytest.raises(AssertionError):
+        G.check_stale_batch_shows([loud[0]] * 3, targets, 128)
+    with pytest.raises(AssertionError):
+        G.check_stale_batch_shows([x[:len(targets[0]) // 4] for x in loud], targets, 128)
+
+
 # ---------------------------------------------------------------- section 4
 def test_guards_of_the_exports_can_be_seen(oracle):
     """Real: the first six floats differ between silence and the guard in front, at every length; every kind: the guards hold a code
