@@ -25,7 +25,8 @@ HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip",
                "decoder_lifecycle.hip", "decoder_batch.hip", "decoder_shard.hip", "unpack12.hip", "unpack12_batch.hip",
                "convert_samples.hip", "power_export_kernel.hip", "decoder_export.hip",
                "power_export_batch_kernel.hip", "decoder_export_batch.hip", "level_kernel.hip", "decoder_level.hip",
-               "level_batch_kernel.hip", "decoder_level_batch.hip", "level_windows_kernel.hip", "decoder_level_windows.hip", "decoder_stage.hip"]
+               "level_batch_kernel.hip", "decoder_level_batch.hip", "level_windows_kernel.hip", "decoder_level_windows.hip", "decoder_stage.hip",
+               "burst_kernel.hip", "decoder_bursts.hip"]
 C_SOURCES = ["format.c"]
 # host-only C++ (no HIP): the multi-GPU driver over the C-ABI, and the part of the C-ABI that needs no device
 CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]

@@ -244,6 +244,10 @@ SYMBOLS = {
     "adsb_level_windows": (C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_level_windows_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_level_add": (None, [C.c_void_p, C.c_void_p]),
+    "adsb_level_percentile": (C.c_float, [C.c_void_p, C.c_double]),
+    "adsb_bursts_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "adsb_bursts_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "adsb_burst_tile_runs": (C.c_uint32, []),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -1091,6 +1095,54 @@ class Decoder:
         reports = [self.level_dict(r[i]) for i in range(k)]
         return (reports, ev) if env else reports
 
+    # ---- the gate behind the envelope (include/adsbdec_amd.h: adsb_bursts_*; adsbdec_amd.levels.bursts is the statement)
+    # The host program's defaults (-U).  hang: a decode call keeps the reference's end-of-file horizon (deqframe runs once 40 980 power
+    # samples are in), so a piece must reach 1 464 runs behind its last frame or it decodes nothing.  factor: an envelope float is the
+    # maximum of 28 samples, and over millions of runs the noise's largest one lies some 35 times above the median SAMPLE.  They rest
+    # on ONE fixture (tests/burst_cases.py), not on live traffic.
+    BURST_LEAD, BURST_HANG, BURST_FACTOR = 2, 1468, 48.0
+
+    def _bursts_call(self, name, ptr, n_env, threshold, lead, hang, cap, table=None):
+        """-> (the first min(B, cap) records as a structured array of adsbdec_amd.levels.BURST_DTYPE, B).  table: an array of that
+        dtype with room for cap records to write into instead of a new one (the result is a view of its head)."""
+        from .levels import BURST_DTYPE
+        t = np.zeros(cap, dtype=BURST_DTYPE) if table is None else table
+        b = getattr(self._L, name)(self._h, ptr or None, n_env, threshold, lead, hang, t.ctypes.data if cap else None, cap)
+        if b < 0:
+            self._check(-1, name)
+        return t[:min(b, cap)], int(b)
+
+    def bursts_device(self, env_ptr: int, n_env: int, threshold: float, lead: int, hang: int, cap: int, table=None):
+        """adsb_bursts_device: the bursts of the n_env floats in HBM at env_ptr -> (records, B); B may exceed cap, cap 0 only counts."""
+        return self._bursts_call("adsb_bursts_device", env_ptr, n_env, threshold, lead, hang, cap, table)
+
+    def bursts_host(self, env, threshold: float, lead: int, hang: int, cap: int | None = None, table=None):
+        """adsb_bursts_host: ... of a float32 array in host memory (cap None: as many as there are, by a second call where the first
+        guess was short)."""
+        env = np.ascontiguousarray(env, dtype=np.float32).reshape(-1)
+        if cap is not None:
+            return self._bursts_call("adsb_bursts_host", env.ctypes.data if env.size else 0, env.size, threshold, lead, hang, cap, table)
+        recs, b = self._bursts_call("adsb_bursts_host", env.ctypes.data if env.size else 0, env.size, threshold, lead, hang, 1024)
+        if b > 1024:
+            recs, b = self._bursts_call("adsb_bursts_host", env.ctypes.data, env.size, threshold, lead, hang, b)
+        return recs, b
+
+    def bursts(self, x: np.ndarray, q: float = 0.5, factor: float = BURST_FACTOR, lead: int = BURST_LEAD, hang: int = BURST_HANG):
+        """A uint16 capture in host memory -> (every burst of its envelope, B): level() with the envelope, the threshold
+        float32(factor * percentile(hist, q)) (adsb_level_percentile), and the gate (adsb_bursts_host)."""
+        rep = self.level(x, env=True)
+        if rep["env"].size == 0:
+            from .levels import BURST_DTYPE
+            return np.zeros(0, dtype=BURST_DTYPE), 0
+        r = LevelReport()
+        for k in ("samples", "negative", "rail_lo", "rail_hi", "over"):
+            setattr(r, k, rep[k])
+        np.ctypeslib.as_array(r.hist)[:] = rep["hist"]
+        p = self._L.adsb_level_percentile(C.byref(r), q)
+        if p < 0:
+            raise AdsbError("adsb_level_percentile: an empty histogram, or q outside [0, 1]")
+        return self.bursts_host(rep["env"], float(np.float32(factor * float(p))), lead, hang)
+
     def format_report(self):
         """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""
         r = FormatReport()
@@ -1394,6 +1446,19 @@ def plan_shards(total_samples: int, n_shards: int):
         raise AdsbError("adsb_plan_shards failed")
     return [dict(g_begin=int(arrs[0][i]), g_end=int(arrs[1][i]), first_sample=int(arrs[2][i]),
                  n_samples=int(arrs[3][i])) for i in range(n_shards)]
+
+
+def burst_tile_runs() -> int:
+    """adsb_burst_tile_runs: T, the runs one workgroup of the gate's kernels takes."""
+    return int(load().adsb_burst_tile_runs())
+
+
+def level_percentile(hist, q: float) -> float:
+    """adsb_level_percentile on a histogram of 2048 counts: what adsbdec_amd.levels.percentile states, computed by the library (-1.0: an
+    empty histogram, or q outside [0, 1])."""
+    r = LevelReport()
+    np.ctypeslib.as_array(r.hist)[:] = np.asarray(hist, dtype=np.uint64)
+    return float(load().adsb_level_percentile(C.byref(r), q))
 
 
 def level_add(r: dict, s: dict) -> dict:

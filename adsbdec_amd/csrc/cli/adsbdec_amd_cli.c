@@ -50,6 +50,15 @@
  *                   p99.9 .. peak .. rail_lo A rail_hi B over C` per window of ms milliseconds (10 000 power samples each, rounded down
  *                   to a multiple of 28), then -L's report of the sum of the windows (a trailing n % 4 samples belong to no window: named
  *                   on stderr, and not on the rails as plain -L has them).  Not with -t, -p, -q or -w.
+ *     -U factor[,lead[,hang]]  EXTENSION, with -L: FIND THE BURSTS (adsb_bursts_device).  The level call also writes the envelope, one float
+ *                   per 28 power samples, into a device array of this program's; threshold = factor * the median bin's lower edge
+ *                   (adsb_level_percentile at 0.5); behind -L's report a line `bursts B threshold T lead L hang H`, then a line per burst
+ *                   `FIRST END HOT PEAK`: power samples [FIRST, END), its hot runs, its largest envelope float.  lead and hang (runs of 28
+ *                   power samples kept before the first and behind the last hot run) default to 2 and 1468.  WIDENED from the 2 and 4
+ *                   first meant: with hang 4 the pipeline fixture (tests/burst_cases.py) loses EVERY planted frame, because a decode call
+ *                   keeps the reference's end-of-file horizon -- deqframe runs only once 40 980 power samples are in (air.c:94-99), so a
+ *                   piece shorter than that decodes nothing; 1468 runs are 41 104 power samples behind the last hot run.  The values
+ *                   rest on that ONE fixture, not on a measurement of live traffic.  Every flavour -L reads; not with -I.
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -199,7 +208,8 @@ static void usage(void)
     printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n");
     printf("        adsbdec_amd_cli [-q type] [-d gpu] -W out.pw -f filename\n");
     printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -f filename\n");
-    printf("        adsbdec_amd_cli [-d gpu] -L -I ms -f filename\n\n");
+    printf("        adsbdec_amd_cli [-d gpu] -L -I ms -f filename\n");
+    printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -U factor[,lead[,hang]] -f filename\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
     printf("\t-b : output binary beast format\n");
@@ -224,6 +234,9 @@ static void usage(void)
     printf("\t-I ms : (extension) with -L on a uint16 file: the levels over time.  A line per window of ms milliseconds (10 000 power samples\n");
     printf("\t     each, rounded down to a multiple of 28): its start in seconds, median, 99.9th percentile and peak, the three rail counters;\n");
     printf("\t     then -L's report of the whole.  The file is read in pieces of bounded size: a FIFO works; not with -t, -p, -q or -w\n");
+    printf("\t-U factor[,lead[,hang]] : (extension) with -L: find the bursts.  Behind the report a line `bursts B threshold T lead L hang H` and a\n");
+    printf("\t     line `first end hot peak` per burst, in power samples: the envelope (a float per 28 power samples) gated at factor x the\n");
+    printf("\t     median, lead (default 2) and hang (default 1468: a piece must outlast the decoder's 40 980-sample horizon) runs kept; not with -I\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
@@ -726,7 +739,48 @@ static void print_level_report(const adsb_level_report *rep)
     }
 }
 
-static int run_level(const char *filename, int device, int kind, int fmt)
+struct burst_opts { /* -U: factor 0 = no gate */
+    double factor;
+    uint32_t lead, hang;
+};
+
+/* -L -U: the gate behind the report.  env: the device array of ceil(m / 28) floats the level call wrote. */
+static int print_bursts(adsb_decoder *dec, const adsb_level_report *rep, const float *d_env, uint64_t m, const struct burst_opts *u)
+{
+    const size_t n_env = (size_t)((m + 27) / 28);
+    const float median = adsb_level_percentile(rep, 0.5);
+    if (median < 0) { /* (no sign-clear sample at all: nothing to take a median of) */
+        printf("bursts 0 threshold none lead %u hang %u\n", u->lead, u->hang);
+        return 0;
+    }
+    const float threshold = (float)(u->factor * median);
+    size_t cap = 4096;
+    adsb_burst *tab = (adsb_burst *)malloc(cap * sizeof *tab);
+    long b = tab ? adsb_bursts_device(dec, d_env, n_env, threshold, u->lead, u->hang, tab, cap) : -1;
+    if (tab && b > (long)cap) { /* grown once: B does not change between two calls on the same array */
+        free(tab);
+        cap = (size_t)b;
+        tab = (adsb_burst *)malloc(cap * sizeof *tab);
+        b = tab ? adsb_bursts_device(dec, d_env, n_env, threshold, u->lead, u->hang, tab, cap) : -1;
+    }
+    if (!tab) {
+        fprintf(stderr, "out of memory for a table of %zu bursts\n", cap);
+        return 255;
+    }
+    if (b < 0) {
+        fprintf(stderr, "adsb_bursts_device() failed: %s\n", adsb_last_error(dec));
+        return 255;
+    }
+    printf("bursts %ld threshold %.9g lead %u hang %u\n", b, (double)threshold, u->lead, u->hang);
+    for (long i = 0; i < b; i++) {
+        const uint64_t first = 28ull * tab[i].begin, end = 28ull * tab[i].end < m ? 28ull * tab[i].end : m;
+        printf("%llu %llu %u %.9g\n", (unsigned long long)first, (unsigned long long)end, tab[i].hot, (double)tab[i].peak);
+    }
+    free(tab);
+    return 0;
+}
+
+static int run_level(const char *filename, int device, int kind, int fmt, const struct burst_opts *u)
 {
     const int fd = open(filename, O_RDONLY);
     struct stat sb;
@@ -757,7 +811,12 @@ static int run_level(const char *filename, int device, int kind, int fmt)
                 kind == 2 ? "not a whole 12-byte group of packed samples" : kind <= 1 ? "the reference reads four samples at a time" : "not a whole sample");
     long got;
     const char *call = "adsb_level_host";
-    if (kind == 0) {
+    /* -U: the envelope too, into a device array of this program's (a real capture: from HBM as well, where the envelope has to be) */
+    const int gate = u->factor > 0;
+    const uint64_t m_guess = kind <= 2 ? 2 * (uint64_t)(n / 4) : n;
+    const size_t env_cap = gate ? (size_t)((m_guess + 27) / 28) : 0;
+    float *d_env = NULL;
+    if (kind == 0 && !gate) {
         got = adsb_level_host(dec, (const uint16_t *)buf, n, rep, NULL, 0);
     } else {
         if (hipSetDevice(device < 0 ? 0 : device) != hipSuccess || (used && hipMalloc(&d_in, used) != hipSuccess) ||
@@ -765,20 +824,33 @@ static int run_level(const char *filename, int device, int kind, int fmt)
             fprintf(stderr, "cannot bring the file's %zu bytes to the device\n", used);
             return 255;
         }
-        if (kind == 1)
-            call = "adsb_level_device_as", got = adsb_level_device_as(dec, fmt, d_in, n, rep, NULL, 0);
+        if (env_cap && hipMalloc((void **)&d_env, env_cap * sizeof(float)) != hipSuccess) {
+            fprintf(stderr, "cannot allocate the envelope's %zu floats on the device\n", env_cap);
+            return 255;
+        }
+        if (kind == 0)
+            call = "adsb_level_device", got = adsb_level_device(dec, d_in, n, rep, d_env, env_cap);
+        else if (kind == 1)
+            call = "adsb_level_device_as", got = adsb_level_device_as(dec, fmt, d_in, n, rep, d_env, env_cap);
         else if (kind == 2)
-            call = "adsb_level_device_packed", got = adsb_level_device_packed(dec, d_in, n, rep, NULL, 0);
+            call = "adsb_level_device_packed", got = adsb_level_device_packed(dec, d_in, n, rep, d_env, env_cap);
         else if (kind == 3)
-            call = "adsb_level_device_iq", got = adsb_level_device_iq(dec, fmt, d_in, n, rep, NULL, 0);
+            call = "adsb_level_device_iq", got = adsb_level_device_iq(dec, fmt, d_in, n, rep, d_env, env_cap);
         else
-            call = "adsb_level_device_power", got = adsb_level_device_power(dec, d_in, n, rep, NULL, 0);
+            call = "adsb_level_device_power", got = adsb_level_device_power(dec, d_in, n, rep, d_env, env_cap);
     }
     if (got < 0) {
         fprintf(stderr, "%s() failed: %s\n", call, adsb_last_error(dec));
         return 255;
     }
     print_level_report(rep);
+    if (gate) {
+        const int rc = print_bursts(dec, rep, d_env, (uint64_t)got, u);
+        if (rc) {
+            fflush(stdout);
+            return rc;
+        }
+    }
     fflush(stdout);
     fflush(stderr);
     if (getenv("ADSB_CLI_CLEAN_EXIT"))
@@ -886,6 +958,8 @@ int main(int argc, char **argv)
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
     int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, level = 0, c;
+    const char *burst_arg = NULL; /* -U: -L's gate, factor[,lead[,hang]] */
+    struct burst_opts burst = {0, 2, 1468};
     const char *interval_arg = NULL; /* -I: -L's windows, in milliseconds */
     double interval_ms = 0;
     long stype = 5; /* -t: ADSB_FMT_RAW */
@@ -895,7 +969,7 @@ int main(int argc, char **argv)
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -967,6 +1041,22 @@ int main(int argc, char **argv)
             interval_arg = optarg;
             break;
         }
+        case 'U': { /* factor[,lead[,hang]]: a finite factor above 0, whole numbers up to 2^30; anything else leaves factor 0 */
+            char *end;
+            burst_arg = optarg;
+            burst.factor = strtod(optarg, &end);
+            int ok = end != optarg && burst.factor > 0 && burst.factor <= 1.7976931348623157e308;
+            uint32_t *field[2] = {&burst.lead, &burst.hang};
+            for (int i = 0; ok && i < 2 && *end == ','; i++) {
+                const char *at = end + 1;
+                const unsigned long long v = strtoull(at, &end, 10);
+                ok = end != at && *at >= '0' && *at <= '9' && v <= (1ull << 30);
+                *field[i] = (uint32_t)v;
+            }
+            if (!ok || *end)
+                burst.factor = 0;
+            break;
+        }
         case 't': {
             char *end;
             stype = strtol(optarg, &end, 10);
@@ -1007,6 +1097,17 @@ int main(int argc, char **argv)
                             "already exact on its own\n", stype_arg ? "-t" : packed ? "-p" : qtype_arg ? "-q" : "-w");
         else
             fprintf(stderr, "-I %s: the windows' length in milliseconds, a number above 0\n", interval_arg);
+        return 1;
+    }
+    if (burst_arg && (!level || interval_arg || !(burst.factor > 0))) {
+        /* -U gates the envelope of -L's one call: refused before any GPU call (-L's own refusals, -G, -B and -W among them, stay in front) */
+        if (!level)
+            fprintf(stderr, "-U is not supported without -L: it gates the envelope the level report's call writes%s\n",
+                    ndev ? " (and not with -G)" : listfile ? " (and not with -B)" : export_path ? " (and not with -W)" : "");
+        else if (interval_arg)
+            fprintf(stderr, "-U is not supported with -I: the windows share one envelope piece by piece, and joining bursts across pieces is the caller's\n");
+        else
+            fprintf(stderr, "-U %s: factor[,lead[,hang]] -- a finite factor above 0, lead and hang whole numbers of runs up to 2^30\n", burst_arg);
         return 1;
     }
     if (qtype_arg && qtype == ADSB_FMT_INT8_IQ && (stype_arg || packed || ndev || listfile || power || export_path)) {
@@ -1102,7 +1203,7 @@ int main(int argc, char **argv)
         }
         if (interval_arg)
             return run_level_windows(filename, device, interval_ms);
-        return run_level(filename, device, converted ? 1 : packed ? 2 : iq ? 3 : power ? 4 : 0, iq ? (int)qtype : (int)stype);
+        return run_level(filename, device, converted ? 1 : packed ? 2 : iq ? 3 : power ? 4 : 0, iq ? (int)qtype : (int)stype, &burst);
     }
     if (export_path) {
         install_signals();

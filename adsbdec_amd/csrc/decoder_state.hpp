@@ -10,6 +10,7 @@
 //   decoder_level.hip      the level calls (adsb_level_*): a capture's power samples reduced to a report and an envelope
 //   decoder_level_batch.hip  the batch level calls (adsb_level_batch_*): the reports of N captures by one launch per sub-batch
 //   decoder_level_windows.hip  the window form (adsb_level_windows*): the reports of K consecutive windows of one stream
+//   decoder_bursts.hip     the gate behind the envelope (adsb_bursts_*): an envelope's bursts as an ordered table
 //   decoder_stage.hip      the staging steps every family calls: samples into unpacked, batch_in, batch_land, batch_unpacked, win_buf, pow_buf
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
@@ -327,6 +328,11 @@ struct adsb_decoder {
     adsb::Table level_tab;
     adsb::Totals<unsigned long long> level_batch;
     int level_batch_blocks = 0; // adsb_debug_set_level_batch_blocks: 0, or the most workgroups a batch level launch may have
+    // the gate behind the envelope (adsb_bursts_*, decoder_bursts.hip; burst.h): every tile's summary and, behind them, its combine
+    // row; B as the combine leaves it and its pinned twin; the device table of min(B, cap) records.  Grown to the largest call seen.
+    adsb::Buf<uint32_t> burst_scratch;
+    adsb::Totals<uint32_t> burst_total;
+    adsb::Buf<uint32_t> burst_tab;
 
     int fail(const char *fmt, ...)
     {

@@ -66,6 +66,33 @@ void adsb_level_add(adsb_level_report *sum, const adsb_level_report *part)
         sum->hist[k] += part->hist[k];
 }
 
+// The lower edge of the bin that holds the q-quantile of a report's sign-clear samples (adsbdec_amd/levels.py percentile): the first
+// bin at which the running count reaches ceil(q total), and one sample at least.  -1: NULL, an empty histogram, q outside [0, 1].
+float adsb_level_percentile(const adsb_level_report *r, double q)
+{
+    constexpr unsigned bins = sizeof r->hist / sizeof r->hist[0];
+    if (!r || !(q >= 0.0 && q <= 1.0))
+        return -1.0f;
+    uint64_t total = 0, run = 0;
+    for (unsigned k = 0; k < bins; k++)
+        total += r->hist[k];
+    if (total == 0)
+        return -1.0f;
+    const double t = q * (double)total; // (numpy's q * total, a double product, then ceil)
+    uint64_t need = (uint64_t)t;
+    if ((double)need < t)
+        need++;
+    if (need == 0)
+        need = 1;
+    unsigned k = 0;
+    while (k < bins - 1 && (run += r->hist[k]) < need)
+        k++;
+    const uint32_t edge = k << 20;
+    float f;
+    std::memcpy(&f, &edge, sizeof f);
+    return f;
+}
+
 // The host side of the decoder*.hip units is built with -mavx2 (adsbdec_amd/_build.py says why); this file is not.  adsb_create asks here,
 // before anything else, whether the host can run it: a C string to show, or NULL.
 const char *adsb_host_cpu_refusal(void)

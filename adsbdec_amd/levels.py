@@ -142,3 +142,59 @@ def level_windows(a, x, edges) -> tuple:
         r["rail_lo"], r["rail_hi"], r["over"] = int((own == 0).sum()), int((own == 4095).sum()), int((own > 4095).sum())
         reports.append(r)
     return reports, level_report(a[e[0]:e[-1]])["env"]
+
+
+# ---- the gate behind the envelope: an envelope's bursts (adsb_bursts_device, csrc/burst_kernel.hip) ----
+BURST_DTYPE = np.dtype([("begin", "<u4"), ("end", "<u4"), ("hot", "<u4"), ("peak", "<f4")])   # adsb_burst; [begin, end) in runs of 28
+BURST_RUN_LIMIT = 1 << 30     # the most lead or hang may be
+
+
+def _burst_args(env, threshold, lead, hang):
+    env = np.ascontiguousarray(env)
+    if env.dtype != np.dtype("<f4"):
+        raise ValueError(f"an envelope is float32, not {env.dtype}")
+    t = np.array([threshold], dtype="<f4")
+    tb = int(t.view("<u4")[0])
+    if np.isnan(t[0]) or tb >> 31:
+        raise ValueError("the threshold is a float with the sign bit clear, and no NaN")
+    lead, hang = int(lead), int(hang)
+    if not (0 <= lead <= BURST_RUN_LIMIT and 0 <= hang <= BURST_RUN_LIMIT):
+        raise ValueError("lead and hang lie in [0, 2^30]")
+    b = env.reshape(-1).view("<u4")
+    return np.where(b >> 31, np.uint32(0), b).astype(np.uint32), tb, lead, hang
+
+
+def bursts(env, threshold, lead, hang) -> np.ndarray:
+    """The bursts of an envelope of R floats: the statement adsb_bursts_device is held to, record for record.
+
+    u[r] = the bit pattern of env[r] if its sign bit is clear, else 0 (the envelope's own rule, level_report); run r is HOT iff
+    u[r] >= bits(threshold), compared as unsigned 32-bit integers -- NaN and Inf are hot at any finite threshold, +0.0 makes every
+    run hot, no float is compared.  join = lead + hang + 1: the hot runs in ascending order, cut wherever two neighbours differ by
+    more than join; a piece with first hot run s and last hot run e is one burst
+        begin = max(0, s - lead)    end = min(R, e + hang + 1), exclusive    hot = the hot runs in [s, e]
+        peak  = the float whose bits are the maximum of u over them
+    -> a structured array (BURST_DTYPE), ascending; two neighbours always have a run between them."""
+    u, tb, lead, hang = _burst_args(env, threshold, lead, hang)
+    r = u.size
+    h = np.flatnonzero(u >= np.uint32(tb)).astype(np.int64)
+    out = np.zeros(0, dtype=BURST_DTYPE)
+    if h.size == 0:
+        return out
+    cut = np.flatnonzero(np.diff(h) > lead + hang + 1) + 1
+    first = np.concatenate(([0], cut))
+    last = np.concatenate((cut, [h.size])) - 1
+    out = np.zeros(first.size, dtype=BURST_DTYPE)
+    out["begin"] = np.maximum(0, h[first] - lead)
+    out["end"] = np.minimum(r, h[last] + hang + 1)
+    out["hot"] = last - first + 1
+    out["peak"] = np.maximum.reduceat(u[h], first).astype("<u4").view("<f4")
+    return out
+
+
+def burst_samples(bursts, M: int) -> np.ndarray:
+    """The bursts of an envelope of M power samples, in power samples: an (B, 2) int64 array of [28 begin, min(28 end, M))."""
+    b = np.asarray(bursts)
+    out = np.empty((b.size, 2), dtype=np.int64)
+    out[:, 0] = RUN * b["begin"].astype(np.int64)
+    out[:, 1] = np.minimum(RUN * b["end"].astype(np.int64), int(M))
+    return out

@@ -338,6 +338,10 @@ int adsb_batch_unpacked_copy(adsb_decoder *d, size_t capture, uint16_t *dst_u16,
  * between two calls on ONE handle, so a test compares both settings on the same device buffers.  The launches of adsb_level_windows
  * are capped by it too (a wave then crosses many windows).  0, or -1 (blocks < 0). */
 int adsb_debug_set_level_batch_blocks(adsb_decoder *d, int blocks);
+/* adsb_bursts_*: T, the consecutive runs one workgroup of the gate's kernels takes (csrc/burst.h).  With a 16-byte aligned envelope tile
+ * t is the runs [t T, (t + 1) T); an envelope p floats behind a 16-byte boundary has its seams p runs earlier.  What happens at a
+ * seam -- a burst across it, a join or a split exactly there, empty tiles between two hot ones -- is what the tests aim at. */
+uint32_t adsb_burst_tile_runs(void);
 
 /* ---- a batch over the devices of adsb_multi (adsb_multi_decode_batch_*; csrc/multi.cpp), without a device ------------------------
  * The plan, a pure function: n_captures captures of n[i] samples over n_workers workers.  Worker w gets the captures

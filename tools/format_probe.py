@@ -9,6 +9,7 @@ comparison interleaved.
     python tools/format_probe.py --export-batch [--reps 20] [--out profiles/r20_export_batch.txt] [--ab path/to/parent/libadsbdec_amd.so]   # export_batch_probe()
     python tools/format_probe.py --level [--reps 20] [--out profiles/r23_level.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_probe()
     python tools/format_probe.py --level-windows [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/r27_level_windows.txt]   # level_windows_probe()
+    python tools/format_probe.py --bursts [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/rNN_bursts.txt]   # bursts_probe(): NN is the next free round
     python tools/format_probe.py --level-batch [--reps 20] [--out profiles/r26_level_batch.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_batch_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
@@ -1182,6 +1183,142 @@ def level_windows_probe(L, reps, lines, parent):
         lines.append("#     not measured in this run: no --ab parent library given")
 
 
+def bursts_probe(L, reps, lines, parent):
+    """The gate behind the envelope (burst_kernel.hip, adsb_bursts_device) on the envelope of the benchmark's 256 Mi samples (about 4.8 M
+    runs), every comparison interleaved in this one process, wall time of the calls (each ends with the table in HOST memory):
+    (a) at three densities of hot runs, beside the same gate written in torch on the device and beside a copy of the envelope to the
+    host and levels.bursts; (b) adsb_level_device with the envelope, alone and followed by the gate; (c) adsb_level_device of this tree
+    beside the library built from the parent commit (--ab).  Before anything is timed every side's table is levels.bursts's."""
+    import numpy as np
+    from adsbdec_amd import levels
+    t, _ = make_workload(torch, N, seed=1)
+    torch.cuda.synchronize()                               # (the library's streams do not wait for torch's)
+    M = N // 2
+    ke = -(-M // 28)
+    env = torch.zeros(ke, dtype=torch.float32, device="cuda")
+    d = capi.Decoder()
+    h = d._h
+    rep1 = capi.LevelReport()
+    steps = 3
+
+    def level(B=L, hh=h):
+        assert B.adsb_level_device(hh, t.data_ptr(), N, C.byref(rep1), env.data_ptr(), ke) == M
+    level()
+    median = L.adsb_level_percentile(C.byref(rep1), 0.5)
+    threshold = float(np.float32(capi.Decoder.BURST_FACTOR * median))
+    tb = int(np.array([threshold], dtype="<f4").view("<u4")[0])
+    big = float(np.float32(1.0e6 * max(median, 1.0)))
+    g = torch.Generator(device="cuda").manual_seed(1)
+    dense = env.clone()                                    # 10 % of the runs hot, in stretches of 43 runs (a long frame is 1200 power samples)
+    starts = torch.randint(0, ke - 43, (ke // 430,), generator=g, device="cuda")
+    dense[(starts[:, None] + torch.arange(43, device="cuda")[None, :]).flatten()] = big
+    second = env.clone().clamp_(max=threshold / 2)         # every second run hot, the others below the threshold
+    second[::2] = big
+    table = np.zeros(ke // 2 + 8, dtype=levels.BURST_DTYPE)
+
+    def lib(e, lead, hang):
+        b = L.adsb_bursts_device(h, e.data_ptr(), ke, threshold, lead, hang, table.ctypes.data, table.size)
+        assert 0 <= b <= table.size
+        return table[:b]
+
+    def torch_gate(e, lead, hang):
+        """What a caller has today: elementwise kernels, two nonzero() (each waits for the device), a segmented maximum, five copies."""
+        u = e.view(torch.int32).clamp(min=0)               # (sign set -> 0; sign-clear patterns compare as signed integers do)
+        hot = torch.nonzero(u >= tb).flatten()
+        if hot.numel() == 0:
+            return np.zeros(0, dtype=levels.BURST_DTYPE)
+        cut = torch.nonzero(hot[1:] - hot[:-1] > lead + hang + 1).flatten() + 1
+        zero, n = torch.zeros(1, dtype=cut.dtype, device="cuda"), torch.full((1,), hot.numel(), dtype=cut.dtype, device="cuda")
+        first, last = torch.cat([zero, cut]), torch.cat([cut, n]) - 1
+        out = np.zeros(first.numel(), dtype=levels.BURST_DTYPE)
+        out["begin"] = (hot[first] - lead).clamp(min=0).cpu().numpy()
+        out["end"] = (hot[last] + hang + 1).clamp(max=ke).cpu().numpy()
+        out["hot"] = (last - first + 1).cpu().numpy()
+        out["peak"] = torch.segment_reduce(e[hot], "max", lengths=last - first + 1).cpu().numpy()    # (no NaN in these envelopes)
+        return out
+
+    def host(e, lead, hang):
+        return levels.bursts(e.cpu().numpy(), threshold, lead, hang)
+
+    def rotate(sides):
+        names = list(sides)
+        wall = {k_: [] for k_ in names}
+        for r in range(reps):
+            for name in names[r % len(names):] + names[:r % len(names)]:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    sides[name]()
+                wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        return names, wall
+
+    def table_of(names, wall, base):
+        for name in names:
+            q = statistics.quantiles(wall[name], n=4)
+            rr = [a_ / b for a_, b in zip(wall[name], wall[base])]
+            qr = statistics.quantiles(rr, n=4)
+            lines.append(f"    {name:46s} {med(wall[name]):9.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med(rr):.4f} ({qr[0]:.4f} .. {qr[2]:.4f})")
+            print(lines[-1], flush=True)
+
+    # (a)
+    lines += [f"# (a) adsb_bursts_device on an envelope of {ke} runs, threshold {threshold:.9g} ({capi.Decoder.BURST_FACTOR:g} x the median {median:.9g}); {reps} rounds x {steps} calls",
+              "#     per side, the sides in rotation; every side ends with its table in host memory, and all three gave levels.bursts's table before",
+              "#     anything was timed.  sparse: the benchmark workload's own envelope; dense: 10 % of its runs made hot in stretches of 43; second:",
+              "#     every second run hot with lead = hang = 0, the most bursts there can be.",
+              "#   side                                              call ms (q1 .. q3)             / adsb_bursts_device (median of rounds, q1 .. q3)"]
+    for what, e, lead, hang in (("sparse, lead 2 hang 4", env, 2, 4), ("sparse, lead 2 hang 1468 (the defaults)", env, 2, capi.Decoder.BURST_HANG),
+                                ("dense 10 %, lead 2 hang 4", dense, 2, 4), ("every second run hot, lead 0 hang 0", second, 0, 0)):
+        want = host(e, lead, hang)
+        for side in (lib, torch_gate):
+            got = side(e, lead, hang)
+            assert got.size == want.size and all(np.array_equal(got[k_], want[k_]) for k_ in ("begin", "end", "hot")), (what, side.__name__)
+            assert np.array_equal(got["peak"].view(np.uint32), want["peak"].view(np.uint32)), (what, side.__name__, "peak")
+        lines.append(f"#   {what}: B = {want.size}, hot runs = {int(want['hot'].sum())}")
+        names, wall = rotate({"adsb_bursts_device": lambda: lib(e, lead, hang), "adsb_bursts_device again (the A/A)": lambda: lib(e, lead, hang),
+                              "the gate in torch on the device": lambda: torch_gate(e, lead, hang),
+                              "envelope to the host, levels.bursts": lambda: host(e, lead, hang)})
+        table_of(names, wall, names[0])
+        table.view(np.uint8)[:] = 0xA5                     # ... and behind the timed calls, into a poisoned table: still that table
+        got = lib(e, lead, hang)
+        assert got.tobytes() == want.tobytes() and (table[want.size:].view(np.uint8) == 0xA5).all(), what
+    # (b)
+    lines += ["#", "# (b) adsb_level_device with the envelope on the 256 Mi samples, alone and followed by the gate (the defaults) on what it wrote"]
+
+    def both():
+        level()
+        lib(env, capi.Decoder.BURST_LEAD, capi.Decoder.BURST_HANG)
+    names, wall = rotate({"adsb_level_device": level, "adsb_level_device again (the A/A)": level, "adsb_level_device + adsb_bursts_device": both})
+    lines.append("#   side                                              call ms (q1 .. q3)             / adsb_level_device (median of rounds, q1 .. q3)")
+    table_of(names, wall, names[0])
+    # (c)
+    lines += ["#", "# (c) adsb_level_device of this tree beside the library built from the parent commit, loaded into this process: the existing call did not move"]
+    if parent:
+        B = C.CDLL(parent)
+        for name in ("adsb_create", "adsb_level_device"):
+            fn = getattr(B, name)
+            fn.restype, fn.argtypes = capi.SYMBOLS[name]
+        assert not hasattr(B, "adsb_bursts_device"), "the --ab library is not the parent's: it has the gate"
+        cfg = capi.make_config()
+        hh = B.adsb_create(C.byref(cfg))
+        assert hh, parent
+        level()
+        want = bytes(rep1)
+        level(B, hh)
+        assert bytes(rep1) == want, "the parent's library reports other levels"
+        names, wall = rotate({"adsb_level_device (tree)": level, "adsb_level_device (tree again: the A/A)": level,
+                              "adsb_level_device (parent commit)": lambda: level(B, hh)})
+        lines.append("#   side                                              call ms (q1 .. q3)             / tree (median of rounds, q1 .. q3)")
+        table_of(names, wall, names[0])
+    else:
+        lines.append("#     not measured in this run: no --ab parent library given")
+
+
+def next_round(stem):
+    """profiles/rNN_<stem>.txt with the next free round number."""
+    import re
+    seen = [int(m.group(1)) for m in (re.match(r"r(\d+)_", f) for f in os.listdir(os.path.join(ROOT, "profiles"))) if m]
+    return os.path.join(ROOT, "profiles", f"r{max(seen, default=0) + 1}_{stem}.txt")
+
+
 def real_kernel_ab(builds, rounds, lines):
     """(c) the existing real-sample kernel across the change: tools/ab_interleaved.py in a process of its own (it dlopens every build
     side by side), the first build listed twice for the A/A."""
@@ -1211,7 +1348,19 @@ def main():
     ap.add_argument("--level-windows", action="store_true", help="the window form of the level report (adsb_level_windows) beside adsb_level_device instead: profiles/r27_level_windows.txt; --ab: the parent commit's library, for (c)")
     ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB", help="with --level or --level-batch: a build of the library with another accumulation, flush or grid, measured beside the tree's")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bursts", action="store_true", help="the gate behind the envelope (adsb_bursts_device) beside a torch gate and a host gate instead: profiles/rNN_bursts.txt with the next free NN; --ab: the parent commit's library, for (c)")
     a = ap.parse_args()
+    if a.bursts:
+        a.out = a.out or next_round("bursts")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --bursts: the gate behind the envelope (burst_kernel.hip, adsb_bursts_device), one process,",
+                 f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; warm-up first (every side runs once, checked, before its rounds).",
+                 "# The samples are the benchmark's: tools/gen_signal.py make_workload, 256 Mi samples, seed 1; the envelope is adsb_level_device's.",
+                 "# Wall time of the calls through ctypes / torch; every side waits for its kernels and leaves its table in host memory.", "#"]
+        bursts_probe(capi.load(), a.reps, lines, a.ab)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.level_windows:
         a.out = a.out or os.path.join(ROOT, "profiles", "r27_level_windows.txt")
         torch.cuda.set_device(0)
