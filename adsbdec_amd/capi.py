@@ -150,6 +150,14 @@ SYMBOLS = {
     "adsb_reset": (C.c_int, [C.c_void_p]),
     "adsb_set_long_stream": (C.c_int, [C.c_void_p, C.c_int]),
     "adsb_get_wraps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "adsb_set_flush": (C.c_int, [C.c_void_p, C.c_int]),
+    "adsb_get_flush": (C.c_int, [C.c_void_p]),
+    "adsb_resolver_finish_flush": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "adsb_batch_layout_flush": (C.c_long, [C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(BatchSegment),
+                                           C.c_size_t, C.POINTER(BatchLaunch), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "adsb_batch_resolve_flush": (C.c_long, [C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(Candidate),
+                                            C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(Frame), C.c_size_t,
+                                            C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     "adsb_multi_set_long_streams": (C.c_int, [C.c_void_p, C.c_int]),
     "adsb_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "adsb_push_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -453,7 +461,7 @@ def make_config(df18: bool = False, device: int = -1, collect_stats: bool = Fals
 class Decoder:
     """One stream (== the statics of air.c / demod.c / valid.c).  Keywords: make_config."""
 
-    def __init__(self, long_stream: bool = False, **cfg_kw):
+    def __init__(self, long_stream: bool = False, flush: bool = False, **cfg_kw):
         L = load()
         cfg = make_config(**cfg_kw)
         self._L = L
@@ -463,6 +471,8 @@ class Decoder:
             raise AdsbError("adsb_create failed: " + (L.adsb_last_error(None) or b"").decode())
         if long_stream:
             self.set_long_stream(True)
+        if flush:
+            self.set_flush(True)
         self._out = C.POINTER(Frame)()          # decode_device_raw's result pointer and its reference, made once
         self._out_ref = C.byref(self._out)
         self._decode_device = L.adsb_decode_device
@@ -488,6 +498,17 @@ class Decoder:
     def set_long_stream(self, on: bool = True):
         """adsb_set_long_stream: streams of 2^32 samples and more (fresh or reset handle, before the first push)."""
         self._check(self._L.adsb_set_long_stream(self._h, int(bool(on))), "adsb_set_long_stream")
+
+    def set_flush(self, on: bool = True):
+        """adsb_set_flush: decode a capture to its last sample -- every decode call, batch call and finished stream of the handle
+        then returns what the reference returns for the capture's silent twin (fresh or reset handle, before the first push;
+        sticky across reset)."""
+        self._check(self._L.adsb_set_flush(self._h, int(bool(on))), "adsb_set_flush")
+
+    @property
+    def flush(self) -> bool:
+        """adsb_get_flush."""
+        return self._L.adsb_get_flush(self._h) == 1
 
     def wraps(self):
         """(wraps of the reference's sample counter in the current stream, offsets that went through the seam kernel)."""
@@ -1129,7 +1150,9 @@ class Decoder:
 
     def bursts(self, x: np.ndarray, q: float = 0.5, factor: float = BURST_FACTOR, lead: int = BURST_LEAD, hang: int = BURST_HANG):
         """A uint16 capture in host memory -> (every burst of its envelope, B): level() with the envelope, the threshold
-        float32(factor * percentile(hist, q)) (adsb_level_percentile), and the gate (adsb_bursts_host)."""
+        float32(factor * percentile(hist, q)) (adsb_level_percentile), and the gate (adsb_bursts_host).
+        The default hang (BURST_HANG, 1468 runs) makes every piece long enough for the reference's end-of-file horizon; pieces that go
+        to a handle with flush=True need no such length, and hang 4 is enough there."""
         rep = self.level(x, env=True)
         if rep["env"].size == 0:
             from .levels import BURST_DTYPE
@@ -1369,6 +1392,11 @@ class Resolver:
         if self._L.adsb_resolver_advance(self._h, power_samples, g_complete) != 0:
             raise AdsbError("adsb_resolver_advance failed")
 
+    def finish_flush(self, power_samples: int):
+        """adsb_resolver_finish_flush: the end of a stream of power_samples power samples on a flush handle."""
+        if self._L.adsb_resolver_finish_flush(self._h, power_samples) != 0:
+            raise AdsbError("adsb_resolver_finish_flush failed")
+
     def drain(self):
         out = []
         buf = (Frame * 4096)()
@@ -1388,18 +1416,18 @@ def _struct_dict(o):
     return {f: int(getattr(o, f)) for f, _ in o._fields_ if f != "pad"}
 
 
-def batch_layout(ns, cus: int = 0, passes: int = 0, launch_offsets: int = 0):
-    """adsb_batch_layout_ex -> (segments, launches) as lists of dicts, or None when the batch is refused (a capture of 2^32 samples).
-    launch_offsets: adsb_debug_config.batch_launch_offsets (0: the default limit of a launch)."""
+def batch_layout(ns, cus: int = 0, passes: int = 0, launch_offsets: int = 0, flush: bool = False):
+    """adsb_batch_layout_flush -> (segments, launches) as lists of dicts, or None when the batch is refused (a capture of 2^32 samples).
+    launch_offsets: adsb_debug_config.batch_launch_offsets (0: the default limit of a launch); flush: as a flush handle lays it out."""
     L = load()
     k = len(ns)
     n = (C.c_size_t * max(1, k))(*[int(v) for v in ns])
     nl = C.c_size_t(0)
-    ns_ = L.adsb_batch_layout_ex(k, n, cus, passes, launch_offsets, None, 0, None, 0, C.byref(nl))
+    ns_ = L.adsb_batch_layout_flush(k, n, cus, passes, launch_offsets, int(flush), None, 0, None, 0, C.byref(nl))
     if ns_ < 0:
         return None
     segs, launches = (BatchSegment * max(1, ns_))(), (BatchLaunch * max(1, nl.value))()
-    if L.adsb_batch_layout_ex(k, n, cus, passes, launch_offsets, segs, ns_, launches, nl.value, C.byref(nl)) != ns_:
+    if L.adsb_batch_layout_flush(k, n, cus, passes, launch_offsets, int(flush), segs, ns_, launches, nl.value, C.byref(nl)) != ns_:
         raise AdsbError("adsb_batch_layout failed")
     return [_struct_dict(segs[i]) for i in range(ns_)], [_struct_dict(launches[i]) for i in range(nl.value)]
 
@@ -1418,7 +1446,7 @@ def multi_batch_plan(ns, n_workers: int, batch_bytes: int = 0, packed: bool = Fa
     return [int(v) for v in rng], [int(subs[i]) for i in range(nsub + 1)]
 
 
-def batch_resolve(ns, cands, tries, cus: int = 0, passes: int = 0, launch_offsets: int = 0):
+def batch_resolve(ns, cands, tries, cus: int = 0, passes: int = 0, launch_offsets: int = 0, flush: bool = False):
     """adsb_batch_resolve_ex (launch_offsets as batch_layout): cands = list of (virtual g, pw, frame bytes) ascending, tries = uint64 (g << 2 | code) ascending ->
     (per-capture frame lists, per-capture Try/Ok tables)."""
     L = load()
@@ -1433,7 +1461,7 @@ def batch_resolve(ns, cands, tries, cus: int = 0, passes: int = 0, launch_offset
     first, st = (C.c_uint64 * (k + 1))(), (Stats * max(1, k))()
     cap = len(cands) + 1
     out = (Frame * cap)()
-    total = L.adsb_batch_resolve_ex(k, n, cus, passes, launch_offsets, arr, len(cands), t.ctypes.data_as(C.POINTER(C.c_uint64)), t.size, out, cap, first, st)
+    total = L.adsb_batch_resolve_flush(k, n, cus, passes, launch_offsets, int(flush), arr, len(cands), t.ctypes.data_as(C.POINTER(C.c_uint64)), t.size, out, cap, first, st)
     if total < 0 or total > cap:
         raise AdsbError("adsb_batch_resolve failed")
     return ([_frames_to_dicts(out[int(first[i]):int(first[i + 1])], int(first[i + 1] - first[i])) for i in range(k)],

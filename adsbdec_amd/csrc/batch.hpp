@@ -52,6 +52,11 @@ inline uint64_t batch_offsets(uint64_t n)
     const uint64_t m = 2 * (n / 4);
     return (batch_power(n) >= ADSB_APBUFFSZ && m >= ADSB_WINDOW) ? m - ADSB_WINDOW + 1 : 0;
 }
+// The same for a flush handle (adsb_set_flush; resolver.hpp stream_end): the capture counts as its silent twin, whose power samples are
+// those of its whole quads -- a trailing partial quad belongs to nothing -- and every one of them is an offset worth scanning: the
+// windows that cross the capture's end read silence there (ScanArgs::p_hi), and the twin's offsets behind it hold nothing.
+inline uint64_t batch_power_flush(uint64_t n) { return 2 * (n / 4); }
+inline uint64_t batch_offsets_flush(uint64_t n) { return batch_power_flush(n); }
 
 // One K for the segments [a, b): the K of 2 .. k_cap that computes the fewest runs -- a tile of K passes computes 252 K runs
 // whatever part of it is owned or filled, so this weighs the halo (44 runs per tile: small K loses) against the partly filled
@@ -85,7 +90,8 @@ inline uint64_t batch_launch_limit(uint64_t wanted, int split_k)
 // capture has at least one segment (an empty one when it has no offsets), in capture order; a launch's segments are consecutive.
 // false: a capture has 2^32 samples or more (*bad = its index) -- a batch has no long-stream mode.
 inline bool batch_layout(size_t n_captures, const size_t *n, int (*passes_cap)(uint64_t, void *), void *ctx, int forced_passes,
-                         uint64_t launch_offsets, std::vector<adsb_batch_segment> &segs, std::vector<adsb_batch_launch> &launches, size_t *bad)
+                         uint64_t launch_offsets, std::vector<adsb_batch_segment> &segs, std::vector<adsb_batch_launch> &launches, size_t *bad,
+                         bool flush = false)
 {
     segs.clear();
     launches.clear();
@@ -127,7 +133,7 @@ inline bool batch_layout(size_t n_captures, const size_t *n, int (*passes_cap)(u
     const uint64_t limit = batch_launch_limit(launch_offsets, split_k);
     const uint64_t split_piece = limit / batch_tile_offsets(split_k) * batch_tile_offsets(split_k);
     for (size_t i = 0; i < n_captures; i++) {
-        const uint64_t n_off = batch_offsets(n[i]), power = batch_power(n[i]);
+        const uint64_t n_off = flush ? batch_offsets_flush(n[i]) : batch_offsets(n[i]), power = flush ? batch_power_flush(n[i]) : batch_power(n[i]);
         uint64_t o = 0;
         for (;;) {
             const uint64_t rest = n_off - o;
@@ -143,6 +149,8 @@ inline bool batch_layout(size_t n_captures, const size_t *n, int (*passes_cap)(u
             sg.o_end = piece ? o + split_piece : n_off;
             segs.push_back(sg);
             // what the segment's offsets read: up to a window beyond the last one; a capture's last segment, up to its last power sample
+            // (flush: the last segment's offsets end AT the last power sample, so the first term reaches ADSB_WINDOW - 1 offsets beyond
+            // it -- silence by p_hi, whatever lies there -- and kBatchGap is counted from that reach, as it is from any other)
             const uint64_t reach = std::max(sg.o_end - sg.o_begin + (sg.o_end > sg.o_begin ? ADSB_WINDOW - 1 : 0), piece ? 0 : power - o);
             V = batch_round_up(V + reach + kBatchGap, kBatchRun);
             o = sg.o_end;
@@ -161,7 +169,7 @@ inline bool batch_layout(size_t n_captures, const size_t *n, int (*passes_cap)(u
 // segment's offsets, or out of order.
 inline bool batch_resolve(Resolver &r, size_t n_captures, const size_t *n, const adsb_batch_segment *segs, size_t n_segs,
                           const adsb_candidate *cands, size_t nc, const uint64_t *tries, size_t nt, std::vector<adsb_frame> &out,
-                          uint64_t *first, adsb_stats *stats, std::vector<adsb_candidate> &cbuf, std::vector<uint64_t> &tbuf)
+                          uint64_t *first, adsb_stats *stats, std::vector<adsb_candidate> &cbuf, std::vector<uint64_t> &tbuf, bool flush = false)
 {
     out.clear();
     size_t ci = 0, ti = 0, s = 0;
@@ -186,7 +194,8 @@ inline bool batch_resolve(Resolver &r, size_t n_captures, const size_t *n, const
         r.reset();
         if (!cbuf.empty() || !tbuf.empty()) { // (a capture without a record has no frame and no visited try)
             r.feed(cbuf.data(), cbuf.size(), tbuf.data(), tbuf.size());
-            r.advance(batch_power(n[i]), batch_offsets(n[i])); // end of file: every offset has been fed (decoder.hip process_stage)
+            const StreamEnd e = stream_end(flush, batch_power_flush(n[i]), batch_power(n[i]), batch_offsets(n[i]));
+            r.advance(e.power_samples, e.g_complete); // end of file: every offset has been fed (decoder.hip process_stage)
             const adsb_frame *fp = nullptr;
             const size_t nf = r.take(&fp);
             out.insert(out.end(), fp, fp + nf);

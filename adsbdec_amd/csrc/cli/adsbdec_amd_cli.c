@@ -59,6 +59,15 @@
  *                   keeps the reference's end-of-file horizon -- deqframe runs only once 40 980 power samples are in (air.c:94-99), so a
  *                   piece shorter than that decodes nothing; 1468 runs are 41 104 power samples behind the last hot run.  The values
  *                   rest on that ONE fixture, not on a measurement of live traffic.  Every flavour -L reads; not with -I.
+ *                   Pieces that are decoded with -E (a flush handle) need no such length: hang 4 is enough there.
+ *     -E            EXTENSION: DECODE TO THE LAST SAMPLE (adsb_set_flush).  The reference never scans the last ~41 k power samples of a
+ *                   file -- deqframe runs only once 40 980 power samples are buffered (air.c:94-99) and scans idx < len - 1200
+ *                   (demod.c:89) -- and a file below 81 960 samples decodes nothing.  With -E the packets and the table are what the
+ *                   reference prints for the file followed by 81 960 power samples of silence: every packet of the run without -E, in
+ *                   front and unchanged, then those of the file's end.  Every input kind of -f (-p, -t, -q, -w), and -B on one GPU
+ *                   (adsb_decode_batch_host* on a flush handle: the captures are read whole into memory).  A real file stays below 2^32
+ *                   samples here (a long stream has no flush).  Not with -G (the multi-GPU driver keeps the horizon), -L or -W (which
+ *                   decode nothing).
  *     -G n | a,b,c  EXTENSION: shard the file over n GPUs (or over the GPUs listed; an ordinal may repeat) through
  *                   the library's multi-GPU driver (adsb_multi_decode_file): same bytes on stdout and stderr.
  *                   With several -f (one capture each) the captures are decoded side by side, one per GPU, and
@@ -204,8 +213,8 @@ static void *locker_main(void *arg)
 static void usage(void)
 {
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
-    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-q type] [-w] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
-    printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-d gpu | -G gpus] -B listfile\n");
+    printf("usage : adsbdec_amd_cli [-a] [-m] [-b] [-p] [-t type] [-q type] [-w] [-E] [-s addr[:port] | -l addr[:port]] [-d gpu | -G gpus] -f filename [-f filename ...]\n");
+    printf("        adsbdec_amd_cli [-a] [-m] [-b] [-p] [-E] [-d gpu | -G gpus] -B listfile\n");
     printf("        adsbdec_amd_cli [-q type] [-d gpu] -W out.pw -f filename\n");
     printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -f filename\n");
     printf("        adsbdec_amd_cli [-d gpu] -L -I ms -f filename\n");
@@ -237,6 +246,10 @@ static void usage(void)
     printf("\t-U factor[,lead[,hang]] : (extension) with -L: find the bursts.  Behind the report a line `bursts B threshold T lead L hang H` and a\n");
     printf("\t     line `first end hot peak` per burst, in power samples: the envelope (a float per 28 power samples) gated at factor x the\n");
     printf("\t     median, lead (default 2) and hang (default 1468: a piece must outlast the decoder's 40 980-sample horizon) runs kept; not with -I\n");
+    printf("\t     (pieces decoded with -E, on a flush handle, have no horizon to outlast: hang 4 is enough for them)\n");
+    printf("\t-E : (extension) decode to the file's last sample: the packets and the table of the file followed by 81 960 power samples of silence,\n");
+    printf("\t     instead of leaving the last ~41 k power samples unscanned as adsbdec does (a file below 81 960 samples decodes nothing there);\n");
+    printf("\t     every input kind of -f, and -B on one GPU; a real file below 2^32 samples; not with -G, -L or -W\n");
     printf("\t-G n | a,b,.. : (extension) shard the file over n GPUs / the GPUs listed; several -f: one capture per GPU,\n");
     printf("\t     packets of capture k written to <file k>.avr | .mlat | .beast\n");
     printf("\t-B listfile : (extension) a batch of captures, one path per line of listfile (any number; empty lines skipped):\n");
@@ -559,6 +572,72 @@ static size_t read_full(int fd, void *buf, size_t want)
         got += (size_t)k;
     }
     return got;
+}
+
+/* -B -E: the captures of the list, read whole into memory, through ONE batch call of a flush handle on one GPU (adsb_set_flush +
+ * adsb_decode_batch_host / _host_packed); packets and tables go where run_batch_list puts them.  The multi-GPU driver has no flush. */
+static int run_batch_list_flush(const adsb_config *cfg, char **paths, size_t n_captures, int packed, int outformat)
+{
+    static const char *ext[3] = {"avr", "mlat", "beast"};
+    void **buf = (void **)calloc(n_captures + 1, sizeof *buf);
+    size_t *n = (size_t *)calloc(n_captures + 1, sizeof *n);
+    uint64_t *first = (uint64_t *)calloc(n_captures + 1, sizeof *first);
+    adsb_stats *st = (adsb_stats *)calloc(n_captures + 1, sizeof *st);
+    if (!buf || !n || !first || !st) {
+        fprintf(stderr, "out of memory for the results of %zu captures\n", n_captures);
+        return 255;
+    }
+    for (size_t k = 0; k < n_captures; k++) {
+        struct stat sb;
+        const int fd = open(paths[k], O_RDONLY);
+        if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+            fprintf(stderr, "%s: cannot read the capture: %s\n", paths[k], fd < 0 ? strerror(errno) : "not a regular file");
+            return 255;
+        }
+        const size_t bytes = (size_t)sb.st_size;
+        buf[k] = malloc(bytes ? bytes : 1);
+        if (!buf[k]) {
+            fprintf(stderr, "%s: out of memory for %zu bytes\n", paths[k], bytes);
+            return 255;
+        }
+        const size_t got = read_full(fd, buf[k], bytes);
+        close(fd);
+        n[k] = packed ? got / 12 * 8 : got / 2; /* (a trailing odd byte, or partial group, is not decoded: as with -f) */
+    }
+    adsb_decoder *dec = adsb_create(cfg);
+    if (!dec) {
+        fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
+        return 255;
+    }
+    const adsb_frame *fr = NULL;
+    int rc = 0;
+    if (adsb_set_flush(dec, 1) != 0 ||
+        (packed ? adsb_decode_batch_host_packed(dec, n_captures, (const void *const *)buf, n, &fr, first, st)
+                : adsb_decode_batch_host(dec, n_captures, (const uint16_t *const *)buf, n, &fr, first, st)) < 0) {
+        fprintf(stderr, "the batch decode failed: %s\n", adsb_last_error(dec));
+        rc = 255;
+    }
+    for (size_t k = 0; k < n_captures && rc == 0; k++) {
+        char path[4096];
+        if ((size_t)snprintf(path, sizeof path, "%s.%s", paths[k], ext[outformat]) >= sizeof path) {
+            fprintf(stderr, "%s: the name of its .%s file is longer than %zu bytes\n", paths[k], ext[outformat], sizeof path - 1);
+            rc = 1;
+            break;
+        }
+        const long nf = (long)(first[k + 1] - first[k]);
+        FILE *out = fopen(path, "wb");
+        if (!out || write_frames_file(out, fr + first[k], nf, outformat) != 0 || fclose(out) != 0) {
+            fprintf(stderr, "%s: cannot write\n", path);
+            rc = 1;
+            break;
+        }
+        fprintf(stderr, "== %s: %ld frames -> %s\n", paths[k], nf, path);
+        print_stats(&st[k]);
+    }
+    fflush(stderr);
+    if (getenv("ADSB_CLI_CLEAN_EXIT"))
+        exit(rc);
+    _exit(rc); /* (no teardown: see the end of main) */
 }
 
 /* -W: the file's power samples into `outpath`; nothing is decoded.  A piece of a uint16 file is EXPORT_PIECE power samples (a
@@ -957,7 +1036,7 @@ int main(int argc, char **argv)
     const char *filename = NULL, *listfile = NULL, *export_path = NULL;
     char *files[MAX_FILES];
     int nfiles = 0, devs[MAX_GPUS], ndev = 0, device = -1;
-    int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, level = 0, c;
+    int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, level = 0, flush = 0, c;
     const char *burst_arg = NULL; /* -U: -L's gate, factor[,lead[,hang]] */
     struct burst_opts burst = {0, 2, 1468};
     const char *interval_arg = NULL; /* -I: -L's windows, in milliseconds */
@@ -969,7 +1048,7 @@ int main(int argc, char **argv)
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:E")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -1033,6 +1112,9 @@ int main(int argc, char **argv)
         case 'L':
             level = 1;
             break;
+        case 'E':
+            flush = 1;
+            break;
         case 'I': {
             char *end;
             interval_ms = strtod(optarg, &end);
@@ -1077,6 +1159,13 @@ int main(int argc, char **argv)
             usage();
             return 1;
         }
+    }
+    if (flush && (ndev || level || export_path)) {
+        /* -E ends a decode on one GPU past the horizon: refused before any GPU call */
+        fprintf(stderr, "-E is not supported with %s: %s\n", ndev ? "-G" : level ? "-L" : "-W",
+                ndev ? "the multi-GPU driver stitches its shards at the reference's end-of-file horizon; -E decodes on one GPU (-d)"
+                     : "it ends a DECODE at the file's last sample, and this run decodes nothing");
+        return 1;
     }
     if (level && (ndev || listfile || export_path || outmode != SINK_STDOUT || nfiles > 1)) {
         /* -L reports the levels of one file in one call and decodes nothing: refused before any GPU call */
@@ -1187,6 +1276,10 @@ int main(int argc, char **argv)
         bcfg.df18 = df18;
         bcfg.fix_1bit = fix1;
         bcfg.collect_stats = 1; /* the reference always prints Try/Ok */
+        if (flush) {
+            bcfg.device = devs[0]; /* (restrict_visible_devices has renumbered it where it narrowed the runtime's view) */
+            return run_batch_list_flush(&bcfg, paths, n_captures, packed, outformat);
+        }
         return run_batch_list(&bcfg, devs, ndev, paths, n_captures, packed, outformat, getenv("ADSB_CLI_TIMING") != NULL);
     }
     /* several captures need -G and go to files; -d and -G exclude each other */
@@ -1322,7 +1415,11 @@ int main(int argc, char **argv)
         fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
         return 255; /* runOutput() == -1 -> exit status 255 (main.c:101-105) */
     }
-    if (!iq && !power && adsb_set_long_stream(dec, 1) != 0) { /* always: the reference reads a file of any length (its counter wraps, air.c:34) */
+    if (flush && adsb_set_flush(dec, 1) != 0) { /* -E: the stream ends as its silent twin does (and below 2^32 samples: a long stream has no flush) */
+        fprintf(stderr, "adsb_set_flush() failed: %s\n", adsb_last_error(dec));
+        return 255;
+    }
+    if (!flush && !iq && !power && adsb_set_long_stream(dec, 1) != 0) { /* always: the reference reads a file of any length (its counter wraps, air.c:34) */
         fprintf(stderr, "adsb_set_long_stream() failed: %s\n", adsb_last_error(dec));
         return 255;
     }

@@ -42,6 +42,8 @@ static uint64_t scannable_end(const adsb_decoder *d, uint64_t n_samples, bool fi
     if (d->shard_on)
         m = n_samples / 2; // every complete pair
     uint64_t g_end = m >= ADSB_WINDOW ? m - ADSB_WINDOW + 1 : 0;
+    if (final && d->flush && !d->shard_on)
+        g_end = m; // flush: the last launch owns every offset of the stream; the windows behind the last power sample read silence
     if (!final && d->long_stream) {
         // run boundaries are those of the EPOCH (a scan launch is given epoch-relative indices, and 2^31 mod 28 = 16); a scan
         // may stop anywhere among the seam offsets of a wrap, which need no alignment -- only the staging tail's (4 offsets)
@@ -543,6 +545,9 @@ int scan_submit(adsb_decoder *d, const uint16_t *buf, uint64_t buf_first, uint64
         a.pbuf0 = (int64_t)(buf_first / 2);
         a.p_lo = a.pbuf0; // stream start: pairs below 0 read as silence (air.c:33)
         a.p_hi = a.pbuf0 + (int64_t)(buf_n / 2);
+        if (d->flush) // the silent twin ends at the stream's last whole pair of power samples: a trailing partial quad (an odd IQ
+                      // or power sample) belongs to nothing, and only the stream's last launch could have read it
+            a.p_hi = std::min<int64_t>(a.p_hi, (int64_t)power_samples_produced(d->n_samples));
         a.g_begin = g_begin;
         a.g_end = g_stop;
         fill_scan_args(d, a);
@@ -601,8 +606,10 @@ int process_stage(adsb_decoder *d, bool final, bool in_flight)
     // offset but they count for the `aidx >= APBUFFSZ` test.
     // (An IQ or power stream has no quads: its power samples enter two at a time and a trailing odd one is never seen.)
     const uint64_t m_ref = final && !adsb::kind_in_twos(d->kind) ? 2 * ((d->n_samples + 3) / 4) : m_real;
-    if (!in_flight) // (in flight: the records below g_scanned are not all in yet; slot_collect advanced as far as they are)
-        d->res.advance(m_ref, d->g_scanned);
+    if (!in_flight) { // (in flight: the records below g_scanned are not all in yet; slot_collect advanced as far as they are)
+        const adsb::StreamEnd e = adsb::stream_end(final && d->flush && !d->shard_on, m_real, m_ref, d->g_scanned);
+        d->res.advance(e.power_samples, e.g_complete);
+    }
     if (final)
         return 0;
 
@@ -926,7 +933,8 @@ static int push_device_impl(adsb_decoder *d, const void *device_samples, size_t 
         if (rc)
             return -1;
         const auto t2 = clk::now();
-        d->res.advance(adsb::kind_in_twos(d->kind) ? m_real : 2 * ((total + 3) / 4), d->g_scanned); // EOF rule: see process_stage()
+        const adsb::StreamEnd e = adsb::stream_end(d->flush, m_real, adsb::kind_in_twos(d->kind) ? m_real : 2 * ((total + 3) / 4), d->g_scanned);
+        d->res.advance(e.power_samples, e.g_complete); // EOF rule: see process_stage()
         if (d->cfg.collect_stats && count_tries_pass(d, d->deferred_slot, d->deferred_slot ? d->deferred_slot->d_tries.p : nullptr,
                                                         d->deferred_slot ? d->deferred_slot->d_try_counts.p : nullptr, d->deferred_n, d->deferred_base, true))
             return -1; // tries beyond the final position are never visited

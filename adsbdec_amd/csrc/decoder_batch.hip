@@ -77,7 +77,8 @@ int batch_launch_collect(adsb_decoder *d, const adsb_batch_launch &L, const void
         b.x = (uint64_t)(uintptr_t)p[sg.capture];
         b.pbuf0 = origin;
         b.p_lo = origin;
-        b.p_hi = origin + (int64_t)(n[sg.capture] / 2);
+        // (flush: the silent twin ends at the capture's last whole quad; the pair of a trailing partial one reads as silence too)
+        b.p_hi = origin + (int64_t)(d->flush ? adsb::batch_power_flush(n[sg.capture]) : n[sg.capture] / 2);
         b.g_begin = sg.base - L.g_begin;
         b.g_end = b.g_begin + (sg.o_end - sg.o_begin);
         b.first_tile = sg.first_tile;
@@ -162,7 +163,7 @@ long decode_batch(adsb_decoder *d, size_t n_captures, const void *const *p, cons
     // so a push without adsb_reset is refused and never meets batch_stats or the batch's frames.
     d->finished = true;
     if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &d->n_cus, batch_forced_passes(d->dbg.passes),
-                            batch_wanted_limit(d->dbg.batch_launch_offsets), d->batch_segs, d->batch_launches, &bad))
+                            batch_wanted_limit(d->dbg.batch_launch_offsets), d->batch_segs, d->batch_launches, &bad, d->flush))
         return d->fail("internal: capture %zu is too long for a batch", bad); // (batch_refusal has looked)
     d->batch_cands.clear();
     d->batch_tries.clear();
@@ -173,7 +174,7 @@ long decode_batch(adsb_decoder *d, size_t n_captures, const void *const *p, cons
     d->batch_per.resize(n_captures); // every capture's table: the caller's `stats`, and the sum adsb_get_stats answers
     const bool ok = adsb::batch_resolve(d->batch_res, n_captures, n, d->batch_segs.data(), d->batch_segs.size(), d->batch_cands.data(),
                                         d->batch_cands.size(), d->batch_tries.data(), d->batch_tries.size(), d->batch_frames, first,
-                                        d->batch_per.data(), d->batch_cbuf, d->batch_tbuf);
+                                        d->batch_per.data(), d->batch_cbuf, d->batch_tbuf, d->flush);
     if (!ok) {
         d->batch_frames.clear();
         return d->fail("internal: a record of a batch launch lies in no capture's offsets");
@@ -485,14 +486,14 @@ long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const voi
     return decode_batch_packed(d, what, n_captures, land.data(), n, frames, first, stats);
 }
 
-long adsb_batch_layout_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, adsb_batch_segment *segs,
-                          size_t seg_cap, adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
+long adsb_batch_layout_flush(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, int flush,
+                             adsb_batch_segment *segs, size_t seg_cap, adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
 {
     if ((n_captures && !n) || (seg_cap && !segs) || (launch_cap && !launches) || !n_launches)
         return -1;
     std::vector<adsb_batch_segment> sv;
     std::vector<adsb_batch_launch> lv;
-    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), launch_offsets, sv, lv, nullptr))
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), launch_offsets, sv, lv, nullptr, flush != 0))
         return -1;
     if (!sv.empty() && seg_cap)
         std::memcpy(segs, sv.data(), std::min(seg_cap, sv.size()) * sizeof sv[0]);
@@ -502,31 +503,44 @@ long adsb_batch_layout_ex(size_t n_captures, const size_t *n, int cus, int passe
     return (long)sv.size();
 }
 
+long adsb_batch_layout_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, adsb_batch_segment *segs,
+                          size_t seg_cap, adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
+{
+    return adsb_batch_layout_flush(n_captures, n, cus, passes, launch_offsets, 0, segs, seg_cap, launches, launch_cap, n_launches);
+}
+
 long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, adsb_batch_segment *segs, size_t seg_cap,
                        adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches)
 {
     return adsb_batch_layout_ex(n_captures, n, cus, passes, 0, segs, seg_cap, launches, launch_cap, n_launches);
 }
 
-long adsb_batch_resolve_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, const adsb_candidate *cands,
-                           size_t n_cands, const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first,
-                           adsb_stats *stats)
+long adsb_batch_resolve_flush(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, int flush,
+                              const adsb_candidate *cands, size_t n_cands, const uint64_t *tries, size_t n_tries, adsb_frame *frames,
+                              size_t frame_cap, uint64_t *first, adsb_stats *stats)
 {
     if ((n_captures && !n) || (n_cands && !cands) || (n_tries && !tries) || (frame_cap && !frames) || !first)
         return -1;
     std::vector<adsb_batch_segment> sv;
     std::vector<adsb_batch_launch> lv;
-    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), launch_offsets, sv, lv, nullptr))
+    if (!adsb::batch_layout(n_captures, n, batch_passes_cap, &cus, batch_forced_passes(passes), launch_offsets, sv, lv, nullptr, flush != 0))
         return -1;
     adsb::Resolver r;
     std::vector<adsb_frame> out;
     std::vector<adsb_candidate> cbuf;
     std::vector<uint64_t> tbuf;
-    if (!adsb::batch_resolve(r, n_captures, n, sv.data(), sv.size(), cands, n_cands, tries, n_tries, out, first, stats, cbuf, tbuf))
+    if (!adsb::batch_resolve(r, n_captures, n, sv.data(), sv.size(), cands, n_cands, tries, n_tries, out, first, stats, cbuf, tbuf, flush != 0))
         return -1;
     if (!out.empty() && out.size() <= frame_cap)
         std::memcpy(frames, out.data(), out.size() * sizeof out[0]);
     return (long)out.size();
+}
+
+long adsb_batch_resolve_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, const adsb_candidate *cands,
+                           size_t n_cands, const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first,
+                           adsb_stats *stats)
+{
+    return adsb_batch_resolve_flush(n_captures, n, cus, passes, launch_offsets, 0, cands, n_cands, tries, n_tries, frames, frame_cap, first, stats);
 }
 
 long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes, const adsb_candidate *cands, size_t n_cands,

@@ -345,6 +345,8 @@ int adsb_set_long_stream(adsb_decoder *d, int on)
         return -1;
     if (d->n_samples || d->finished || d->slot_count || d->stage_fill || d->shard_on)
         return d->fail("adsb_set_long_stream: only on a fresh or reset handle, before the first push");
+    if (on && d->flush)
+        return d->fail("adsb_set_long_stream: the handle was given adsb_set_flush, and a long stream has no flush (adsb_set_flush(d, 0) first)");
     if (on && !d->seam_out) {
         HIP_TRY(d, hipSetDevice(d->device));
         HIP_TRY(d, d->seam_out.reserve(adsb::kSeamOutWords));
@@ -353,6 +355,24 @@ int adsb_set_long_stream(adsb_decoder *d, int on)
     }
     d->long_stream = on != 0;
     return 0;
+}
+
+// Decode a stream to its last sample: its end counts as its silent twin's (DESIGN.md "Flush"; resolver.hpp stream_end).
+int adsb_set_flush(adsb_decoder *d, int on)
+{
+    if (!d)
+        return -1;
+    if (d->n_samples || d->finished || d->slot_count || d->stage_fill || d->shard_on)
+        return d->fail("adsb_set_flush: only on a fresh or reset handle, before the first push");
+    if (on && d->long_stream)
+        return d->fail("adsb_set_flush: the handle was given adsb_set_long_stream, and a long stream has no flush (adsb_set_long_stream(d, 0) first)");
+    d->flush = on != 0;
+    return 0;
+}
+
+int adsb_get_flush(const adsb_decoder *d)
+{
+    return d ? (d->flush ? 1 : 0) : -1;
 }
 
 int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets)

@@ -40,11 +40,20 @@ int shard_tries(adsb_decoder *d, adsb_shard_head *head)
     return 0;
 }
 
+// A flush handle (adsb_set_flush) decodes a stream's end as its silent twin's; a shard or a chain window has no end of its own.
+int flush_refusal(adsb_decoder *d, const char *what)
+{
+    if (!d->flush)
+        return 0;
+    return d->fail("%s: the handle was given adsb_set_flush, which ends a stream of its own past the reference's horizon; the shard and chain "
+                   "primitives scan windows of somebody else's stream (adsb_set_flush(d, 0) on a reset handle, or a handle of its own)", what);
+}
+
 // What a shard scan asks of its window in HBM, before anything of the handle changes.
 int shard_window_refusal(adsb_decoder *d, const char *what, const void *device_samples, uint64_t first_sample, size_t n,
                          uint64_t g_begin, uint64_t g_end, uint64_t total_samples)
 {
-    if (shard_too_long(d, what, first_sample, n, total_samples))
+    if (flush_refusal(d, what) || shard_too_long(d, what, first_sample, n, total_samples))
         return -1;
     if (first_sample % 8 || (uintptr_t)device_samples % 16)
         return d->fail("%s: buffer must start at a multiple of 8 samples, 16-byte aligned", what);
@@ -153,6 +162,8 @@ int adsb_scan_wrap_window(adsb_decoder *d, const void *device_samples, uint64_t 
     const char *what = "adsb_scan_wrap_window";
     if (!d || !device_samples || !n_cands || !n_tries)
         return -1;
+    if (flush_refusal(d, what))
+        return -1;
     if (!d->long_stream)
         return d->fail("%s: the handle was not given adsb_set_long_stream (below 2^32 samples: adsb_scan_shard)", what);
     if (first_sample % 8 || (uintptr_t)device_samples % 16)
@@ -183,7 +194,7 @@ int adsb_scan_shard_host(adsb_decoder *d, const uint16_t *host_samples, uint64_t
 {
     if (!d || !host_samples || !n_cands || !n_tries)
         return -1;
-    if (shard_too_long(d, "adsb_scan_shard_host", first_sample, n, 0))
+    if (flush_refusal(d, "adsb_scan_shard_host") || shard_too_long(d, "adsb_scan_shard_host", first_sample, n, 0))
         return -1;
     // (copied and waited for: the scan's launches may go to either compute stream, and a window is a few hundred KB.  On a
     // copy stream of the handle's: the synchronous hipMemcpy was seen to cost the process ~1 KB of host memory per call
@@ -256,7 +267,7 @@ int adsb_shard_begin(adsb_decoder *d, uint64_t first_sample, uint64_t g_begin, u
 {
     if (!d)
         return -1;
-    if (shard_too_long(d, "adsb_shard_begin", first_sample, 0, total_samples))
+    if (flush_refusal(d, "adsb_shard_begin") || shard_too_long(d, "adsb_shard_begin", first_sample, 0, total_samples))
         return -1;
     if (first_sample % 8)
         return d->fail("adsb_shard_begin: first_sample must be a multiple of 8 samples");

@@ -199,7 +199,10 @@ struct adsb_decoder {
     // Long streams (adsb_set_long_stream): no refusal at 2^32 samples; launches are cut at every wrap of the reference's
     // sample counter and the offsets around it go through the seam kernel (scan_submit, seam_kernel.h)
     bool long_stream = false;
-    uint64_t seam_offsets = 0;     // offsets of the current stream that went through the seam kernel
+    // Flush (adsb_set_flush; DESIGN.md "Flush"): a stream's end is decoded as its silent twin's -- the last launch owns every
+    // offset up to the last power sample, and the resolver's end is adsb::stream_end(true, ...).  Sticky across adsb_reset.
+    bool flush = false;
+    uint64_t seam_offsets = 0;    // offsets of the current stream that went through the seam kernel
     adsb::Buf<uint32_t, adsb::Mem::Pinned> seam_out; // adsb::kSeamOutWords (the seam kernel's records and try words)
     ScanLaunch seam_slot;          // the seam launch: its completion event (ev_ready[0]), and its count pass's
 

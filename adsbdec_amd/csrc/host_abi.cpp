@@ -241,6 +241,15 @@ int adsb_resolver_advance(adsb_resolver *r, uint64_t power_samples, uint64_t g_c
     return 0;
 }
 
+int adsb_resolver_finish_flush(adsb_resolver *r, uint64_t power_samples)
+{
+    if (!r)
+        return -1;
+    const adsb::StreamEnd e = adsb::stream_end(true, power_samples, power_samples, power_samples);
+    r->r.advance(e.power_samples, e.g_complete);
+    return 0;
+}
+
 long adsb_resolver_drain(adsb_resolver *r, adsb_frame *out, size_t cap)
 {
     if (!r || (!out && cap))

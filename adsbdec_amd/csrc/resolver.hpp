@@ -77,6 +77,29 @@ private:
     size_t n_ = 0, cap_ = 0;
 };
 
+// The END of a stream, in ONE place: what Resolver::advance() is told once the last sample is in -- by the plain loop and the
+// tile loops alike (decide_calls, adopt_calls), which read nothing but these two numbers.
+//   reference (flush off): the front end has produced m_ref power samples and will produce no more; the device has scanned every
+//     offset below g_scanned.  A call that has not fired never will (air.c:94), so the last ~41 k power samples stay unscanned.
+//   flush (adsb_set_flush; DESIGN.md "Flush"): the stream counts as its SILENT TWIN -- its m power samples followed by
+//     kFlushSilence power samples of silence.  The device has scanned the offsets below m; no offset from m - 32 on can pass the
+//     preamble test (its p2 sums silence, and 0 > 0 is false: no record, no try word), so every offset of the twin counts as
+//     scanned, and the calls go on firing over the silence exactly as the reference's would.  A call fires at base +
+//     ADSB_APBUFFSZ + (base & 1), so every call with a base below m has fired once m + ADSB_APBUFFSZ power samples are in, and its
+//     limit lies ADSB_DECOFFSET below its fire (fires are at most ADSB_APBUFFSZ + ADSB_DECOFFSET apart): any even silence of
+//     43 400 power samples or more gives the same frames and the same table, and twice the buffer is the round figure above it.
+//     The calls whose base lies at or beyond m find nothing and only move the base.
+constexpr uint64_t kFlushSilence = 2 * ADSB_APBUFFSZ;
+struct StreamEnd {
+    uint64_t power_samples, g_complete;
+};
+inline StreamEnd stream_end(bool flush, uint64_t m, uint64_t m_ref, uint64_t g_scanned)
+{
+    if (!flush)
+        return StreamEnd{m_ref, g_scanned};
+    return StreamEnd{m + kFlushSilence, m + kFlushSilence - ADSB_WINDOW + 1};
+}
+
 class Resolver {
 public:
     // More hands (gang.hpp): from now on a batch of tiles that yields kGangMinFrames frames or more is only DECIDED here; the

@@ -170,8 +170,8 @@ long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t
 long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap); typedef struct adsb_level_report { uint64_t samples, negative, rail_lo, rail_hi, over; uint64_t hist[2048]; } adsb_level_report;
 long adsb_level_device(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_packed(adsb_decoder *d, const void *device_packed, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_power(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_host(adsb_decoder *d, const uint16_t *samples, size_t n, adsb_level_report *out, float *env, size_t env_cap); long adsb_level_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, adsb_level_report *out, float *const *env, const size_t *env_cap); long adsb_level_windows(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_windows_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *env, size_t env_cap); void adsb_level_add(adsb_level_report *sum, const adsb_level_report *part); float adsb_level_percentile(const adsb_level_report *r, double q); typedef struct adsb_burst { uint32_t begin, end, hot; float peak; } adsb_burst; /* runs of 28 power samples, [begin, end) */ long adsb_bursts_device(adsb_decoder *d, const float *device_env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); long adsb_bursts_host(adsb_decoder *d, const float *env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap);
 /* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
- * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. */
-int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets);
+ * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. adsb_set_flush (off by default; same rule: fresh or reset handle, sticky): decode a capture to its LAST sample instead of keeping the reference's end-of-file horizon (air.c:94-99, demod.c:89: the last ~41 k power samples are never scanned, a capture below 81 960 samples decodes nothing).  adsb_decode_device*, adsb_decode_batch_* and a stream ended by adsb_finish / a _final push then return, record for record and with the same Try/Ok table, what the reference returns for the capture's SILENT TWIN: its whole units (4 floor(n / 4) real samples, 2 floor(n / 2) IQ or power samples) followed by 81 960 power samples of silence (code 2048, (0, 0), +0.0) -- without padding or copying anything (DESIGN.md "Flush").  Every frame the horizon keeps comes back unchanged, in front.  Refuses, and is refused by, adsb_set_long_stream. */
+int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets); int adsb_set_flush(adsb_decoder *d, int on); int adsb_get_flush(const adsb_decoder *d);
 int adsb_finish(adsb_decoder *d); /* end of input (EOF, air.c:241-244): the remaining offsets and the end-of-file horizon (SURVEY Q10) */
 /* Page-locked host buffers: the counterpart of `iqbuff = malloc(...)` (air.c:230), so that a push is one DMA.  adsb_host_alloc_on binds the memory to the NUMA node of `device` (best effort).  adsb_host_register page-locks memory the caller already owns.  0 / -1. */
 void *adsb_host_alloc(size_t bytes); void *adsb_host_alloc_on(size_t bytes, int device); void adsb_host_free(void *p); int adsb_host_register(void *p, size_t bytes); int adsb_host_unregister(void *p);

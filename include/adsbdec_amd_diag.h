@@ -64,6 +64,10 @@ int adsb_resolver_feed(adsb_resolver *r, const adsb_candidate *cands, size_t n_c
 /* Everything with g < g_complete has been fed; the stream has produced
  * power_samples 10 MS/s samples so far. Appends accepted frames internally. */
 int adsb_resolver_advance(adsb_resolver *r, uint64_t power_samples, uint64_t g_complete);
+/* The end of a stream on a flush handle (adsb_set_flush; csrc/resolver.hpp stream_end, the ONE place the decoder reads too): the
+ * stream has produced power_samples power samples (even), every record and try word with g < power_samples has been fed, and the
+ * reference's calls go on firing over the silent twin's silence until the base has passed the stream's end. */
+int adsb_resolver_finish_flush(adsb_resolver *r, uint64_t power_samples);
 long adsb_resolver_drain(adsb_resolver *r, adsb_frame *out, size_t cap);
 int adsb_resolver_stats(const adsb_resolver *r, adsb_stats *out);
 
@@ -303,6 +307,11 @@ long adsb_batch_layout(size_t n_captures, const size_t *n, int cus, int passes, 
  * what a handle created with that knob lays out. */
 long adsb_batch_layout_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, adsb_batch_segment *segs,
                           size_t seg_cap, adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches);
+/* adsb_batch_layout_ex as a handle with adsb_set_flush == flush lays the batch out (flush == 0: adsb_batch_layout_ex itself): a
+ * capture of n samples then has 2 floor(n / 4) offsets -- every power sample of its whole quads -- and its last segment reaches
+ * ADSB_WINDOW - 1 offsets beyond the last of them, which read as silence; the free offsets are counted from that reach. */
+long adsb_batch_layout_flush(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, int flush,
+                             adsb_batch_segment *segs, size_t seg_cap, adsb_batch_launch *launches, size_t launch_cap, size_t *n_launches);
 /* What adsb_decode_batch_* does with the records of its launches: cands (ascending g) and tries (ascending (g << 2) | code) of the
  * whole batch in the VIRTUAL offsets of that layout -> per capture the frames the reference decodes from it alone (g and ts from
  * 0; demod.c:89,99,125-141, air.c:94-99 through adsb_resolver's code), capture i's at frames[first[i] .. first[i+1]) (first:
@@ -315,6 +324,10 @@ long adsb_batch_resolve(size_t n_captures, const size_t *n, int cus, int passes,
 long adsb_batch_resolve_ex(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, const adsb_candidate *cands,
                            size_t n_cands, const uint64_t *tries, size_t n_tries, adsb_frame *frames, size_t frame_cap, uint64_t *first,
                            adsb_stats *stats);
+/* ... and of adsb_batch_layout_flush(..., launch_offsets, flush, ...), every capture ended as a flush handle ends it. */
+long adsb_batch_resolve_flush(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, int flush,
+                              const adsb_candidate *cands, size_t n_cands, const uint64_t *tries, size_t n_tries, adsb_frame *frames,
+                              size_t frame_cap, uint64_t *first, adsb_stats *stats);
 /* What the last adsb_decode_batch_* call on d collected, before the per-capture resolve, as read-only views: the sorted candidates
  * of all its launches and their try words ((g << 2) | code; none without collect_stats), both in VIRTUAL offsets, and the layout
  * it used (segments, launches: a record of capture i at offset o lies at segs[k].base + o - segs[k].o_begin of the segment k of

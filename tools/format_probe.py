@@ -10,6 +10,7 @@ comparison interleaved.
     python tools/format_probe.py --level [--reps 20] [--out profiles/r23_level.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_probe()
     python tools/format_probe.py --level-windows [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/r27_level_windows.txt]   # level_windows_probe()
     python tools/format_probe.py --bursts [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/rNN_bursts.txt]   # bursts_probe(): NN is the next free round
+    python tools/format_probe.py --flush [--reps 10] [--ab parent/libadsbdec_amd.so] [--out profiles/r30_flush.txt]   # flush_probe()
     python tools/format_probe.py --level-batch [--reps 20] [--out profiles/r26_level_batch.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_batch_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
@@ -1312,6 +1313,147 @@ def bursts_probe(L, reps, lines, parent):
         lines.append("#     not measured in this run: no --ab parent library given")
 
 
+def flush_probe(L, reps, lines, parent):
+    """Flush (adsb_set_flush), every comparison interleaved in this one process, wall time of the calls, the run's A/A beside every ratio:
+    (1) adsb_decode_device on the benchmark capture: the tree without flush beside itself (the A/A), beside the library built from the
+    parent commit (--ab) and beside a flush handle; (2) 4 096 captures of 2 048 samples through adsb_decode_batch_device on a flush
+    handle, beside the loop of single flush calls and beside adsb_power_batch_device on the same batch; (3) the gated pipeline --
+    adsb_level_device with the envelope, adsb_bursts_device at lead 2 hang 4, ONE adsb_decode_batch_device of the pieces on a flush handle
+    -- beside the whole decode, on a sparse capture (the pipeline fixture's density: 6 frames per million power samples) and on the
+    benchmark workload (a frame per millisecond)."""
+    import numpy as np
+    from adsbdec_amd import levels
+    out = C.POINTER(capi.Frame)()
+    steps = 3
+
+    def rotate(sides, steps=steps):
+        names = list(sides)
+        wall = {k_: [] for k_ in names}
+        for r in range(-1, reps):                            # (round -1: the warm-up)
+            for name in names[r % len(names):] + names[:r % len(names)]:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    sides[name]()
+                if r >= 0:
+                    wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        return names, wall
+
+    def table_of(names, wall, base):
+        for name in names:
+            q = statistics.quantiles(wall[name], n=4)
+            rr = [a_ / b for a_, b in zip(wall[name], wall[base])]
+            qr = statistics.quantiles(rr, n=4)
+            lines.append(f"    {name:58s} {med(wall[name]):10.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med(rr):.4f} ({qr[0]:.4f} .. {qr[2]:.4f})")
+            print(lines[-1], flush=True)
+
+    head = "#   side                                                          call ms (q1 .. q3)               / the first side (median of rounds, q1 .. q3)"
+    t, _ = make_workload(torch, N, seed=1)
+    torch.cuda.synchronize()                               # (the library's streams do not wait for torch's)
+    plain, flush = capi.Decoder(), capi.Decoder(flush=True)
+
+    def dec(B, hh):
+        k = B.adsb_decode_device(hh, t.data_ptr(), N, C.byref(out))
+        assert k >= 0
+        return k
+    k_plain, k_flush = dec(L, plain._h), dec(L, flush._h)
+    lines += [f"# (1) adsb_decode_device on the benchmark capture (make_workload, 256 Mi samples, seed 1): {k_plain} frames without flush, {k_flush} with it;",
+              f"#     {reps} rounds x {steps} calls per side, the sides in rotation", head]
+    sides = {"tree, flush off": lambda: dec(L, plain._h), "tree, flush off again (the A/A)": lambda: dec(L, plain._h)}
+    if parent:
+        B = C.CDLL(parent)
+        for name in ("adsb_create", "adsb_decode_device"):
+            fn = getattr(B, name)
+            fn.restype, fn.argtypes = capi.SYMBOLS[name]
+        assert not hasattr(B, "adsb_set_flush"), "the --ab library is not the parent's: it has the flush"
+        cfg = capi.make_config()
+        hh = B.adsb_create(C.byref(cfg))
+        assert hh, parent
+        assert dec(B, hh) == k_plain
+        sides["parent commit"] = lambda: dec(B, hh)
+    else:
+        lines.append("#     (no --ab parent library given: the parent's side is missing)")
+    sides["tree, flush on"] = lambda: dec(L, flush._h)
+    names, wall = rotate(sides)
+    table_of(names, wall, names[0])
+
+    # (2)
+    K, NS = 4096, 2048
+    rng = np.random.default_rng(30)
+    from tools import gen_signal as G
+    host = np.empty((K, NS), np.uint16)
+    for i in range(K):
+        frames = [(int(rng.integers(0, NS - 1300)), G.make_frame(11, rng), float(rng.uniform(300, 1500)), 0.3)] if i % 16 == 7 else []
+        host[i] = G.synth(NS, frames, 8.0, 4000 + i)
+    batch = torch.from_numpy(host.view(np.int16)).cuda()
+    ptrs = (C.c_void_p * K)(*[batch.data_ptr() + 2 * NS * i for i in range(K)])
+    ns = (C.c_size_t * K)(*[NS] * K)
+    first = (C.c_uint64 * (K + 1))()
+    pw = torch.empty(K * NS // 2, dtype=torch.float32, device="cuda")
+    pptrs = (C.c_void_p * K)(*[pw.data_ptr() + 4 * (NS // 2) * i for i in range(K)])
+    caps = (C.c_size_t * K)(*[NS // 2] * K)
+
+    def batch_flush():
+        k = L.adsb_decode_batch_device(flush._h, K, ptrs, ns, C.byref(out), first, None)
+        assert k >= 0
+        return k
+
+    def loop_flush():
+        tot = 0
+        for i in range(K):
+            tot += L.adsb_decode_device(flush._h, ptrs[i], NS, C.byref(out))
+        return tot
+
+    def export():
+        assert L.adsb_power_batch_device(plain._h, K, ptrs, ns, pptrs, caps) >= 0
+    kb = batch_flush()
+    assert kb == loop_flush() and kb >= K // 32, kb
+    assert L.adsb_decode_batch_device(plain._h, K, ptrs, ns, C.byref(out), first, None) == 0
+    lines += ["#", f"# (2) {K} captures of {NS} samples, a short frame in every 16th: adsb_decode_batch_device on a flush handle ({kb} frames; without flush: 0,",
+              "#     by construction), the loop of single flush calls, and adsb_power_batch_device on the same batch; one call per side and round", head]
+    names, wall = rotate({"adsb_decode_batch_device, flush": batch_flush, "adsb_decode_batch_device, flush again (the A/A)": batch_flush,
+                          "loop of 4 096 adsb_decode_device, flush": loop_flush, "adsb_power_batch_device": export}, steps=1)
+    table_of(names, wall, names[0])
+    del batch, pw
+
+    # (3)
+    M = N // 2
+    ke = -(-M // 28)
+    env = torch.zeros(ke, dtype=torch.float32, device="cuda")
+    rep1 = capi.LevelReport()
+    for what, cap_t in (("sparse: 805 frames in 256 Mi samples (the pipeline fixture's 6 per million power samples)", make_workload(torch, N, n_frames=805, seed=2)[0]),
+                        ("the benchmark workload: a frame per millisecond", t)):
+        torch.cuda.synchronize()
+        table = np.zeros(1 << 15, dtype=levels.BURST_DTYPE)
+        state = {}
+
+        def whole():
+            k = L.adsb_decode_device(plain._h, cap_t.data_ptr(), N, C.byref(out))
+            assert k >= 0
+            return k
+
+        def gated():
+            assert L.adsb_level_device(plain._h, cap_t.data_ptr(), N, C.byref(rep1), env.data_ptr(), ke) == M
+            thr = float(np.float32(capi.Decoder.BURST_FACTOR * L.adsb_level_percentile(C.byref(rep1), 0.5)))
+            b = L.adsb_bursts_device(plain._h, env.data_ptr(), ke, thr, 2, 4, table.ctypes.data, table.size)
+            assert 0 <= b <= table.size, b
+            begin, end = table["begin"][:b].astype(np.int64), np.minimum(table["end"][:b].astype(np.int64) * 28, M)
+            pp = (C.c_void_p * max(1, b))(*[cap_t.data_ptr() + 112 * int(v) for v in begin])          # (56 samples a run: 112 bytes, 16-byte aligned)
+            nn = (C.c_size_t * max(1, b))(*[int(2 * (e - 28 * s)) for s, e in zip(begin, end)])
+            ff = (C.c_uint64 * (b + 1))()
+            k = L.adsb_decode_batch_device(flush._h, b, pp, nn, C.byref(out), ff, None)
+            assert k >= 0
+            state.update(b=b, k=k, cover=float(sum(nn)) / N)
+            return k
+        kw, kg = whole(), gated()
+        lines += ["#", f"# (3) {what}: the whole decode finds {kw} frames; the gate gives {state['b']} pieces that cover {100 * state['cover']:.2f} % of the capture",
+                  f"#     and hold {kg} frames (a piece is decoded as a capture of its own: a frame the gate cuts, or one behind the whole decode's horizon, differs)", head]
+        names, wall = rotate({"adsb_decode_device (the whole capture)": whole, "adsb_decode_device again (the A/A)": whole,
+                              "level + gate (lead 2, hang 4) + batch flush decode": gated}, steps=1)
+        table_of(names, wall, names[0])
+    lines += ["#", "# The pipeline's cost on the benchmark workload is tile count: every piece takes a tile of two passes (12 880 offsets) of its own whatever its",
+              "# length, beside the gate's round trips.  Pieces that share a tile are the follow-up; not built here."]
+
+
 def next_round(stem):
     """profiles/rNN_<stem>.txt with the next free round number."""
     import re
@@ -1349,7 +1491,18 @@ def main():
     ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB", help="with --level or --level-batch: a build of the library with another accumulation, flush or grid, measured beside the tree's")
     ap.add_argument("--out", default=None)
     ap.add_argument("--bursts", action="store_true", help="the gate behind the envelope (adsb_bursts_device) beside a torch gate and a host gate instead: profiles/rNN_bursts.txt with the next free NN; --ab: the parent commit's library, for (c)")
+    ap.add_argument("--flush", action="store_true", help="flush (adsb_set_flush): the decode call across the change, the batch of short captures, the gated pipeline: profiles/r30_flush.txt; --ab: the parent commit's library")
     a = ap.parse_args()
+    if a.flush:
+        a.out = a.out or os.path.join(ROOT, "profiles", "r30_flush.txt")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --flush: decoding past the end-of-file horizon (adsb_set_flush), one process,",
+                 f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved, a warm-up round first.",
+                 "# Wall time of the C calls through ctypes; every call ends with its frames in host memory.", "#"]
+        flush_probe(capi.load(), a.reps, lines, a.ab)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.bursts:
         a.out = a.out or next_round("bursts")
         torch.cuda.set_device(0)
