@@ -8,6 +8,7 @@
 
 #include "scan_kernel.h"
 #include "scan_stages.h"
+#include "scan_tile.h" // the stagger, the launcher (after scan_stages.h: see there)
 
 namespace adsb {
 
@@ -15,6 +16,8 @@ template <bool kStats>
 __global__ __launch_bounds__(kThreads, kMinWaves) void scan_batch_kernel(const ScanArgs launch, const BatchSeg *__restrict__ segs,
                                                                          const uint32_t *__restrict__ tile_seg)
 {
+    // The tile shell in this kernel's own lines, not scan_tile's (scan_tile.h): over scan_tile the <false> instantiation's scalar
+    // registers are renamed inside Stage B's loops (profiles/r31_tile_shell_isa_identity.txt).  The stagger and the launcher are shared.
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int K = launch.passes; // one K per launch, no taper
     const int nplane = kPassRuns * K + kPlanePad;
@@ -26,11 +29,7 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void scan_batch_kernel(const S
     uint32_t *cl_rec = qcount + 16; // kClistCap records of kCandWords
 
     const int tid = threadIdx.x;
-    if (gridDim.x >= 256u * kMinWaves * 4 / kWaves && blockIdx.x < 256u * kMinWaves * 4 / kWaves) { // (scan_kernel's stagger)
-        const uint32_t slot = blockIdx.x >> 8;
-        for (uint32_t i = 0; i < slot; i++)
-            __builtin_amdgcn_s_sleep(kSleepStagger);
-    }
+    stagger_start();
     const uint64_t prof_begin = launch.profile ? __builtin_amdgcn_s_memrealtime() : 0;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -73,15 +72,7 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void scan_batch_kernel(const S
 hipError_t launch_scan_batch(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
                              hipStream_t stream)
 {
-    if (n_tiles == 0)
-        return hipSuccess;
-    const size_t lds = lds_bytes(args.passes);
-    if (stats)
-        hipLaunchKernelGGL(scan_batch_kernel<true>, dim3(n_tiles), dim3(kThreads), lds, stream, args, segs, tile_seg);
-    else
-        hipLaunchKernelGGL(scan_batch_kernel<false>, dim3(n_tiles), dim3(kThreads), lds, stream, args, segs, tile_seg);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : launch_report(args, stream);
+    return launch_batch_tiles(scan_batch_kernel<true>, scan_batch_kernel<false>, args, segs, tile_seg, n_tiles, stats, stream);
 }
 
 } // namespace adsb

@@ -16,55 +16,9 @@
 
 #include "scan_kernel.h"
 #include "scan_stages.h"
+#include "scan_tile.h" // the tile shell, the stagger, the launchers (after scan_stages.h: see there)
 
 namespace adsb {
-
-// One tile of either entry: the planes' pad words, Stage A, a barrier, Stage B, the profile clocks.
-template <bool kStats>
-__device__ __forceinline__ void scan_iq_tile(const ScanArgs &args, const int K, const int64_t t0, const uint64_t prof_begin, uint32_t *smem)
-{
-    const int nplane = kPassRuns * K + kPlanePad;
-    uint32_t *pl_d = smem;
-    uint32_t *pl_e1 = smem + nplane;
-    uint32_t *pl_e2 = smem + 2 * nplane;
-    uint32_t *queue = smem + 3 * nplane;
-    uint32_t *qcount = queue + kQueueCap;
-    uint32_t *cl_rec = qcount + 16; // kClistCap records of kCandWords
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-
-    // plane words past the last computed run are read (never used) by Stage B
-    if (tid < kPlanePad) {
-        pl_d[kPassRuns * K + tid] = 0;
-        pl_e1[kPassRuns * K + tid] = 0;
-        pl_e2[kPassRuns * K + tid] = 0;
-    }
-
-    uint64_t stamp_last = 0;
-    stage_a_iq(args.x, args.pbuf0, args.p_lo, args.p_hi, t0, K, wave, lane, pl_d, pl_e1, pl_e2);
-    __syncthreads();
-    stage_b<kStats, kFrontIq>(args, blockIdx.x, K, t0, tid, pl_d, pl_e1, pl_e2, queue, qcount, cl_rec, args.clist_cap, stamp_last);
-
-    if (args.profile) { // the launch's duration is (latest tile end) - (earliest tile start)
-        __syncthreads();
-        if (tid == 64) { // not wave 0: that one has just issued the tile's write-through stores
-            unsigned long long *c64 = reinterpret_cast<unsigned long long *>(args.counters);
-            atomicMax(&c64[2 * kCounterPad], ~(unsigned long long)prof_begin); // = counters 4 and 5
-            atomicMax(&c64[(5 * kCounterPad) / 2], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-        }
-    }
-}
-
-// (scan_kernel's stagger of the workgroups that start together on a CU)
-__device__ __forceinline__ void stagger_start()
-{
-    if (gridDim.x >= 256u * kMinWaves * 4 / kWaves && blockIdx.x < 256u * kMinWaves * 4 / kWaves) {
-        const uint32_t slot = blockIdx.x >> 8;
-        for (uint32_t i = 0; i < slot; i++)
-            __builtin_amdgcn_s_sleep(kSleepStagger);
-    }
-}
 
 // scan_kernel for complex samples: the tiles partition one stream
 template <bool kStats>
@@ -76,7 +30,7 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void scan_iq_kernel(const Scan
     const uint64_t prof_begin = args.profile ? __builtin_amdgcn_s_memrealtime() : 0;
     const int64_t t0 = // first owned offset
         (int64_t)args.g_begin + (int64_t)kRun * (int64_t)tile_first_run(blockIdx.x, args.big_tiles, args.passes);
-    scan_iq_tile<kStats>(args, K, t0, prof_begin, smem);
+    scan_tile<kStats, kFrontIq>(args, K, t0, prof_begin, smem);
 }
 
 // scan_batch_kernel for complex samples: the tiles belong to the captures of a batch (scan_kernel.h BatchSeg)
@@ -96,35 +50,18 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void scan_iq_batch_kernel(cons
     args.p_hi = sg.p_hi;
     args.g_end = sg.g_end;
     const int64_t t0 = (int64_t)sg.g_begin + (int64_t)kRun * (int64_t)tile_first_run(blockIdx.x - sg.first_tile, 0u, K);
-    scan_iq_tile<kStats>(args, K, t0, prof_begin, smem);
+    scan_tile<kStats, kFrontIq>(args, K, t0, prof_begin, smem);
 }
 
 hipError_t launch_scan_iq(const ScanArgs &args, bool stats, hipStream_t stream)
 {
-    if (args.g_end <= args.g_begin)
-        return hipSuccess;
-    const unsigned blocks = tile_count(args.g_end - args.g_begin, args.big_tiles, args.passes);
-    const size_t lds = lds_bytes(args.passes);
-    if (stats)
-        hipLaunchKernelGGL(scan_iq_kernel<true>, dim3(blocks), dim3(kThreads), lds, stream, args);
-    else
-        hipLaunchKernelGGL(scan_iq_kernel<false>, dim3(blocks), dim3(kThreads), lds, stream, args);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : launch_report(args, stream);
+    return launch_stream_tiles(scan_iq_kernel<true>, scan_iq_kernel<false>, args, stats, stream);
 }
 
 hipError_t launch_scan_batch_iq(const ScanArgs &args, const BatchSeg *segs, const uint32_t *tile_seg, uint32_t n_tiles, bool stats,
                                 hipStream_t stream)
 {
-    if (n_tiles == 0)
-        return hipSuccess;
-    const size_t lds = lds_bytes(args.passes);
-    if (stats)
-        hipLaunchKernelGGL(scan_iq_batch_kernel<true>, dim3(n_tiles), dim3(kThreads), lds, stream, args, segs, tile_seg);
-    else
-        hipLaunchKernelGGL(scan_iq_batch_kernel<false>, dim3(n_tiles), dim3(kThreads), lds, stream, args, segs, tile_seg);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : launch_report(args, stream);
+    return launch_batch_tiles(scan_iq_batch_kernel<true>, scan_iq_batch_kernel<false>, args, segs, tile_seg, n_tiles, stats, stream);
 }
 
 } // namespace adsb

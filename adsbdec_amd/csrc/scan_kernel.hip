@@ -71,67 +71,23 @@
 #include "slicer_bits.h"
 #include "scan_stamps.h" // ADSB_STAMP / ADSB_COUNT: nothing in the shipped build (a measurement build's per-phase tile clocks)
 #include "scan_stages.h" // stage_a, stage_b and what they use
+#include "scan_tile.h"   // the tile shell, the stagger, the launcher (after scan_stages.h: see there)
 
 namespace adsb {
 
-// The classic kernel: one workgroup of four waves per tile; Stage A, a barrier, Stage B between barriers.
+// The classic kernel: one workgroup of four waves per tile; Stage A, a barrier, Stage B between barriers (scan_tile.h).
+// (Over scan_tile the kernel differs from its own former lines at three sites that run once per tile; timed against them,
+// interleaved, inside the run's A/A: profiles/r31_tile_shell_isa_identity.txt, r31_tile_shell_ab.txt.)
 template <bool kStats>
 __global__ __launch_bounds__(kThreads, kMinWaves) void scan_kernel(const ScanArgs args)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int K = tile_passes(blockIdx.x, args.big_tiles, args.passes);
-    const int nplane = kPassRuns * K + kPlanePad;
-    uint32_t *pl_d = smem;
-    uint32_t *pl_e1 = smem + nplane;
-    uint32_t *pl_e2 = smem + 2 * nplane;
-    uint32_t *queue = smem + 3 * nplane;
-    uint32_t *qcount = queue + kQueueCap;
-    uint32_t *cl_rec = qcount + 16; // kClistCap records of kCandWords
-
-    const int tid = threadIdx.x;
-    // The kMinWaves workgroups that start together on a CU at the head of a large launch (blocks b, b + 256, b + 512,
-    // ... with the observed round-robin placement; nothing depends on it) begin 0, 1, 2, ... x kSleepStagger x 64 cycles
-    // apart (2.6 us steps), so that their load phases do not coincide from the first pass on.  Measured in bench.py
-    // with four per CU: -3.2 .. -4.0 % kernel time on one MI355X box, +-0.5 % on another; steps of 1.2 us did nothing,
-    // steps of 3.7 us and more were worse than 2.6.  With five per CU (96 VGPRs since round 4) and only the first four
-    // staggered the step was 3 % slower than with all five (profiles/r4_ab_runs.txt section 7).
-    if (gridDim.x >= 256u * kMinWaves * 4 / kWaves && blockIdx.x < 256u * kMinWaves * 4 / kWaves) {
-        const uint32_t slot = blockIdx.x >> 8;
-        for (uint32_t i = 0; i < slot; i++)
-            __builtin_amdgcn_s_sleep(kSleepStagger);
-    }
-    // cfg.profile: the launch's duration is (latest tile end) - (earliest tile start)
-    const uint64_t prof_begin = args.profile ? __builtin_amdgcn_s_memrealtime() : 0;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    stagger_start();
+    const uint64_t prof_begin = args.profile ? __builtin_amdgcn_s_memrealtime() : 0; // (the launch's duration: scan_tile's last lines)
     const int64_t t0 = // first owned offset
         (int64_t)args.g_begin + (int64_t)kRun * (int64_t)tile_first_run(blockIdx.x, args.big_tiles, args.passes);
-
-    // plane words past the last computed run are read (never used) by Stage B
-    if (tid < kPlanePad) {
-        pl_d[kPassRuns * K + tid] = 0;
-        pl_e1[kPassRuns * K + tid] = 0;
-        pl_e2[kPassRuns * K + tid] = 0;
-    }
-
-    // kernel arguments are only ever used by value (taking their address would
-    // demote the sample pointer to a flat/scratch access)
-    ADSB_STAMP_BEGIN();
-    stage_a(args.x, args.pbuf0, args.p_lo, args.p_hi, t0, K, wave, lane, pl_d, pl_e1, pl_e2);
-    __syncthreads();
-    ADSB_STAMP(1); // Stage A
-    ADSB_COUNT(0, 1);
-    stage_b<kStats>(args, blockIdx.x, K, t0, tid, pl_d, pl_e1, pl_e2, queue, qcount, cl_rec, args.clist_cap, stamp_last);
-    ADSB_STAMP_END(13); // the marker
-
-    if (args.profile) { // the launch's duration is (latest tile end) - (earliest tile start)
-        __syncthreads();
-        if (tid == 64) { // not wave 0: that one has just issued the tile's write-through stores
-            unsigned long long *c64 = reinterpret_cast<unsigned long long *>(args.counters);
-            atomicMax(&c64[2 * kCounterPad], ~(unsigned long long)prof_begin); // = counters 4 and 5
-            atomicMax(&c64[(5 * kCounterPad) / 2], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-        }
-    }
+    scan_tile<kStats, kFrontReal>(args, K, t0, prof_begin, smem);
 }
 
 // Behind every scan launch, one wave: hand the launch counters to the host (two
@@ -445,17 +401,7 @@ hipError_t launch_report(const ScanArgs &args, hipStream_t stream)
 
 hipError_t launch_scan(const ScanArgs &args, bool stats, hipStream_t stream)
 {
-    if (args.g_end <= args.g_begin)
-        return hipSuccess;
-    const unsigned blocks = tile_count(args.g_end - args.g_begin, args.big_tiles, args.passes);
-    const size_t lds = lds_bytes(args.passes);
-    if (stats)
-        hipLaunchKernelGGL(scan_kernel<true>, dim3(blocks), dim3(kThreads), lds, stream, args);
-    else
-        hipLaunchKernelGGL(scan_kernel<false>, dim3(blocks), dim3(kThreads), lds, stream, args);
-    if (args.report)
-        hipLaunchKernelGGL(report_kernel, dim3(1), dim3(64), 0, stream, args.counters, args.report, args.gen);
-    return hipGetLastError();
+    return launch_stream_tiles(scan_kernel<true>, scan_kernel<false>, args, stats, stream);
 }
 
 } // namespace adsb

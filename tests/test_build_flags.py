@@ -73,7 +73,7 @@ def test_shipped_library_reads_no_environment():
     assert not [n for n in names if n.startswith("ADSB_")]
     dyn = subprocess.run(["nm", "-D", "--undefined-only", lib], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in dyn
-    for f in ("scan_kernel.hip", "scan_kernel.h"):
+    for f in ("scan_kernel.hip", "scan_kernel.h", "scan_tile.h"):
         src = open(os.path.join(ROOT, "adsbdec_amd", "csrc", f)).read()
         assert "#if" not in src.replace("#ifndef ADSBDEC", ""), f
     # The ONE knob the kernel source has lives in a header of its own: the per-phase tile clocks of a measurement build

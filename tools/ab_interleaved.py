@@ -8,7 +8,7 @@ Separate processes on the same box differ by 2-3 % from run to run (clock govern
 than most of the changes round 6 tried.  Here every build is dlopen'ed side by side (they share the one HIP runtime), each
 gets its own handle, and the rounds go A B C A B C ..: `--steps` decodes of the same device-resident capture per build and
 round, timed by the kernel's own clock (adsb_profile.big_ms / big_launches).  Prints the median, the quartiles and the
-per-round ratio to the first build.
+per-round ratio to the first build with its quartiles (those of a build loaded twice, an A/A, are the run's own noise).
 """
 import ctypes as C
 import os
@@ -127,10 +127,11 @@ def main():
     for name, _, _ in hs:
         v = sorted(per[name])
         q = statistics.quantiles(v, n=4)
-        ratio = statistics.median(a / b for a, b in zip(per[name], base))
+        ratios = [a / b for a, b in zip(per[name], base)]
+        ratio, rq = statistics.median(ratios), statistics.quantiles(ratios, n=4)  # (the quartiles of an A/A pair: the run's own noise)
         wr = statistics.median(a / b for a, b in zip(wall[name], wall[hs[0][0]]))
         print(f"  {name:10s} median {statistics.median(v):.5f}  quartiles {q[0]:.5f} .. {q[2]:.5f}  min {v[0]:.5f}  ratio to {hs[0][0]} (median of rounds) {ratio:.4f}"
-              f"  | call {statistics.median(wall[name]):.5f} ms, ratio {wr:.4f}")
+              f"  | call {statistics.median(wall[name]):.5f} ms, ratio {wr:.4f}  | the rounds' kernel ratios: quartiles {rq[0]:.4f} .. {rq[2]:.4f}")
     for name, L, h in hs:
         L.adsb_destroy(h)
 
