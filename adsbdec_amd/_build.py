@@ -26,7 +26,7 @@ HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip",
                "convert_samples.hip", "power_export_kernel.hip", "decoder_export.hip",
                "power_export_batch_kernel.hip", "decoder_export_batch.hip", "level_kernel.hip", "decoder_level.hip",
                "level_batch_kernel.hip", "decoder_level_batch.hip", "level_windows_kernel.hip", "decoder_level_windows.hip", "decoder_stage.hip",
-               "burst_kernel.hip", "decoder_bursts.hip"]
+               "burst_kernel.hip", "decoder_bursts.hip", "gather_kernel.hip", "decoder_gather.hip"]
 C_SOURCES = ["format.c"]
 # host-only C++ (no HIP): the multi-GPU driver over the C-ABI, and the part of the C-ABI that needs no device
 CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]
@@ -108,10 +108,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-lm", "-lpthread"])
     cli_src = os.path.join(CSRC, "cli", "adsbdec_amd_cli.c")
     sink_src = os.path.join(CSRC, "cli", "sink.c")
-    if os.path.exists(cli_src) and (force or _newer(CLI, [cli_src, sink_src, os.path.join(CSRC, "cli", "sink.h"), LIB,
+    brs_src = os.path.join(CSRC, "cli", "burst_archive.c")  # the burst archive's reader and writer (-K, -k)
+    if os.path.exists(cli_src) and (force or _newer(CLI, [cli_src, sink_src, os.path.join(CSRC, "cli", "sink.h"), brs_src,
+                                                           os.path.join(CSRC, "cli", "burst_archive.h"), LIB,
                                                            os.path.join(ROOT, "include", "adsbdec_amd.h")])):
         # (the HIP runtime's C API: the device buffer of the program's own that -W -q exports through)
-        _run(["gcc", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__", "-o", CLI, cli_src, sink_src, "-I", os.path.join(ROOT, "include"),
+        _run(["gcc", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__", "-o", CLI, cli_src, sink_src, brs_src, "-I", os.path.join(ROOT, "include"),
               "-I", os.path.join(ROCM, "include"), "-L", LIBDIR, "-ladsbdec_amd", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-lpthread",
               "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ROCM, "lib")])
     return LIB

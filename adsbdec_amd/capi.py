@@ -256,6 +256,10 @@ SYMBOLS = {
     "adsb_bursts_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     "adsb_bursts_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     "adsb_burst_tile_runs": (C.c_uint32, []),
+    "adsb_gather_layout": (C.c_long, [C.c_uint64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "adsb_gather_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    "adsb_gather_chunk_words": (C.c_uint32, []),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -1166,6 +1170,19 @@ class Decoder:
             raise AdsbError("adsb_level_percentile: an empty histogram, or q outside [0, 1]")
         return self.bursts_host(rep["env"], float(np.float32(factor * float(p))), lead, hang)
 
+    # ---- a capture's bursts as one array (include/adsbdec_amd.h: adsb_gather_*; adsbdec_amd.burst_archive.gather is the statement)
+    def gather_device(self, ptr: int, capture_bytes: int, sample_bytes: int, m: int, bursts, out_ptr: int, out_cap: int):
+        """adsb_gather_device: the pieces that the burst table names, of the capture in HBM at ptr, packed into out_ptr (both 16-byte
+        aligned) -> offsets, a uint64 array of len(bursts) + 1 byte offsets; offsets[-1] is the total the call returned."""
+        b = _burst_table(bursts)
+        off = np.zeros(b.size + 1, dtype=np.uint64)
+        total = self._L.adsb_gather_device(self._h, ptr or None, capture_bytes, sample_bytes, m, b.ctypes.data if b.size else None, b.size,
+                                           out_ptr or None, out_cap, off.ctypes.data)
+        if total < 0:
+            self._check(-1, "adsb_gather_device")
+        assert total == int(off[-1])
+        return off
+
     def format_report(self):
         """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""
         r = FormatReport()
@@ -1474,6 +1491,29 @@ def plan_shards(total_samples: int, n_shards: int):
         raise AdsbError("adsb_plan_shards failed")
     return [dict(g_begin=int(arrs[0][i]), g_end=int(arrs[1][i]), first_sample=int(arrs[2][i]),
                  n_samples=int(arrs[3][i])) for i in range(n_shards)]
+
+
+def _burst_table(bursts) -> np.ndarray:
+    from .levels import BURST_DTYPE
+    return np.ascontiguousarray(np.asarray(bursts, dtype=BURST_DTYPE).reshape(-1))
+
+
+def gather_layout(bursts, m: int, sample_bytes: int) -> np.ndarray:
+    """adsb_gather_layout (no device): the byte offsets of the pieces of a burst table in what adsb_gather_device writes, a uint64
+    array of len(bursts) + 1; offsets[-1] is the total.  AdsbError, naming the record, where the call refuses."""
+    L = load()
+    b = _burst_table(bursts)
+    off = np.zeros(b.size + 1, dtype=np.uint64)
+    total = C.c_uint64(0)
+    if L.adsb_gather_layout(m, sample_bytes, b.ctypes.data if b.size else None, b.size, off.ctypes.data, C.byref(total)) != 0:
+        raise AdsbError((L.adsb_last_error(None) or b"").decode())
+    assert int(total.value) == int(off[-1])
+    return off
+
+
+def gather_chunk_words() -> int:
+    """adsb_gather_chunk_words: C, the 16-byte output words one workgroup of the gather kernel takes at once."""
+    return int(load().adsb_gather_chunk_words())
 
 
 def burst_tile_runs() -> int:

@@ -60,6 +60,20 @@
  *                   piece shorter than that decodes nothing; 1468 runs are 41 104 power samples behind the last hot run.  The values
  *                   rest on that ONE fixture, not on a measurement of live traffic.  Every flavour -L reads; not with -I.
  *                   Pieces that are decoded with -E (a flush handle) need no such length: hang 4 is enough there.
+ *     -K out.brs    EXTENSION, with -L -U: KEEP ONLY THE BURSTS (adsb_gather_device).  Behind -L's report and -U's lines the pieces the gate
+ *                   found are packed, on the GPU and out of the capture the level call has already read in HBM, into one array -- piece i
+ *                   is the capture's own bytes of power samples [28 begin_i, min(28 end_i, M)), each piece from a multiple of 16 bytes on,
+ *                   pad bytes zero -- copied back in ONE device-to-host copy and written to out.brs: a burst archive (burst_archive.h;
+ *                   adsbdec_amd/burst_archive.py reads and writes the same bytes).  On stderr `kept B bursts, X of Y bytes`.  A uint16 file,
+ *                   -q 2 | 0 | 8 or -w.  Not without -L -U; not with -t or -p (their pieces are not in the capture's own bytes), -I (one
+ *                   file, one call: bursts are not joined across pieces), -G, -B or -W.
+ *     -k            EXTENSION: the file of -f is a BURST ARCHIVE.  Its pieces are decoded by ONE adsb_decode_batch_host* call of the
+ *                   archive's kind on a flush handle (a piece is far below the end-of-file horizon, so each is decoded as -E decodes a
+ *                   file: as its silent twin); the packets are printed in order with positions in the original capture: g + 28 begin_i
+ *                   is exact, the timestamp ts + 28 begin_i is the original's only up to what the frames accepted before the piece had
+ *                   jumped (demod.c:99,128,134).  The table is the sum of the pieces' tables.  -a, -m, -b, -x, -s, -l as for a capture; the
+ *                   kind comes from the header: not with -t, -p, -q, -w, -E, -G, -B, -L, -W or -K.  A file that is no archive of this
+ *                   version, or whose table and payload do not go together, is refused before any GPU call.
  *     -E            EXTENSION: DECODE TO THE LAST SAMPLE (adsb_set_flush).  The reference never scans the last ~41 k power samples of a
  *                   file -- deqframe runs only once 40 980 power samples are buffered (air.c:94-99) and scans idx < len - 1200
  *                   (demod.c:89) -- and a file below 81 960 samples decodes nothing.  With -E the packets and the table are what the
@@ -109,6 +123,7 @@
 #include <hip/hip_runtime_api.h> /* -W -q: a device buffer of this program's own (three calls) */
 
 #include "adsbdec_amd.h"
+#include "burst_archive.h"
 #include "sink.h"
 
 /* fileInput (air.c:217-246) reads 2 MiB at a time into one buffer and decodes it before the
@@ -218,7 +233,9 @@ static void usage(void)
     printf("        adsbdec_amd_cli [-q type] [-d gpu] -W out.pw -f filename\n");
     printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -f filename\n");
     printf("        adsbdec_amd_cli [-d gpu] -L -I ms -f filename\n");
-    printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -U factor[,lead[,hang]] -f filename\n\n");
+    printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -U factor[,lead[,hang]] -f filename\n");
+    printf("        adsbdec_amd_cli [-q type | -w] [-d gpu] -L -U factor[,lead[,hang]] -K out.brs -f filename\n");
+    printf("        adsbdec_amd_cli [-a] [-m] [-b] [-x] [-s addr[:port] | -l addr[:port]] [-d gpu] -k -f in.brs\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
     printf("\t-b : output binary beast format\n");
@@ -247,6 +264,14 @@ static void usage(void)
     printf("\t     line `first end hot peak` per burst, in power samples: the envelope (a float per 28 power samples) gated at factor x the\n");
     printf("\t     median, lead (default 2) and hang (default 1468: a piece must outlast the decoder's 40 980-sample horizon) runs kept; not with -I\n");
     printf("\t     (pieces decoded with -E, on a flush handle, have no horizon to outlast: hang 4 is enough for them)\n");
+    printf("\t-K out.brs : (extension) with -L -U: keep only the bursts.  Behind the report and the burst lines the pieces the gate found are\n");
+    printf("\t     gathered on the GPU out of the capture's own bytes (adsb_gather_device), copied back once and written to out.brs, a burst\n");
+    printf("\t     archive (header, burst table, the pieces each from a multiple of 16 bytes on); stderr: `kept B bursts, X of Y bytes`; a\n");
+    printf("\t     uint16, -q 2 | 0 | 8 or -w file; for an archive meant for -k, hang 4 is enough; not with -t, -p, -I, -G, -B or -W\n");
+    printf("\t-k : (extension) the file of -f is a burst archive: decode its pieces in one batch call, each to its last sample (as -E does),\n");
+    printf("\t     and print the packets in order, positions counted in the original capture (a packet's 12 MHz timestamp is the\n");
+    printf("\t     original's only up to the jumps of the frames accepted before its piece); the kind of the samples comes from the\n");
+    printf("\t     header: not with -t, -p, -q, -w, -E, -G, -B, -L, -W or -K\n");
     printf("\t-E : (extension) decode to the file's last sample: the packets and the table of the file followed by 81 960 power samples of silence,\n");
     printf("\t     instead of leaving the last ~41 k power samples unscanned as adsbdec does (a file below 81 960 samples decodes nothing there);\n");
     printf("\t     every input kind of -f, and -B on one GPU; a real file below 2^32 samples; not with -G, -L or -W\n");
@@ -823,13 +848,25 @@ struct burst_opts { /* -U: factor 0 = no gate */
     uint32_t lead, hang;
 };
 
-/* -L -U: the gate behind the report.  env: the device array of ceil(m / 28) floats the level call wrote. */
-static int print_bursts(adsb_decoder *dec, const adsb_level_report *rep, const float *d_env, uint64_t m, const struct burst_opts *u)
+/* -L -U: the gate behind the report.  env: the device array of ceil(m / 28) floats the level call wrote.  keep (-K; else NULL): the
+ * table, its length and the threshold stay with the caller, who frees the table. */
+struct kept_bursts {
+    adsb_burst *tab;
+    size_t n;
+    float threshold;
+};
+static int print_bursts(adsb_decoder *dec, const adsb_level_report *rep, const float *d_env, uint64_t m, const struct burst_opts *u,
+                        struct kept_bursts *keep)
 {
     const size_t n_env = (size_t)((m + 27) / 28);
     const float median = adsb_level_percentile(rep, 0.5);
     if (median < 0) { /* (no sign-clear sample at all: nothing to take a median of) */
         printf("bursts 0 threshold none lead %u hang %u\n", u->lead, u->hang);
+        if (keep) { /* -K: there is no threshold to gate with, so there is no archive to write; say so, and fail */
+            fflush(stdout);
+            fprintf(stderr, "-K: the capture has no sign-clear power sample, so the gate has no threshold: no archive is written\n");
+            return 255;
+        }
         return 0;
     }
     const float threshold = (float)(u->factor * median);
@@ -855,11 +892,58 @@ static int print_bursts(adsb_decoder *dec, const adsb_level_report *rep, const f
         const uint64_t first = 28ull * tab[i].begin, end = 28ull * tab[i].end < m ? 28ull * tab[i].end : m;
         printf("%llu %llu %u %.9g\n", (unsigned long long)first, (unsigned long long)end, tab[i].hot, (double)tab[i].peak);
     }
-    free(tab);
+    if (keep)
+        keep->tab = tab, keep->n = (size_t)b, keep->threshold = threshold;
+    else
+        free(tab);
     return 0;
 }
 
-static int run_level(const char *filename, int device, int kind, int fmt, const struct burst_opts *u)
+/* -K: the pieces the table names, out of the capture the level call has read in HBM -- ONE adsb_gather_device call, ONE copy back,
+ * the archive (burst_archive.h).  s: bytes per power sample of the capture's kind. */
+static int keep_bursts(adsb_decoder *dec, const char *path, const void *d_in, size_t used, uint32_t kind, uint64_t n_units, uint64_t m,
+                       const struct kept_bursts *k, const struct burst_opts *u)
+{
+    brs_archive a;
+    memset(&a, 0, sizeof a);
+    a.kind = kind, a.sample_bytes = brs_sample_bytes(kind);
+    a.n_units = n_units, a.m = m;
+    a.threshold = k->threshold, a.lead = u->lead, a.hang = u->hang;
+    a.n_bursts = k->n, a.bursts = k->tab;
+    char why[512];
+    uint64_t total = 0;
+    if (adsb_gather_layout(m, (int)a.sample_bytes, k->tab, k->n, NULL, &total) != 0) {
+        fprintf(stderr, "adsb_gather_layout() failed: %s\n", adsb_last_error(NULL));
+        return 255;
+    }
+    void *d_out = NULL;
+    unsigned char *out = (unsigned char *)malloc(total ? (size_t)total : 1);
+    int rc = 255; /* (one way out: what was allocated here is released on it) */
+    long got;
+    if (!out || (total && hipMalloc(&d_out, (size_t)total) != hipSuccess)) {
+        d_out = NULL;
+        fprintf(stderr, "cannot allocate the %llu bytes of the %zu bursts, on the host and on the device\n", (unsigned long long)total, k->n);
+    } else if ((got = adsb_gather_device(dec, d_in, used, (int)a.sample_bytes, m, k->tab, k->n, d_out, (size_t)total, NULL)) < 0 ||
+               (uint64_t)got != total) {
+        fprintf(stderr, "adsb_gather_device() failed: %s\n", got < 0 ? adsb_last_error(dec) : "another total than the layout's");
+    } else if (total && hipMemcpy(out, d_out, (size_t)total, hipMemcpyDeviceToHost) != hipSuccess) {
+        fprintf(stderr, "cannot copy the %llu bytes of the bursts back from the device\n", (unsigned long long)total);
+    } else {
+        a.payload = out, a.payload_bytes = total;
+        if (brs_write(path, &a, why, sizeof why) != 0) {
+            fprintf(stderr, "%s: %s\n", path, why);
+        } else {
+            fprintf(stderr, "kept %zu bursts, %llu of %llu bytes\n", k->n, (unsigned long long)total, (unsigned long long)(a.sample_bytes * m));
+            rc = 0;
+        }
+    }
+    if (d_out)
+        (void)hipFree(d_out);
+    free(out);
+    return rc;
+}
+
+static int run_level(const char *filename, int device, int kind, int fmt, const struct burst_opts *u, const char *archive_out)
 {
     const int fd = open(filename, O_RDONLY);
     struct stat sb;
@@ -924,7 +1008,14 @@ static int run_level(const char *filename, int device, int kind, int fmt, const 
     }
     print_level_report(rep);
     if (gate) {
-        const int rc = print_bursts(dec, rep, d_env, (uint64_t)got, u);
+        struct kept_bursts kept = {NULL, 0, 0};
+        int rc = print_bursts(dec, rep, d_env, (uint64_t)got, u, archive_out ? &kept : NULL);
+        if (rc == 0 && archive_out) { /* (main has refused -K with -t and -p: kind is 0, 3 or 4 here) */
+            fflush(stdout);
+            rc = keep_bursts(dec, archive_out, d_in, used, kind == 0 ? BRS_KIND_UINT16_REAL : kind == 4 ? BRS_KIND_FLOAT32_POWER : (uint32_t)fmt,
+                             (uint64_t)n, (uint64_t)got, &kept, u);
+        }
+        free(kept.tab);
         if (rc) {
             fflush(stdout);
             return rc;
@@ -1031,6 +1122,93 @@ static int run_level_windows(const char *filename, int device, double ms)
     _exit(0); /* (no teardown: see the end of main) */
 }
 
+/* -k: decode a burst archive.  The pieces go through ONE adsb_decode_batch_host* call of the archive's kind on a flush handle (a piece
+ * is far below the end-of-file horizon), pointers payload + offsets[i]; piece i's packets are its silent twin's, written in order with
+ * g + 28 begin_i -- exact -- and ts + 28 begin_i: in the original stream ts lags g by what accepted frames have jumped
+ * (demod.c:99,128,134), so this is the original's ts only up to those jumps.  The table is the sum of the pieces' tables. */
+static int run_archive(const char *filename, const adsb_config *cfg, int outformat)
+{
+    brs_archive a;
+    char why[512];
+    if (brs_read(filename, &a, why, sizeof why) != 0) {
+        fprintf(stderr, "%s: %s\n", filename, why);
+        return 255;
+    }
+    const size_t nb = (size_t)a.n_bursts;
+    const void **piece = (const void **)calloc(nb + 1, sizeof *piece);
+    size_t *n = (size_t *)calloc(nb + 1, sizeof *n);
+    uint64_t *first = (uint64_t *)calloc(nb + 1, sizeof *first);
+    adsb_stats *st = (adsb_stats *)calloc(nb + 1, sizeof *st);
+    if (!piece || !n || !first || !st) {
+        fprintf(stderr, "out of memory for the results of %zu pieces\n", nb);
+        return 255;
+    }
+    const uint64_t per = brs_units_per_power_sample(a.kind);
+    for (size_t i = 0; i < nb; i++) {
+        const uint64_t lo = 28ull * a.bursts[i].begin, hi = 28ull * a.bursts[i].end < a.m ? 28ull * a.bursts[i].end : a.m;
+        piece[i] = a.payload + a.offsets[i];
+        n[i] = (size_t)(per * (hi - lo));
+    }
+    {
+        const int prc = sink_wait_peer(&out_sink);
+        if (prc == 2) { /* told to end before a peer came */
+            adsb_stats z;
+            memset(&z, 0, sizeof z);
+            print_stats(&z);
+            fflush(stderr);
+            _exit(0);
+        }
+        if (prc != 0)
+            return 255;
+    }
+    adsb_decoder *dec = adsb_create(cfg);
+    if (!dec) {
+        fprintf(stderr, "adsb_create() failed: %s\n", adsb_last_error(NULL));
+        return 255;
+    }
+    if (adsb_set_flush(dec, 1) != 0) {
+        fprintf(stderr, "adsb_set_flush() failed: %s\n", adsb_last_error(dec));
+        return 255;
+    }
+    const adsb_frame *fr = NULL;
+    long total = 0;
+    if (nb)
+        total = a.kind == BRS_KIND_UINT16_REAL      ? adsb_decode_batch_host(dec, nb, (const uint16_t *const *)piece, n, &fr, first, st)
+                : a.kind == BRS_KIND_FLOAT32_POWER ? adsb_decode_batch_host_power(dec, nb, (const float *const *)piece, n, &fr, first, st)
+                                                   : adsb_decode_batch_host_iq(dec, (int)a.kind, nb, piece, n, &fr, first, st);
+    if (total < 0) {
+        fprintf(stderr, "the batch decode of the archive's %zu pieces failed: %s\n", nb, adsb_last_error(dec));
+        return 255;
+    }
+    int rc = 0;
+    adsb_stats sum;
+    memset(&sum, 0, sizeof sum);
+    adsb_frame *mine = (adsb_frame *)malloc((total ? (size_t)total : 1) * sizeof *mine);
+    if (!mine) {
+        fprintf(stderr, "out of memory for %ld packets\n", total);
+        return 255;
+    }
+    for (size_t i = 0; i < nb; i++) {
+        const uint64_t shift = 28ull * a.bursts[i].begin;
+        for (uint64_t k = first[i]; k < first[i + 1]; k++) {
+            mine[k] = fr[k];
+            mine[k].g += shift, mine[k].ts += shift;
+        }
+        for (int j = 0; j < 3; j++)
+            sum.try_[j] += st[i].try_[j], sum.ok[j] += st[i].ok[j];
+        sum.fixed += st[i].fixed;
+    }
+    if (write_frames(&out_sink, mine, total, outformat) != 0)
+        rc = 1;
+    if (sink_close(&out_sink) != 0 && rc == 0)
+        rc = 1;
+    print_stats(&sum);
+    fflush(stderr);
+    if (getenv("ADSB_CLI_CLEAN_EXIT"))
+        exit(rc);
+    _exit(rc); /* (no teardown: see the end of main) */
+}
+
 int main(int argc, char **argv)
 {
     const char *filename = NULL, *listfile = NULL, *export_path = NULL;
@@ -1039,6 +1217,8 @@ int main(int argc, char **argv)
     int outformat = 0, df18 = 0, fix1 = 0, packed = 0, power = 0, level = 0, flush = 0, c;
     const char *burst_arg = NULL; /* -U: -L's gate, factor[,lead[,hang]] */
     struct burst_opts burst = {0, 2, 1468};
+    const char *archive_out = NULL; /* -K: keep only the bursts of -L -U, as a burst archive */
+    int archive_in = 0;             /* -k: the file of -f is a burst archive */
     const char *interval_arg = NULL; /* -I: -L's windows, in milliseconds */
     double interval_ms = 0;
     long stype = 5; /* -t: ADSB_FMT_RAW */
@@ -1048,7 +1228,7 @@ int main(int argc, char **argv)
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:E")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:EK:k")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -1115,6 +1295,12 @@ int main(int argc, char **argv)
         case 'E':
             flush = 1;
             break;
+        case 'K':
+            archive_out = optarg;
+            break;
+        case 'k':
+            archive_in = 1;
+            break;
         case 'I': {
             char *end;
             interval_ms = strtod(optarg, &end);
@@ -1159,6 +1345,31 @@ int main(int argc, char **argv)
             usage();
             return 1;
         }
+    }
+    if (archive_in && (stype_arg || packed || qtype_arg || power || flush || ndev || listfile || level || export_path || archive_out || nfiles > 1)) {
+        /* -k decodes a burst archive, whose header says what it holds: refused before any GPU call */
+        fprintf(stderr, "-k is not supported with %s: %s\n",
+                stype_arg ? "-t" : packed ? "-p" : qtype_arg ? "-q" : power ? "-w" : flush ? "-E" : ndev ? "-G" : listfile ? "-B" : level ? "-L"
+                : export_path ? "-W" : archive_out ? "-K" : "several -f",
+                stype_arg || packed || qtype_arg || power ? "the kind of the samples comes from the archive's header"
+                : flush                                    ? "an archive is always decoded to the last sample of every piece"
+                : ndev || listfile                         ? "an archive is decoded on one GPU (-d) by one batch call: no multi-GPU and no list form"
+                : level || export_path || archive_out      ? "the pieces of an archive are decoded, not measured, exported or gathered again"
+                                                           : "one archive at a time");
+        return 1;
+    }
+    if (archive_out && (!level || !burst_arg || stype_arg || packed || interval_arg || ndev || listfile || export_path)) {
+        /* -K keeps the pieces -L -U finds, out of the capture's own bytes: refused before any GPU call */
+        if (!level || !burst_arg)
+            fprintf(stderr, "-K is not supported without -L -U: it keeps the bursts that the gate behind the level report finds\n");
+        else
+            fprintf(stderr, "-K is not supported with %s: %s\n",
+                    stype_arg ? "-t" : packed ? "-p" : interval_arg ? "-I" : ndev ? "-G" : listfile ? "-B" : "-W",
+                    stype_arg || packed ? "the pieces of a converted or packed capture are not in the capture's own bytes (adsb_gather_device reads those)"
+                    : interval_arg      ? "the windows are pieces of a stream, and joining bursts across pieces is the caller's: one file, one call"
+                    : ndev || listfile  ? "the gather runs on one GPU (-d), one file at a time: no batch and no multi-GPU form"
+                                        : "a run writes the power samples or keeps the capture's bursts, not both");
+        return 1;
     }
     if (flush && (ndev || level || export_path)) {
         /* -E ends a decode on one GPU past the horizon: refused before any GPU call */
@@ -1296,7 +1507,7 @@ int main(int argc, char **argv)
         }
         if (interval_arg)
             return run_level_windows(filename, device, interval_ms);
-        return run_level(filename, device, converted ? 1 : packed ? 2 : iq ? 3 : power ? 4 : 0, iq ? (int)qtype : (int)stype, &burst);
+        return run_level(filename, device, converted ? 1 : packed ? 2 : iq ? 3 : power ? 4 : 0, iq ? (int)qtype : (int)stype, &burst, archive_out);
     }
     if (export_path) {
         install_signals();
@@ -1307,6 +1518,26 @@ int main(int argc, char **argv)
             restrict_visible_devices(&first, 1);
         }
         return run_export(filename, export_path, device, iq, (int)qtype);
+    }
+    if (archive_in) {
+        install_signals();
+        sink_init(&out_sink, outmode, rawaddr);
+        out_sink.stop = &stop_requested;
+        if (getenv("ADSB_CLI_RETRY_S"))
+            out_sink.retry_s = (unsigned)atoi(getenv("ADSB_CLI_RETRY_S"));
+        if (device >= 0) {
+            restrict_visible_devices(&device, 1);
+        } else if (!getenv("ROCR_VISIBLE_DEVICES") && !getenv("HIP_VISIBLE_DEVICES") && !getenv("ADSB_CLI_ALL_DEVICES")) {
+            int first = 0;
+            restrict_visible_devices(&first, 1);
+        }
+        adsb_config kcfg;
+        adsb_config_default(&kcfg);
+        kcfg.df18 = df18;
+        kcfg.fix_1bit = fix1;
+        kcfg.collect_stats = 1; /* the reference always prints Try/Ok */
+        kcfg.device = device;
+        return run_archive(filename, &kcfg, outformat);
     }
     if (packed && ndev) {
         fprintf(stderr, "-p (packed 12-bit input) is not supported with -G: the multi-GPU driver reads uint16 files only\n");

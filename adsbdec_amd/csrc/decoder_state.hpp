@@ -11,6 +11,7 @@
 //   decoder_level_batch.hip  the batch level calls (adsb_level_batch_*): the reports of N captures by one launch per sub-batch
 //   decoder_level_windows.hip  the window form (adsb_level_windows*): the reports of K consecutive windows of one stream
 //   decoder_bursts.hip     the gate behind the envelope (adsb_bursts_*): an envelope's bursts as an ordered table
+//   decoder_gather.hip     a capture's bursts as one array (adsb_gather_device): the pieces of a burst table, packed by one launch
 //   decoder_stage.hip      the staging steps every family calls: samples into unpacked, batch_in, batch_land, batch_unpacked, win_buf, pow_buf
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
@@ -336,6 +337,9 @@ struct adsb_decoder {
     adsb::Buf<uint32_t> burst_scratch;
     adsb::Totals<uint32_t> burst_total;
     adsb::Buf<uint32_t> burst_tab;
+    // a capture's bursts as one array (adsb_gather_device, decoder_gather.hip; gather.h): the row table of one call, filled in the
+    // pinned half and uploaded on the scan stream
+    adsb::Table gather_tab;
 
     int fail(const char *fmt, ...)
     {

@@ -10,6 +10,7 @@
 
 #include "../../include/adsbdec_amd_diag.h"
 #include "batch.hpp"
+#include "gather.h"
 #include "handoff.hpp"
 #include "resolver.hpp"
 #include "stitch.hpp"
@@ -49,6 +50,11 @@ uint64_t tile_first_offset(uint32_t tile, uint32_t big_tiles, int k)
     return big_tiles * adsb::batch_tile_offsets(k) + (tile - big_tiles) * adsb::batch_tile_offsets(kTaper);
 }
 } // namespace
+
+// decoder_lifecycle.hip: what adsb_last_error(NULL) shows.  Weak: this file also builds into harnesses that have no decoder.
+namespace adsb {
+__attribute__((weak, visibility("hidden"))) void set_create_error(const char *why);
+}
 
 extern "C" {
 
@@ -91,6 +97,21 @@ float adsb_level_percentile(const adsb_level_report *r, double q)
     float f;
     std::memcpy(&f, &edge, sizeof f);
     return f;
+}
+
+// The size and the piece offsets of what adsb_gather_device writes for a burst table, without a device (gather.h gather_layout;
+// adsbdec_amd/burst_archive.py layout).  0, or -1 with adsb_last_error(NULL) naming the record.
+long adsb_gather_layout(uint64_t m, int sample_bytes, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes)
+{
+    char why[256];
+    if (adsb::gather_layout(m, sample_bytes, bursts, n_bursts, nullptr, nullptr, nullptr, why, sizeof why) == 0) // (a refusal writes nothing)
+        return adsb::gather_layout(m, sample_bytes, bursts, n_bursts, offsets, nullptr, total_bytes, why, sizeof why);
+    if (adsb::set_create_error) {
+        char msg[300];
+        snprintf(msg, sizeof msg, "adsb_gather_layout: %s", why);
+        adsb::set_create_error(msg);
+    }
+    return -1;
 }
 
 // The host side of the decoder*.hip units is built with -mavx2 (adsbdec_amd/_build.py says why); this file is not.  adsb_create asks here,

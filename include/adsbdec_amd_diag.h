@@ -355,6 +355,9 @@ int adsb_debug_set_level_batch_blocks(adsb_decoder *d, int blocks);
  * t is the runs [t T, (t + 1) T); an envelope p floats behind a 16-byte boundary has its seams p runs earlier.  What happens at a
  * seam -- a burst across it, a join or a split exactly there, empty tiles between two hot ones -- is what the tests aim at. */
 uint32_t adsb_burst_tile_runs(void);
+/* adsb_gather_device: C, the consecutive 16-byte output words one workgroup of the gather kernel takes at once (csrc/gather.h).  A chunk
+ * that holds many pieces, ends inside one, or lies inside one long piece is what the tests aim at. */
+uint32_t adsb_gather_chunk_words(void);
 
 /* ---- a batch over the devices of adsb_multi (adsb_multi_decode_batch_*; csrc/multi.cpp), without a device ------------------------
  * The plan, a pure function: n_captures captures of n[i] samples over n_workers workers.  Worker w gets the captures

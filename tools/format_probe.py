@@ -11,6 +11,7 @@ comparison interleaved.
     python tools/format_probe.py --level-windows [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/r27_level_windows.txt]   # level_windows_probe()
     python tools/format_probe.py --bursts [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/rNN_bursts.txt]   # bursts_probe(): NN is the next free round
     python tools/format_probe.py --flush [--reps 10] [--ab parent/libadsbdec_amd.so] [--out profiles/r30_flush.txt]   # flush_probe()
+    python tools/format_probe.py --gather [--reps 10] [--ab parent/libadsbdec_amd.so] [--variant name=path/to/libadsbdec_amd.so ...] [--out profiles/r32_gather.txt]   # gather_probe()
     python tools/format_probe.py --level-batch [--reps 20] [--out profiles/r26_level_batch.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_batch_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
@@ -1454,6 +1455,255 @@ def flush_probe(L, reps, lines, parent):
               "# length, beside the gate's round trips.  Pieces that share a tile are the follow-up; not built here."]
 
 
+def gather_probe(L, reps, lines, parent, variants=()):
+    """The burst gather (adsb_gather_device, gather_kernel.hip) and the burst archive, every comparison interleaved in this one process,
+    wall time of the calls, the run's A/A beside every ratio:
+    (a) the gather of the bursts the gate finds at lead 2, hang 4 on the benchmark workload and on the sparse capture, beside itself (the
+        A/A), beside a loop of one device-to-device copy per piece, a loop of one device-to-host copy per
+        piece, and the same gather written in torch on the device;
+    (b) its effective bytes per second beside adsb_power_device's, the nearest all-load-all-store kernel, with one burst that is the
+        whole capture and with the benchmark's bursts;
+    (c) archive bytes over capture bytes for both captures;
+    (d) end to end from page-locked host memory: the archive's pieces through ONE adsb_decode_batch_host on a flush handle beside the
+        host-fed decode of the whole capture (adsb_push);
+    (e) s = 2 with every begin odd beside every begin even, and the same two tables through every --variant name=path: a measurement
+        build of the library whose gather_kernel.hip loads a full word another way (-DADSB_GATHER_LOAD=0);
+    (f) adsb_level_device and adsb_decode_device beside the parent commit's library (--ab)."""
+    import numpy as np
+    from adsbdec_amd import burst_archive as BA, levels
+    out = C.POINTER(capi.Frame)()
+
+    order_rng = __import__("random").Random(32)
+
+    def rotate(sides, steps=1):
+        """Every round runs the sides in a NEW random order (seeded), so no side always runs behind the same neighbour."""
+        names = list(sides)
+        wall = {k_: [] for k_ in names}
+        for r in range(-1, reps):                            # (round -1: the warm-up)
+            order = names[:]
+            order_rng.shuffle(order)
+            for name in order:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    sides[name]()
+                if r >= 0:
+                    wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        return names, wall
+
+    def table_of(names, wall, base, note=None):
+        for name in names:
+            q = statistics.quantiles(wall[name], n=4)
+            rr = [a_ / b for a_, b in zip(wall[name], wall[base])]
+            qr = statistics.quantiles(rr, n=4)
+            lines.append(f"    {name:62s} {med(wall[name]):10.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med(rr):.4f} ({qr[0]:.4f} .. {qr[2]:.4f})"
+                         + (note(name, med(wall[name])) if note else ""))
+            print(lines[-1], flush=True)
+
+    head = "#   side                                                              call ms (q1 .. q3)               / the first side (median of rounds, q1 .. q3)"
+    M = N // 2
+    ke = -(-M // 28)
+    d = capi.Decoder()
+    flush = capi.Decoder(flush=True)
+    env = torch.zeros(ke, dtype=torch.float32, device="cuda")
+    rep1 = capi.LevelReport()
+    dst = torch.empty(2 * N, dtype=torch.uint8, device="cuda")
+    pinned = torch.empty(2 * N, dtype=torch.uint8).pin_memory()
+    t_bench = make_workload(torch, N, seed=1)[0]
+    captures = (("the benchmark workload: a frame per millisecond", t_bench),
+                ("sparse: 805 frames in 256 Mi samples", make_workload(torch, N, n_frames=805, seed=2)[0]))
+    torch.cuda.synchronize()
+    kept = {}
+    for what, cap_t in captures:
+        assert L.adsb_level_device(d._h, cap_t.data_ptr(), N, C.byref(rep1), env.data_ptr(), ke) == M
+        thr = float(np.float32(capi.Decoder.BURST_FACTOR * L.adsb_level_percentile(C.byref(rep1), 0.5)))
+        tab, b = d.bursts_device(env.data_ptr(), ke, thr, 2, 4, 1 << 16)
+        assert 0 < b <= 1 << 16
+        tab = np.ascontiguousarray(tab)
+        off = BA.layout(tab, M, 4)
+        total = int(off[-1])
+        sl = levels.burst_samples(tab, M)
+        cap_b = cap_t.view(torch.uint8)
+        src_lo, nbytes = [4 * int(lo) for lo, _ in sl], [4 * int(hi - lo) for lo, hi in sl]
+        offs = [int(o) for o in off[:-1]]
+        offp = np.zeros(b + 1, np.uint64)
+
+        def call():
+            got = L.adsb_gather_device(d._h, cap_t.data_ptr(), 2 * N, 4, M, tab.ctypes.data, b, dst.data_ptr(), 2 * N, offp.ctypes.data)
+            assert got == total, (got, capi.load().adsb_last_error(d._h))
+
+        def call_and_copy():
+            call()
+            pinned[:total].copy_(dst[:total], non_blocking=True)
+            torch.cuda.synchronize()
+
+        def loop_d2d():
+            for a_, n_, o_ in zip(src_lo, nbytes, offs):
+                dst[o_:o_ + n_].copy_(cap_b[a_:a_ + n_], non_blocking=True)
+            torch.cuda.synchronize()
+
+        def loop_d2h():
+            for a_, n_, o_ in zip(src_lo, nbytes, offs):
+                pinned[o_:o_ + n_].copy_(cap_b[a_:a_ + n_], non_blocking=True)
+            torch.cuda.synchronize()
+
+        cap_w, dst_w = cap_t.view(torch.int32), dst.view(torch.int32)     # (a piece of a real capture is whole 4-byte words)
+        lo_h = torch.tensor([v // 4 for v in src_lo], dtype=torch.int64).pin_memory()
+        n_h = torch.tensor([v // 4 for v in nbytes], dtype=torch.int64).pin_memory()
+        o_h = torch.tensor([v // 4 for v in offs], dtype=torch.int64).pin_memory()
+
+        def torch_gather():
+            lo_d, n_d, o_d = (v.cuda(non_blocking=True) for v in (lo_h, n_h, o_h))
+            first = torch.cumsum(n_d, 0) - n_d
+            k = torch.arange(int(n_h.sum()), device="cuda") - torch.repeat_interleave(first, n_d)
+            dst_w[:total // 4].zero_()
+            dst_w[torch.repeat_interleave(o_d, n_d) + k] = cap_w[torch.repeat_interleave(lo_d, n_d) + k]
+            torch.cuda.synchronize()
+
+        want, _ = BA.gather(cap_t.cpu().numpy(), tab, M, 4)
+        for side in (call, loop_d2d, torch_gather):
+            dst[:total].fill_(0xA5)
+            side()
+            assert np.array_equal(dst[:total].cpu().numpy(), want), side
+        pinned[:total].fill_(0)
+        loop_d2h()
+        assert np.array_equal(pinned[:total].numpy(), want)        # (where the pad is zero already)
+        lines += [f"# (a) {what}: {b} bursts at factor 48, lead 2, hang 4; {total} bytes of {2 * N} ({100.0 * total / (2 * N):.3f} %); every side checked",
+                  f"#     against burst_archive.gather first; {reps} rounds, the sides in a new random order every round, one call per side and round", head]
+        names, wall = rotate({"adsb_gather_device": call, "adsb_gather_device again (the A/A)": call,
+                              "adsb_gather_device + ONE device-to-host copy": call_and_copy,
+                              "loop: one device-to-device copy per piece": loop_d2d, "loop: one device-to-host copy per piece": loop_d2h,
+                              "the same gather in torch on the device": torch_gather})
+        table_of(names, wall, names[0])
+        arch = 64 + 16 * b + total
+        lines += [f"# (c) the archive: {arch} bytes (64 + 16 x {b} + {total}) over the capture's {2 * N}: {100.0 * arch / (2 * N):.3f} %", "#"]
+        kept[what] = (tab, b, total, thr)
+
+    # (b)
+    pw = torch.empty(M, dtype=torch.float32, device="cuda")
+    whole = np.zeros(1, dtype=levels.BURST_DTYPE)
+    whole[0] = (0, ke, 1, 1.0)
+    tab, b, total, _ = kept[captures[0][0]]
+
+    def export():
+        assert L.adsb_power_device(d._h, t_bench.data_ptr(), N, pw.data_ptr(), M) == M
+
+    def gather_whole():
+        assert L.adsb_gather_device(d._h, t_bench.data_ptr(), 2 * N, 4, M, whole.ctypes.data, 1, dst.data_ptr(), 2 * N, None) == 4 * M
+
+    def gather_bench():
+        assert L.adsb_gather_device(d._h, t_bench.data_ptr(), 2 * N, 4, M, tab.ctypes.data, b, dst.data_ptr(), 2 * N, None) == total
+    moved = {"adsb_power_device (2 N bytes in, 2 N out)": 4 * N, "adsb_power_device again (the A/A)": 4 * N,
+             "adsb_gather_device, one burst = the whole capture": 4 * N, "adsb_gather_device, the benchmark's bursts": 2 * total}
+    lines += ["# (b) effective bytes per second (bytes loaded + bytes stored over the call's wall time) beside adsb_power_device on the same capture", head]
+    names, wall = rotate(dict(zip(moved, (export, export, gather_whole, gather_bench))))
+    table_of(names, wall, names[0], note=lambda name, ms: f"   {moved[name] / ms / 1e9:8.3f} TB/s")
+    lines.append("#")
+    del pw
+
+    # (d)
+    host_cap = torch.empty(N, dtype=torch.int16).pin_memory()
+    host_cap.copy_(t_bench.view(torch.int16))
+    lines += ["# (d) end to end from page-locked host memory, frames in host memory at the end: ONE adsb_decode_batch_host of the archive's pieces on a",
+              "#     flush handle beside the host-fed decode of the whole capture (adsb_reset, adsb_push, adsb_finish)", head]
+    for what, cap_t in captures:
+        tab, b, total, _ = kept[what]
+        assert L.adsb_gather_device(d._h, cap_t.data_ptr(), 2 * N, 4, M, tab.ctypes.data, b, dst.data_ptr(), 2 * N, None) == total
+        pinned[:total].copy_(dst[:total])
+        host_cap.copy_(cap_t.view(torch.int16))
+        torch.cuda.synchronize()
+        off = BA.layout(tab, M, 4)
+        sl = levels.burst_samples(tab, M)
+        pp = (C.c_void_p * b)(*[pinned.data_ptr() + int(o) for o in off[:-1]])
+        nn = (C.c_size_t * b)(*[2 * int(hi - lo) for lo, hi in sl])
+        ff = (C.c_uint64 * (b + 1))()
+        state = {}
+
+        def archive_route():
+            k = L.adsb_decode_batch_host(flush._h, b, pp, nn, C.byref(out), ff, None)
+            assert k >= 0
+            state["k"] = k
+
+        def whole_route():
+            assert L.adsb_reset(d._h) == 0 and L.adsb_push(d._h, host_cap.data_ptr(), N) == 0 and L.adsb_finish(d._h) == 0
+            state["w"] = L.adsb_pending(d._h)
+            L.adsb_take(d._h, C.byref(out))
+        archive_route(), whole_route()
+        lines.append(f"#   {what}: {state['w']} frames from the whole capture, {state['k']} from the archive's {b} pieces ({total} bytes)")
+        names, wall = rotate({"adsb_push of the whole capture + adsb_finish": whole_route, "the same again (the A/A)": whole_route,
+                              "adsb_decode_batch_host of the archive's pieces, flush": archive_route})
+        table_of(names, wall, names[0])
+    lines.append("#")
+    del host_cap
+
+    # (e)
+    M8 = N                                                   # 256 Mi power samples of int8 IQ: 512 MiB, as the real capture
+    cap8 = captures[0][1].view(torch.uint8)
+    R8 = M8 // 28
+    even = np.zeros(R8 // 128, dtype=levels.BURST_DTYPE)
+    even["begin"] = 128 * np.arange(even.size)
+    even["end"] = even["begin"] + 64
+    odd = even.copy()
+    odd["begin"] += 1
+    odd["end"] += 1
+    tot8 = int(BA.layout(even, M8, 2)[-1])
+    assert tot8 == int(BA.layout(odd, M8, 2)[-1])
+
+    builds = [("tree (one 16-byte load at 8-byte alignment)", L, d._h)]
+    for spec in variants:
+        vname, _, vpath = spec.partition("=")
+        V = C.CDLL(vpath)
+        for fname in ("adsb_create", "adsb_gather_device"):
+            fn = getattr(V, fname)
+            fn.restype, fn.argtypes = capi.SYMBOLS[fname]
+        vcfg = capi.make_config()
+        vh = V.adsb_create(C.byref(vcfg))
+        assert vh, vpath
+        builds.append((vname, V, vh))
+
+    def g8(tab8, lib, h):
+        assert lib.adsb_gather_device(h, cap8.data_ptr(), 2 * N, 2, M8, tab8.ctypes.data, tab8.size, dst.data_ptr(), 2 * N, None) == tot8
+    for tab8 in (even, odd):
+        for _, lib, h in builds:
+            g8(tab8, lib, h)
+            head8 = BA.gather(cap8[:1 << 22].cpu().numpy(), tab8[:100], 1 << 21, 2)[0]           # (the first hundred pieces, checked)
+            assert np.array_equal(dst[:head8.size].cpu().numpy(), head8)
+    lines += [f"# (e) s = 2 (int8 IQ, {M8} power samples): {even.size} pieces of 64 runs, one in every 128 runs, {tot8} bytes; every begin even (each source",
+              "#     16-byte aligned) beside every begin odd (each source 8 bytes behind a 16-byte boundary); builds named with --variant differ in",
+              "#     gather_kernel.hip alone (-DADSB_GATHER_LOAD=0: an aligned source by one 16-byte load, a source 8 behind by two 8-byte loads)", head]
+    sides8 = {"begin even, tree": lambda: g8(even, L, d._h), "begin even, tree again (the A/A)": lambda: g8(even, L, d._h),
+              "begin odd, tree": lambda: g8(odd, L, d._h)}
+    for vname, lib, h in builds[1:]:
+        sides8[f"begin even, {vname}"] = lambda lib=lib, h=h: g8(even, lib, h)
+        sides8[f"begin odd, {vname}"] = lambda lib=lib, h=h: g8(odd, lib, h)
+    names, wall = rotate(sides8)
+    table_of(names, wall, names[0], note=lambda name, ms: f"   {2 * tot8 / ms / 1e9:8.3f} TB/s")
+    lines.append("#")
+
+    # (f)
+    lines += ["# (f) the untouched paths beside the parent commit's library (--ab), adsb_level_device and adsb_decode_device on the benchmark capture", head]
+    if not parent:
+        lines.append("#     (no --ab parent library given: not measured in this run)")
+        return
+    B = C.CDLL(parent)
+    for name in ("adsb_create", "adsb_decode_device", "adsb_level_device"):
+        fn = getattr(B, name)
+        fn.restype, fn.argtypes = capi.SYMBOLS[name]
+    assert not hasattr(B, "adsb_gather_device"), "the --ab library is not the parent's: it has the gather"
+    cfg = capi.make_config()
+    hh = B.adsb_create(C.byref(cfg))
+    assert hh, parent
+
+    def level(lib, h):
+        assert lib.adsb_level_device(h, t_bench.data_ptr(), N, C.byref(rep1), env.data_ptr(), ke) == M
+
+    def decode(lib, h):
+        assert lib.adsb_decode_device(h, t_bench.data_ptr(), N, C.byref(out)) >= 0
+    for what, fn, steps in (("adsb_level_device", level, 1), ("adsb_decode_device", decode, 3)):
+        names, wall = rotate({f"{what}, tree": lambda: fn(L, d._h), f"{what}, tree again (the A/A)": lambda: fn(L, d._h),
+                              f"{what}, parent commit": lambda: fn(B, hh)}, steps=steps)
+        table_of(names, wall, names[0])
+
+
 def next_round(stem):
     """profiles/rNN_<stem>.txt with the next free round number."""
     import re
@@ -1488,11 +1738,23 @@ def main():
     ap.add_argument("--level", action="store_true", help="the level report (the adsb_level_* calls) instead: profiles/r23_level.txt")
     ap.add_argument("--level-batch", action="store_true", help="the batch level report (the adsb_level_batch_* calls) against the loop of single calls instead: profiles/r26_level_batch.txt")
     ap.add_argument("--level-windows", action="store_true", help="the window form of the level report (adsb_level_windows) beside adsb_level_device instead: profiles/r27_level_windows.txt; --ab: the parent commit's library, for (c)")
-    ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB", help="with --level or --level-batch: a build of the library with another accumulation, flush or grid, measured beside the tree's")
+    ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB", help="with --level, --level-batch or --gather: a build of the library with another accumulation, flush, grid or load width, measured beside the tree's")
     ap.add_argument("--out", default=None)
     ap.add_argument("--bursts", action="store_true", help="the gate behind the envelope (adsb_bursts_device) beside a torch gate and a host gate instead: profiles/rNN_bursts.txt with the next free NN; --ab: the parent commit's library, for (c)")
     ap.add_argument("--flush", action="store_true", help="flush (adsb_set_flush): the decode call across the change, the batch of short captures, the gated pipeline: profiles/r30_flush.txt; --ab: the parent commit's library")
+    ap.add_argument("--gather", action="store_true", help="the burst gather (adsb_gather_device) beside copy loops and a torch gather, its bytes per second, the archive's size, the archive route end to end, odd against even begins (and --variant builds with another load): profiles/r32_gather.txt; --ab: the parent commit's library")
     a = ap.parse_args()
+    if a.gather:
+        a.out = a.out or os.path.join(ROOT, "profiles", "r32_gather.txt")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --gather: a capture cut down to its bursts (gather_kernel.hip, adsb_gather_device) and the burst archive, one",
+                 f"# process, {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved in a new random order every round, a warm-up round first.",
+                 "# The captures are tools/gen_signal.py make_workload, 256 Mi samples (512 MiB): seed 1 (the benchmark's) and 805 frames, seed 2 (sparse).",
+                 "# Wall time of the calls through ctypes / torch; every side waits for its kernels and copies.", "#"]
+        gather_probe(capi.load(), a.reps, lines, a.ab, a.variant)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.flush:
         a.out = a.out or os.path.join(ROOT, "profiles", "r30_flush.txt")
         torch.cuda.set_device(0)
