@@ -26,7 +26,8 @@ HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip",
                "convert_samples.hip", "power_export_kernel.hip", "decoder_export.hip",
                "power_export_batch_kernel.hip", "decoder_export_batch.hip", "level_kernel.hip", "decoder_level.hip",
                "level_batch_kernel.hip", "decoder_level_batch.hip", "level_windows_kernel.hip", "decoder_level_windows.hip", "decoder_stage.hip",
-               "burst_kernel.hip", "decoder_bursts.hip", "gather_kernel.hip", "decoder_gather.hip"]
+               "burst_kernel.hip", "decoder_bursts.hip", "gather_kernel.hip", "decoder_gather.hip",
+               "gather_pack12_kernel.hip", "decoder_gather_pack12.hip"]
 C_SOURCES = ["format.c"]
 # host-only C++ (no HIP): the multi-GPU driver over the C-ABI, and the part of the C-ABI that needs no device
 CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]
@@ -108,7 +109,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-lm", "-lpthread"])
     cli_src = os.path.join(CSRC, "cli", "adsbdec_amd_cli.c")
     sink_src = os.path.join(CSRC, "cli", "sink.c")
-    brs_src = os.path.join(CSRC, "cli", "burst_archive.c")  # the burst archive's reader and writer (-K, -k)
+    brs_src = os.path.join(CSRC, "cli", "burst_archive.c")  # the burst archive's reader and writer (-K, -P, -k)
     if os.path.exists(cli_src) and (force or _newer(CLI, [cli_src, sink_src, os.path.join(CSRC, "cli", "sink.h"), brs_src,
                                                            os.path.join(CSRC, "cli", "burst_archive.h"), LIB,
                                                            os.path.join(ROOT, "include", "adsbdec_amd.h")])):

@@ -30,8 +30,22 @@ piece is far below the end-of-file horizon), pointers payload + off_i.  Piece i'
 reported with g + 28 begin_i, which is exact, and ts + 28 begin_i -- in the original stream ts lags g by what accepted frames jumped
 (demod.c:99,128,134), so this is the original's ts only up to those jumps.  The Try/Ok table is the sum of the pieces' tables.
 
-Out of scope: _as and _packed captures (their pieces are not in the capture's own bytes), joining bursts across the slices of a
-stream, a batch form, the multi-GPU driver.
+The 12-bit layout (kind 12, BRS_KIND_PACKED12_REAL; layout12, gather12; adsb_gather_pack12_*, csrc/gather_pack12.h).  A real capture
+is n uint16 samples x carrying 12-bit codes, M = 2 (n // 4); piece i is the samples x[2 lo_i : 2 hi_i].  2 lo_i is a multiple of 8;
+2 hi_i is one too, or -- where M clips the last piece and M % 4 == 2 -- 4 behind one.  The piece is completed to whole groups of 8
+with code 2048 (the silence the decoders read outside a buffer: at most four codes, on that clipped last piece only), masked with
+0x0FFF and packed as Airspy packed 12-bit samples (packed12.pack12): 12 ceil((hi_i - lo_i) / 4) bytes, 84 per run, 3 bytes per power
+sample where kind 4 takes 4.
+
+    off_0 = 0        off_{i+1} = round_up(off_i + 12 ceil((hi_i - lo_i) / 4), 16)        total = off_B        pad bytes are zero
+
+A piece's start is a legal adsb_decode_batch_device_packed pointer (4-byte aligned, a multiple of 8 samples).  `over` counts the
+pieces' OWN samples above 4095 -- never the fill, never a sample outside the pieces; their low 12 bits are what is stored.  Every
+real flavour has a uint16 twin to gather from: a uint16 capture itself, the unpacked or converted scratch of a packed or _as one.
+In the archive kind 12 goes with sample_bytes 3, n_units counts the capture's samples, and the payload is checked against layout12.
+
+Out of scope: gathering straight from a packed source without the unpack, 12-bit forms of the IQ and power kinds, joining bursts
+across the slices of a stream, a batch form, the multi-GPU driver.
 
     python -m adsbdec_amd.burst_archive info file.brs      the header and the kept share
 """
@@ -43,15 +57,18 @@ import sys
 import numpy as np
 
 from .levels import BURST_DTYPE, RUN, burst_samples
+from .packed12 import pack12
 
 MAGIC = b"ADSBBRS1"
 VERSION = 1
 HEADER = struct.Struct("<8sIIIQQfIIQQ")
 assert HEADER.size == 64
-KINDS = {4: "uint16 real", 2: "int16 IQ", 0: "float32 IQ", 8: "int8 IQ", 16: "float32 power"}
-SAMPLE_BYTES = {4: 4, 2: 4, 0: 8, 8: 2, 16: 4}                # bytes per POWER sample
-UNITS_PER_POWER_SAMPLE = {4: 2, 2: 1, 0: 1, 8: 1, 16: 1}      # the capture's own samples per power sample
-UNIT_DTYPES = {4: "<u2", 2: "<i2", 0: "<f4", 8: "i1", 16: "<f4"}
+BRS_KIND_PACKED12_REAL = 12                                   # a real capture's pieces as Airspy packed 12-bit samples (layout12)
+KINDS = {4: "uint16 real", 2: "int16 IQ", 0: "float32 IQ", 8: "int8 IQ", 16: "float32 power", BRS_KIND_PACKED12_REAL: "packed 12-bit real"}
+SAMPLE_BYTES = {4: 4, 2: 4, 0: 8, 8: 2, 16: 4, BRS_KIND_PACKED12_REAL: 3}             # bytes per POWER sample
+UNITS_PER_POWER_SAMPLE = {4: 2, 2: 1, 0: 1, 8: 1, 16: 1, BRS_KIND_PACKED12_REAL: 2}   # the capture's own samples per power sample
+UNIT_DTYPES = {4: "<u2", 2: "<i2", 0: "<f4", 8: "i1", 16: "<f4", BRS_KIND_PACKED12_REAL: "u1"}  # (kind 12: a piece is bytes, 12 per 8 samples)
+FILL12 = 2048                                                 # the code that completes a clipped last piece to a whole group
 
 
 class ArchiveError(ValueError):
@@ -61,7 +78,7 @@ class ArchiveError(ValueError):
 def power_samples(kind: int, n_units: int) -> int:
     """The most power samples a capture of n_units of its own samples has: 2 floor(n / 4) for real samples (the reference reads four
     at a time), n for complex and power samples (what the export and level calls of the kind count)."""
-    return 2 * (n_units // 4) if kind == 4 else n_units
+    return 2 * (n_units // 4) if kind in (4, BRS_KIND_PACKED12_REAL) else n_units
 
 
 def _table(bursts) -> np.ndarray:
@@ -106,6 +123,46 @@ def gather(capture_bytes, bursts, M: int, s: int):
     return out, off
 
 
+# ------------------------------------------------------------------ the 12-bit layout
+def piece_bytes12(lo: int, hi: int) -> int:
+    """Bytes of the packed piece of power samples [lo, hi): whole groups of 8 samples, 12 bytes each."""
+    return 12 * -(-(hi - lo) // 4)
+
+
+def layout12(bursts, M: int) -> np.ndarray:
+    """offsets[B + 1], uint64: where packed piece i starts in the output of gather12 / adsb_gather_pack12_*, and the total."""
+    b = check(bursts, M, 4)
+    off = np.zeros(b.size + 1, dtype=np.uint64)
+    at = 0
+    for i, (lo, hi) in enumerate(burst_samples(b, M)):
+        at = (at + piece_bytes12(int(lo), int(hi)) + 15) // 16 * 16
+        off[i + 1] = at
+    return off
+
+
+def gather12(x, bursts, M: int):
+    """-> (payload, offsets, over): the pieces of the uint16 capture x, each completed to whole groups with code 2048, masked to 12
+    bits and packed; over = the pieces' own samples above 4095."""
+    x = np.ascontiguousarray(x, dtype=np.uint16).reshape(-1)
+    if x.size < 2 * M:
+        raise ArchiveError(f"the capture's {x.size} samples hold fewer than m = {M} power samples")
+    off = layout12(bursts, M)
+    out = np.zeros(int(off[-1]), dtype=np.uint8)
+    over = 0
+    for (lo, hi), at in zip(burst_samples(_table(bursts), M), off[:-1]):
+        own = x[2 * int(lo):2 * int(hi)]
+        over += int(np.count_nonzero(own > 0x0FFF))
+        whole = np.full(-(-own.size // 8) * 8, FILL12, dtype=np.uint16)
+        whole[:own.size] = own
+        p = pack12(whole & 0x0FFF)
+        out[int(at):int(at) + p.size] = p
+    return out, off, over
+
+
+def _layout_of(kind: int, bursts, M: int) -> np.ndarray:
+    return layout12(bursts, M) if kind == BRS_KIND_PACKED12_REAL else layout(bursts, M, SAMPLE_BYTES[kind])
+
+
 # ------------------------------------------------------------------ the archive
 def pack(kind: int, n_units: int, M: int, threshold: float, lead: int, hang: int, bursts, payload) -> bytes:
     """The archive's bytes.  The payload is what gather returns for the table (its size is checked, its bytes are not)."""
@@ -114,7 +171,7 @@ def pack(kind: int, n_units: int, M: int, threshold: float, lead: int, hang: int
     s = SAMPLE_BYTES[kind]
     b = _table(bursts)
     payload = np.ascontiguousarray(payload).reshape(-1).view(np.uint8)
-    total = int(layout(b, M, s)[-1])
+    total = int(_layout_of(kind, b, M)[-1])
     if payload.size != total:
         raise ArchiveError(f"the payload has {payload.size} bytes, the table's layout {total}")
     head = HEADER.pack(MAGIC, VERSION, kind, s, n_units, M, threshold, lead, hang, b.size, total)
@@ -145,7 +202,7 @@ def unpack(data: bytes) -> dict:
     if n_bursts > (len(data) - HEADER.size) // BURST_DTYPE.itemsize:
         raise ArchiveError(f"the file is too short for its table of {n_bursts} bursts")
     b = np.frombuffer(data, dtype=BURST_DTYPE, count=n_bursts, offset=HEADER.size)
-    off = layout(b, M, s)
+    off = _layout_of(kind, b, M)
     at = HEADER.size + BURST_DTYPE.itemsize * n_bursts
     if payload_bytes != int(off[-1]) or len(data) - at != payload_bytes:
         raise ArchiveError(f"the payload has {len(data) - at} bytes, the header says {payload_bytes}, the table's layout {int(off[-1])}")
@@ -161,6 +218,8 @@ def read(path) -> dict:
 def piece_units(archive: dict) -> list:
     """The length of every piece in the capture's own samples: what the batch call of the archive's kind counts."""
     per = UNITS_PER_POWER_SAMPLE[archive["kind"]]
+    if archive["kind"] == BRS_KIND_PACKED12_REAL:  # whole groups of 8 samples: a clipped last piece counts its fill
+        return [8 * -(-int(hi - lo) // 4) for lo, hi in burst_samples(archive["bursts"], archive["M"])]
     return [per * int(hi - lo) for lo, hi in burst_samples(archive["bursts"], archive["M"])]
 
 
@@ -174,12 +233,17 @@ def decode(decoder, archive: dict):
     payload = np.ascontiguousarray(archive["payload"])
     units = piece_units(archive)
     item = np.dtype(UNIT_DTYPES[kind]).itemsize
-    per_unit = archive["sample_bytes"] // UNITS_PER_POWER_SAMPLE[kind]
-    pieces = [payload[int(o):int(o) + per_unit * n].view(UNIT_DTYPES[kind]) for o, n in zip(off[:-1], units)]
-    assert all(p.size * item == per_unit * n for p, n in zip(pieces, units))
+    if kind == BRS_KIND_PACKED12_REAL:
+        pieces = [payload[int(o):int(o) + n // 8 * 12] for o, n in zip(off[:-1], units)]
+    else:
+        per_unit = archive["sample_bytes"] // UNITS_PER_POWER_SAMPLE[kind]
+        pieces = [payload[int(o):int(o) + per_unit * n].view(UNIT_DTYPES[kind]) for o, n in zip(off[:-1], units)]
+        assert all(p.size * item == per_unit * n for p, n in zip(pieces, units))
     if not pieces:
         return [], {"try": {11: 0, 17: 0, 18: 0}, "ok": {11: 0, 17: 0, 18: 0}}
-    if kind == 4:
+    if kind == BRS_KIND_PACKED12_REAL:
+        frames, stats = decoder.decode_batch_packed(pieces, stats=True)
+    elif kind == 4:
         frames, stats = decoder.decode_batch(pieces, stats=True)
     elif kind == 16:
         frames, stats = decoder.decode_batch_power(pieces, stats=True)

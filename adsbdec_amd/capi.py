@@ -260,6 +260,13 @@ SYMBOLS = {
     "adsb_gather_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
     "adsb_gather_chunk_words": (C.c_uint32, []),
+    "adsb_gather_pack12_layout": (C.c_long, [C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "adsb_gather_pack12_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.POINTER(C.c_uint64)]),
+    "adsb_gather_pack12_device_as": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.POINTER(C.c_uint64)]),
+    "adsb_gather_pack12_device_packed": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p, C.POINTER(C.c_uint64)]),
     "adsb_convert_iq_float32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "adsb_get_format_report": (C.c_int, [C.c_void_p, C.POINTER(FormatReport)]),
     "adsb_convert_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -1183,6 +1190,32 @@ class Decoder:
         assert total == int(off[-1])
         return off
 
+    # ---- ... of a real capture, packed to 12 bits (adsb_gather_pack12_*; adsbdec_amd.burst_archive.gather12 is the statement)
+    def _gather_pack12_call(self, name, *head, n: int, bursts, out_ptr: int, out_cap: int):
+        b = _burst_table(bursts)
+        off = np.zeros(b.size + 1, dtype=np.uint64)
+        over = C.c_uint64(0)
+        total = getattr(self._L, name)(self._h, *head, n, b.ctypes.data if b.size else None, b.size, out_ptr or None, out_cap, off.ctypes.data,
+                                       C.byref(over))
+        if total < 0:
+            self._check(-1, name)
+        assert total == int(off[-1])
+        return off, int(over.value)
+
+    def gather_pack12_device(self, ptr: int, n: int, bursts, out_ptr: int, out_cap: int):
+        """adsb_gather_pack12_device: the pieces that the burst table names, of the n uint16 samples in HBM at ptr, packed to 12 bits
+        into out_ptr (both 16-byte aligned) -> (offsets, over): len(bursts) + 1 byte offsets, offsets[-1] the total the call returned;
+        the pieces' own samples above 4095."""
+        return self._gather_pack12_call("adsb_gather_pack12_device", ptr or None, n=n, bursts=bursts, out_ptr=out_ptr, out_cap=out_cap)
+
+    def gather_pack12_device_as(self, fmt: int, ptr: int, n: int, bursts, out_ptr: int, out_cap: int):
+        """adsb_gather_pack12_device_as: the same for n samples of format fmt (1 float32, 3 int16), converted first."""
+        return self._gather_pack12_call("adsb_gather_pack12_device_as", fmt, ptr or None, n=n, bursts=bursts, out_ptr=out_ptr, out_cap=out_cap)
+
+    def gather_pack12_device_packed(self, ptr: int, n: int, bursts, out_ptr: int, out_cap: int):
+        """adsb_gather_pack12_device_packed: the same for n samples of packed 12-bit input (4-byte aligned, n % 8 == 0), unpacked first."""
+        return self._gather_pack12_call("adsb_gather_pack12_device_packed", ptr or None, n=n, bursts=bursts, out_ptr=out_ptr, out_cap=out_cap)
+
     def format_report(self):
         """adsb_get_format_report -> (converted, inexact, clamped) since the handle was created or reset."""
         r = FormatReport()
@@ -1506,6 +1539,19 @@ def gather_layout(bursts, m: int, sample_bytes: int) -> np.ndarray:
     off = np.zeros(b.size + 1, dtype=np.uint64)
     total = C.c_uint64(0)
     if L.adsb_gather_layout(m, sample_bytes, b.ctypes.data if b.size else None, b.size, off.ctypes.data, C.byref(total)) != 0:
+        raise AdsbError((L.adsb_last_error(None) or b"").decode())
+    assert int(total.value) == int(off[-1])
+    return off
+
+
+def gather_pack12_layout(bursts, m: int) -> np.ndarray:
+    """adsb_gather_pack12_layout (no device): the byte offsets of the packed pieces of a burst table in what adsb_gather_pack12_*
+    write, a uint64 array of len(bursts) + 1; offsets[-1] is the total.  AdsbError, naming the record, where the call refuses."""
+    L = load()
+    b = _burst_table(bursts)
+    off = np.zeros(b.size + 1, dtype=np.uint64)
+    total = C.c_uint64(0)
+    if L.adsb_gather_pack12_layout(m, b.ctypes.data if b.size else None, b.size, off.ctypes.data, C.byref(total)) != 0:
         raise AdsbError((L.adsb_last_error(None) or b"").decode())
     assert int(total.value) == int(off[-1])
     return off

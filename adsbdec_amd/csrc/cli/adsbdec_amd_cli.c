@@ -67,6 +67,14 @@
  *                   adsbdec_amd/burst_archive.py reads and writes the same bytes).  On stderr `kept B bursts, X of Y bytes`.  A uint16 file,
  *                   -q 2 | 0 | 8 or -w.  Not without -L -U; not with -t or -p (their pieces are not in the capture's own bytes), -I (one
  *                   file, one call: bursts are not joined across pieces), -G, -B or -W.
+ *     -P out.brs    EXTENSION, with -L -U: KEEP ONLY THE BURSTS OF A REAL CAPTURE, AT 12 BITS (adsb_gather_pack12_*).  What -K does, for
+ *                   a uint16 file (the default), -p or -t 3 | 1: the pieces are gathered out of the capture's uint16 twin in HBM -- the
+ *                   capture itself, or the scratch its level call has unpacked or converted it into -- and packed while they are copied
+ *                   into Airspy packed 12-bit samples, 3 bytes per power sample where -K writes 4; a clipped last piece is completed to
+ *                   a whole group of 8 with code 2048.  The archive's kind is 12 (sample_bytes 3); -k decodes it through
+ *                   adsb_decode_batch_host_packed.  On stderr `kept B bursts, X of Y bytes`.  A sample above 4095 inside a burst does
+ *                   not fit 12 bits: the run says how many there are, writes NO archive and exits with status 255 (-K keeps all 16
+ *                   bits).  Not without -L -U; not with -q, -w, -K, -I, -G, -B, -W or -k.
  *     -k            EXTENSION: the file of -f is a BURST ARCHIVE.  Its pieces are decoded by ONE adsb_decode_batch_host* call of the
  *                   archive's kind on a flush handle (a piece is far below the end-of-file horizon, so each is decoded as -E decodes a
  *                   file: as its silent twin); the packets are printed in order with positions in the original capture: g + 28 begin_i
@@ -235,6 +243,7 @@ static void usage(void)
     printf("        adsbdec_amd_cli [-d gpu] -L -I ms -f filename\n");
     printf("        adsbdec_amd_cli [-p | -t type | -q type | -w] [-d gpu] -L -U factor[,lead[,hang]] -f filename\n");
     printf("        adsbdec_amd_cli [-q type | -w] [-d gpu] -L -U factor[,lead[,hang]] -K out.brs -f filename\n");
+    printf("        adsbdec_amd_cli [-p | -t type] [-d gpu] -L -U factor[,lead[,hang]] -P out.brs -f filename\n");
     printf("        adsbdec_amd_cli [-a] [-m] [-b] [-x] [-s addr[:port] | -l addr[:port]] [-d gpu] -k -f in.brs\n\n");
     printf("\t-a : decode DF18 too\n");
     printf("\t-m : output avrmlat format (ie : with 12Mhz timestamp)\n");
@@ -268,6 +277,11 @@ static void usage(void)
     printf("\t     gathered on the GPU out of the capture's own bytes (adsb_gather_device), copied back once and written to out.brs, a burst\n");
     printf("\t     archive (header, burst table, the pieces each from a multiple of 16 bytes on); stderr: `kept B bursts, X of Y bytes`; a\n");
     printf("\t     uint16, -q 2 | 0 | 8 or -w file; for an archive meant for -k, hang 4 is enough; not with -t, -p, -I, -G, -B or -W\n");
+    printf("\t-P out.brs : (extension) with -L -U: keep only the bursts of a real capture, at 12 bits.  As -K, for a uint16 (default), -p or\n");
+    printf("\t     -t 3 | 1 file: the pieces are packed on the GPU into Airspy packed 12-bit samples while they are gathered\n");
+    printf("\t     (adsb_gather_pack12_*), 3 bytes per power sample where -K writes 4; archive kind 12, which -k decodes; stderr: `kept B\n");
+    printf("\t     bursts, X of Y bytes`; a sample above 4095 inside a burst: status 255, no archive, use -K; not with -q, -w, -K, -I, -G,\n");
+    printf("\t     -B, -W or -k\n");
     printf("\t-k : (extension) the file of -f is a burst archive: decode its pieces in one batch call, each to its last sample (as -E does),\n");
     printf("\t     and print the packets in order, positions counted in the original capture (a packet's 12 MHz timestamp is the\n");
     printf("\t     original's only up to the jumps of the frames accepted before its piece); the kind of the samples comes from the\n");
@@ -943,7 +957,57 @@ static int keep_bursts(adsb_decoder *dec, const char *path, const void *d_in, si
     return rc;
 }
 
-static int run_level(const char *filename, int device, int kind, int fmt, const struct burst_opts *u, const char *archive_out)
+/* -P: the same out of the capture's uint16 twin, packed to 12 bits while it is gathered -- ONE adsb_gather_pack12_* call of the file's
+ * flavour (kind 0: uint16; 1: -t fmt; 2: -p), ONE copy back, the archive of kind 12.  A piece's own sample above 4095: no archive. */
+static int keep_bursts_pack12(adsb_decoder *dec, const char *path, int kind, int fmt, const void *d_in, size_t n, uint64_t m,
+                              const struct kept_bursts *k, const struct burst_opts *u)
+{
+    brs_archive a;
+    memset(&a, 0, sizeof a);
+    a.kind = BRS_KIND_PACKED12_REAL, a.sample_bytes = brs_sample_bytes(BRS_KIND_PACKED12_REAL);
+    a.n_units = n, a.m = m;
+    a.threshold = k->threshold, a.lead = u->lead, a.hang = u->hang;
+    a.n_bursts = k->n, a.bursts = k->tab;
+    char why[512];
+    uint64_t total = 0, over = 0;
+    if (adsb_gather_pack12_layout(m, k->tab, k->n, NULL, &total) != 0) {
+        fprintf(stderr, "adsb_gather_pack12_layout() failed: %s\n", adsb_last_error(NULL));
+        return 255;
+    }
+    void *d_out = NULL;
+    unsigned char *out = (unsigned char *)malloc(total ? (size_t)total : 1);
+    int rc = 255; /* (one way out: what was allocated here is released on it) */
+    long got = -1;
+    if (!out || (total && hipMalloc(&d_out, (size_t)total) != hipSuccess)) {
+        d_out = NULL;
+        fprintf(stderr, "cannot allocate the %llu bytes of the %zu bursts, on the host and on the device\n", (unsigned long long)total, k->n);
+    } else if ((got = kind == 1   ? adsb_gather_pack12_device_as(dec, fmt, d_in, n, k->tab, k->n, d_out, (size_t)total, NULL, &over)
+                      : kind == 2 ? adsb_gather_pack12_device_packed(dec, d_in, n, k->tab, k->n, d_out, (size_t)total, NULL, &over)
+                                  : adsb_gather_pack12_device(dec, d_in, n, k->tab, k->n, d_out, (size_t)total, NULL, &over)) < 0 ||
+               (uint64_t)got != total) {
+        fprintf(stderr, "adsb_gather_pack12_device%s() failed: %s\n", kind == 1 ? "_as" : kind == 2 ? "_packed" : "",
+                got < 0 ? adsb_last_error(dec) : "another total than the layout's");
+    } else if (over > 0) {
+        fprintf(stderr, "-P: %llu samples inside the bursts are above 4095 and do not fit 12 bits: no archive is written (-K keeps all 16 bits)\n",
+                (unsigned long long)over);
+    } else if (total && hipMemcpy(out, d_out, (size_t)total, hipMemcpyDeviceToHost) != hipSuccess) {
+        fprintf(stderr, "cannot copy the %llu bytes of the bursts back from the device\n", (unsigned long long)total);
+    } else {
+        a.payload = out, a.payload_bytes = total;
+        if (brs_write(path, &a, why, sizeof why) != 0) {
+            fprintf(stderr, "%s: %s\n", path, why);
+        } else {
+            fprintf(stderr, "kept %zu bursts, %llu of %llu bytes\n", k->n, (unsigned long long)total, (unsigned long long)(a.sample_bytes * m));
+            rc = 0;
+        }
+    }
+    if (d_out)
+        (void)hipFree(d_out);
+    free(out);
+    return rc;
+}
+
+static int run_level(const char *filename, int device, int kind, int fmt, const struct burst_opts *u, const char *archive_out, int pack12)
 {
     const int fd = open(filename, O_RDONLY);
     struct stat sb;
@@ -1010,7 +1074,10 @@ static int run_level(const char *filename, int device, int kind, int fmt, const 
     if (gate) {
         struct kept_bursts kept = {NULL, 0, 0};
         int rc = print_bursts(dec, rep, d_env, (uint64_t)got, u, archive_out ? &kept : NULL);
-        if (rc == 0 && archive_out) { /* (main has refused -K with -t and -p: kind is 0, 3 or 4 here) */
+        if (rc == 0 && archive_out && pack12) { /* (main has refused -P with -q and -w: kind is 0, 1 or 2 here) */
+            fflush(stdout);
+            rc = keep_bursts_pack12(dec, archive_out, kind, fmt, d_in, n, (uint64_t)got, &kept, u);
+        } else if (rc == 0 && archive_out) { /* (main has refused -K with -t and -p: kind is 0, 3 or 4 here) */
             fflush(stdout);
             rc = keep_bursts(dec, archive_out, d_in, used, kind == 0 ? BRS_KIND_UINT16_REAL : kind == 4 ? BRS_KIND_FLOAT32_POWER : (uint32_t)fmt,
                              (uint64_t)n, (uint64_t)got, &kept, u);
@@ -1143,11 +1210,9 @@ static int run_archive(const char *filename, const adsb_config *cfg, int outform
         fprintf(stderr, "out of memory for the results of %zu pieces\n", nb);
         return 255;
     }
-    const uint64_t per = brs_units_per_power_sample(a.kind);
     for (size_t i = 0; i < nb; i++) {
-        const uint64_t lo = 28ull * a.bursts[i].begin, hi = 28ull * a.bursts[i].end < a.m ? 28ull * a.bursts[i].end : a.m;
         piece[i] = a.payload + a.offsets[i];
-        n[i] = (size_t)(per * (hi - lo));
+        n[i] = (size_t)brs_piece_units(&a, i); /* (kind 12: whole groups of 8 samples, a clipped last piece's fill included) */
     }
     {
         const int prc = sink_wait_peer(&out_sink);
@@ -1173,7 +1238,8 @@ static int run_archive(const char *filename, const adsb_config *cfg, int outform
     const adsb_frame *fr = NULL;
     long total = 0;
     if (nb)
-        total = a.kind == BRS_KIND_UINT16_REAL      ? adsb_decode_batch_host(dec, nb, (const uint16_t *const *)piece, n, &fr, first, st)
+        total = a.kind == BRS_KIND_PACKED12_REAL   ? adsb_decode_batch_host_packed(dec, nb, piece, n, &fr, first, st)
+                : a.kind == BRS_KIND_UINT16_REAL    ? adsb_decode_batch_host(dec, nb, (const uint16_t *const *)piece, n, &fr, first, st)
                 : a.kind == BRS_KIND_FLOAT32_POWER ? adsb_decode_batch_host_power(dec, nb, (const float *const *)piece, n, &fr, first, st)
                                                    : adsb_decode_batch_host_iq(dec, (int)a.kind, nb, piece, n, &fr, first, st);
     if (total < 0) {
@@ -1218,6 +1284,7 @@ int main(int argc, char **argv)
     const char *burst_arg = NULL; /* -U: -L's gate, factor[,lead[,hang]] */
     struct burst_opts burst = {0, 2, 1468};
     const char *archive_out = NULL; /* -K: keep only the bursts of -L -U, as a burst archive */
+    const char *pack_out = NULL;    /* -P: ... of a real capture, packed to 12 bits (archive kind 12) */
     int archive_in = 0;             /* -k: the file of -f is a burst archive */
     const char *interval_arg = NULL; /* -I: -L's windows, in milliseconds */
     double interval_ms = 0;
@@ -1228,7 +1295,7 @@ int main(int argc, char **argv)
     int outmode = SINK_STDOUT;
     const char *rawaddr = NULL;
 
-    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:EK:k")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:EK:kP:")) != EOF) {
         switch (c) {
         case 'f':
             filename = optarg;
@@ -1301,6 +1368,9 @@ int main(int argc, char **argv)
         case 'k':
             archive_in = 1;
             break;
+        case 'P':
+            pack_out = optarg;
+            break;
         case 'I': {
             char *end;
             interval_ms = strtod(optarg, &end);
@@ -1345,6 +1415,21 @@ int main(int argc, char **argv)
             usage();
             return 1;
         }
+    }
+    if (pack_out && (!level || !burst_arg || qtype_arg || power || archive_out || interval_arg || ndev || listfile || export_path || archive_in)) {
+        /* -P keeps the pieces -L -U finds of a REAL capture, packed to 12 bits: refused before any GPU call */
+        if (!level || !burst_arg)
+            fprintf(stderr, "-P is not supported without -L -U: it keeps the bursts that the gate behind the level report finds\n");
+        else
+            fprintf(stderr, "-P is not supported with %s: %s\n",
+                    qtype_arg ? "-q" : power ? "-w" : archive_out ? "-K" : interval_arg ? "-I" : ndev ? "-G" : listfile ? "-B" : export_path ? "-W" : "-k",
+                    qtype_arg || power  ? "12-bit codes are what a REAL capture carries (a uint16 file, -p or -t 3 | 1); -K keeps IQ and power samples as they are"
+                    : archive_out       ? "a run writes one archive: the capture's own bytes (-K) or its 12-bit codes (-P)"
+                    : interval_arg      ? "the windows are pieces of a stream, and joining bursts across pieces is the caller's: one file, one call"
+                    : ndev || listfile  ? "the gather runs on one GPU (-d), one file at a time: no batch and no multi-GPU form"
+                    : export_path       ? "a run writes the power samples or keeps the capture's bursts, not both"
+                                        : "-k reads an archive, -P writes one");
+        return 1;
     }
     if (archive_in && (stype_arg || packed || qtype_arg || power || flush || ndev || listfile || level || export_path || archive_out || nfiles > 1)) {
         /* -k decodes a burst archive, whose header says what it holds: refused before any GPU call */
@@ -1507,7 +1592,8 @@ int main(int argc, char **argv)
         }
         if (interval_arg)
             return run_level_windows(filename, device, interval_ms);
-        return run_level(filename, device, converted ? 1 : packed ? 2 : iq ? 3 : power ? 4 : 0, iq ? (int)qtype : (int)stype, &burst, archive_out);
+        return run_level(filename, device, converted ? 1 : packed ? 2 : iq ? 3 : power ? 4 : 0, iq ? (int)qtype : (int)stype, &burst, pack_out ? pack_out : archive_out,
+                         pack_out != NULL);
     }
     if (export_path) {
         install_signals();

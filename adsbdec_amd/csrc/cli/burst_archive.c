@@ -18,6 +18,8 @@ uint32_t brs_sample_bytes(uint32_t kind)
     switch (kind) {
     case BRS_KIND_INT8_IQ:
         return 2;
+    case BRS_KIND_PACKED12_REAL:
+        return 3;
     case BRS_KIND_UINT16_REAL:
     case BRS_KIND_INT16_IQ:
     case BRS_KIND_FLOAT32_POWER:
@@ -29,7 +31,37 @@ uint32_t brs_sample_bytes(uint32_t kind)
     }
 }
 
-uint32_t brs_units_per_power_sample(uint32_t kind) { return kind == BRS_KIND_UINT16_REAL ? 2 : 1; }
+uint32_t brs_units_per_power_sample(uint32_t kind) { return kind == BRS_KIND_UINT16_REAL || kind == BRS_KIND_PACKED12_REAL ? 2 : 1; }
+
+/* The layout of the archive's kind.  Kind 12's is the 12-bit one, what adsb_gather_pack12_layout gives (tests hold the two together):
+ * the table is checked as a uint16 capture's is (adsb_gather_layout at 4 bytes per power sample, the one library call this file makes:
+ * it builds into a stand-alone program that restates it), then piece i takes 12 ceil((hi - lo) / 4) bytes from a multiple of 16 on. */
+static long brs_layout(const brs_archive *a, uint64_t *offsets, uint64_t *total)
+{
+    if (a->kind != BRS_KIND_PACKED12_REAL)
+        return adsb_gather_layout(a->m, (int)a->sample_bytes, a->bursts, (size_t)a->n_bursts, offsets, total);
+    if (adsb_gather_layout(a->m, 4, a->bursts, (size_t)a->n_bursts, NULL, NULL) != 0)
+        return -1;
+    uint64_t off = 0;
+    for (uint64_t i = 0; i < a->n_bursts; i++) {
+        const uint64_t lo = 28ull * a->bursts[i].begin, hi = 28ull * a->bursts[i].end < a->m ? 28ull * a->bursts[i].end : a->m;
+        if (offsets)
+            offsets[i] = off;
+        off = (off + 12 * ((hi - lo + 3) / 4) + 15) & ~(uint64_t)15;
+    }
+    if (offsets)
+        offsets[a->n_bursts] = off;
+    *total = off;
+    return 0;
+}
+
+uint64_t brs_piece_units(const brs_archive *a, uint64_t i)
+{
+    const uint64_t lo = 28ull * a->bursts[i].begin, hi = 28ull * a->bursts[i].end < a->m ? 28ull * a->bursts[i].end : a->m;
+    if (a->kind == BRS_KIND_PACKED12_REAL)
+        return 8 * ((hi - lo + 3) / 4);
+    return brs_units_per_power_sample(a->kind) * (hi - lo);
+}
 
 static void put32(unsigned char *h, size_t at, uint32_t v) { memcpy(h + at, &v, 4); }
 static void put64(unsigned char *h, size_t at, uint64_t v) { memcpy(h + at, &v, 8); }
@@ -53,7 +85,7 @@ int brs_write(const char *path, const brs_archive *a, char *why, size_t cap)
         snprintf(why, cap, "kind %u with sample_bytes %u: no format of the archive's", a->kind, a->sample_bytes);
         return -1;
     }
-    if (adsb_gather_layout(a->m, (int)a->sample_bytes, a->bursts, (size_t)a->n_bursts, NULL, &total) != 0) {
+    if (brs_layout(a, NULL, &total) != 0) {
         snprintf(why, cap, "%s", adsb_last_error(NULL));
         return -1;
     }
@@ -113,7 +145,7 @@ int brs_read(const char *path, brs_archive *a, char *why, size_t cap)
         a->lead = get32(h, 40), a->hang = get32(h, 44);
         a->n_bursts = get64(h, 48), a->payload_bytes = get64(h, 56);
         const uint64_t rest = (uint64_t)size - sizeof h;
-        const uint64_t m_most = a->kind == BRS_KIND_UINT16_REAL ? 2 * (a->n_units / 4) : a->n_units;
+        const uint64_t m_most = brs_units_per_power_sample(a->kind) == 2 ? 2 * (a->n_units / 4) : a->n_units;
         if (a->m > m_most) {
             snprintf(why, cap, "M = %llu power samples are more than the capture's %llu samples make", (unsigned long long)a->m,
                      (unsigned long long)a->n_units);
@@ -135,7 +167,7 @@ int brs_read(const char *path, brs_archive *a, char *why, size_t cap)
                 a->payload = (const unsigned char *)a->mem + a->n_bursts * sizeof(adsb_burst);
                 a->offsets = (uint64_t *)((unsigned char *)a->mem + ((body + 15) & ~(size_t)15));
                 uint64_t total = 0;
-                if (adsb_gather_layout(a->m, (int)a->sample_bytes, a->bursts, (size_t)a->n_bursts, a->offsets, &total) != 0)
+                if (brs_layout(a, a->offsets, &total) != 0)
                     snprintf(why, cap, "%s", adsb_last_error(NULL));
                 else if (total != a->payload_bytes)
                     snprintf(why, cap, "the payload has %llu bytes, the table's layout %llu", (unsigned long long)a->payload_bytes,

@@ -12,6 +12,7 @@
 //   decoder_level_windows.hip  the window form (adsb_level_windows*): the reports of K consecutive windows of one stream
 //   decoder_bursts.hip     the gate behind the envelope (adsb_bursts_*): an envelope's bursts as an ordered table
 //   decoder_gather.hip     a capture's bursts as one array (adsb_gather_device): the pieces of a burst table, packed by one launch
+//   decoder_gather_pack12.hip  ... of a real capture, packed to 12 bits while they are copied (adsb_gather_pack12_*)
 //   decoder_stage.hip      the staging steps every family calls: samples into unpacked, batch_in, batch_land, batch_unpacked, win_buf, pow_buf
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
@@ -340,6 +341,9 @@ struct adsb_decoder {
     // a capture's bursts as one array (adsb_gather_device, decoder_gather.hip; gather.h): the row table of one call, filled in the
     // pinned half and uploaded on the scan stream
     adsb::Table gather_tab;
+    // ... packed to 12 bits (adsb_gather_pack12_*, decoder_gather_pack12.hip; gather_pack12.h): the pieces' own samples above 4095, one
+    // word the kernel adds to, zeroed on the scan stream in front of the launch and copied to its pinned twin behind it
+    adsb::Totals<unsigned long long> gather_over;
 
     int fail(const char *fmt, ...)
     {

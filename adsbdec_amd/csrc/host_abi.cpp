@@ -11,6 +11,7 @@
 #include "../../include/adsbdec_amd_diag.h"
 #include "batch.hpp"
 #include "gather.h"
+#include "gather_pack12.h"
 #include "handoff.hpp"
 #include "resolver.hpp"
 #include "stitch.hpp"
@@ -109,6 +110,21 @@ long adsb_gather_layout(uint64_t m, int sample_bytes, const adsb_burst *bursts, 
     if (adsb::set_create_error) {
         char msg[300];
         snprintf(msg, sizeof msg, "adsb_gather_layout: %s", why);
+        adsb::set_create_error(msg);
+    }
+    return -1;
+}
+
+// ... of what adsb_gather_pack12_* write: a real capture of m power samples, its pieces packed to 12 bits (gather_pack12.h
+// gather_pack12_layout; adsbdec_amd/burst_archive.py layout12).
+long adsb_gather_pack12_layout(uint64_t m, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes)
+{
+    char why[256];
+    if (adsb::gather_pack12_layout(m, bursts, n_bursts, nullptr, nullptr, nullptr, why, sizeof why) == 0) // (a refusal writes nothing)
+        return adsb::gather_pack12_layout(m, bursts, n_bursts, offsets, nullptr, total_bytes, why, sizeof why);
+    if (adsb::set_create_error) {
+        char msg[300];
+        snprintf(msg, sizeof msg, "adsb_gather_pack12_layout: %s", why);
         adsb::set_create_error(msg);
     }
     return -1;

@@ -29,6 +29,18 @@ ADSB_HD inline void unpack12_group(uint32_t w0, uint32_t w1, uint32_t w2, uint16
     s[7] = (uint16_t)(w2 & 0xfffu);
 }
 
+// The inverse: the words of the group whose samples are s[0..7], each taken & 0xfff (gather_pack12_kernel.hip packs a capture's
+// bursts with it; tests/cpp/pack12_group.cpp holds it to unpack12_group and to the known answers of the format).
+ADSB_HD inline void pack12_group(const uint16_t s[8], uint32_t w[3])
+{
+    uint32_t c[8];
+    for (int k = 0; k < 8; k++)
+        c[k] = s[k] & 0xfffu;
+    w[0] = (c[0] << 20) | (c[1] << 8) | (c[2] >> 4);
+    w[1] = ((c[2] & 0xfu) << 28) | (c[3] << 16) | (c[4] << 4) | (c[5] >> 8);
+    w[2] = ((c[5] & 0xffu) << 24) | (c[6] << 12) | c[7];
+}
+
 // The same group as four dwords, samples 2k (low half) and 2k+1 (high half) in dword k: the 16-byte store of the kernel.
 ADSB_HD inline void unpack12_group_pairs(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t out[4])
 {

@@ -168,7 +168,7 @@ long adsb_power_device(adsb_decoder *d, const void *device_samples, size_t n, fl
 long adsb_power_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
 long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, float *const *device_power, const size_t *power_cap);
 long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap); typedef struct adsb_level_report { uint64_t samples, negative, rail_lo, rail_hi, over; uint64_t hist[2048]; } adsb_level_report;
-long adsb_level_device(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_packed(adsb_decoder *d, const void *device_packed, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_power(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_host(adsb_decoder *d, const uint16_t *samples, size_t n, adsb_level_report *out, float *env, size_t env_cap); long adsb_level_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, adsb_level_report *out, float *const *env, const size_t *env_cap); long adsb_level_windows(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_windows_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *env, size_t env_cap); void adsb_level_add(adsb_level_report *sum, const adsb_level_report *part); float adsb_level_percentile(const adsb_level_report *r, double q); typedef struct adsb_burst { uint32_t begin, end, hot; float peak; } adsb_burst; /* runs of 28 power samples, [begin, end) */ long adsb_bursts_device(adsb_decoder *d, const float *device_env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); long adsb_bursts_host(adsb_decoder *d, const float *env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); /* adsb_gather_*: KEEP ONLY THE BURSTS -- a capture of m power samples at sample_bytes bytes each (2: int8 IQ; 4: uint16 real, int16 IQ, float32 power; 8: float32 IQ) and an ordered burst table, as adsb_bursts_* returns it; piece i is the power samples [28 begin_i, min(28 end_i, m)), its bytes are capture[s lo_i : s hi_i]; the pieces lie in the output in table order, each from a multiple of 16 bytes on: offsets[0] = 0, offsets[i + 1] = round_up(offsets[i] + s (hi_i - lo_i), 16); pad bytes are zero; the total is offsets[n_bursts].  A piece's start is then a legal adsb_decode_batch_device* pointer (16-byte aligned, at a multiple of 4 samples), and on a flush handle (adsb_set_flush) the piece decodes as its silent twin: report g + 28 begin_i, which is exact, and ts + 28 begin_i, which is the original stream's ts only up to what accepted frames before the piece jumped (demod.c:99,128,134).  adsb_gather_layout: no device; offsets (n_bursts + 1, or NULL) and *total_bytes (or NULL) in host memory; 0, or -1 with adsb_last_error(NULL) naming the record: sample_bytes not 2, 4 or 8, a record with end <= begin or 28 begin >= m, records that do not ascend with a run between neighbours.  adsb_gather_device: device_capture and device_out in device memory, 16-byte aligned; bursts and offsets (n_bursts + 1, or NULL) in host memory; ONE launch on the handle's stream, returned when the bytes are there; returns the total bytes written (n_bursts 0: 0, nothing launched), nothing at or behind device_out + total is written; export rule 5 holds (callable between pushes).  Refused (-1, the message names the burst, nothing launched or written): what the layout refuses, capture_bytes < sample_bytes m, a pointer off 16 bytes or NULL with work to do, out_cap_bytes < total.  Not for _as and _packed captures (their pieces are not in the capture's own bytes); no batch form, no joining across the slices of a stream, no multi-GPU form. */ long adsb_gather_layout(uint64_t m, int sample_bytes, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes); long adsb_gather_device(adsb_decoder *d, const void *device_capture, size_t capture_bytes, int sample_bytes, uint64_t m, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets);
+long adsb_level_device(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_packed(adsb_decoder *d, const void *device_packed, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_power(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_host(adsb_decoder *d, const uint16_t *samples, size_t n, adsb_level_report *out, float *env, size_t env_cap); long adsb_level_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, adsb_level_report *out, float *const *env, const size_t *env_cap); long adsb_level_windows(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_windows_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *env, size_t env_cap); void adsb_level_add(adsb_level_report *sum, const adsb_level_report *part); float adsb_level_percentile(const adsb_level_report *r, double q); typedef struct adsb_burst { uint32_t begin, end, hot; float peak; } adsb_burst; /* runs of 28 power samples, [begin, end) */ long adsb_bursts_device(adsb_decoder *d, const float *device_env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); long adsb_bursts_host(adsb_decoder *d, const float *env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); /* adsb_gather_*: KEEP ONLY THE BURSTS -- a capture of m power samples at sample_bytes bytes each (2: int8 IQ; 4: uint16 real, int16 IQ, float32 power; 8: float32 IQ) and an ordered burst table, as adsb_bursts_* returns it; piece i is the power samples [28 begin_i, min(28 end_i, m)), its bytes are capture[s lo_i : s hi_i]; the pieces lie in the output in table order, each from a multiple of 16 bytes on: offsets[0] = 0, offsets[i + 1] = round_up(offsets[i] + s (hi_i - lo_i), 16); pad bytes are zero; the total is offsets[n_bursts].  A piece's start is then a legal adsb_decode_batch_device* pointer (16-byte aligned, at a multiple of 4 samples), and on a flush handle (adsb_set_flush) the piece decodes as its silent twin: report g + 28 begin_i, which is exact, and ts + 28 begin_i, which is the original stream's ts only up to what accepted frames before the piece jumped (demod.c:99,128,134).  adsb_gather_layout: no device; offsets (n_bursts + 1, or NULL) and *total_bytes (or NULL) in host memory; 0, or -1 with adsb_last_error(NULL) naming the record: sample_bytes not 2, 4 or 8, a record with end <= begin or 28 begin >= m, records that do not ascend with a run between neighbours.  adsb_gather_device: device_capture and device_out in device memory, 16-byte aligned; bursts and offsets (n_bursts + 1, or NULL) in host memory; ONE launch on the handle's stream, returned when the bytes are there; returns the total bytes written (n_bursts 0: 0, nothing launched), nothing at or behind device_out + total is written; export rule 5 holds (callable between pushes).  Refused (-1, the message names the burst, nothing launched or written): what the layout refuses, capture_bytes < sample_bytes m, a pointer off 16 bytes or NULL with work to do, out_cap_bytes < total.  _as and _packed captures go through adsb_gather_pack12_* (their pieces are not in the capture's own bytes); no batch form, no joining across the slices of a stream, no multi-GPU form.  adsb_gather_pack12_*: THE SAME FOR A REAL CAPTURE AT 12 BITS -- n uint16 samples x carrying 12-bit codes, m = 2 (n / 4); piece i is the samples x[2 lo_i : 2 hi_i] completed to whole groups of 8 with code 2048 (at most four codes, only where m clips the last piece and m % 4 == 2), taken & 0x0fff and packed as Airspy packed 12-bit samples (ADSB_PACKED12_BYTES): 12 ceil((hi_i - lo_i) / 4) bytes, 84 per run, 3 per power sample where adsb_gather_device writes 4; offsets[i + 1] = round_up(offsets[i] + those, 16), pad bytes zero.  A piece's start is a legal adsb_decode_batch_device_packed pointer with n = 8 ceil((hi_i - lo_i) / 4), and on a flush handle it decodes as the uint16 piece does (the fill is the silence of its twin).  *over (or NULL): the pieces' OWN samples above 4095 -- never the fill, never a sample outside the pieces; their low 12 bits are what is stored.  _layout: no device, the table checked as adsb_gather_layout checks it.  _device: device_samples and device_out 16-byte aligned.  _as (fmt 1 | 3) / _packed (n % 8 == 0, 4-byte aligned): converted or unpacked first, by the launch and into the scratch of adsb_decode_device_as / _packed, then gathered from there; _as adds to adsb_get_format_report.  ONE gather launch on the handle's stream; returns the total bytes (n_bursts 0: 0, nothing launched), nothing at or behind device_out + total is written; export rules 5 and 6 hold.  Refused (-1, the message names the burst, nothing launched, written or counted): what the layout refuses, n >= 2^32, a capture or output pointer off 16 bytes (_packed's capture: 4) or NULL with work to do, out_cap_bytes < total, fmt not 1 or 3, _packed with n % 8 != 0.  Not built: gathering straight from a packed source without the unpack, IQ and power kinds, a batch form, stream slices, a multi-GPU form. */ long adsb_gather_layout(uint64_t m, int sample_bytes, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes); long adsb_gather_device(adsb_decoder *d, const void *device_capture, size_t capture_bytes, int sample_bytes, uint64_t m, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets); long adsb_gather_pack12_layout(uint64_t m, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes); long adsb_gather_pack12_device(adsb_decoder *d, const void *device_samples, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over); long adsb_gather_pack12_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over); long adsb_gather_pack12_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over);
 /* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
  * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. adsb_set_flush (off by default; same rule: fresh or reset handle, sticky): decode a capture to its LAST sample instead of keeping the reference's end-of-file horizon (air.c:94-99, demod.c:89: the last ~41 k power samples are never scanned, a capture below 81 960 samples decodes nothing).  adsb_decode_device*, adsb_decode_batch_* and a stream ended by adsb_finish / a _final push then return, record for record and with the same Try/Ok table, what the reference returns for the capture's SILENT TWIN: its whole units (4 floor(n / 4) real samples, 2 floor(n / 2) IQ or power samples) followed by 81 960 power samples of silence (code 2048, (0, 0), +0.0) -- without padding or copying anything (DESIGN.md "Flush").  Every frame the horizon keeps comes back unchanged, in front.  Refuses, and is refused by, adsb_set_long_stream. */
 int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets); int adsb_set_flush(adsb_decoder *d, int on); int adsb_get_flush(const adsb_decoder *d);

@@ -12,6 +12,7 @@ comparison interleaved.
     python tools/format_probe.py --bursts [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/rNN_bursts.txt]   # bursts_probe(): NN is the next free round
     python tools/format_probe.py --flush [--reps 10] [--ab parent/libadsbdec_amd.so] [--out profiles/r30_flush.txt]   # flush_probe()
     python tools/format_probe.py --gather [--reps 10] [--ab parent/libadsbdec_amd.so] [--variant name=path/to/libadsbdec_amd.so ...] [--out profiles/r32_gather.txt]   # gather_probe()
+    python tools/format_probe.py --gather-pack12 [--reps 10] [--ab parent/libadsbdec_amd.so] [--variant name=path/to/libadsbdec_amd.so ...] [--out profiles/r33_pack12.txt]   # gather_pack12_probe()
     python tools/format_probe.py --level-batch [--reps 20] [--out profiles/r26_level_batch.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_batch_probe()
 
 (a) The kernels alone at 256 Mi samples, timed with device events around each launch: adsb_convert_samples for both formats
@@ -1704,6 +1705,160 @@ def gather_probe(L, reps, lines, parent, variants=()):
         table_of(names, wall, names[0])
 
 
+def gather_pack12_probe(L, reps, lines, parent, variants=()):
+    """The 12-bit burst gather (adsb_gather_pack12_*, gather_pack12_kernel.hip), every comparison interleaved in this one process, wall
+    time of the calls, the run's A/A beside every ratio.  On the benchmark workload's table and on the sparse capture's (factor 48,
+    lead 2, hang 4):
+    (a) adsb_gather_pack12_device beside itself (the A/A), beside adsb_gather_device on the same table, beside that gather followed by
+        a separate pack in torch, beside _packed and _as (fmt 3) with their unpack / conversion launch, and through every --variant
+        name=path: a measurement build of the library whose gather_pack12_kernel.hip differs;
+    (b) archive bytes of kind 12 over kind 4's and over the capture's;
+    (c) adsb_level_device and adsb_decode_device beside the parent commit's library (--ab)."""
+    import numpy as np
+    from adsbdec_amd import burst_archive as BA, levels, packed12, sample_formats
+    out = C.POINTER(capi.Frame)()
+    order_rng = __import__("random").Random(33)
+
+    def rotate(sides, steps=1):
+        names = list(sides)
+        wall = {k_: [] for k_ in names}
+        for r in range(-1, reps):                            # (round -1: the warm-up)
+            order = names[:]
+            order_rng.shuffle(order)
+            for name in order:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    sides[name]()
+                if r >= 0:
+                    wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        return names, wall
+
+    def table_of(names, wall, base):
+        for name in names:
+            q = statistics.quantiles(wall[name], n=4)
+            rr = [a_ / b for a_, b in zip(wall[name], wall[base])]
+            qr = statistics.quantiles(rr, n=4)
+            lines.append(f"    {name:62s} {med(wall[name]):10.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med(rr):.4f} ({qr[0]:.4f} .. {qr[2]:.4f})")
+            print(lines[-1], flush=True)
+
+    head = "#   side                                                              call ms (q1 .. q3)               / the first side (median of rounds, q1 .. q3)"
+    M = N // 2
+    ke = -(-M // 28)
+    d = capi.Decoder()
+    env = torch.zeros(ke, dtype=torch.float32, device="cuda")
+    rep1 = capi.LevelReport()
+    dst = torch.empty(2 * N, dtype=torch.uint8, device="cuda")
+    dst16 = torch.empty(2 * N, dtype=torch.uint8, device="cuda")
+    t_bench = make_workload(torch, N, seed=1)[0]
+    captures = (("the benchmark workload: a frame per millisecond", t_bench),
+                ("sparse: 805 frames in 256 Mi samples", make_workload(torch, N, n_frames=805, seed=2)[0]))
+    builds = []
+    for spec in variants:
+        vname, _, vpath = spec.partition("=")
+        V = C.CDLL(vpath)
+        for fname in ("adsb_create", "adsb_gather_pack12_device"):
+            fn = getattr(V, fname)
+            fn.restype, fn.argtypes = capi.SYMBOLS[fname]
+        vcfg = capi.make_config()
+        vh = V.adsb_create(C.byref(vcfg))
+        assert vh, vpath
+        builds.append((vname, V, vh))
+    torch.cuda.synchronize()
+    for what, cap_t in captures:
+        assert L.adsb_level_device(d._h, cap_t.data_ptr(), N, C.byref(rep1), env.data_ptr(), ke) == M
+        thr = float(np.float32(capi.Decoder.BURST_FACTOR * L.adsb_level_percentile(C.byref(rep1), 0.5)))
+        tab, b = d.bursts_device(env.data_ptr(), ke, thr, 2, 4, 1 << 16)
+        assert 0 < b <= 1 << 16
+        tab = np.ascontiguousarray(tab)
+        host = cap_t.cpu().numpy().view(np.uint16)
+        want12, off12, over = BA.gather12(host, tab, M)
+        total12, total16 = int(off12[-1]), int(BA.layout(tab, M, 4)[-1])
+        assert over == 0
+        sl = levels.burst_samples(tab, M)
+        # the twins of the capture for _packed and _as: the same codes, so the same table and the same bytes
+        t_p12 = torch.from_numpy(packed12.pack12(host)).cuda()
+        t_i16 = torch.from_numpy(sample_formats.to_format(3, host)).cuda()
+        over_c = C.c_uint64(0)
+
+        def g12(lib=L, h=d._h):
+            assert lib.adsb_gather_pack12_device(h, cap_t.data_ptr(), N, tab.ctypes.data, b, dst.data_ptr(), 2 * N, None, C.byref(over_c)) == total12
+
+        def g12_packed():
+            assert L.adsb_gather_pack12_device_packed(d._h, t_p12.data_ptr(), N, tab.ctypes.data, b, dst.data_ptr(), 2 * N, None, C.byref(over_c)) == total12
+
+        def g12_as():
+            assert L.adsb_gather_pack12_device_as(d._h, 3, t_i16.data_ptr(), N, tab.ctypes.data, b, dst.data_ptr(), 2 * N, None, C.byref(over_c)) == total12
+
+        def g16():
+            assert L.adsb_gather_device(d._h, cap_t.data_ptr(), 2 * N, 4, M, tab.ctypes.data, b, dst16.data_ptr(), 2 * N, None) == total16
+
+        # the separate pack in torch: adsb_gather_device's pieces (whole groups here: M % 4 == 0) -> the 12-bit layout, on the device
+        assert M % 4 == 0
+        groups = [int(hi - lo) // 4 for lo, hi in sl]
+        g_h = torch.tensor(groups, dtype=torch.int64).pin_memory()
+        s_h = torch.tensor([int(o) // 16 for o in BA.layout(tab, M, 4)[:-1]], dtype=torch.int64).pin_memory()   # a group is 16 bytes there
+        o_h = torch.tensor([int(o) // 4 for o in off12[:-1]], dtype=torch.int64).pin_memory()                   # ... and 3 dwords here
+        dst_w = dst.view(torch.int32)
+
+        def g16_then_torch_pack():
+            g16()
+            g_d, s_d, o_d = (v.cuda(non_blocking=True) for v in (g_h, s_h, o_h))
+            first = torch.cumsum(g_d, 0) - g_d
+            k = torch.arange(int(g_h.sum()), device="cuda") - torch.repeat_interleave(first, g_d)
+            c = dst16.view(torch.int16).view(-1, 8)[torch.repeat_interleave(s_d, g_d) + k].to(torch.int64) & 0xFFF
+            w0 = (c[:, 0] << 20) | (c[:, 1] << 8) | (c[:, 2] >> 4)
+            w1 = ((c[:, 2] & 0xF) << 28) | (c[:, 3] << 16) | (c[:, 4] << 4) | (c[:, 5] >> 8)
+            w2 = ((c[:, 5] & 0xFF) << 24) | (c[:, 6] << 12) | c[:, 7]
+            at = torch.repeat_interleave(o_d, g_d) + 3 * k
+            dst_w[:total12 // 4].zero_()
+            for j, w in enumerate((w0, w1, w2)):
+                dst_w[at + j] = ((w + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)                 # (the dword's bits as a signed int32)
+            torch.cuda.synchronize()
+
+        sides = {"adsb_gather_pack12_device": g12, "adsb_gather_pack12_device again (the A/A)": g12, "adsb_gather_device, the same table": g16,
+                 "adsb_gather_device, then a pack in torch": g16_then_torch_pack, "adsb_gather_pack12_device_packed (unpack + gather)": g12_packed,
+                 "adsb_gather_pack12_device_as fmt 3 (convert + gather)": g12_as}
+        for vname, lib, h in builds:
+            sides[f"adsb_gather_pack12_device, {vname}"] = lambda lib=lib, h=h: g12(lib, h)
+        for name, side in sides.items():
+            if side is g16:
+                continue
+            dst[:total12].fill_(0xA5)
+            side()
+            assert np.array_equal(dst[:total12].cpu().numpy(), want12), name
+        lines += [f"# (a) {what}: {b} bursts at factor 48, lead 2, hang 4; {total12} bytes at 12 bits, {total16} as uint16, of {2 * N}; every side checked",
+                  f"#     against burst_archive.gather12 first; {reps} rounds, the sides in a new random order every round, one call per side and round", head]
+        names, wall = rotate(sides)
+        table_of(names, wall, names[0])
+        a12, a16 = 64 + 16 * b + total12, 64 + 16 * b + total16
+        lines += [f"# (b) the archive: kind 12 {a12} bytes (64 + 16 x {b} + {total12}), kind 4 {a16}: {100.0 * a12 / a16:.2f} % of it; over the capture's "
+                  f"{2 * N}: {100.0 * a12 / (2 * N):.3f} % against {100.0 * a16 / (2 * N):.3f} %", "#"]
+        del t_p12, t_i16
+
+    lines += ["# (c) the untouched paths beside the parent commit's library (--ab), adsb_level_device and adsb_decode_device on the benchmark capture", head]
+    if not parent:
+        lines.append("#     (no --ab parent library given: not measured in this run)")
+        return
+    B = C.CDLL(parent)
+    for name in ("adsb_create", "adsb_decode_device", "adsb_level_device"):
+        fn = getattr(B, name)
+        fn.restype, fn.argtypes = capi.SYMBOLS[name]
+    assert not hasattr(B, "adsb_gather_pack12_device"), "the --ab library is not the parent's: it has the 12-bit gather"
+    cfg = capi.make_config()
+    hh = B.adsb_create(C.byref(cfg))
+    assert hh, parent
+
+    def level(lib, h):
+        assert lib.adsb_level_device(h, t_bench.data_ptr(), N, C.byref(rep1), env.data_ptr(), ke) == M
+
+    def decode(lib, h):
+        assert lib.adsb_decode_device(h, t_bench.data_ptr(), N, C.byref(out)) >= 0
+    for what, fn, steps in (("adsb_level_device", level, 1), ("adsb_decode_device", decode, 3)):
+        names, wall = rotate({f"{what}, tree": lambda: fn(L, d._h), f"{what}, tree again (the A/A)": lambda: fn(L, d._h),
+                              f"{what}, parent commit": lambda: fn(B, hh)}, steps=steps)
+        table_of(names, wall, names[0])
+
+
 def next_round(stem):
     """profiles/rNN_<stem>.txt with the next free round number."""
     import re
@@ -1743,7 +1898,19 @@ def main():
     ap.add_argument("--bursts", action="store_true", help="the gate behind the envelope (adsb_bursts_device) beside a torch gate and a host gate instead: profiles/rNN_bursts.txt with the next free NN; --ab: the parent commit's library, for (c)")
     ap.add_argument("--flush", action="store_true", help="flush (adsb_set_flush): the decode call across the change, the batch of short captures, the gated pipeline: profiles/r30_flush.txt; --ab: the parent commit's library")
     ap.add_argument("--gather", action="store_true", help="the burst gather (adsb_gather_device) beside copy loops and a torch gather, its bytes per second, the archive's size, the archive route end to end, odd against even begins (and --variant builds with another load): profiles/r32_gather.txt; --ab: the parent commit's library")
+    ap.add_argument("--gather-pack12", action="store_true", help="the 12-bit burst gather (adsb_gather_pack12_*) beside adsb_gather_device, a separate pack in torch, the _packed and _as flavours (and --variant builds with another kernel), the archive's size: profiles/r33_pack12.txt; --ab: the parent commit's library")
     a = ap.parse_args()
+    if a.gather_pack12:
+        a.out = a.out or os.path.join(ROOT, "profiles", "r33_pack12.txt")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --gather-pack12: a real capture's bursts kept at 12 bits (gather_pack12_kernel.hip, adsb_gather_pack12_*), one",
+                 f"# process, {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved in a new random order every round, a warm-up round first.",
+                 "# The captures are tools/gen_signal.py make_workload, 256 Mi samples (512 MiB): seed 1 (the benchmark's) and 805 frames, seed 2 (sparse).",
+                 "# Wall time of the calls through ctypes / torch; every side waits for its kernels and copies.", "#"]
+        gather_pack12_probe(capi.load(), a.reps, lines, a.ab, a.variant)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.gather:
         a.out = a.out or os.path.join(ROOT, "profiles", "r32_gather.txt")
         torch.cuda.set_device(0)
