@@ -31,6 +31,9 @@ HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip",
 C_SOURCES = ["format.c"]
 # host-only C++ (no HIP): the multi-GPU driver over the C-ABI, and the part of the C-ABI that needs no device
 CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]
+# the host program (csrc/cli/): one gcc line over all of them; it is rebuilt when any of them or any header beside them changes
+CLI_DIR = os.path.join(CSRC, "cli")
+CLI_SOURCES = ["adsbdec_amd_cli.c", "options.c", "common.c", "stream.c", "batch.c", "export.c", "level.c", "bursts.c", "sink.c", "burst_archive.c"]
 # What an object depends on is what the compiler says it read: every compile writes <object>.d (-MMD) and the next build
 # reads it.  (Until round 6 this was a hand-kept list of headers, and gang.hpp -- included by resolver.hpp -- was not on
 # it: editing it alone left stale objects.  tests/test_host_logic.py touches a header and watches the rebuild.)
@@ -107,17 +110,19 @@ def build(force: bool = False, verbose: bool = False) -> str:
         objs.append(obj)
     if force or _newer(LIB, objs):
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-lm", "-lpthread"])
-    cli_src = os.path.join(CSRC, "cli", "adsbdec_amd_cli.c")
-    sink_src = os.path.join(CSRC, "cli", "sink.c")
-    brs_src = os.path.join(CSRC, "cli", "burst_archive.c")  # the burst archive's reader and writer (-K, -P, -k)
-    if os.path.exists(cli_src) and (force or _newer(CLI, [cli_src, sink_src, os.path.join(CSRC, "cli", "sink.h"), brs_src,
-                                                           os.path.join(CSRC, "cli", "burst_archive.h"), LIB,
-                                                           os.path.join(ROOT, "include", "adsbdec_amd.h")])):
-        # (the HIP runtime's C API: the device buffer of the program's own that -W -q exports through)
-        _run(["gcc", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__", "-o", CLI, cli_src, sink_src, brs_src, "-I", os.path.join(ROOT, "include"),
-              "-I", os.path.join(ROCM, "include"), "-L", LIBDIR, "-ladsbdec_amd", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-lpthread",
-              "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ROCM, "lib")])
+    cli_srcs = [os.path.join(CLI_DIR, s) for s in CLI_SOURCES]
+    cli_headers = [os.path.join(CLI_DIR, h) for h in sorted(os.listdir(CLI_DIR)) if h.endswith(".h")] if os.path.isdir(CLI_DIR) else []
+    if cli_headers and (force or _newer(CLI, cli_srcs + cli_headers + [LIB, os.path.join(ROOT, "include", "adsbdec_amd.h")])):
+        _run(cli_command(CLI, cli_srcs))
     return LIB
+
+
+def cli_command(out: str, srcs: list[str], extra: list[str] | None = None) -> list[str]:
+    """The one gcc line of the host program: `srcs` against this tree's library and public header.
+    (The HIP runtime's C API: the device buffers of the program's own that -W -q, -L and -K | -P work through.)"""
+    return (["gcc", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__"] + (extra or []) + ["-o", out] + srcs +
+            ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROCM, "include"), "-L", LIBDIR, "-ladsbdec_amd",
+             "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-lpthread", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ROCM, "lib")])
 
 
 if __name__ == "__main__":

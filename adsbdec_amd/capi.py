@@ -1,7 +1,7 @@
 """ctypes binding of include/adsbdec_amd.h.
 
 This is plumbing for tests/ and bench.py: the product's host side is C
-(csrc/cli/adsbdec_amd_cli.c) and everything of substance lives behind the C-ABI.
+(csrc/cli/, adsbdec_amd_cli.c and the files beside it) and everything of substance lives behind the C-ABI.
 There is no Python or CPU fallback: if the shared library is missing or no
 gfx950 device is present, calls fail loudly.
 """

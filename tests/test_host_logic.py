@@ -136,17 +136,28 @@ def test_drop_in_header_is_short_and_self_contained(tmp_path):
     src.write_text('#include "adsbdec_amd.h"\nint main(void) { adsb_config c; adsb_config_default(&c); adsb_profile p; (void)p; '
                    'return c.abi == ADSB_ABI_VERSION ? 0 : 1; }\n')
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", inc, "-c", str(src), "-o", str(tmp_path / "o.o")], check=True)
+    public = r'#include\s+"[./]*(include/)?adsbdec_amd\.h"'
     for f in (os.path.join(ROOT, "adsbdec_amd", "csrc", "cli", "adsbdec_amd_cli.c"), os.path.join(ROOT, "adsbdec_amd", "csrc", "format.c"),
               os.path.join(ROOT, "oracle", "dropin_decodeiq.c")):
         text = open(f).read()
-        assert "adsbdec_amd_diag.h" not in text and re.search(r'#include\s+"[./]*(include/)?adsbdec_amd\.h"', text), f
+        assert "adsbdec_amd_diag.h" not in text and re.search(public, text), f
+    # the host program is every file of csrc/cli/: none of them names the diag header, and every .c that calls the library has the
+    # public one, itself or through a header of cli/ that includes it
+    cli = os.path.join(ROOT, "adsbdec_amd", "csrc", "cli")
+    texts = {f: open(os.path.join(cli, f)).read() for f in sorted(os.listdir(cli)) if f.endswith((".c", ".h"))}
+    assert sum(f.endswith(".c") for f in texts) >= 10 and all("adsbdec_amd_diag.h" not in t for t in texts.values())
+    with_public = {f for f, t in texts.items() if f.endswith(".h") and re.search(public, t)}
+    for f, t in texts.items():
+        if f.endswith(".c") and re.search(r"\badsb_[a-z0-9_]+\s*\(", re.sub(r"/\*.*?\*/", "", t, flags=re.S)):
+            assert re.search(public, t) or with_public & set(re.findall(r'#include\s+"([a-z_0-9]+\.h)"', t)), f
+    from adsbdec_amd import _build
+    assert sorted(_build.CLI_SOURCES) == sorted(f for f in texts if f.endswith(".c"))          # (and the build compiles every one of them)
     # every entry point the two headers declare is exported, and nothing else with the library's prefix is
     declared = set()
     for h in ("adsbdec_amd.h", "adsbdec_amd_diag.h"):
         text = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, h)).read(), flags=re.S)
         declared |= set(re.findall(r"\b(adsb_[a-z0-9_]+)\s*\(", text))
     declared -= {"adsb_get_profile", "adsb_multi_worker_profile"}          # macros over the _sized calls
-    from adsbdec_amd import _build
     out = subprocess.run(["nm", "-D", "--defined-only", _build.LIB], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r" T (adsb_[a-z0-9_]+)", out))
     assert declared == exported, (sorted(declared - exported), sorted(exported - declared))
