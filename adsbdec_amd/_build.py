@@ -25,7 +25,7 @@ HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip",
                "decoder_lifecycle.hip", "decoder_batch.hip", "decoder_shard.hip", "unpack12.hip", "unpack12_batch.hip",
                "convert_samples.hip", "power_export_kernel.hip", "decoder_export.hip",
                "power_export_batch_kernel.hip", "decoder_export_batch.hip", "level_kernel.hip", "decoder_level.hip",
-               "level_batch_kernel.hip", "decoder_level_batch.hip", "level_windows_kernel.hip", "decoder_level_windows.hip", "decoder_stage.hip",
+               "level_batch_kernel.hip", "decoder_level_batch.hip", "level_windows_kernel.hip", "decoder_level_windows.hip", "decoder_stage.hip", "decoder_flavour.hip",
                "burst_kernel.hip", "decoder_bursts.hip", "gather_kernel.hip", "decoder_gather.hip",
                "gather_pack12_kernel.hip", "decoder_gather_pack12.hip"]
 C_SOURCES = ["format.c"]

@@ -789,20 +789,6 @@ int format_counters(adsb_decoder *d, unsigned long long out[2])
     return 0;
 }
 
-// What every _as call checks first: the format.  0: converted (*elem bytes per sample); 1: the uint16 code itself; -1: refused.
-int format_dispatch(adsb_decoder *d, const char *what, int fmt, size_t *elem)
-{
-    *elem = adsb::format_element_bytes(fmt);
-    if (*elem)
-        return 0;
-    if (fmt == adsb::kFmtUint16Real || fmt == adsb::kFmtRaw)
-        return 1;
-    if (fmt == 0 || fmt == 2)
-        return d->fail("%s: format %d (%s) is not a real format: libairspy has already mixed, filtered and decimated an IQ stream, so it has no "
-                       "raw twin to be decoded as", what, fmt, fmt == 0 ? "FLOAT32_IQ" : "INT16_IQ");
-    return d->fail("%s: unknown sample format %d (1 FLOAT32_REAL, 3 INT16_REAL, 4 UINT16_REAL, 5 RAW)", what, fmt);
-}
-
 // The stream's kind is fixed by its first push with samples; a push of another kind is refused, the handle as it was.
 int kind_refusal(adsb_decoder *d, const char *what, int kind)
 {
@@ -1038,27 +1024,7 @@ static int push_device_as_impl(adsb_decoder *d, int fmt, const void *p, size_t n
 }
 
 // ---- complex samples (the _iq calls; include/adsbdec_amd.h) ----
-// What every _iq call checks before anything of the handle changes.  n counts complex samples; the stream counts 16-bit units
-// (two per complex sample), so everything behind these checks is the uint16 machinery with 2 n.  An int8 stream (fmt 8) counts
-// bytes, two per complex sample as well: the same machinery with the same 2 n, and a unit of one byte where it copies.
-int iq_refusal(adsb_decoder *d, const char *what, int fmt, const void *p, size_t n, bool device, uint64_t at_units)
-{
-    const size_t align = fmt == adsb::kFmtInt8Iq ? 2 : 4;
-    if (!adsb::iq_sample_bytes(fmt))
-        return d->fail("%s: format %d is not an IQ format (0 FLOAT32_IQ, 2 INT16_IQ, 8 INT8_IQ; real samples go through the _as calls)", what, fmt);
-    if ((uint64_t)n >= (1ull << 31) || at_units + 2 * (uint64_t)n >= (1ull << 32))
-        return d->fail("%s: the stream would reach 2^31 complex samples (%llu + %zu): IQ streams end below", what,
-                       (unsigned long long)(at_units / 2), n);
-    if (n && !p)
-        return d->fail("%s: NULL samples", what);
-    if (device && (uintptr_t)p % align != 0)
-        return d->fail("%s: device pointer %p is not %zu-byte aligned", what, p, align);
-    return 0;
-}
-
-// the stream kind an _iq format makes: fmt 0 is converted to fmt 2's int16 pairs; fmt 8 is a kind of its own, its units bytes
-static inline int iq_kind(int fmt) { return fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq; }
-
+// (what every _iq call checks first, and the stream kind a format makes: flavour.hpp iq_refusal, iq_kind)
 static int push_host_iq(adsb_decoder *d, int fmt, const void *samples, size_t n, bool async, const char *what)
 {
     if (!d)
@@ -1089,21 +1055,7 @@ static int push_device_iq(adsb_decoder *d, int fmt, const void *p, size_t n, boo
 }
 
 // ---- float32 power samples (the _power calls; include/adsbdec_amd.h) ----
-// What every _power call checks before anything of the handle changes.  n counts power samples; the stream counts 16-bit units
-// (two per power sample), so everything behind these checks is INT16_IQ's road with 2 n: copies, staging, compaction, in-place
-// scans, the EOF rule and the count pass -- a power sample is 4 bytes, as a complex int16 sample is.
-int power_refusal(adsb_decoder *d, const char *what, const void *p, size_t n, bool device, uint64_t at_units)
-{
-    if ((uint64_t)n >= (1ull << 31) || at_units + 2 * (uint64_t)n >= (1ull << 32))
-        return d->fail("%s: the stream would reach 2^31 power samples (%llu + %zu): power streams end below", what,
-                       (unsigned long long)(at_units / 2), n);
-    if (n && !p)
-        return d->fail("%s: NULL samples", what);
-    if (device && (uintptr_t)p % 4 != 0)
-        return d->fail("%s: device pointer %p is not 4-byte aligned", what, p);
-    return 0;
-}
-
+// (what every _power call checks first: flavour.hpp power_refusal)
 static int push_host_power(adsb_decoder *d, const float *samples, size_t n, bool async, const char *what)
 {
     if (!d)

@@ -1,8 +1,6 @@
 // decoder_batch.hip -- a batch of independent captures in as few launches as they fit (adsb_decode_batch_*, batch.hpp): the
 // launches borrow a scan slot of the handle's (decoder_state.hpp) and are waited for one by one.
 #include "decoder_state.hpp"
-#include "packed12.h"
-#include "sample_format.h"
 
 using namespace adsb;
 
@@ -19,24 +17,45 @@ inline int batch_forced_passes(int passes) { return (passes >= 2 && passes <= ad
 
 inline uint64_t batch_wanted_limit(int32_t knob) { return knob > 0 ? (uint64_t)knob : 0; } // (batch_launch_limit judges it)
 
-// The refusals of adsb_decode_batch_*, before anything of the handle changes.  A device pointer must be aligned to `align`
-// bytes; packed captures come in whole 8-sample groups.
-int batch_refusal(adsb_decoder *d, const char *what, size_t n_captures, const void *const *p, const size_t *n, bool device,
-                  unsigned align, bool packed)
+// What every adsb_decode_batch_* call asks of its two arrays, first.
+int batch_arrays_refusal(adsb_decoder *d, const char *what, size_t n_captures, const void *const *p, const size_t *n)
 {
-    if (n_captures && (!p || !n))
-        return d->fail("%s: NULL capture arrays", what);
+    return n_captures && (!p || !n) ? d->fail("%s: NULL capture arrays", what) : 0;
+}
+
+// The complex or power captures of a batch (n[] counts those samples): what a stream of the kind asks (flavour.hpp), per capture.
+int batch_refusal_twos(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *p, const size_t *n)
+{
+    if (d->long_stream)
+        return kind_refusal(d, what, F.kind);
+    char who[96];
+    for (size_t i = 0; i < n_captures; i++) {
+        snprintf(who, sizeof who, "%s: capture %zu", what, i);
+        if (units_refusal(d, who, F, p[i], n[i], 0))
+            return -1;
+    }
+    return 0;
+}
+
+// The refusals of adsb_decode_batch_*, before anything of the handle changes, of the flavour F's captures (F.in_align = 0: in host
+// memory).
+int batch_refusal(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *p, const size_t *n)
+{
+    if (batch_arrays_refusal(d, what, n_captures, p, n))
+        return -1;
+    if (!F.real())
+        return batch_refusal_twos(d, what, F, n_captures, p, n);
     for (size_t i = 0; i < n_captures; i++) {
         if ((uint64_t)n[i] >= (1ull << 32))
             return d->fail("%s: capture %zu has %zu samples: 2^32 or more, where the reference's sample counter wraps (air.c:34); "
                            "a batch has no long-stream mode", what, i, n[i]);
-        if (packed && n[i] % adsb::kPackedGroupSamples != 0)
+        if (F.groups8 && n[i] % adsb::kPackedGroupSamples != 0)
             return d->fail("%s: capture %zu: n = %zu is not a multiple of 8 (packed 12-bit input comes in whole 8-sample groups)", what,
                            i, n[i]);
         if (n[i] && !p[i])
             return d->fail("%s: capture %zu: NULL samples", what, i);
-        if (device && (uintptr_t)p[i] % align != 0)
-            return d->fail("%s: capture %zu: device pointer %p is not %u-byte aligned", what, i, p[i], align);
+        if (F.in_align && (uintptr_t)p[i] % F.in_align != 0)
+            return d->fail("%s: capture %zu: device pointer %p is not %u-byte aligned", what, i, p[i], F.in_align);
     }
     return 0;
 }
@@ -197,102 +216,52 @@ long decode_batch(adsb_decoder *d, size_t n_captures, const void *const *p, cons
 }
 
 
-// unpack, decode; and the stream idle behind it whatever the result (a batch without an offset launches no scan that would have
-// been waited for: the table and the scratch are the next call's to rewrite)
-long decode_batch_packed(adsb_decoder *d, const char *what, size_t n_captures, const void *const *src, const size_t *n,
-                         const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+// Unpack or convert, decode; and the stream idle behind it whatever the result (a batch without an offset launches no scan that would
+// have been waited for: the table and the scratch are the next call's to rewrite).  Every sample goes through the launch in front, not
+// Flavour::scratch_elements' choice: a decode reads a capture's trailing partial quad too.
+long decode_batch_front(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *src, const size_t *n,
+                        const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
     std::vector<const void *> at;
     d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
-    if (batch_to_scratch(d, what, 0, n_captures, src, n, at))
+    if (batch_to_scratch(d, what, F.conv, n_captures, src, n, at))
         return -1;
     const long k = decode_batch(d, n_captures, at.data(), n, frames, first, stats);
     WAIT_STREAM(d, d->stream, "the scan stream");
     return k;
 }
 
-// convert, decode; and the stream idle behind it whatever the result (as decode_batch_packed)
-long decode_batch_as(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
-                     const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
+// ---- batches of IQ and float32 power captures (adsb_decode_batch_*_iq, _power) ----
+// n[] counts complex or power samples.  The batch machinery counts 16-bit units and ends a capture by the real streams' rule (a
+// trailing partial quad still yields two power samples); these captures' power samples enter in twos and a trailing odd one is never
+// seen (air.c:94-99), which is exactly what the machinery does for the capture WITHOUT that sample: units[i] = 4 (n[i] / 2).
+// The captures in device memory at src[] (int16 pairs or float32 power samples, 4-byte aligned; float pairs; int8 pairs, 2-byte
+// aligned) -> frames.  Whatever is not 16-byte aligned int16 goes through scratch first: FLOAT32_IQ by the batch conversion launch, a
+// misaligned capture of the others by a copy.  The layout is asked at the number the widened twin is asked at, 4 (n / 2), so
+// segments, tiles and launches are the twin's; a unit of an int8 capture is a BYTE there (kind_unit_bytes), which only the scratch
+// copies of the captures that are not 16-byte aligned see -- the segment table counts complex samples either way.
+long decode_batch_twos(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *src, const size_t *n,
+                       const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
-    std::vector<const void *> at;
-    d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
-    if (batch_to_scratch(d, what, fmt, n_captures, src, n, at))
-        return -1;
-    const long k = decode_batch(d, n_captures, at.data(), n, frames, first, stats);
-    WAIT_STREAM(d, d->stream, "the scan stream");
-    return k;
-}
-
-// ---- batches of IQ captures (adsb_decode_batch_*_iq) ----
-// n[] counts complex samples.  The batch machinery counts 16-bit units and ends a capture by the real streams' rule (a trailing
-// partial quad still yields two power samples); an IQ capture's power samples enter in twos and a trailing odd one is never seen
-// (air.c:94-99), which is exactly what the machinery does for the capture WITHOUT that sample: units[i] = 4 (n[i] / 2).
-int batch_refusal_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *p, const size_t *n, bool device)
-{
-    if (n_captures && (!p || !n))
-        return d->fail("%s: NULL capture arrays", what);
-    if (!adsb::iq_sample_bytes(fmt))
-        return iq_refusal(d, what, fmt, nullptr, 0, device, 0);
-    if (d->long_stream)
-        return kind_refusal(d, what, fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq);
-    char who[96];
-    for (size_t i = 0; i < n_captures; i++) {
-        snprintf(who, sizeof who, "%s: capture %zu", what, i);
-        if (iq_refusal(d, who, fmt, p[i], n[i], device, 0))
-            return -1;
-    }
-    return 0;
-}
-
-// The captures in device memory at src[] (fmt 2: int16 pairs, 4-byte aligned; fmt 0: float pairs) -> frames.  Whatever is not
-// 16-byte aligned int16 goes through scratch first: fmt 0 by the batch conversion launch, a misaligned fmt-2 capture by a copy.
-// kind = kKindPower (fmt 2): the captures are float32 power samples, n[] counts them -- the same 4-byte units on the same road.
-// kind = kKindIq8 (fmt 8): int8 pairs, 2-byte aligned.  The layout is asked at the number the widened twin is asked at, 4 (n / 2),
-// so segments, tiles and launches are the twin's; a unit is a BYTE there (decoder_state.hpp kind_unit_bytes), which only the
-// scratch copies of the captures that are not 16-byte aligned see -- the segment table counts complex samples either way.
-long decode_batch_iq(adsb_decoder *d, const char *what, int fmt, size_t n_captures, const void *const *src, const size_t *n,
-                     const adsb_frame **frames, uint64_t *first, adsb_stats *stats, int kind = adsb::kKindIq)
-{
-    std::vector<size_t> units(n_captures), scalars(n_captures);
-    for (size_t i = 0; i < n_captures; i++) {
+    std::vector<size_t> units(n_captures);
+    for (size_t i = 0; i < n_captures; i++)
         units[i] = 4 * (n[i] / 2);
-        scalars[i] = 2 * n[i];
-    }
-    std::vector<const void *> at(src, src + n_captures);
-    const size_t unit = adsb::kind_unit_bytes(kind);
+    std::vector<const void *> at;
     d->finished = true; // (as decode_batch: a failure from here on leaves a finished handle too)
-    if (fmt == 0) {
-        if (batch_to_scratch(d, what, adsb::kConvFloat32Iq, n_captures, src, scalars.data(), at))
-            return -1;
-    } else {
+    if (flavour_batch_to_scratch(d, what, F, n_captures, src, n, at))
+        return -1;
+    if (F.front == Flavour::kNone) {
         d->batch_unpacked_at.clear(); // (adsb_batch_unpacked_copy: no table of this call's; the copies rewrite the scratch)
         std::vector<size_t> bytes(n_captures);
         for (size_t i = 0; i < n_captures; i++)
-            bytes[i] = units[i] * unit;
+            bytes[i] = units[i] * adsb::kind_unit_bytes(F.kind);
         if (batch_realign(d, what, n_captures, bytes.data(), at))
             return -1;
     }
-    d->kind = kind; // (behind the reset: the batch launches are scan_iq_batch_kernel's or scan_power_batch_kernel's)
+    d->kind = F.kind; // (behind the reset: the batch launches are this kind's kernel's)
     const long k = decode_batch(d, n_captures, at.data(), units.data(), frames, first, stats);
     WAIT_STREAM(d, d->stream, "the scan stream");
     return k;
-}
-
-// ---- batches of float32 power captures (adsb_decode_batch_*_power): n[] counts power samples ----
-int batch_refusal_power(adsb_decoder *d, const char *what, size_t n_captures, const void *const *p, const size_t *n, bool device)
-{
-    if (n_captures && (!p || !n))
-        return d->fail("%s: NULL capture arrays", what);
-    if (d->long_stream)
-        return kind_refusal(d, what, adsb::kKindPower);
-    char who[96];
-    for (size_t i = 0; i < n_captures; i++) {
-        snprintf(who, sizeof who, "%s: capture %zu", what, i);
-        if (power_refusal(d, who, p[i], n[i], device, 0))
-            return -1;
-    }
-    return 0;
 }
 
 // The host captures of a batch (bytes_of(n[i]) bytes each) into `buf`, each at a multiple of `align` bytes: copied on the copy streams in
@@ -307,6 +276,15 @@ int land_batch(adsb_decoder *d, const char *what, adsb::Buf<uint8_t> &buf, const
     return land_captures(d, what, buf, of, n_captures, src, bytes.data(), align, adsb::Land::InTurnWaited, at);
 }
 
+// every entry point behind its refusals: a fresh stream on the handle's device
+int batch_begin(adsb_decoder *d)
+{
+    if (adsb_reset(d) != 0)
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -317,108 +295,95 @@ long adsb_decode_batch_device_power(adsb_decoder *d, size_t n_captures, const vo
     const char *what = "adsb_decode_batch_device_power";
     if (!d || !frames || !first)
         return -1;
-    if (batch_refusal_power(d, what, n_captures, device_samples, n, true))
+    if (batch_refusal(d, what, flavour_power(), n_captures, device_samples, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return decode_batch_iq(d, what, 2, n_captures, device_samples, n, frames, first, stats, adsb::kKindPower);
+    return decode_batch_twos(d, what, flavour_power(), n_captures, device_samples, n, frames, first, stats);
 }
 
 long adsb_decode_batch_host_power(adsb_decoder *d, size_t n_captures, const float *const *samples, const size_t *n,
                                   const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
     const char *what = "adsb_decode_batch_host_power";
+    const void *const *src = reinterpret_cast<const void *const *>(samples);
     if (!d || !frames || !first)
         return -1;
-    if (batch_refusal_power(d, what, n_captures, reinterpret_cast<const void *const *>(samples), n, false))
+    if (batch_refusal(d, what, flavour_power().on_host(), n_captures, src, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
     // every capture as it is at a 128-byte boundary of the landing buffer the other host batches use
     std::vector<const void *> land;
-    if (land_batch(d, what, d->batch_land, "the captures as they are", n_captures, reinterpret_cast<const void *const *>(samples), n,
-                   [](size_t k) { return k * sizeof(float); }, 128, land))
+    if (land_batch(d, what, d->batch_land, "the captures as they are", n_captures, src, n, [](size_t k) { return k * sizeof(float); }, 128, land))
         return -1;
-    return decode_batch_iq(d, what, 2, n_captures, land.data(), n, frames, first, stats, adsb::kKindPower);
+    return decode_batch_twos(d, what, flavour_power(), n_captures, land.data(), n, frames, first, stats);
 }
 
 long adsb_decode_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
     const char *what = "adsb_decode_batch_device_iq";
+    Flavour F;
     if (!d || !frames || !first)
         return -1;
-    if (batch_refusal_iq(d, what, fmt, n_captures, device_samples, n, true))
+    if (batch_arrays_refusal(d, what, n_captures, device_samples, n) || flavour_iq(d, what, fmt, &F) ||
+        batch_refusal(d, what, F, n_captures, device_samples, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return decode_batch_iq(d, what, fmt, n_captures, device_samples, n, frames, first, stats, fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq);
+    return decode_batch_twos(d, what, F, n_captures, device_samples, n, frames, first, stats);
 }
 
 long adsb_decode_batch_host_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
                                const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
     const char *what = "adsb_decode_batch_host_iq";
+    Flavour F;
     if (!d || !frames || !first)
         return -1;
-    if (batch_refusal_iq(d, what, fmt, n_captures, samples, n, false))
+    if (batch_arrays_refusal(d, what, n_captures, samples, n) || flavour_iq(d, what, fmt, &F) ||
+        batch_refusal(d, what, F.on_host(), n_captures, samples, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
     // every capture as it is at a 128-byte boundary of the landing buffer the other host batches use
     std::vector<const void *> land;
     const size_t elem = adsb::iq_sample_bytes(fmt);
     if (land_batch(d, what, d->batch_land, "the captures as they are", n_captures, samples, n, [elem](size_t k) { return k * elem; }, 128, land))
         return -1;
-    return decode_batch_iq(d, what, fmt, n_captures, land.data(), n, frames, first, stats, fmt == adsb::kFmtInt8Iq ? adsb::kKindIq8 : adsb::kKindIq);
+    return decode_batch_twos(d, what, F, n_captures, land.data(), n, frames, first, stats);
 }
 
 long adsb_decode_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                  const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
     const char *what = "adsb_decode_batch_device_as";
-    size_t elem;
+    Flavour F;
     if (!d || !frames || !first)
         return -1;
-    const int k = format_dispatch(d, what, fmt, &elem);
+    const int k = flavour_as(d, what, fmt, &F);
     if (k < 0)
         return -1;
     if (k)
         return adsb_decode_batch_device(d, n_captures, device_samples, n, frames, first, stats);
-    if (batch_refusal(d, what, n_captures, device_samples, n, true, (unsigned)elem, false))
+    if (batch_refusal(d, what, F, n_captures, device_samples, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return decode_batch_as(d, what, fmt, n_captures, device_samples, n, frames, first, stats);
+    return decode_batch_front(d, what, F, n_captures, device_samples, n, frames, first, stats);
 }
 
 long adsb_decode_batch_host_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *samples, const size_t *n,
                                const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
     const char *what = "adsb_decode_batch_host_as";
-    size_t elem;
+    Flavour F;
     if (!d || !frames || !first)
         return -1;
-    const int k = format_dispatch(d, what, fmt, &elem);
+    const int k = flavour_as(d, what, fmt, &F);
     if (k < 0)
         return -1;
     if (k)
         return adsb_decode_batch_host(d, n_captures, reinterpret_cast<const uint16_t *const *>(samples), n, frames, first, stats);
-    if (batch_refusal(d, what, n_captures, samples, n, false, (unsigned)elem, false))
+    if (batch_refusal(d, what, F.on_host(), n_captures, samples, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
     // every capture's samples at a 16-byte boundary of the landing buffer the packed batches use
     std::vector<const void *> land;
+    const size_t elem = F.in_align; // (a converted format's alignment is its element)
     if (land_batch(d, what, d->batch_land, "the captures as they are", n_captures, samples, n, [elem](size_t k) { return k * elem; }, 16, land))
         return -1;
-    return decode_batch_as(d, what, fmt, n_captures, land.data(), n, frames, first, stats);
+    return decode_batch_front(d, what, F, n_captures, land.data(), n, frames, first, stats);
 }
 
 long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
@@ -426,11 +391,8 @@ long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *co
 {
     if (!d || !frames || !first)
         return -1;
-    if (batch_refusal(d, "adsb_decode_batch_device", n_captures, device_samples, n, true, 16, false))
+    if (batch_refusal(d, "adsb_decode_batch_device", flavour_uint16(), n_captures, device_samples, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
     d->batch_unpacked_at.clear(); // (adsb_batch_unpacked_copy: this call unpacks and converts nothing)
     return decode_batch(d, n_captures, device_samples, n, frames, first, stats);
 }
@@ -438,18 +400,16 @@ long adsb_decode_batch_device(adsb_decoder *d, size_t n_captures, const void *co
 long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n,
                             const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
+    const char *what = "adsb_decode_batch_host";
+    const void *const *src = reinterpret_cast<const void *const *>(samples);
     if (!d || !frames || !first)
         return -1;
-    if (batch_refusal(d, "adsb_decode_batch_host", n_captures, reinterpret_cast<const void *const *>(samples), n, false, 16, false))
+    if (batch_refusal(d, what, flavour_uint16().on_host(), n_captures, src, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
     // every capture at a 128-byte boundary of one scratch array of the handle's
     d->batch_unpacked_at.clear(); // (as adsb_decode_batch_device)
     std::vector<const void *> at;
-    if (land_batch(d, "adsb_decode_batch_host", d->batch_in, "the captures", n_captures, reinterpret_cast<const void *const *>(samples), n,
-                   [](size_t k) { return k * sizeof(uint16_t); }, 128, at))
+    if (land_batch(d, what, d->batch_in, "the captures", n_captures, src, n, [](size_t k) { return k * sizeof(uint16_t); }, 128, at))
         return -1;
     return decode_batch(d, n_captures, at.data(), n, frames, first, stats);
 }
@@ -457,14 +417,12 @@ long adsb_decode_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *
 long adsb_decode_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n,
                                      const adsb_frame **frames, uint64_t *first, adsb_stats *stats)
 {
+    const char *what = "adsb_decode_batch_device_packed";
     if (!d || !frames || !first)
         return -1;
-    if (batch_refusal(d, "adsb_decode_batch_device_packed", n_captures, device_packed, n, true, 4, true))
+    if (batch_refusal(d, what, flavour_packed(), n_captures, device_packed, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return decode_batch_packed(d, "adsb_decode_batch_device_packed", n_captures, device_packed, n, frames, first, stats);
+    return decode_batch_front(d, what, flavour_packed(), n_captures, device_packed, n, frames, first, stats);
 }
 
 long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const void *const *packed, const size_t *n,
@@ -473,17 +431,14 @@ long adsb_decode_batch_host_packed(adsb_decoder *d, size_t n_captures, const voi
     const char *what = "adsb_decode_batch_host_packed";
     if (!d || !frames || !first)
         return -1;
-    if (batch_refusal(d, what, n_captures, packed, n, false, 4, true))
+    if (batch_refusal(d, what, flavour_packed().on_host(), n_captures, packed, n) || batch_begin(d))
         return -1;
-    if (adsb_reset(d) != 0)
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
     // only the packed bytes cross the link: every capture's at a 16-byte boundary of one landing buffer of the handle's
     std::vector<const void *> land;
     if (land_batch(d, what, d->batch_land, "the packed captures (1.5 bytes per sample)", n_captures, packed, n,
                    [](size_t k) { return (size_t)ADSB_PACKED12_BYTES(k); }, 16, land))
         return -1;
-    return decode_batch_packed(d, what, n_captures, land.data(), n, frames, first, stats);
+    return decode_batch_front(d, what, flavour_packed(), n_captures, land.data(), n, frames, first, stats);
 }
 
 long adsb_batch_layout_flush(size_t n_captures, const size_t *n, int cus, int passes, uint64_t launch_offsets, int flush,

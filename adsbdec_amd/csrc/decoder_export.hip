@@ -3,9 +3,7 @@
 // beside them (decoder_shard.hip): a call changes neither the handle's stream position nor its resolver; its kernel goes to the
 // scan stream, behind whatever a push has left there, and the call returns when the floats are written.  (The handle: decoder_state.hpp.)
 #include "decoder_state.hpp"
-#include "packed12.h"
 #include "power_export.h"
-#include "sample_format.h"
 
 using namespace adsb;
 
@@ -56,13 +54,27 @@ long export_window(adsb_decoder *d, const void *device_samples, uint64_t first_s
     return (long)(m_end - m_begin);
 }
 
-// a whole capture of uint16 codes in HBM as a fresh stream (checked by the caller but for the window's own rules)
-long export_capture(adsb_decoder *d, const char *what, const void *device_u16, size_t n, float *device_power, size_t power_cap)
+// A whole real capture of the flavour F in HBM as a fresh stream.  A uint16 capture is read where it lies: its pointers are checked
+// first, in the window call's words; a packed or converted one is read by the launch in front (decoder_stage.hip), on the same stream.
+long export_capture(adsb_decoder *d, const char *what, const Flavour &F, const void *device_samples, size_t n, float *device_power, size_t power_cap)
 {
-    const uint64_t m_end = power_samples_produced(n);
-    if (export_window_refusal(d, what, 0, n, 0, m_end, power_cap))
+    const bool own = F.front == Flavour::kNone;
+    const uint64_t m_end = F.power_samples(n);
+    if (F.groups8 && n % kPackedGroupSamples)
+        return d->fail("%s: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes)", what, n);
+    if (own) {
+        if (export_pointer_refusal(d, what, device_samples, device_power, m_end == 0))
+            return -1;
+    } else if ((uintptr_t)device_samples % F.in_align)
+        return d->fail("%s: device pointer %p is not %zu-byte aligned", what, device_samples, (size_t)F.in_align);
+    if (export_window_refusal(d, what, 0, n, 0, m_end, power_cap) || (!own && export_pointer_refusal(d, what, nullptr, device_power, true)))
         return -1;
-    return export_window(d, device_u16, 0, n, 0, m_end, device_power);
+    if (m_end == 0)
+        return 0;
+    if (!device_samples || !device_power)
+        return d->fail("%s: NULL buffer", what);
+    const void *u16 = flavour_to_scratch(d, what, F, device_samples, n);
+    return u16 ? export_window(d, u16, 0, n, 0, m_end, device_power) : -1;
 }
 
 } // namespace
@@ -102,58 +114,26 @@ long adsb_power_window_host(adsb_decoder *d, const uint16_t *samples, uint64_t f
 
 long adsb_power_device(adsb_decoder *d, const void *device_samples, size_t n, float *device_power, size_t power_cap)
 {
-    const char *what = "adsb_power_device";
-    if (!d)
-        return -1;
-    if (export_pointer_refusal(d, what, device_samples, device_power, power_samples_produced(n) == 0))
-        return -1;
-    return export_capture(d, what, device_samples, n, device_power, power_cap);
+    return d ? export_capture(d, "adsb_power_device", flavour_uint16(), device_samples, n, device_power, power_cap) : -1;
 }
 
 long adsb_power_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap)
 {
     const char *what = "adsb_power_device_as";
-    size_t elem;
+    Flavour F;
     if (!d)
         return -1;
-    const int k = format_dispatch(d, what, fmt, &elem);
+    const int k = flavour_as(d, what, fmt, &F);
     if (k < 0)
         return -1;
     if (k)
         return adsb_power_device(d, device_samples, n, device_power, power_cap);
-    const uint64_t m_end = power_samples_produced(n);
-    if ((uintptr_t)device_samples % elem)
-        return d->fail("%s: device pointer %p is not %zu-byte aligned", what, device_samples, elem);
-    if (export_window_refusal(d, what, 0, n, 0, m_end, power_cap) || export_pointer_refusal(d, what, nullptr, device_power, true))
-        return -1;
-    if (m_end == 0)
-        return 0;
-    if (!device_samples || !device_power)
-        return d->fail("%s: NULL buffer", what);
-    if (to_scratch(d, what, fmt, device_samples, n))
-        return -1;
-    return export_window(d, d->unpacked, 0, n, 0, m_end, device_power); // (the same stream: behind the conversion)
+    return export_capture(d, what, F, device_samples, n, device_power, power_cap);
 }
 
 long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t n, float *device_power, size_t power_cap)
 {
-    const char *what = "adsb_power_device_packed";
-    if (!d)
-        return -1;
-    if (n % kPackedGroupSamples)
-        return d->fail("%s: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes)", what, n);
-    if ((uintptr_t)device_packed % 4)
-        return d->fail("%s: device pointer %p is not 4-byte aligned", what, device_packed);
-    const uint64_t m_end = power_samples_produced(n);
-    if (export_window_refusal(d, what, 0, n, 0, m_end, power_cap) || export_pointer_refusal(d, what, nullptr, device_power, true))
-        return -1;
-    if (m_end == 0)
-        return 0;
-    if (!device_packed || !device_power)
-        return d->fail("%s: NULL buffer", what);
-    if (to_scratch(d, what, 0, device_packed, n))
-        return -1;
-    return export_window(d, d->unpacked, 0, n, 0, m_end, device_power); // (the same stream: behind the unpack)
+    return d ? export_capture(d, "adsb_power_device_packed", flavour_packed(), device_packed, n, device_power, power_cap) : -1;
 }
 
 long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap)
@@ -174,13 +154,11 @@ long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, 
     if (!device_power)
         return d->fail("%s: NULL buffer", what);
     HIP_TRY(d, hipSetDevice(d->device));
-    const uint32_t *iq16 = static_cast<const uint32_t *>(device_samples);
-    if (fmt == 0) { // FLOAT32_IQ: to the int16 grid first, by the conversion the _iq pushes use (and into their scratch)
-        if (to_scratch(d, what, kConvFloat32Iq, device_samples, 2 * n))
-            return -1;
-        iq16 = reinterpret_cast<const uint32_t *>(d->unpacked.p);
-    }
-    HIP_TRY(d, launch_iq_power_export(iq16, n, device_power, d->stream));
+    // (FLOAT32_IQ: to the int16 grid first, by the conversion the _iq pushes use and into their scratch)
+    const void *iq16 = flavour_to_scratch(d, what, flavour_of_iq(fmt), device_samples, n);
+    if (!iq16)
+        return -1;
+    HIP_TRY(d, launch_iq_power_export(static_cast<const uint32_t *>(iq16), n, device_power, d->stream));
     WAIT_STREAM(d, d->stream, "the scan stream");
     return (long)n;
 }

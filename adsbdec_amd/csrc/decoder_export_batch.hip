@@ -5,26 +5,15 @@
 // changes; the launches go to the scan stream, behind whatever a push has left there, and the call returns when the floats are
 // written.  Every refusal comes before anything is launched or counted.  (The handle: decoder_state.hpp.)
 #include "decoder_state.hpp"
-#include "packed12.h"
 #include "power_export_batch.hpp"
-#include "sample_format.h"
 
 using namespace adsb;
 
 namespace {
 
-// What a flavour asks of every capture.
-struct ExportBatchRules {
-    bool iq;           // n[] counts complex samples, and as many power samples come out; else real samples, 2 (n / 4)
-    bool packed;       // whole 8-sample groups
-    unsigned in_align; // bytes a device input pointer is aligned to (0: host memory, any)
-    bool out_device;   // the output pointers are device memory: 16-byte aligned
-};
-
-inline uint64_t export_count(const ExportBatchRules &R, size_t n) { return R.iq ? (uint64_t)n : power_samples_produced(n); }
-
-// The refusals of adsb_power_batch_*, by capture, before anything is launched.
-int export_batch_refusal(adsb_decoder *d, const char *what, const ExportBatchRules &R, size_t n_captures, const void *const *src,
+// The refusals of adsb_power_batch_*, by capture, before anything is launched.  out_device: the output pointers are device memory,
+// 16-byte aligned.
+int export_batch_refusal(adsb_decoder *d, const char *what, const Flavour &F, bool out_device, size_t n_captures, const void *const *src,
                          const size_t *n, float *const *out, const size_t *cap)
 {
     if ((uint64_t)n_captures > kExportMaxCaptures)
@@ -32,13 +21,13 @@ int export_batch_refusal(adsb_decoder *d, const char *what, const ExportBatchRul
     if (n_captures && (!src || !n || !out || !cap))
         return d->fail("%s: NULL capture arrays", what);
     for (size_t i = 0; i < n_captures; i++) {
-        if (R.iq && (uint64_t)n[i] >= (1ull << 31))
+        if (!F.real() && (uint64_t)n[i] >= (1ull << 31))
             return d->fail("%s: capture %zu has %zu complex samples: 2^31 or more; IQ streams end below", what, i, n[i]);
-        if (batch_samples_refusal(d, what, i, src[i], n[i], !R.iq, R.packed, R.in_align))
+        if (batch_samples_refusal(d, what, i, src[i], n[i], F))
             return -1;
-        if (R.out_device && (uintptr_t)out[i] % 16 != 0)
+        if (out_device && (uintptr_t)out[i] % 16 != 0)
             return d->fail("%s: capture %zu: the power array must be 16-byte aligned (%p)", what, i, (const void *)out[i]);
-        const uint64_t count = export_count(R, n[i]);
+        const uint64_t count = F.power_samples(n[i]);
         if (count > cap[i])
             return d->fail("%s: capture %zu has %llu power samples, the array holds %zu", what, i, (unsigned long long)count, cap[i]);
         if (count && (!src[i] || !out[i]))
@@ -49,13 +38,13 @@ int export_batch_refusal(adsb_decoder *d, const char *what, const ExportBatchRul
 
 // The export launch of a checked batch on `st`, behind its table's upload: capture i's samples (uint16 real ones, or int16 complex
 // ones) are in device memory at at[i].  Not waited for.  Returns the floats the launch writes, or -1.
-long export_batch_launch(adsb_decoder *d, const ExportBatchRules &R, size_t n_captures, const void *const *at, const size_t *n,
+long export_batch_launch(adsb_decoder *d, const Flavour &F, size_t n_captures, const void *const *at, const size_t *n,
                          float *const *out, hipStream_t st)
 {
     std::vector<uint64_t> m(n_captures), p_hi(n_captures);
     uint64_t total = 0;
     for (size_t i = 0; i < n_captures; i++) {
-        m[i] = export_count(R, n[i]);
+        m[i] = F.power_samples(n[i]);
         p_hi[i] = n[i] / 2;
         total += m[i];
     }
@@ -64,28 +53,35 @@ long export_batch_launch(adsb_decoder *d, const ExportBatchRules &R, size_t n_ca
     HIP_TRY(d, d->export_tab.reserve((n_captures + 1) * sizeof(ExportSeg))); // (every earlier launch that read it has been waited for)
     ExportSeg *tab = reinterpret_cast<ExportSeg *>(d->export_tab.host.p);
     uint64_t units = 0;
-    const uint32_t rows = export_table(n_captures, m.data(), R.iq ? nullptr : p_hi.data(), at, out, R.iq ? kExportIqGroup : kExportPass, tab, &units);
+    const bool iq = !F.real();
+    const uint32_t rows = export_table(n_captures, m.data(), iq ? nullptr : p_hi.data(), at, out, iq ? kExportIqGroup : kExportPass, tab, &units);
     HIP_TRY(d, hipMemcpyAsync(d->export_tab.dev, d->export_tab.host, ((size_t)rows + 1) * sizeof(ExportSeg), hipMemcpyHostToDevice, st));
     const ExportSeg *tab_d = reinterpret_cast<const ExportSeg *>(d->export_tab.dev.p);
-    if (R.iq)
+    if (iq)
         HIP_TRY(d, launch_iq_power_export_batch(tab_d, rows, units, st));
     else
         HIP_TRY(d, launch_power_export_batch(tab_d, rows, units, st));
     return (long)total;
 }
 
-// ... on the scan stream, which is waited for -- with the unpack or conversion a caller has put in front, also where the batch has no
-// power sample to launch for: the scratch and the tables are the next call's to rewrite
-long export_batch(adsb_decoder *d, const ExportBatchRules &R, size_t n_captures, const void *const *at, const size_t *n, float *const *out)
+// A batch in device memory: the checks, what the flavour puts in front (decoder_stage.hip: one launch, and a conversion's samples in
+// the format report), the export launch behind it on the scan stream, and the wait -- also where the batch has no power sample to
+// launch for: the scratch and the tables are the next call's to rewrite.
+long export_batch(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *src, const size_t *n,
+                  float *const *out, const size_t *cap)
 {
-    const long k = export_batch_launch(d, R, n_captures, at, n, out, d->stream);
+    if (export_batch_refusal(d, what, F, true, n_captures, src, n, out, cap))
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
+    std::vector<const void *> at;
+    if (flavour_batch_to_scratch(d, what, F, n_captures, src, n, at))
+        return -1;
+    const long k = export_batch_launch(d, F, n_captures, at.data(), n, out, d->stream);
     if (k < 0)
         return -1;
     WAIT_STREAM(d, d->stream, "the scan stream");
     return k;
 }
-
-constexpr ExportBatchRules kRulesDevice = {false, false, 16, true};
 
 } // namespace
 
@@ -94,81 +90,42 @@ extern "C" {
 long adsb_power_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
                              float *const *device_power, const size_t *power_cap)
 {
-    const char *what = "adsb_power_batch_device";
-    if (!d)
-        return -1;
-    if (export_batch_refusal(d, what, kRulesDevice, n_captures, device_samples, n, device_power, power_cap))
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return export_batch(d, kRulesDevice, n_captures, device_samples, n, device_power);
+    return d ? export_batch(d, "adsb_power_batch_device", flavour_uint16(), n_captures, device_samples, n, device_power, power_cap) : -1;
 }
 
 long adsb_power_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                 float *const *device_power, const size_t *power_cap)
 {
     const char *what = "adsb_power_batch_device_as";
-    size_t elem;
+    Flavour F;
     if (!d)
         return -1;
-    const int k = format_dispatch(d, what, fmt, &elem);
+    const int k = flavour_as(d, what, fmt, &F);
     if (k < 0)
         return -1;
     if (k)
         return adsb_power_batch_device(d, n_captures, device_samples, n, device_power, power_cap);
-    const ExportBatchRules R = {false, false, (unsigned)elem, true};
-    if (export_batch_refusal(d, what, R, n_captures, device_samples, n, device_power, power_cap))
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    // (a capture without a power sample is not converted and not counted, as the single call returns before its conversion)
-    std::vector<size_t> converted(n_captures);
-    for (size_t i = 0; i < n_captures; i++)
-        converted[i] = power_samples_produced(n[i]) ? n[i] : 0;
-    std::vector<const void *> at;
-    if (batch_to_scratch(d, what, fmt, n_captures, device_samples, converted.data(), at)) // (one launch, and the format report's samples)
-        return -1;
-    return export_batch(d, kRulesDevice, n_captures, at.data(), n, device_power); // (the same stream: behind the conversion)
+    return export_batch(d, what, F, n_captures, device_samples, n, device_power, power_cap);
 }
 
 long adsb_power_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n,
                                     float *const *device_power, const size_t *power_cap)
 {
-    const char *what = "adsb_power_batch_device_packed";
-    if (!d)
-        return -1;
-    const ExportBatchRules R = {false, true, 4, true};
-    if (export_batch_refusal(d, what, R, n_captures, device_packed, n, device_power, power_cap))
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    std::vector<const void *> at;
-    if (batch_to_scratch(d, what, 0, n_captures, device_packed, n, at))
-        return -1;
-    return export_batch(d, kRulesDevice, n_captures, at.data(), n, device_power); // (the same stream: behind the unpack)
+    return d ? export_batch(d, "adsb_power_batch_device_packed", flavour_packed(), n_captures, device_packed, n, device_power, power_cap) : -1;
 }
 
 long adsb_power_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                 float *const *device_power, const size_t *power_cap)
 {
     const char *what = "adsb_power_batch_device_iq";
+    Flavour F;
     if (!d)
         return -1;
     if (fmt == kFmtInt8Iq) // (the single call's refusal, word for word: decoder_export.hip)
         return d->fail("%s: format 8 (INT8_IQ) is not exported: the power export takes fmt 0 FLOAT32_IQ and 2 INT16_IQ only", what);
-    if (!iq_sample_bytes(fmt))
-        return iq_refusal(d, what, fmt, nullptr, 0, true, 0);
-    const ExportBatchRules R = {true, false, 4, true};
-    if (export_batch_refusal(d, what, R, n_captures, device_samples, n, device_power, power_cap))
+    if (flavour_iq(d, what, fmt, &F))
         return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    if (fmt != 0)
-        return export_batch(d, R, n_captures, device_samples, n, device_power);
-    // FLOAT32_IQ: to the int16 grid first, by the one conversion launch the _iq batch decodes use (n[] in scalars there)
-    std::vector<size_t> scalars(n_captures);
-    for (size_t i = 0; i < n_captures; i++)
-        scalars[i] = 2 * n[i];
-    std::vector<const void *> at;
-    if (batch_to_scratch(d, what, kConvFloat32Iq, n_captures, device_samples, scalars.data(), at))
-        return -1;
-    return export_batch(d, R, n_captures, at.data(), n, device_power);
+    return export_batch(d, what, F, n_captures, device_samples, n, device_power, power_cap);
 }
 
 long adsb_power_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, float *const *power,
@@ -177,9 +134,8 @@ long adsb_power_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *c
     const char *what = "adsb_power_batch_host";
     if (!d)
         return -1;
-    const ExportBatchRules R = {false, false, 0, false};
     const void *const *src = reinterpret_cast<const void *const *>(samples);
-    if (export_batch_refusal(d, what, R, n_captures, src, n, power, power_cap))
+    if (export_batch_refusal(d, what, flavour_uint16().on_host(), false, n_captures, src, n, power, power_cap))
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     // every capture at a 128-byte boundary of the scratch adsb_decode_batch_host lands its captures in, every capture's power
@@ -200,7 +156,7 @@ long adsb_power_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *c
     if (pow_slots(d, n_captures, floats.data(), out) ||
         land_captures(d, what, d->batch_in, "the captures", n_captures, src, in_bytes.data(), 128, Land::FirstCopyStream, at))
         return -1;
-    const long r = export_batch_launch(d, kRulesDevice, n_captures, at.data(), n, out.data(), cs);
+    const long r = export_batch_launch(d, flavour_uint16(), n_captures, at.data(), n, out.data(), cs);
     if (r < 0 || pow_slots_out(d, n_captures, power, out, floats.data(), cs))
         return -1;
     WAIT_STREAM(d, cs, "a copy stream");

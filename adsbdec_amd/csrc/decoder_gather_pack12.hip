@@ -8,8 +8,6 @@
 // launches, writes and counts nothing -- the checks all stand in front of the conversion.
 #include "decoder_state.hpp"
 #include "gather_pack12.h"
-#include "packed12.h"
-#include "sample_format.h"
 
 #include <algorithm>
 #include <cstring>
@@ -27,7 +25,7 @@ struct Pack12Plan {
     uint64_t total = 0;
 };
 
-// The checks every flavour shares, and the layout.  in_align: what the flavour's own capture pointer must be a multiple of.
+// The checks every flavour shares, and the layout.  in_align: the flavour's (flavour.hpp).
 int pack12_plan(adsb_decoder *d, const char *what, const void *device_in, unsigned in_align, size_t n, const adsb_burst *bursts, size_t n_bursts,
                 const void *device_out, size_t out_cap_bytes, Pack12Plan &p)
 {
@@ -100,6 +98,22 @@ bool pack12_done_early(const Pack12Plan &p, size_t n_bursts, uint64_t *offsets, 
     return true;
 }
 
+// One call over its flavour F: the checks and the layout, what F puts in front (decoder_stage.hip: a table with a burst has a power
+// sample to read), the launch behind it on the same stream.
+long gather_pack12(adsb_decoder *d, const char *what, const Flavour &F, const void *device_in, size_t n, const adsb_burst *bursts, size_t n_bursts,
+                   void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over)
+{
+    if (F.groups8 && n % kPackedGroupSamples)
+        return d->fail("%s: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes; burst 0 onward)", what, n);
+    Pack12Plan p;
+    if (pack12_plan(d, what, device_in, F.in_align, n, bursts, n_bursts, device_out, out_cap_bytes, p))
+        return -1;
+    if (pack12_done_early(p, n_bursts, offsets, over))
+        return 0;
+    const void *u16 = flavour_to_scratch(d, what, F, device_in, n);
+    return u16 ? pack12_run(d, what, static_cast<const uint16_t *>(u16), p, n_bursts, device_out, over) : -1;
+}
+
 } // namespace
 
 extern "C" {
@@ -107,15 +121,8 @@ extern "C" {
 long adsb_gather_pack12_device(adsb_decoder *d, const void *device_samples, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out,
                                size_t out_cap_bytes, uint64_t *offsets, uint64_t *over)
 {
-    const char *what = "adsb_gather_pack12_device";
-    if (!d)
-        return -1;
-    Pack12Plan p;
-    if (pack12_plan(d, what, device_samples, 16, n, bursts, n_bursts, device_out, out_cap_bytes, p))
-        return -1;
-    if (pack12_done_early(p, n_bursts, offsets, over))
-        return 0;
-    return pack12_run(d, what, static_cast<const uint16_t *>(device_samples), p, n_bursts, device_out, over);
+    return d ? gather_pack12(d, "adsb_gather_pack12_device", flavour_uint16(), device_samples, n, bursts, n_bursts, device_out, out_cap_bytes, offsets, over)
+             : -1;
 }
 
 long adsb_gather_pack12_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_burst *bursts, size_t n_bursts,
@@ -124,35 +131,19 @@ long adsb_gather_pack12_device_as(adsb_decoder *d, int fmt, const void *device_s
     const char *what = "adsb_gather_pack12_device_as";
     if (!d)
         return -1;
-    if (fmt != kFmtFloat32Real && fmt != kFmtInt16Real)
+    if (!format_element_bytes(fmt)) // (this call forwards nothing: its sentence, not flavour_as's)
         return d->fail("%s: format %d is none of 1 (FLOAT32_REAL), 3 (INT16_REAL): a uint16 capture goes to adsb_gather_pack12_device (burst 0 onward)",
                        what, fmt);
-    Pack12Plan p;
-    if (pack12_plan(d, what, device_samples, 16, n, bursts, n_bursts, device_out, out_cap_bytes, p))
-        return -1;
-    if (pack12_done_early(p, n_bursts, offsets, over))
-        return 0;
-    if (to_scratch(d, what, fmt, device_samples, n))
-        return -1;
-    return pack12_run(d, what, d->unpacked, p, n_bursts, device_out, over); // (the same stream: behind the conversion)
+    // (16 bytes, not the element's size as the other _as calls ask)
+    return gather_pack12(d, what, flavour_converted(fmt).at(16), device_samples, n, bursts, n_bursts, device_out, out_cap_bytes, offsets, over);
 }
 
 long adsb_gather_pack12_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_burst *bursts, size_t n_bursts,
                                       void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over)
 {
-    const char *what = "adsb_gather_pack12_device_packed";
-    if (!d)
-        return -1;
-    if (n % kPackedGroupSamples)
-        return d->fail("%s: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes; burst 0 onward)", what, n);
-    Pack12Plan p;
-    if (pack12_plan(d, what, device_packed, 4, n, bursts, n_bursts, device_out, out_cap_bytes, p))
-        return -1;
-    if (pack12_done_early(p, n_bursts, offsets, over))
-        return 0;
-    if (to_scratch(d, what, 0, device_packed, n))
-        return -1;
-    return pack12_run(d, what, d->unpacked, p, n_bursts, device_out, over); // (the same stream: behind the unpack)
+    return d ? gather_pack12(d, "adsb_gather_pack12_device_packed", flavour_packed(), device_packed, n, bursts, n_bursts, device_out, out_cap_bytes,
+                             offsets, over)
+             : -1;
 }
 
 } // extern "C"

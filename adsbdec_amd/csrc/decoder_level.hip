@@ -5,8 +5,6 @@
 // behind whatever a push has left there, and the call returns when the report is in *out.  A refusal writes nothing.
 #include "decoder_state.hpp"
 #include "level.h"
-#include "packed12.h"
-#include "sample_format.h"
 
 using namespace adsb;
 
@@ -83,12 +81,36 @@ long level_capture(adsb_decoder *d, const char *what, const void *device_u16, si
     return level_end(d, m, out, static_cast<const uint16_t *>(device_u16) + 4 * (n / 4), (unsigned)(n % 4));
 }
 
-// n units at p that ARE power samples
-long level_units(adsb_decoder *d, const char *what, int kind, const void *p, size_t n, adsb_level_report *out, float *env)
+// A capture of the flavour F in device memory: the flavour's checks of the samples where the entry point has not made them (the real
+// flavours': a uint16 capture is read where it lies and says so in the export's words), the report's and the envelope's, what the
+// flavour puts in front (decoder_stage.hip), and the launch behind it on the same stream.
+long level_device(adsb_decoder *d, const char *what, const Flavour &F, const void *device_samples, size_t n, adsb_level_report *out,
+                  float *device_env, size_t env_cap)
 {
-    if (level_begin(d, what))
+    const uint64_t m = F.power_samples(n);
+    if (F.real()) {
+        if (F.groups8 && n % kPackedGroupSamples)
+            return d->fail("%s: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes)", what, n);
+        if ((uintptr_t)device_samples % F.in_align)
+            return F.front == Flavour::kNone ? d->fail("%s: buffer must start 16-byte aligned (%p)", what, device_samples)
+                                             : d->fail("%s: device pointer %p is not %zu-byte aligned", what, device_samples, (size_t)F.in_align);
+        if (level_real_refusal(d, what, n))
+            return -1;
+    }
+    if (level_out_refusal(d, what, m, out, device_env, env_cap))
         return -1;
-    HIP_TRY(d, launch_level_units(kind, p, n, d->level.dev, env, d->level_rows, d->stream));
+    if (m == 0)
+        return level_empty(out);
+    if (!device_samples)
+        return d->fail("%s: NULL buffer", what);
+    const void *p = flavour_to_scratch(d, what, F, device_samples, n);
+    if (!p)
+        return -1;
+    if (F.real())
+        return level_capture(d, what, p, n, out, device_env);
+    if (level_begin(d, what)) // n units at p that ARE power samples
+        return -1;
+    HIP_TRY(d, launch_level_units(F.level_kind, p, n, d->level.dev, device_env, d->level_rows, d->stream));
     return level_end(d, n, out);
 }
 
@@ -98,99 +120,44 @@ extern "C" {
 
 long adsb_level_device(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap)
 {
-    const char *what = "adsb_level_device";
-    if (!d)
-        return -1;
-    const uint64_t m = power_samples_produced(n);
-    if ((uintptr_t)device_samples % 16)
-        return d->fail("%s: buffer must start 16-byte aligned (%p)", what, device_samples);
-    if (level_real_refusal(d, what, n) || level_out_refusal(d, what, m, out, device_env, env_cap))
-        return -1;
-    if (m == 0)
-        return level_empty(out);
-    if (!device_samples)
-        return d->fail("%s: NULL buffer", what);
-    return level_capture(d, what, device_samples, n, out, device_env);
+    return d ? level_device(d, "adsb_level_device", flavour_uint16(), device_samples, n, out, device_env, env_cap) : -1;
 }
 
 long adsb_level_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env,
                           size_t env_cap)
 {
     const char *what = "adsb_level_device_as";
-    size_t elem;
+    Flavour F;
     if (!d)
         return -1;
-    const int k = format_dispatch(d, what, fmt, &elem);
+    const int k = flavour_as(d, what, fmt, &F);
     if (k < 0)
         return -1;
     if (k)
         return adsb_level_device(d, device_samples, n, out, device_env, env_cap);
-    const uint64_t m = power_samples_produced(n);
-    if ((uintptr_t)device_samples % elem)
-        return d->fail("%s: device pointer %p is not %zu-byte aligned", what, device_samples, elem);
-    if (level_real_refusal(d, what, n) || level_out_refusal(d, what, m, out, device_env, env_cap))
-        return -1;
-    if (m == 0)
-        return level_empty(out);
-    if (!device_samples)
-        return d->fail("%s: NULL buffer", what);
-    if (to_scratch(d, what, fmt, device_samples, n))
-        return -1;
-    return level_capture(d, what, d->unpacked, n, out, device_env); // (the same stream: behind the conversion)
+    return level_device(d, what, F, device_samples, n, out, device_env, env_cap);
 }
 
 long adsb_level_device_packed(adsb_decoder *d, const void *device_packed, size_t n, adsb_level_report *out, float *device_env, size_t env_cap)
 {
-    const char *what = "adsb_level_device_packed";
-    if (!d)
-        return -1;
-    if (n % kPackedGroupSamples)
-        return d->fail("%s: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes)", what, n);
-    if ((uintptr_t)device_packed % 4)
-        return d->fail("%s: device pointer %p is not 4-byte aligned", what, device_packed);
-    const uint64_t m = power_samples_produced(n);
-    if (level_real_refusal(d, what, n) || level_out_refusal(d, what, m, out, device_env, env_cap))
-        return -1;
-    if (m == 0)
-        return level_empty(out);
-    if (!device_packed)
-        return d->fail("%s: NULL buffer", what);
-    if (to_scratch(d, what, 0, device_packed, n))
-        return -1;
-    return level_capture(d, what, d->unpacked, n, out, device_env); // (the same stream: behind the unpack)
+    return d ? level_device(d, "adsb_level_device_packed", flavour_packed(), device_packed, n, out, device_env, env_cap) : -1;
 }
 
 long adsb_level_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env,
                           size_t env_cap)
 {
     const char *what = "adsb_level_device_iq";
-    if (!d)
+    if (!d || iq_refusal(d, what, fmt, device_samples, n, true, 0))
         return -1;
-    if (iq_refusal(d, what, fmt, device_samples, n, true, 0) || level_out_refusal(d, what, n, out, device_env, env_cap))
-        return -1;
-    if (n == 0)
-        return level_empty(out);
-    if (fmt == kFmtInt8Iq) // (never converted: the kernel squares the bytes as scan_iq8_kernel.hip does)
-        return level_units(d, what, kLevelIq8, device_samples, n, out, device_env);
-    const void *iq16 = device_samples;
-    if (fmt == 0) { // FLOAT32_IQ: to the int16 grid first, by the conversion the _iq pushes and the export use (and into their scratch)
-        if (to_scratch(d, what, kConvFloat32Iq, device_samples, 2 * n))
-            return -1;
-        iq16 = d->unpacked.p;
-    }
-    return level_units(d, what, kLevelIq16, iq16, n, out, device_env);
+    return level_device(d, what, flavour_of_iq(fmt), device_samples, n, out, device_env, env_cap);
 }
 
 long adsb_level_device_power(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap)
 {
     const char *what = "adsb_level_device_power";
-    if (!d)
+    if (!d || power_refusal(d, what, device_samples, n, true, 0))
         return -1;
-    if (power_refusal(d, what, device_samples, n, true, 0) || level_out_refusal(d, what, n, out, device_env, env_cap))
-        return -1;
-    if (n == 0)
-        return level_empty(out);
-    return level_units(d, what, kLevelPower, device_samples, n, out, device_env);
+    return level_device(d, what, flavour_power(), device_samples, n, out, device_env, env_cap);
 }
 
 long adsb_level_host(adsb_decoder *d, const uint16_t *samples, size_t n, adsb_level_report *out, float *env, size_t env_cap)

@@ -9,27 +9,14 @@
 #include "decoder_state.hpp"
 #include "level.h"
 #include "level_batch.hpp"
-#include "packed12.h"
-#include "sample_format.h"
 
 using namespace adsb;
 
 namespace {
 
-constexpr int kLevelReal = -1; // the `kind` of real uint16 captures (level.h has the kinds whose units are power samples)
-
-// What a flavour asks of every capture.
-struct LevelBatchRules {
-    int kind;          // kLevelReal: n[] counts real samples, 2 (n / 4) power samples; else complex / power samples, as many
-    bool packed;       // whole 8-sample groups
-    unsigned in_align; // bytes a device input pointer is aligned to (0: host memory, any)
-};
-
-inline uint64_t level_count(const LevelBatchRules &R, size_t n) { return R.kind == kLevelReal ? power_samples_produced(n) : (uint64_t)n; }
-
 // The refusals of adsb_level_batch_*, by capture, before anything is launched: the batch export's (decoder_export_batch.hip
 // export_batch_refusal) of the samples, the single level call's (decoder_level.hip level_out_refusal) of report and envelope.
-int level_batch_refusal(adsb_decoder *d, const char *what, const LevelBatchRules &R, size_t n_captures, const void *const *src,
+int level_batch_refusal(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *src,
                         const size_t *n, const adsb_level_report *out, float *const *env, const size_t *env_cap)
 {
     if ((uint64_t)n_captures > kExportMaxCaptures)
@@ -41,12 +28,12 @@ int level_batch_refusal(adsb_decoder *d, const char *what, const LevelBatchRules
     if (!env != !env_cap)
         return d->fail("%s: the envelope arrays are both NULL (no envelope for any capture) or both given", what);
     for (size_t i = 0; i < n_captures; i++) {
-        if (R.kind != kLevelReal && (uint64_t)n[i] >= (1ull << 31))
+        if (!F.real() && (uint64_t)n[i] >= (1ull << 31))
             return d->fail("%s: capture %zu has %zu %s samples: 2^31 or more; such streams end below", what, i, n[i],
-                           R.kind == kLevelPower ? "power" : "complex");
-        if (batch_samples_refusal(d, what, i, src[i], n[i], R.kind == kLevelReal, R.packed, R.in_align))
+                           F.kind == kKindPower ? "power" : "complex");
+        if (batch_samples_refusal(d, what, i, src[i], n[i], F))
             return -1;
-        const uint64_t m = level_count(R, n[i]);
+        const uint64_t m = F.power_samples(n[i]);
         if (env) {
             if (!env[i] && env_cap[i])
                 return d->fail("%s: capture %zu: NULL envelope with env_cap = %zu (no envelope: NULL and 0)", what, i, env_cap[i]);
@@ -62,18 +49,18 @@ int level_batch_refusal(adsb_decoder *d, const char *what, const LevelBatchRules
     return 0;
 }
 
-// One sub-batch of k checked captures on `st`: capture i's samples (uint16 real ones, or the units of R.kind) are in device memory
+// One sub-batch of k checked captures on `st`: capture i's samples (uint16 real ones, or the units of F.kind) are in device memory
 // at at[i], its envelope (env != NULL and env[i] != NULL) goes to env[i] in device memory.  The table, the zeroed totals, the launch,
 // the totals back into the pinned half; not waited for.  row_of[i]: which of the totals are capture i's (level_batch.hpp).
 // tail_on_device: the launch counts a real capture's trailing n % 4 codes.
-int level_sub_launch(adsb_decoder *d, const char *what, const LevelBatchRules &R, size_t k, const void *const *at, const size_t *n,
+int level_sub_launch(adsb_decoder *d, const char *what, const Flavour &F, size_t k, const void *const *at, const size_t *n,
                      float *const *env, bool tail_on_device, hipStream_t st, std::vector<uint32_t> &row_of)
 {
     std::vector<uint64_t> m(k), p_hi(k), tail(k);
     row_of.assign(k, UINT32_MAX);
     size_t rows_max = 0;
     for (size_t i = 0; i < k; i++) {
-        m[i] = level_count(R, n[i]);
+        m[i] = F.power_samples(n[i]);
         p_hi[i] = n[i] / 2;
         tail[i] = tail_on_device ? n[i] % 4 : 0;
         rows_max += m[i] != 0;
@@ -88,19 +75,19 @@ int level_sub_launch(adsb_decoder *d, const char *what, const LevelBatchRules &R
     }
     LevelSeg *tab = reinterpret_cast<LevelSeg *>(d->level_tab.host.p);
     uint64_t units = 0;
-    const bool real = R.kind == kLevelReal;
+    const bool real = F.real();
     const uint32_t rows = level_table(k, m.data(), real ? p_hi.data() : nullptr, real ? tail.data() : nullptr, at, env, tab, row_of.data(), &units);
     const size_t bytes = (size_t)rows * kLevelWords * sizeof(unsigned long long);
     HIP_TRY(d, hipMemcpyAsync(d->level_tab.dev, d->level_tab.host, ((size_t)rows + 1) * sizeof(LevelSeg), hipMemcpyHostToDevice, st));
     HIP_TRY(d, hipMemsetAsync(d->level_batch.dev, 0, bytes, st));
-    HIP_TRY(d, launch_level_batch(R.kind, reinterpret_cast<const LevelSeg *>(d->level_tab.dev.p), rows, units, d->level_batch.dev,
+    HIP_TRY(d, launch_level_batch(F.level_kind, reinterpret_cast<const LevelSeg *>(d->level_tab.dev.p), rows, units, d->level_batch.dev,
                                   (unsigned)std::max(0, d->level_batch_blocks), st));
     HIP_TRY(d, hipMemcpyAsync(d->level_batch.host, d->level_batch.dev, bytes, hipMemcpyDeviceToHost, st));
     return 0;
 }
 
 // ... behind the wait: the reports of the sub-batch's captures
-void level_sub_reports(const adsb_decoder *d, const LevelBatchRules &R, size_t k, const size_t *n, const std::vector<uint32_t> &row_of,
+void level_sub_reports(const adsb_decoder *d, const Flavour &F, size_t k, const size_t *n, const std::vector<uint32_t> &row_of,
                        adsb_level_report *out)
 {
     static_assert(sizeof(adsb_level_report) == kLevelWords * sizeof(unsigned long long), "level.h kLevelWords");
@@ -110,46 +97,34 @@ void level_sub_reports(const adsb_decoder *d, const LevelBatchRules &R, size_t k
             continue;
         }
         memcpy(&out[i], d->level_batch.host.p + (size_t)row_of[i] * kLevelWords, sizeof out[i]);
-        out[i].samples = level_count(R, n[i]);
+        out[i].samples = F.power_samples(n[i]);
     }
 }
 
-// What a flavour puts in front of the level launch of a sub-batch, into the batch decodes' scratch.
-enum class Prep { None, Unpack, ConvertReal, ConvertIq };
-
-// A checked batch in sub-batches of kLevelBatchCaptures, each on the scan stream and waited for: the scratch, the table and the
-// totals are the next sub-batch's to rewrite.  Returns the power samples reported in all, or -1.
-long level_batch(adsb_decoder *d, const char *what, const LevelBatchRules &R, Prep prep, int fmt, size_t n_captures, const void *const *src,
-                 const size_t *n, adsb_level_report *out, float *const *env)
+// A checked batch in sub-batches of kLevelBatchCaptures, each behind what the flavour puts in front (decoder_stage.hip), on the scan
+// stream and waited for: the scratch, the table and the totals are the next sub-batch's to rewrite.  Returns the power samples
+// reported in all, or -1.
+long level_batch(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *src, const size_t *n,
+                 adsb_level_report *out, float *const *env, const size_t *env_cap)
 {
+    if (level_batch_refusal(d, what, F, n_captures, src, n, out, env, env_cap))
+        return -1;
+    HIP_TRY(d, hipSetDevice(d->device));
     uint64_t total = 0;
     std::vector<uint32_t> row_of;
-    std::vector<size_t> sized;
     std::vector<const void *> at;
     for (size_t c0 = 0; c0 < n_captures; c0 += kLevelBatchCaptures) {
         const size_t k = std::min(kLevelBatchCaptures, n_captures - c0);
-        const void *const *from = src + c0;
-        if (prep != Prep::None) {
-            // (a capture without a power sample is not converted and not counted, as the single call returns before its conversion;
-            // complex float32 samples are two scalars each there)
-            sized.assign(k, 0);
-            for (size_t i = 0; i < k; i++)
-                sized[i] = level_count(R, n[c0 + i]) == 0 ? 0 : prep == Prep::ConvertIq ? 2 * n[c0 + i] : n[c0 + i];
-            if (batch_to_scratch(d, what, prep == Prep::Unpack ? 0 : fmt, k, from, sized.data(), at))
-                return -1;
-            from = at.data();
-        }
-        if (level_sub_launch(d, what, R, k, from, n + c0, env ? env + c0 : nullptr, true, d->stream, row_of))
+        if (flavour_batch_to_scratch(d, what, F, k, src + c0, n + c0, at) ||
+            level_sub_launch(d, what, F, k, at.data(), n + c0, env ? env + c0 : nullptr, true, d->stream, row_of))
             return -1;
         WAIT_STREAM(d, d->stream, "the scan stream");
-        level_sub_reports(d, R, k, n + c0, row_of, out + c0);
+        level_sub_reports(d, F, k, n + c0, row_of, out + c0);
         for (size_t i = 0; i < k; i++)
-            total += level_count(R, n[c0 + i]);
+            total += F.power_samples(n[c0 + i]);
     }
     return (long)total;
 }
-
-constexpr LevelBatchRules kRulesDevice = {kLevelReal, false, 16};
 
 } // namespace
 
@@ -158,74 +133,44 @@ extern "C" {
 long adsb_level_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out,
                              float *const *device_env, const size_t *env_cap)
 {
-    const char *what = "adsb_level_batch_device";
-    if (!d)
-        return -1;
-    if (level_batch_refusal(d, what, kRulesDevice, n_captures, device_samples, n, out, device_env, env_cap))
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return level_batch(d, what, kRulesDevice, Prep::None, 0, n_captures, device_samples, n, out, device_env);
+    return d ? level_batch(d, "adsb_level_batch_device", flavour_uint16(), n_captures, device_samples, n, out, device_env, env_cap) : -1;
 }
 
 long adsb_level_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                 adsb_level_report *out, float *const *device_env, const size_t *env_cap)
 {
     const char *what = "adsb_level_batch_device_as";
-    size_t elem;
+    Flavour F;
     if (!d)
         return -1;
-    const int k = format_dispatch(d, what, fmt, &elem);
+    const int k = flavour_as(d, what, fmt, &F);
     if (k < 0)
         return -1;
     if (k)
         return adsb_level_batch_device(d, n_captures, device_samples, n, out, device_env, env_cap);
-    const LevelBatchRules R = {kLevelReal, false, (unsigned)elem};
-    if (level_batch_refusal(d, what, R, n_captures, device_samples, n, out, device_env, env_cap))
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return level_batch(d, what, kRulesDevice, Prep::ConvertReal, fmt, n_captures, device_samples, n, out, device_env);
+    return level_batch(d, what, F, n_captures, device_samples, n, out, device_env, env_cap);
 }
 
 long adsb_level_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n,
                                     adsb_level_report *out, float *const *device_env, const size_t *env_cap)
 {
-    const char *what = "adsb_level_batch_device_packed";
-    if (!d)
-        return -1;
-    const LevelBatchRules R = {kLevelReal, true, 4};
-    if (level_batch_refusal(d, what, R, n_captures, device_packed, n, out, device_env, env_cap))
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return level_batch(d, what, kRulesDevice, Prep::Unpack, 0, n_captures, device_packed, n, out, device_env);
+    return d ? level_batch(d, "adsb_level_batch_device_packed", flavour_packed(), n_captures, device_packed, n, out, device_env, env_cap) : -1;
 }
 
 long adsb_level_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n,
                                 adsb_level_report *out, float *const *device_env, const size_t *env_cap)
 {
     const char *what = "adsb_level_batch_device_iq";
-    if (!d)
+    Flavour F;
+    if (!d || flavour_iq(d, what, fmt, &F))
         return -1;
-    if (!iq_sample_bytes(fmt))
-        return iq_refusal(d, what, fmt, nullptr, 0, true, 0);
-    const LevelBatchRules R = {fmt == kFmtInt8Iq ? kLevelIq8 : kLevelIq16, false, fmt == kFmtInt8Iq ? 2u : 4u};
-    if (level_batch_refusal(d, what, R, n_captures, device_samples, n, out, device_env, env_cap))
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    // FLOAT32_IQ: to the int16 grid first, by the one conversion launch the _iq batch decodes use; fmt 8 is never converted
-    return level_batch(d, what, R, fmt == 0 ? Prep::ConvertIq : Prep::None, kConvFloat32Iq, n_captures, device_samples, n, out, device_env);
+    return level_batch(d, what, F, n_captures, device_samples, n, out, device_env, env_cap);
 }
 
 long adsb_level_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n,
                                    adsb_level_report *out, float *const *device_env, const size_t *env_cap)
 {
-    const char *what = "adsb_level_batch_device_power";
-    if (!d)
-        return -1;
-    const LevelBatchRules R = {kLevelPower, false, 4};
-    if (level_batch_refusal(d, what, R, n_captures, device_samples, n, out, device_env, env_cap))
-        return -1;
-    HIP_TRY(d, hipSetDevice(d->device));
-    return level_batch(d, what, R, Prep::None, 0, n_captures, device_samples, n, out, device_env);
+    return d ? level_batch(d, "adsb_level_batch_device_power", flavour_power(), n_captures, device_samples, n, out, device_env, env_cap) : -1;
 }
 
 long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, adsb_level_report *out,
@@ -234,9 +179,9 @@ long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *c
     const char *what = "adsb_level_batch_host";
     if (!d)
         return -1;
-    const LevelBatchRules R = {kLevelReal, false, 0};
+    const Flavour F = flavour_uint16().on_host(), kDevice = flavour_uint16();
     const void *const *src = reinterpret_cast<const void *const *>(samples);
-    if (level_batch_refusal(d, what, R, n_captures, src, n, out, env, env_cap))
+    if (level_batch_refusal(d, what, F, n_captures, src, n, out, env, env_cap))
         return -1;
     HIP_TRY(d, hipSetDevice(d->device));
     // per sub-batch: every capture at a 128-byte boundary of the scratch adsb_decode_batch_host lands its captures in, every
@@ -267,11 +212,11 @@ long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *c
         if ((env_all && pow_slots(d, k, floats.data(), env_dev)) ||
             land_captures(d, what, d->batch_in, "the captures", k, src + c0, in_bytes.data(), 128, Land::FirstCopyStream, at))
             return -1;
-        if (level_sub_launch(d, what, kRulesDevice, k, at.data(), n + c0, env_all ? env_dev.data() : nullptr, false, cs, row_of) ||
+        if (level_sub_launch(d, what, kDevice, k, at.data(), n + c0, env_all ? env_dev.data() : nullptr, false, cs, row_of) ||
             (env_all && pow_slots_out(d, k, env + c0, env_dev, floats.data(), cs)))
             return -1;
         WAIT_STREAM(d, cs, "a copy stream");
-        level_sub_reports(d, kRulesDevice, k, n + c0, row_of, out + c0);
+        level_sub_reports(d, kDevice, k, n + c0, row_of, out + c0);
         for (size_t i = 0; i < k; i++) {
             const uint64_t m = power_samples_produced(n[c0 + i]);
             total += m;

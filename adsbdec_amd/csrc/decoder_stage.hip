@@ -1,6 +1,7 @@
 // decoder_stage.hip -- the staging steps: a call's samples to where, and in the form, its kernel reads them.  Each step is written
 // once here and called by every family (pushes, batch decodes, exports, levels; decoder_state.hpp names the buffers):
 //   to_scratch        one capture in device memory -> uint16 / int16 in `unpacked`, by the unpack or a conversion on the scan stream
+//   flavour_to_scratch / flavour_batch_to_scratch   ... what a flavour (flavour.hpp) puts in front of a kernel, one capture | a batch
 //   land_captures     a batch's host captures -> batch_in or batch_land, side by side (stage_layout.hpp)
 //   batch_to_scratch  a batch in device memory -> batch_unpacked by ONE unpack or conversion launch on the scan stream
 //   window_in / floats_out   one host window -> win_buf; floats of pow_buf -> the caller's array
@@ -11,8 +12,6 @@
 // conversion adds its samples to fmt_converted and marks fmt_dirty; an unpack counts nothing; what is not converted is not counted.
 // No kernel lives here.
 #include "decoder_state.hpp"
-#include "packed12.h"
-#include "sample_format.h"
 #include "stage_layout.hpp"
 
 using namespace adsb;
@@ -52,6 +51,16 @@ int adsb::to_scratch(adsb_decoder *d, const char *what, int conv, const void *sr
     d->fmt_converted += n;
     d->fmt_dirty = true;
     return 0;
+}
+
+// What the flavour F puts in front of the kernel that reads ONE capture of n at src, which has a power sample (the callers return
+// before): nothing, the unpack, or the conversion of F.scratch_elements(n) elements.  Returns what the kernel reads -- src itself, or
+// d->unpacked -- or NULL: failed.
+const void *adsb::flavour_to_scratch(adsb_decoder *d, const char *what, const Flavour &F, const void *src, size_t n)
+{
+    if (F.front == Flavour::kNone)
+        return src;
+    return to_scratch(d, what, F.conv, src, F.scratch_elements(n)) ? nullptr : d->unpacked.p;
 }
 
 // The in-place launches of a device push alternate onto the second scan stream, which nothing else orders behind to_scratch.
@@ -136,6 +145,22 @@ int adsb::batch_to_scratch(adsb_decoder *d, const char *what, int conv, size_t n
     return 0;
 }
 
+// ... of a batch: at[i] is where the kernel reads capture i -- src[i] itself (and nothing of the handle changes), or its place in
+// batch_unpacked behind the ONE launch of batch_to_scratch.  The two rules every operation keeps are Flavour::scratch_elements': a
+// capture without a power sample is not converted and not counted; complex float32 samples are converted as 2 n scalars.
+int adsb::flavour_batch_to_scratch(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *src, const size_t *n,
+                                   std::vector<const void *> &at)
+{
+    if (F.front == Flavour::kNone) {
+        at.assign(src, src + n_captures);
+        return 0;
+    }
+    std::vector<size_t> sized(n_captures);
+    for (size_t i = 0; i < n_captures; i++)
+        sized[i] = F.scratch_elements(n[i]);
+    return batch_to_scratch(d, what, F.conv, n_captures, src, sized.data(), at);
+}
+
 // The captures in device memory at at[] (bytes[i] each) that are not 16-byte aligned -> copies in batch_unpacked, each at a 128-byte
 // boundary, by copies on the scan stream; at[i] then names the copy.  Not waited for.
 int adsb::batch_realign(adsb_decoder *d, const char *what, size_t n_captures, const size_t *bytes, std::vector<const void *> &at)
@@ -202,16 +227,16 @@ int adsb::pow_slots_out(adsb_decoder *d, size_t n_captures, float *const *dst, c
 }
 
 // What the batch exports and the batch level calls ask of capture i's samples, in this order and these words (the batch decodes word
-// two of them differently: decoder_batch.hip batch_refusal).  real: n counts real samples, which end below 2^32 (the bound of complex
-// and power samples is worded per family, by the caller).
-int adsb::batch_samples_refusal(adsb_decoder *d, const char *what, size_t i, const void *src, size_t n, bool real, bool packed, unsigned in_align)
+// two of them differently: decoder_batch.hip batch_refusal).  Real samples end below 2^32 (the bound of complex and power samples is
+// worded per family, by the caller).
+int adsb::batch_samples_refusal(adsb_decoder *d, const char *what, size_t i, const void *src, size_t n, const Flavour &F)
 {
-    if (real && (uint64_t)n >= (1ull << 32))
+    if (F.real() && (uint64_t)n >= (1ull << 32))
         return d->fail("%s: capture %zu has %zu samples: 2^32 or more, where the reference's sample counter wraps (air.c:34); "
                        "a batch has no long-stream mode", what, i, n);
-    if (packed && n % kPackedGroupSamples != 0)
+    if (F.groups8 && n % kPackedGroupSamples != 0)
         return d->fail("%s: capture %zu: n = %zu is not a multiple of 8 (packed samples come in groups of 8 in 12 bytes)", what, i, n);
-    if (in_align && (uintptr_t)src % in_align != 0)
-        return d->fail("%s: capture %zu: device pointer %p is not %u-byte aligned", what, i, src, in_align);
+    if (F.in_align && (uintptr_t)src % F.in_align != 0)
+        return d->fail("%s: capture %zu: device pointer %p is not %u-byte aligned", what, i, src, F.in_align);
     return 0;
 }

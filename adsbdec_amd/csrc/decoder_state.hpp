@@ -13,6 +13,7 @@
 //   decoder_bursts.hip     the gate behind the envelope (adsb_bursts_*): an envelope's bursts as an ordered table
 //   decoder_gather.hip     a capture's bursts as one array (adsb_gather_device): the pieces of a burst table, packed by one launch
 //   decoder_gather_pack12.hip  ... of a real capture, packed to 12 bits while they are copied (adsb_gather_pack12_*)
+//   decoder_flavour.hip    what a sample flavour is (flavour.hpp): the judgement of a format number, the _iq and _power checks
 //   decoder_stage.hip      the staging steps every family calls: samples into unpacked, batch_in, batch_land, batch_unpacked, win_buf, pow_buf
 // Every call from one unit into another is made per launch or per API call; what runs per record or per tile is in decoder_collect.hip.
 #pragma once
@@ -39,10 +40,14 @@
 #include "config_abi.hpp"
 #include "device_mem.hpp"
 #include "handoff.hpp"
+#include "packed12.h"
 #include "resolver.hpp"
+#include "sample_format.h"
 #include "scan_kernel.h"
 
 #pragma GCC visibility push(hidden)
+
+#include "flavour.hpp" // the stream kinds, power_samples_produced, struct Flavour
 
 namespace adsb {
 
@@ -58,15 +63,6 @@ inline const char *tuning_env(const char *) { return nullptr; }
 constexpr uint64_t kDefaultStageSamples = 32ull << 20; // 64 MiB per staging buffer
 constexpr uint64_t kStageSlack = 4096;                 // samples kept free for alignment padding
 constexpr size_t kInPlaceMinSamples = 1u << 16;
-constexpr int kKindNone = 0, kKindReal = 1, kKindIq = 2, kKindPower = 3, kKindIq8 = 4; // adsb_decoder::kind
-// a PAIR of the stream's units IS a power sample (complex int16 samples, float32 power samples, complex int8 samples): no FIR
-// ring, no quads, and the power samples enter the demodulator two at a time (air.c:94-99)
-constexpr bool kind_in_twos(int kind) { return kind == kKindIq || kind == kKindPower || kind == kKindIq8; }
-// Bytes of one unit of the stream -- what n_samples, stage_first and stage_fill count.  Every kind counts TWO units per pair /
-// power sample, so the index arithmetic of the stream machinery (pairs, the carry in twos, compaction, the in-place rule at a
-// multiple of 8 units, the EOF horizon) is one for all of them; a unit is 16 bits everywhere except in an int8 IQ stream, whose
-// unit is ONE BYTE (I or Q).  Only where the machinery turns units into addresses and byte counts does the kind matter.
-constexpr size_t kind_unit_bytes(int kind) { return kind == kKindIq8 ? 1 : 2; }
 constexpr size_t kSeamSamples = 4096; // > 2*(28+8+1196): enough for the first in-place tile's pre-halo
 constexpr int kSlots = 4;
 constexpr size_t kTryStateBytes = 4 * sizeof(unsigned long long) + 4 * sizeof(uint32_t); // d_try_acc + d_carry_n
@@ -442,11 +438,6 @@ inline int wait_stream(adsb_decoder *d, hipStream_t st, const char *what)
 #define WAIT_EVENT(d, ev, what)   do { if (adsb::wait_event((d), (ev), (what))) return -1; } while (0)
 #define WAIT_STREAM(d, st, what)  do { if (adsb::wait_stream((d), (st), (what))) return -1; } while (0)
 
-inline uint64_t power_samples_produced(uint64_t n_samples)
-{
-    return 2 * (n_samples / 4); // air.c:59-92: two power samples per four input samples
-}
-
 // Did the previous launch of this handle hand over a record per 2 048 offsets or more (and 16 384 at least)?  The traffic of a
 // channel does not change from one launch to the next: the host side starts its helper threads on this (decoder_collect.hip
 // choose_helpers), and the next launch takes tiles of six passes instead of seven (adsb::choose_passes).
@@ -477,10 +468,7 @@ int wait_last_copy(adsb_decoder *d);
 bool stream_too_long(adsb_decoder *d, size_t n);
 int format_prepare(adsb_decoder *d, const char *what, size_t land_bytes);
 int format_counters(adsb_decoder *d, unsigned long long out[2]);
-int format_dispatch(adsb_decoder *d, const char *what, int fmt, size_t *elem);
 int kind_refusal(adsb_decoder *d, const char *what, int kind);
-int iq_refusal(adsb_decoder *d, const char *what, int fmt, const void *p, size_t n, bool device, uint64_t at_units);
-int power_refusal(adsb_decoder *d, const char *what, const void *p, size_t n, bool device, uint64_t at_units);
 bool shard_too_long(adsb_decoder *d, const char *what, uint64_t first_sample, uint64_t n, uint64_t total_samples);
 // decoder_collect.hip
 int slot_collect(adsb_decoder *d);
@@ -496,17 +484,20 @@ void start_gang(adsb_decoder *d, int helpers);
 // decoder_stage.hip: the staging steps (conv = 0: packed 12-bit input is unpacked; else the conversion of sample_format.h)
 int to_scratch(adsb_decoder *d, const char *what, int conv, const void *src, size_t n);
 int scratch_before_stream2(adsb_decoder *d);
+const void *flavour_to_scratch(adsb_decoder *d, const char *what, const Flavour &F, const void *src, size_t n);
 enum class Land { InTurnWaited, FirstCopyStream }; // the copy streams in turn, all waited for | copy_stream[0] in order, not waited for
 int land_captures(adsb_decoder *d, const char *what, Buf<uint8_t> &buf, const char *of, size_t n_captures, const void *const *src,
                   const size_t *bytes, size_t align, Land how, std::vector<const void *> &at);
 int batch_to_scratch(adsb_decoder *d, const char *what, int conv, size_t n_captures, const void *const *src, const size_t *n,
                      std::vector<const void *> &at);
+int flavour_batch_to_scratch(adsb_decoder *d, const char *what, const Flavour &F, size_t n_captures, const void *const *src, const size_t *n,
+                             std::vector<const void *> &at);
 int batch_realign(adsb_decoder *d, const char *what, size_t n_captures, const size_t *bytes, std::vector<const void *> &at);
 int window_in(adsb_decoder *d, const uint16_t *samples, size_t n, size_t floats);
 int floats_out(adsb_decoder *d, float *dst, size_t floats);
 int pow_slots(adsb_decoder *d, size_t n_captures, const size_t *floats, std::vector<float *> &at);
 int pow_slots_out(adsb_decoder *d, size_t n_captures, float *const *dst, const std::vector<float *> &at, const size_t *floats, hipStream_t st);
-int batch_samples_refusal(adsb_decoder *d, const char *what, size_t i, const void *src, size_t n, bool real, bool packed, unsigned in_align);
+int batch_samples_refusal(adsb_decoder *d, const char *what, size_t i, const void *src, size_t n, const Flavour &F);
 // decoder_lifecycle.hip
 void set_create_error(const char *why); // what adsb_last_error(NULL) shows: a call without a handle has failed
 

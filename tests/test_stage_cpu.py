@@ -11,6 +11,8 @@ def test_the_staging_unit_is_built_by_both_builds():
     from adsbdec_amd import _build
     assert "decoder_stage.hip" in _build.HIP_SOURCES
     assert "decoder_stage.hip.o" in open(os.path.join(ROOT, "Makefile")).read()
+    assert "decoder_flavour.hip" in _build.HIP_SOURCES
+    assert "decoder_flavour.hip.o" in open(os.path.join(ROOT, "Makefile")).read()
 
 
 def test_layout_and_tables_under_the_sanitizers(tmp_path):
@@ -23,3 +25,15 @@ def test_layout_and_tables_under_the_sanitizers(tmp_path):
                     os.path.join(ROOT, "tests", "cpp", "stage_layout.cpp"), "-o", str(exe)], check=True)
     p = subprocess.run([str(exe)], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("ok: 132 lists"), p.stdout + p.stderr
+
+
+def test_flavours_under_the_sanitizers(tmp_path):
+    """csrc/flavour.hpp compiled for the host with -fsanitize=address,undefined, a program of its own (tests/cpp/flavour.cpp): for
+    every flavour and the capture lengths of the GPU rows (and every length below 4200, and four near 2^31 and 2^32) the power-sample
+    count and the elements that go into scratch against the rules written out per flavour in the program; alignment, groups of 8,
+    kinds and conversion numbers; .on_host() and .at() change the alignment alone."""
+    exe = tmp_path / "flavour"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "cpp", "flavour.cpp"), "-o", str(exe)], check=True)
+    p = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert p.returncode == 0 and p.stdout.startswith("ok: 33672 checks of 8 flavours"), p.stdout + p.stderr
