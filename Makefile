@@ -27,11 +27,11 @@ $(LIBDIR)/%.cpp.o: $(CSRC)/%.cpp
 	@mkdir -p $(LIBDIR)
 	g++ -O2 -fPIC -std=c++17 -Wall -Wextra -pthread -MMD -MF $@.d -c $< -o $@
 
-$(LIB): $(LIBDIR)/scan_kernel.hip.o $(LIBDIR)/scan_batch_kernel.hip.o $(LIBDIR)/scan_iq_kernel.hip.o $(LIBDIR)/scan_iq8_kernel.hip.o $(LIBDIR)/scan_power_kernel.hip.o $(LIBDIR)/seam_kernel.hip.o $(LIBDIR)/decoder.hip.o $(LIBDIR)/decoder_collect.hip.o $(LIBDIR)/decoder_lifecycle.hip.o $(LIBDIR)/decoder_batch.hip.o $(LIBDIR)/decoder_shard.hip.o $(LIBDIR)/unpack12.hip.o $(LIBDIR)/unpack12_batch.hip.o $(LIBDIR)/convert_samples.hip.o $(LIBDIR)/power_export_kernel.hip.o $(LIBDIR)/decoder_export.hip.o $(LIBDIR)/power_export_batch_kernel.hip.o $(LIBDIR)/decoder_export_batch.hip.o $(LIBDIR)/level_kernel.hip.o $(LIBDIR)/decoder_level.hip.o $(LIBDIR)/level_batch_kernel.hip.o $(LIBDIR)/decoder_level_batch.hip.o $(LIBDIR)/level_windows_kernel.hip.o $(LIBDIR)/decoder_level_windows.hip.o $(LIBDIR)/decoder_stage.hip.o $(LIBDIR)/decoder_flavour.hip.o $(LIBDIR)/burst_kernel.hip.o $(LIBDIR)/decoder_bursts.hip.o $(LIBDIR)/gather_kernel.hip.o $(LIBDIR)/decoder_gather.hip.o $(LIBDIR)/gather_pack12_kernel.hip.o $(LIBDIR)/decoder_gather_pack12.hip.o $(LIBDIR)/format.c.o $(LIBDIR)/multi.cpp.o $(LIBDIR)/host_abi.cpp.o $(LIBDIR)/numa.cpp.o
+$(LIB): $(LIBDIR)/scan_kernel.hip.o $(LIBDIR)/scan_batch_kernel.hip.o $(LIBDIR)/scan_iq_kernel.hip.o $(LIBDIR)/scan_iq8_kernel.hip.o $(LIBDIR)/scan_power_kernel.hip.o $(LIBDIR)/seam_kernel.hip.o $(LIBDIR)/decoder.hip.o $(LIBDIR)/decoder_collect.hip.o $(LIBDIR)/decoder_lifecycle.hip.o $(LIBDIR)/decoder_batch.hip.o $(LIBDIR)/decoder_shard.hip.o $(LIBDIR)/unpack12.hip.o $(LIBDIR)/unpack12_batch.hip.o $(LIBDIR)/convert_samples.hip.o $(LIBDIR)/power_export_kernel.hip.o $(LIBDIR)/decoder_export.hip.o $(LIBDIR)/power_export_batch_kernel.hip.o $(LIBDIR)/decoder_export_batch.hip.o $(LIBDIR)/level_kernel.hip.o $(LIBDIR)/decoder_level.hip.o $(LIBDIR)/level_batch_kernel.hip.o $(LIBDIR)/decoder_level_batch.hip.o $(LIBDIR)/level_windows_kernel.hip.o $(LIBDIR)/decoder_level_windows.hip.o $(LIBDIR)/decoder_stage.hip.o $(LIBDIR)/decoder_flavour.hip.o $(LIBDIR)/burst_kernel.hip.o $(LIBDIR)/burst_slice_kernel.hip.o $(LIBDIR)/decoder_bursts.hip.o $(LIBDIR)/gather_kernel.hip.o $(LIBDIR)/decoder_gather.hip.o $(LIBDIR)/gather_pack12_kernel.hip.o $(LIBDIR)/decoder_gather_pack12.hip.o $(LIBDIR)/format.c.o $(LIBDIR)/multi.cpp.o $(LIBDIR)/host_abi.cpp.o $(LIBDIR)/numa.cpp.o
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^ -lm -lpthread
 
 # the host program (_build.py CLI_SOURCES): one line over all its sources, rebuilt when any of them or a header beside them changes
-CLI_SRCS := $(addprefix $(CSRC)/cli/,adsbdec_amd_cli.c options.c common.c stream.c batch.c export.c level.c bursts.c sink.c burst_archive.c)
+CLI_SRCS := $(addprefix $(CSRC)/cli/,adsbdec_amd_cli.c options.c common.c stream.c batch.c export.c level.c bursts.c record.c sink.c burst_archive.c)
 $(CLI): $(CLI_SRCS) $(wildcard $(CSRC)/cli/*.h) $(LIB) include/adsbdec_amd.h
 	$(CC) -O2 -Wall -D__HIP_PLATFORM_AMD__ -o $@ $(CLI_SRCS) -Iinclude -I$(ROCM)/include -L$(LIBDIR) -ladsbdec_amd -L$(ROCM)/lib -lamdhip64 -lpthread -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(ROCM)/lib
 

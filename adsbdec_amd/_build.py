@@ -26,14 +26,14 @@ HIP_SOURCES = ["scan_kernel.hip", "scan_batch_kernel.hip", "scan_iq_kernel.hip",
                "convert_samples.hip", "power_export_kernel.hip", "decoder_export.hip",
                "power_export_batch_kernel.hip", "decoder_export_batch.hip", "level_kernel.hip", "decoder_level.hip",
                "level_batch_kernel.hip", "decoder_level_batch.hip", "level_windows_kernel.hip", "decoder_level_windows.hip", "decoder_stage.hip", "decoder_flavour.hip",
-               "burst_kernel.hip", "decoder_bursts.hip", "gather_kernel.hip", "decoder_gather.hip",
+               "burst_kernel.hip", "burst_slice_kernel.hip", "decoder_bursts.hip", "gather_kernel.hip", "decoder_gather.hip",
                "gather_pack12_kernel.hip", "decoder_gather_pack12.hip"]
 C_SOURCES = ["format.c"]
 # host-only C++ (no HIP): the multi-GPU driver over the C-ABI, and the part of the C-ABI that needs no device
 CXX_SOURCES = ["multi.cpp", "host_abi.cpp", "numa.cpp"]
 # the host program (csrc/cli/): one gcc line over all of them; it is rebuilt when any of them or any header beside them changes
 CLI_DIR = os.path.join(CSRC, "cli")
-CLI_SOURCES = ["adsbdec_amd_cli.c", "options.c", "common.c", "stream.c", "batch.c", "export.c", "level.c", "bursts.c", "sink.c", "burst_archive.c"]
+CLI_SOURCES = ["adsbdec_amd_cli.c", "options.c", "common.c", "stream.c", "batch.c", "export.c", "level.c", "bursts.c", "record.c", "sink.c", "burst_archive.c"]
 # What an object depends on is what the compiler says it read: every compile writes <object>.d (-MMD) and the next build
 # reads it.  (Until round 6 this was a hand-kept list of headers, and gang.hpp -- included by resolver.hpp -- was not on
 # it: editing it alone left stale objects.  tests/test_host_logic.py touches a header and watches the rebuild.)

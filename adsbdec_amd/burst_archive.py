@@ -44,8 +44,14 @@ pieces' OWN samples above 4095 -- never the fill, never a sample outside the pie
 real flavour has a uint16 twin to gather from: a uint16 capture itself, the unpacked or converted scratch of a packed or _as one.
 In the archive kind 12 goes with sample_bytes 3, n_units counts the capture's samples, and the payload is checked against layout12.
 
-Out of scope: gathering straight from a packed source without the unpack, 12-bit forms of the IQ and power kinds, joining bursts
-across the slices of a stream, a batch form, the multi-GPU driver.
+A stream of any length (record_statement; the host program's -S -O).  The archive of a uint16 stream that is read in pieces of
+`piece` runs is the archive of the whole: levels.bursts of the whole envelope at ONE threshold, fixed by the first piece (a factor
+times the median of its power samples, or a float given outright), and the gather of that table.  The host program gets there
+piece by piece -- adsb_bursts_slice_device joins the bursts across the pieces, and a piece's gathered bytes, a multiple of 16, are
+appended to those before -- and the result does not depend on the piece.
+
+Out of scope: gathering straight from a packed source without the unpack, 12-bit forms of the IQ and power kinds, a batch form,
+the multi-GPU driver; in the record mode: other input than uint16, kind 12, run numbers beyond 32 bits.
 
     python -m adsbdec_amd.burst_archive info file.brs      the header and the kept share
 """
@@ -56,6 +62,7 @@ import sys
 
 import numpy as np
 
+from . import levels
 from .levels import BURST_DTYPE, RUN, burst_samples
 from .packed12 import pack12
 
@@ -184,6 +191,29 @@ def write(path, kind: int, n_units: int, M: int, threshold: float, lead: int, ha
     with open(path, "wb") as f:
         f.write(data)
     return len(data)
+
+
+def record_statement(x, piece: int, factor_or_threshold: float, lead: int, hang: int, *, a, absolute: bool = False) -> bytes:
+    """The archive the host program's -S factor,lead,hang,piece -O must write for the uint16 stream x, numpy only.  a: the 2 (n // 4)
+    power samples of x (the reference's ampbuff: adsb_power_device, or the oracle).  The threshold is float32(factor x the median of
+    the first piece's power samples, a[:28 piece]) -- levels.percentile of their report at 0.5 -- or, with absolute, the float given;
+    the table is levels.bursts of the WHOLE envelope, the payload gather's, the bytes pack's: version 1, kind 4.  ArchiveError where
+    the first piece has no sign-clear sample to take a median of."""
+    x = np.ascontiguousarray(x, dtype=np.uint16).reshape(-1)
+    a = np.ascontiguousarray(a, dtype="<f4").reshape(-1)
+    M = 2 * (x.size // 4)
+    if a.size != M or int(piece) < 1:
+        raise ArchiveError(f"{a.size} power samples for a stream of {x.size} samples (M = {M}), in pieces of {piece} runs")
+    if absolute:
+        threshold = float(np.float32(factor_or_threshold))
+    else:
+        first = levels.level_report(a[:RUN * int(piece)])
+        if int(np.asarray(first["hist"]).sum()) == 0:
+            raise ArchiveError("the first piece has no sign-clear power sample: the gate has no threshold")
+        threshold = float(np.float32(factor_or_threshold * levels.percentile(first["hist"], 0.5)))
+    table = levels.bursts(levels.level_report(a)["env"], threshold, lead, hang)
+    payload, _ = gather(x, table, M, 4)
+    return pack(4, x.size, M, threshold, lead, hang, table, payload)
 
 
 def unpack(data: bytes) -> dict:

@@ -255,6 +255,8 @@ SYMBOLS = {
     "adsb_level_percentile": (C.c_float, [C.c_void_p, C.c_double]),
     "adsb_bursts_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     "adsb_bursts_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "adsb_bursts_slice_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adsb_bursts_slice_host": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adsb_burst_tile_runs": (C.c_uint32, []),
     "adsb_gather_layout": (C.c_long, [C.c_uint64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64)]),
     "adsb_gather_device": (C.c_long, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -1159,6 +1161,37 @@ class Decoder:
             recs, b = self._bursts_call("adsb_bursts_host", env.ctypes.data, env.size, threshold, lead, hang, b)
         return recs, b
 
+    # ---- the gate of a slice of a stream (adsb_bursts_slice_*; adsbdec_amd.levels.bursts_slice is the statement)
+    def _bursts_slice_call(self, name, ptr, n_env, threshold, lead, hang, carry, final, cap, table=None, out=None):
+        """-> (the first min(B, cap) closed records in stream runs, B, the carry out).  carry: a burst_carry(); out: the array to write
+        the carry into instead of a new one (carry itself is allowed: in == out)."""
+        from .levels import BURST_DTYPE
+        t = np.zeros(cap, dtype=BURST_DTYPE) if table is None else table
+        o = burst_carry() if out is None else out
+        b = getattr(self._L, name)(self._h, ptr or None, n_env, threshold, lead, hang, _carry_array(carry).ctypes.data, int(bool(final)),
+                                   t.ctypes.data if cap else None, cap, o.ctypes.data)
+        if b < 0:
+            self._check(-1, name)
+        return t[:min(b, cap)], int(b), o
+
+    def bursts_slice_device(self, env_ptr: int, n_env: int, threshold: float, lead: int, hang: int, carry, final: bool, cap: int, table=None, out=None):
+        """adsb_bursts_slice_device: the bursts that the n_env floats in HBM at env_ptr, the next slice of a stream, close -> (records in
+        stream runs, B, carry out); B may exceed cap: the same call again with the same carry and more room."""
+        return self._bursts_slice_call("adsb_bursts_slice_device", env_ptr, n_env, threshold, lead, hang, carry, final, cap, table, out)
+
+    def bursts_slice_host(self, env, threshold: float, lead: int, hang: int, carry, final: bool, cap: int | None = None, table=None, out=None):
+        """adsb_bursts_slice_host: ... of a float32 array in host memory (cap None: as many as there are, by a second call with the same
+        carry where the first guess was short)."""
+        env = np.ascontiguousarray(env, dtype=np.float32).reshape(-1)
+        ptr = env.ctypes.data if env.size else 0
+        if cap is not None:
+            return self._bursts_slice_call("adsb_bursts_slice_host", ptr, env.size, threshold, lead, hang, carry, final, cap, table, out)
+        carry = _carry_array(carry).copy()                       # (out may be carry: the second call needs what came in)
+        recs, b, o = self._bursts_slice_call("adsb_bursts_slice_host", ptr, env.size, threshold, lead, hang, carry, final, 1024, out=out)
+        if b > 1024:
+            recs, b, o = self._bursts_slice_call("adsb_bursts_slice_host", ptr, env.size, threshold, lead, hang, carry, final, b, out=out)
+        return recs, b, o
+
     def bursts(self, x: np.ndarray, q: float = 0.5, factor: float = BURST_FACTOR, lead: int = BURST_LEAD, hang: int = BURST_HANG):
         """A uint16 capture in host memory -> (every burst of its envelope, B): level() with the envelope, the threshold
         float32(factor * percentile(hist, q)) (adsb_level_percentile), and the gate (adsb_bursts_host).
@@ -1529,6 +1562,20 @@ def plan_shards(total_samples: int, n_shards: int):
 def _burst_table(bursts) -> np.ndarray:
     from .levels import BURST_DTYPE
     return np.ascontiguousarray(np.asarray(bursts, dtype=BURST_DTYPE).reshape(-1))
+
+
+def burst_carry() -> np.ndarray:
+    """A zeroed adsb_burst_carry, the start of a stream: one record of adsbdec_amd.levels.BURST_CARRY_DTYPE."""
+    from .levels import burst_carry as zeroed
+    return zeroed()
+
+
+def _carry_array(carry) -> np.ndarray:
+    from .levels import BURST_CARRY_DTYPE
+    c = np.ascontiguousarray(np.asarray(carry, dtype=BURST_CARRY_DTYPE).reshape(-1))
+    if c.size != 1:
+        raise ValueError("a carry is one record of levels.BURST_CARRY_DTYPE")
+    return c
 
 
 def gather_layout(bursts, m: int, sample_bytes: int) -> np.ndarray:

@@ -31,12 +31,25 @@ struct BurstArgs {
     uint32_t cap;
 };
 
+// What the launches of a SLICE of a stream take besides (burst_slice_kernel.hip; adsb_bursts_slice_*): run r of the slice is run
+// first_run + r of the stream, and every run the kernels hold or write is a stream run.  The cluster that earlier slices left
+// open is burst 0 of the slice: its last hot run + 1 (0: none is open) is the hot run before tile 0, and it is the one start in
+// front of the slice.  The table has cap + 1 records: the bursts k < cap as {max(0, first - lead), last + hang + 1, hot, peak},
+// and behind them the LAST burst, k = B - 1, as {first, last + 1, hot, peak}; cap <= B - 1.  Of the carried cluster the kernels
+// write only what the slice adds: its begin stays 0, its end too where no hot run of the slice joins it, and the host sees to both.
+struct BurstSlice {
+    uint32_t first_run, prev_last1, prev_starts;
+};
+
 inline uint32_t burst_tiles(uint64_t runs, uint32_t pad) { return (uint32_t)((runs + pad + kBurstTileRuns - 1) / kBurstTileRuns); }
 
 // The summaries of every tile, then the combine (one workgroup): rows and *total are complete when the stream reaches what follows.
 hipError_t launch_burst_count(const BurstArgs &a, hipStream_t stream);
 // The emit: the records k < cap of the table.  The table holds zeroes when it starts.
 hipError_t launch_burst_emit(const BurstArgs &a, hipStream_t stream);
+// The same two of a slice (burst_slice_kernel.hip): *total counts the carried cluster; the table's cap + 1 records hold zeroes.
+hipError_t launch_burst_slice_count(const BurstArgs &a, const BurstSlice &s, hipStream_t stream);
+hipError_t launch_burst_slice_emit(const BurstArgs &a, const BurstSlice &s, hipStream_t stream);
 
 } // namespace adsb
 

@@ -2,7 +2,7 @@
  * adsbdec_amd_cli.c -- host program in C for the offline "-f" path, calling the
  * HIP library through the C-ABI of include/adsbdec_amd.h.  This file: the manual, and main() = parse, refuse, dispatch.
  * options.c: the command line and which options go together; common.c: what every mode uses; one file per mode --
- * stream.c (the plain decode), batch.c (-G, -B), export.c (-W), level.c (-L, -I), bursts.c (-U, -K, -P, -k); cli.h.
+ * stream.c (the plain decode), batch.c (-G, -B), export.c (-W), level.c (-L, -I), bursts.c (-U, -K, -P, -k), record.c (-S, -O); cli.h.
  *
  * Mirrors the reference's command line for this path (main.c:60-89):
  *     -f filename   input file (air.c:217-246 fileInput)
@@ -84,6 +84,24 @@
  *                   jumped (demod.c:99,128,134).  The table is the sum of the pieces' tables.  -a, -m, -b, -x, -s, -l as for a capture; the
  *                   kind comes from the header: not with -t, -p, -q, -w, -E, -G, -B, -L, -W or -K.  A file that is no archive of this
  *                   version, or whose table and payload do not go together, is refused before any GPU call.
+ *     -S factor[,lead[,hang[,piece]]]  EXTENSION: GATE A STREAM OF ANY LENGTH (adsb_level_windows, adsb_bursts_slice_device).  The uint16 file
+ *                   or FIFO of -f is read in pieces of `piece` runs (28 power samples each; default 299 593, about 16 Mi samples); a
+ *                   piece is one window call for its report and envelope and one gate call that JOINS BURSTS ACROSS THE PIECES: the
+ *                   bursts are those -L -U finds in the whole stream with the same threshold, whatever the piece.  threshold = factor x
+ *                   the median of the FIRST piece (adsb_level_percentile at 0.5), fixed for the stream; `@value` in place of the factor is
+ *                   the threshold itself.  stdout: once `bursts threshold T lead L hang H`, then `FIRST END HOT PEAK` per burst as it
+ *                   closes, in power samples of the stream.  lead and hang default to -U's 2 and 1468 (for -k, hang 4 is enough).  Memory
+ *                   is bounded: the device holds the piece and, in front of it, the samples from the open burst's begin on (or the last
+ *                   lead runs).  More than 64 Mi samples retained: the gate never closes -- a message that says to raise the factor,
+ *                   status 255.  The stream ends at the end of the file or at SIGINT / SIGTERM / SIGQUIT, and what is open is closed
+ *                   there; at 2^31 runs (about 100 minutes) it is ended as if the file did: a message, status 255.  A first piece
+ *                   without a sign-clear power sample: no threshold, status 255.  uint16 input only (the one flavour with a window
+ *                   call): not with -L, -I, -U, -K, -P, -k, -t, -p, -q, -w, -W, -G, -B, -E, -x, -m, -b, -s, -l or several -f.
+ *     -O out.brs    EXTENSION, with -S: KEEP ONLY THE BURSTS.  The samples of the bursts a piece closes are gathered on the GPU
+ *                   (adsb_gather_device, one call and one copy back per piece) and appended to out.brs.spool; at the end out.brs -- the
+ *                   archive -L -U -K writes for the whole stream with that threshold: version 1, kind 4 -- is written as out.brs.tmp
+ *                   (header, table, the spool) and renamed, so a run that fails leaves no out.brs; the spool file is removed.  On
+ *                   stderr `kept B bursts, X of Y bytes`.  Not without -S.
  *     -E            EXTENSION: DECODE TO THE LAST SAMPLE (adsb_set_flush).  The reference never scans the last ~41 k power samples of a
  *                   file -- deqframe runs only once 40 980 power samples are buffered (air.c:94-99) and scans idx < len - 1200
  *                   (demod.c:89) -- and a file below 81 960 samples decodes nothing.  With -E the packets and the table are what the
@@ -131,6 +149,8 @@ int main(int argc, char **argv)
         return rc;
     if (o.listfile)
         return run_batch(&o);
+    if (o.record_arg)
+        return run_record(&o);
     if (o.level)
         return o.interval_arg ? run_level_windows(&o) : run_level(&o);
     if (o.export_path)

@@ -78,7 +78,8 @@ static uint64_t get64(const unsigned char *h, size_t at)
     return v;
 }
 
-int brs_write(const char *path, const brs_archive *a, char *why, size_t cap)
+/* the payload from memory (spool NULL) or from the start of a file that holds it */
+static int brs_write_from(const char *path, const brs_archive *a, FILE *spool, char *why, size_t cap)
 {
     uint64_t total = 0;
     if (brs_sample_bytes(a->kind) == 0 || brs_sample_bytes(a->kind) != a->sample_bytes) {
@@ -108,12 +109,33 @@ int brs_write(const char *path, const brs_archive *a, char *why, size_t cap)
     }
     int ok = fwrite(h, 1, sizeof h, f) == sizeof h;
     ok = ok && (a->n_bursts == 0 || fwrite(a->bursts, sizeof(adsb_burst), (size_t)a->n_bursts, f) == (size_t)a->n_bursts);
-    ok = ok && (total == 0 || fwrite(a->payload, 1, (size_t)total, f) == (size_t)total);
+    if (!spool) {
+        ok = ok && (total == 0 || fwrite(a->payload, 1, (size_t)total, f) == (size_t)total);
+    } else {
+        static unsigned char block[1 << 16];
+        ok = ok && fflush(spool) == 0 && fseeko(spool, 0, SEEK_SET) == 0;
+        for (uint64_t left = total; ok && left;) {
+            const size_t want = left < sizeof block ? (size_t)left : sizeof block;
+            ok = fread(block, 1, want, spool) == want && fwrite(block, 1, want, f) == want;
+            left -= want;
+        }
+    }
     if (fclose(f) != 0 || !ok) {
         snprintf(why, cap, "cannot write: %s", strerror(errno));
         return -1;
     }
     return 0;
+}
+
+int brs_write(const char *path, const brs_archive *a, char *why, size_t cap) { return brs_write_from(path, a, NULL, why, cap); }
+
+int brs_write_spooled(const char *path, const brs_archive *a, FILE *spool, char *why, size_t cap)
+{
+    if (!spool) {
+        snprintf(why, cap, "no spool file to take the payload from");
+        return -1;
+    }
+    return brs_write_from(path, a, spool, why, cap);
 }
 
 int brs_read(const char *path, brs_archive *a, char *why, size_t cap)

@@ -5,6 +5,7 @@
 #define ADSBDEC_AMD_CLI_BURST_ARCHIVE_H
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "adsbdec_amd.h"
 
@@ -33,6 +34,9 @@ uint64_t brs_piece_units(const brs_archive *a, uint64_t i);
 /* 0, or -1 with the reason in why[cap].  brs_write checks the table and the payload's size by the layout of the kind first
  * (adsb_gather_layout; kind 12: adsb_gather_pack12_layout). */
 int brs_write(const char *path, const brs_archive *a, char *why, size_t cap);
+/* The same file with the payload taken from the first payload_bytes bytes of `spool`, a file open for reading and writing (the record
+ * mode appends each piece's gathered bytes to one): a->payload is not read, and the payload is never in memory in one piece. */
+int brs_write_spooled(const char *path, const brs_archive *a, FILE *spool, char *why, size_t cap);
 /* The whole file into memory of the archive's own.  Refused: a file that cannot be read, another magic or version, a kind and
  * sample_bytes that do not go together, an M the capture's units cannot make, a table the kind's layout refuses, a payload of another
  * size than the layout's total. */

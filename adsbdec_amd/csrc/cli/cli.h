@@ -22,6 +22,13 @@ struct burst_opts { /* -U: factor 0 = no gate */
     uint32_t lead, hang;
 };
 
+struct record_opts { /* -S: factor 0 = malformed.  absolute: the argument began with @ and factor is the threshold itself */
+    double factor;
+    int absolute;
+    uint32_t lead, hang;
+    uint64_t piece; /* runs read per slice */
+};
+
 /* The command line as cli_parse leaves it.  A malformed -t, -q, -I or -U is remembered here (stype / qtype -1, interval_ms 0,
  * burst.factor 0) beside the text the refusal echoes; cli_refuse turns it away. */
 struct cli_options {
@@ -38,6 +45,9 @@ struct cli_options {
     const char *archive_out; /* -K: keep only the bursts of -L -U, as a burst archive */
     const char *pack_out;    /* -P: ... of a real capture, packed to 12 bits (archive kind 12) */
     int archive_in;          /* -k: the file of -f is a burst archive */
+    const char *record_arg;  /* -S: gate a stream of any length, factor[,lead[,hang[,piece]]] */
+    struct record_opts record;
+    const char *record_out;  /* -O: ... and keep its bursts as a burst archive */
     const char *interval_arg; /* -I: -L's windows, in milliseconds */
     double interval_ms;
     long stype; /* -t: ADSB_FMT_RAW without it */
@@ -85,4 +95,5 @@ int run_level_windows(const struct cli_options *o);             /* -L -I */
 int level_bursts(adsb_decoder *dec, const struct cli_options *o, const adsb_level_report *rep, const float *d_env, uint64_t m,
                  int flavour, int fmt, const void *d_in, size_t n, size_t used);
 int run_archive(const struct cli_options *o);                   /* -k */
+int run_record(const struct cli_options *o);                    /* record.c: -S [-O] */
 #endif

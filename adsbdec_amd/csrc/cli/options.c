@@ -2,6 +2,8 @@
  * touches the input file, a peer or the GPU runtime. */
 #include "cli.h"
 
+/* (The text is pinned word for word by the recorded grid of tests/test_cli_options_cpu.py; the record mode, -S and -O, came after
+ * that recording and is described in the manual at the head of adsbdec_amd_cli.c and by its own refusals.) */
 static void usage(void)
 {
     printf("adsbdec_amd : MI355X offline ADS-B decoder (adsbdec -f compatible)\n\n");
@@ -114,15 +116,16 @@ int cli_parse(int argc, char **argv, struct cli_options *o)
     memset(o, 0, sizeof *o);
     o->device = -1;
     o->burst.lead = 2, o->burst.hang = 1468;
+    o->record.lead = 2, o->record.hang = 1468, o->record.piece = 299593;
     o->stype = ADSB_FMT_RAW;
     o->qtype = -1;
     o->outmode = SINK_STDOUT;
     /* the options that only switch something on, and the ones that only name a file */
-    static const char switches[] = "axpwLEk", paths[] = "BWKP";
+    static const char switches[] = "axpwLEk", paths[] = "BWKPO";
     int *const on[] = {&o->df18, &o->fix1, &o->packed, &o->power, &o->level, &o->flush, &o->archive_in};
-    const char **const path[] = {&o->listfile, &o->export_path, &o->archive_out, &o->pack_out};
+    const char **const path[] = {&o->listfile, &o->export_path, &o->archive_out, &o->pack_out, &o->record_out};
     int c;
-    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:EK:kP:")) != EOF) {
+    while ((c = getopt(argc, argv, "f:g:ambxpwd:G:s:l:B:t:q:W:LI:U:EK:kP:S:O:")) != EOF) {
         char *end;
         const char *at;
         switch (c) {
@@ -174,6 +177,25 @@ int cli_parse(int argc, char **argv, struct cli_options *o)
             }
             if (!ok || *end)
                 o->burst.factor = 0;
+            break;
+        }
+        case 'S': { /* factor | @threshold, then [,lead[,hang[,piece]]]: whole numbers, lead and hang up to 2^30, piece 1 .. 2^24 runs */
+            const char *num = optarg;
+            o->record_arg = optarg;
+            o->record.absolute = *num == '@';
+            num += o->record.absolute;
+            o->record.factor = strtod(num, &end);
+            int ok = end != num && o->record.factor > 0 && o->record.factor <= (o->record.absolute ? 3.4028234663852886e38 : 1.7976931348623157e308);
+            uint64_t field[3] = {o->record.lead, o->record.hang, o->record.piece};
+            for (int i = 0; ok && i < 3 && *end == ','; i++) {
+                num = end + 1;
+                const unsigned long long v = strtoull(num, &end, 10);
+                ok = end != num && *num >= '0' && *num <= '9' && v <= (i < 2 ? 1ull << 30 : 1ull << 24) && (i < 2 || v > 0);
+                field[i] = v;
+            }
+            o->record.lead = (uint32_t)field[0], o->record.hang = (uint32_t)field[1], o->record.piece = field[2];
+            if (!ok || *end)
+                o->record.factor = 0;
             break;
         }
         case 't':
@@ -235,6 +257,29 @@ int cli_refuse(const struct cli_options *o)
     static const char iq_or_power[] = "a file holds IQ samples (-q) or power samples (-w), not both";
     static const char packed_or_iq[] = "a file is packed 12-bit real or IQ, not both";
     char subject[32];
+    const int S = o->record_arg != NULL, O = o->record_out != NULL, x = o->fix1, m = o->outformat == 1, b = o->outformat == 2;
+
+    if (S) { /* -S gates a uint16 stream piece by piece and decodes nothing */
+        static const char own_gate[] = "-S reads the stream in pieces and has a level call, a gate and an archive (-O) of its own";
+        static const char uint16[] = "the pieces go through adsb_level_windows, which only uint16 samples have";
+        static const char one_stream[] = "a stream is recorded on one GPU (-d), one at a time";
+        static const char no_packets[] = "a recording decodes nothing: there are no packets to repair, format or send";
+        if (refuse_with("-S", (const struct clash[]){
+                {L, "-L", own_gate}, {I, "-I", own_gate}, {U, "-U", own_gate}, {K, "-K", own_gate}, {P, "-P", own_gate},
+                {k, "-k", "-k reads an archive, -S writes one"},
+                {t, "-t", uint16}, {p, "-p", uint16}, {q, "-q", uint16}, {w, "-w", uint16},
+                {W, "-W", "a run writes the power samples or records the stream's bursts, not both"},
+                {G, "-G", one_stream}, {B, "-B", one_stream},
+                {E, "-E", no_packets}, {x, "-x", no_packets}, {m, "-m", no_packets}, {b, "-b", no_packets}, {s, "-s", no_packets},
+                {l, "-l", no_packets},
+                {several, "several -f", one_stream}, {0}}))
+            return 1;
+        if (!(o->record.factor > 0))
+            return refuse("-S %s: factor[,lead[,hang[,piece]]] -- a finite factor above 0 (or @threshold, a finite float above 0), lead and hang "
+                          "whole numbers of runs up to 2^30, piece a whole number of runs from 1 to 2^24\n", o->record_arg);
+    }
+    if (O && !S)
+        return refuse("-O is not supported without -S: it is the archive of the stream that -S gates\n", NULL);
 
     if (P) { /* -P keeps the pieces -L -U finds of a REAL capture, packed to 12 bits */
         static const char real12[] = "12-bit codes are what a REAL capture carries (a uint16 file, -p or -t 3 | 1); -K keeps IQ and power samples as they are";

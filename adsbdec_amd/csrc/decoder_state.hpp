@@ -331,6 +331,8 @@ struct adsb_decoder {
     int level_batch_blocks = 0; // adsb_debug_set_level_batch_blocks: 0, or the most workgroups a batch level launch may have
     // the gate behind the envelope (adsb_bursts_*, decoder_bursts.hip; burst.h): every tile's summary and, behind them, its combine
     // row; B as the combine leaves it and its pinned twin; the device table of min(B, cap) records.  Grown to the largest call seen.
+    // adsb_bursts_slice_* use the same three: the table with one more record, the last burst's, whose copy lands in the pinned
+    // words 4 .. 7 behind B.
     adsb::Buf<uint32_t> burst_scratch;
     adsb::Totals<uint32_t> burst_total;
     adsb::Buf<uint32_t> burst_tab;

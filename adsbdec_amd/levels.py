@@ -191,6 +191,72 @@ def bursts(env, threshold, lead, hang) -> np.ndarray:
     return out
 
 
+# ---- the gate of a slice of a stream (adsb_bursts_slice_*, csrc/burst_slice_kernel.hip) ----
+# adsb_burst_carry: what the slices so far leave to the next one.  runs: the runs they covered; open: a cluster is open, and then
+# its first and last hot run (stream runs), its hot count and its peak.  Zeroed: the start of a stream.
+BURST_CARRY_DTYPE = np.dtype([("runs", "<u8"), ("open", "<u4"), ("first", "<u4"), ("last", "<u4"), ("hot", "<u4"), ("peak", "<f4"), ("reserved", "<u4")])
+BURST_STREAM_RUNS = 1 << 31   # a stream's runs stay below this
+
+
+def burst_carry() -> np.ndarray:
+    """A zeroed carry, the start of a stream: one record of BURST_CARRY_DTYPE."""
+    return np.zeros(1, dtype=BURST_CARRY_DTYPE)
+
+
+def bursts_slice(env, threshold, lead, hang, carry, final):
+    """The bursts that the next slice of a stream closes: the statement adsb_bursts_slice_device is held to -> (table, carry_out).
+
+    The stream's runs count from 0 and `carry` says what the slices before left: run r of env is stream run carry.runs + r, hot by
+    bursts()'s rule.  The carried cluster's hot runs (first .. last; only the two ends matter) followed by the slice's, as stream
+    runs, are cut into clusters wherever two neighbours differ by more than join = lead + hang + 1 -- so the carried cluster and the
+    slice's first hot run h0 are one cluster iff h0 - last <= join: the counts add, peak is the float of the larger bits.  A cluster
+    with first hot run s and last hot run e is CLOSED iff final or e + join < carry.runs + R (every run that could still join it has
+    been seen and was not hot), and is then the record
+        begin = max(0, s - lead)    end = min(carry.runs + R, e + hang + 1)    hot    peak        in STREAM runs, ascending
+    (the minimum binds under final only).  At most one cluster, the last, stays open: it is carry_out, carry_out.runs = carry.runs + R.
+    A pure function: carry is not changed.  For one threshold, lead and hang the tables of consecutive calls, the last one final,
+    concatenated, are bursts() of the concatenated envelope, however it is cut; threshold, lead and hang may also differ from
+    call to call, and closing and merging then go by the current call's join."""
+    u, tb, lead, hang = _burst_args(env, threshold, lead, hang)
+    c = np.asarray(carry, dtype=BURST_CARRY_DTYPE).reshape(-1)
+    if c.size != 1:
+        raise ValueError("a carry is one record of BURST_CARRY_DTYPE")
+    c = c[0]
+    runs, join = int(c["runs"]), lead + hang + 1
+    seen = runs + u.size
+    if seen >= BURST_STREAM_RUNS:
+        raise ValueError("a stream's runs stay below 2^31")
+    h = runs + np.flatnonzero(u >= np.uint32(tb)).astype(np.int64)
+    cut = np.flatnonzero(np.diff(h) > join) + 1
+    lo = np.concatenate(([0], cut)) if h.size else np.zeros(0, dtype=np.int64)
+    hi = (np.concatenate((cut, [h.size])) - 1) if h.size else np.zeros(0, dtype=np.int64)
+    s, e, hot = h[lo], h[hi], hi - lo + 1
+    peak = np.maximum.reduceat(u[h - runs], lo).astype(np.uint32) if h.size else np.zeros(0, dtype=np.uint32)
+    if c["open"]:
+        first, last, chot, cpeak = int(c["first"]), int(c["last"]), int(c["hot"]), np.uint32(np.array([c["peak"]], dtype="<f4").view("<u4")[0])
+        if not (first <= last < runs and chot >= 1):
+            raise ValueError("an open carry has first <= last < runs and hot >= 1")
+        if h.size and h[0] - last <= join:
+            s, hot, peak = s.copy(), hot.copy(), peak.copy()
+            s[0], hot[0], peak[0] = first, hot[0] + chot, max(peak[0], cpeak)
+        else:
+            s, e, hot = np.concatenate(([first], s)), np.concatenate(([last], e)), np.concatenate(([chot], hot))
+            peak = np.concatenate((np.array([cpeak], dtype=np.uint32), peak))
+    out = burst_carry()
+    out["runs"] = seen
+    n = s.size
+    if n and not final and e[-1] + join >= seen:
+        n -= 1
+        out["open"], out["first"], out["last"], out["hot"] = 1, s[n], e[n], hot[n]
+        out["peak"] = peak[n:n + 1].view("<f4")[0]
+    table = np.zeros(n, dtype=BURST_DTYPE)
+    table["begin"] = np.maximum(0, s[:n] - lead)
+    table["end"] = np.minimum(seen, e[:n] + hang + 1)
+    table["hot"] = hot[:n]
+    table["peak"] = peak[:n].view("<f4")
+    return table, out
+
+
 def burst_samples(bursts, M: int) -> np.ndarray:
     """The bursts of an envelope of M power samples, in power samples: an (B, 2) int64 array of [28 begin, min(28 end, M))."""
     b = np.asarray(bursts)

@@ -161,14 +161,14 @@ long adsb_decode_batch_host_power(adsb_decoder *d, size_t n_captures, const floa
  *   5. The handle's stream and resolver stay untouched: callable between pushes.  6. _as and _iq (fmt 0) add to adsb_get_format_report.
  * _host: through buffers the handle keeps.  adsb_power_device: the window (0, n, 0, 2 (n / 4)).  _as (fmt 1 | 3) / _packed: through the scratch of
  * adsb_decode_device_as / _packed, shared with them.  _iq (fmt 2 | 0): n COMPLEX samples -> n power samples.  adsb_power_batch_*: a BATCH of captures, capture i exactly as the single call of the same flavour exports it alone (the same floats from device_power[i][0] on; a fresh stream each: the six pairs before its first sample read as silence, never as a neighbour's samples), in ONE export launch behind at most one unpack (_packed) or conversion (_as fmt 1 | 3, _iq fmt 0) launch into the scratch of adsb_decode_batch_device_packed / _as; returns the floats written in all; rules 5 and 6 hold.  Refused (-1, the message names the capture, nothing launched, written or counted; INTEGRATION.md): what the single call refuses of a capture, n[i] >= 2^32 (IQ: 2^31), power_cap[i] below its count, n_captures >= 2^32 - 1.  A capture without power samples (n[i] < 4; IQ: 0) may have NULL pointers and costs nothing.
- * adsb_level_*: HOW LOUD a capture is, in one pass that stores almost nothing: the report of exactly the M floats a[] that the export call of the same flavour writes (_iq takes fmt 8 too: a = 256 (I^2 + Q^2); _power: the caller's floats), b = their bit patterns.  negative: samples with the sign bit set (-0.0 counts); hist[k]: sign-clear samples with b >> 20 == k (8 bins per octave, 0.75 dB; 1.0 is bin 1016, 2^29 is 1248, Inf / NaN 2040 and up; sum + negative == samples; the _power domain holds iff negative == 0 and hist[1248 ..] == 0); rail_lo / rail_hi / over: input codes == 0 / == 4095 / > 4095 over EVERY sample of the capture, the trailing n % 4 too (real; _as / _packed: of the converted codes), scalars == -32768 / 32767 (IQ fmt 2, and 0 behind its conversion: a clamped float shows) or -128 / 127 (fmt 8), over 0; all 0 for _power.  device_env: NULL with env_cap 0, or env_cap >= ceil(M / 28) floats, 4-byte aligned: env[r] = the float whose bits are the unsigned maximum of (b, sign clear, else 0) over samples [28 r, 28 r + 28) -- in the domain the run's maximum.  Returns M (0: a zeroed report, nothing launched) or -1, nothing written, not the format report either; pointers and lengths as the export call of the flavour (fmt 8: 2-byte aligned, n < 2^31); export rules 5 and 6 hold.  adsb_level_batch_*: a BATCH of captures, capture i exactly the report -- and, where device_env[i] is given, the envelope -- that the single call of the same flavour gives for it alone (a fresh stream each: the six pairs before its first sample read as silence, never as a neighbour's samples; the rail counters over every code of the capture, its trailing n % 4 too); out: n_captures reports in host memory; device_env and env_cap both NULL (no envelope at all), or per capture the single call's NULL with 0 / ceil(M_i / 28) floats.  Up to 1024 captures share ONE level launch behind at most one unpack (_packed) or conversion (_as fmt 1 | 3, _iq fmt 0) launch into the scratch of adsb_decode_batch_device_packed / _as, one memset and one copy back of their totals (16 KiB a capture: 16 MiB of device and of pinned memory, kept by the handle); larger batches go in such sub-batches.  Returns the sum of the M_i; export rules 5 and 6 hold.  Refused (-1, the message names the capture, nothing launched, written or counted; INTEGRATION.md): what the single call refuses of a capture, n[i] >= 2^32 (IQ, fmt 8 and _power: 2^31), NULL arrays or out, n_captures >= 2^32 - 1.  A capture without power samples (n[i] < 4; IQ and _power: 0) gets a zeroed report, may have NULL pointers and costs nothing.  adsb_level_windows: ONE stream, n_windows consecutive WINDOWS of it in one launch per 1024 -- the buffer holds uint16 samples [first_sample, first_sample + n) as adsb_power_window's does (rules 1 to 3 and 5), edges[0] <= ... <= edges[n_windows] are power samples of the stream, every edge but the last a multiple of 28; out[i] = the report of the floats adsb_power_window writes for [edges[i], edges[i + 1]) (the six older pairs from the buffer where it holds them, else silence) with the rail counters of the codes of their OWN pairs, samples 2 edges[i] .. 2 edges[i + 1]; an empty window: a zeroed report.  The reports add (adsb_level_add: *sum += *part, no device) to the report of [edges[0], edges[n_windows]).  This is where ONE window over a whole capture differs from adsb_level_device: a stream's trailing n % 4 codes belong to no window, so the rails leave them out.  device_env: NULL with 0, or ceil((edges[n_windows] - edges[0]) / 28) floats for ALL windows, env[r] the run at power sample edges[0] + 28 r.  Returns edges[n_windows] - edges[0] (n_windows == 0: 0, nothing launched).  Refused (-1, the message names the window, nothing launched, written or counted): a broken rule, an inner edge off 28, descending edges, 2 edges[0] < first_sample, 2 edges[n_windows] > first_sample + n, NULL edges or out, NULL samples with a non-empty span, the envelope's rules, n_windows >= 2^32 - 1.  _host: through buffers the handle keeps.  No multi-GPU or stream-window form of the batch, _as, _packed, _iq and _power calls (INTEGRATION.md).  adsb_level_percentile: no device; the lower edge of the bin that holds the q-quantile of the sign-clear samples (the first bin at which the running count reaches ceil(q total), and 1); -1 on NULL, an empty histogram or q outside [0, 1].  adsb_bursts_*: THE GATE behind the envelope -- env: n_env floats, the envelope a level call wrote or the caller's own; u[r] = the bits of env[r], 0 where its sign is set; run r is HOT iff u[r] >= bits(threshold) as unsigned integers (NaN and Inf are hot, +0.0 makes every run hot); the hot runs, cut wherever two neighbours differ by more than lead + hang + 1, are the bursts: begin = max(0, first - lead), end = min(n_env, last + hang + 1), hot = the hot runs, peak = the float of the largest u among them; ascending, at least one run apart; in power samples [28 begin, min(28 end, M)).  Returns B, the number of bursts, which may exceed cap: the first min(B, cap) records are written to bursts (HOST memory), complete and in order, nothing at or behind bursts[cap]; NULL with cap 0 only counts; n_env 0: 0, nothing launched.  Waits for its kernels; export rule 5 holds.  Refused (-1, nothing launched or written): NULL env with n_env > 0, a pointer off 4 bytes, n_env >= 2^31, a threshold that is NaN or has its sign set, lead or hang above 2^30, a NULL table with cap > 0.  No batch form, no joining across the slices of a stream (a burst with begin == 0 or end == n_env touches the edge: the caller joins), no multi-GPU form. */
+ * adsb_level_*: HOW LOUD a capture is, in one pass that stores almost nothing: the report of exactly the M floats a[] that the export call of the same flavour writes (_iq takes fmt 8 too: a = 256 (I^2 + Q^2); _power: the caller's floats), b = their bit patterns.  negative: samples with the sign bit set (-0.0 counts); hist[k]: sign-clear samples with b >> 20 == k (8 bins per octave, 0.75 dB; 1.0 is bin 1016, 2^29 is 1248, Inf / NaN 2040 and up; sum + negative == samples; the _power domain holds iff negative == 0 and hist[1248 ..] == 0); rail_lo / rail_hi / over: input codes == 0 / == 4095 / > 4095 over EVERY sample of the capture, the trailing n % 4 too (real; _as / _packed: of the converted codes), scalars == -32768 / 32767 (IQ fmt 2, and 0 behind its conversion: a clamped float shows) or -128 / 127 (fmt 8), over 0; all 0 for _power.  device_env: NULL with env_cap 0, or env_cap >= ceil(M / 28) floats, 4-byte aligned: env[r] = the float whose bits are the unsigned maximum of (b, sign clear, else 0) over samples [28 r, 28 r + 28) -- in the domain the run's maximum.  Returns M (0: a zeroed report, nothing launched) or -1, nothing written, not the format report either; pointers and lengths as the export call of the flavour (fmt 8: 2-byte aligned, n < 2^31); export rules 5 and 6 hold.  adsb_level_batch_*: a BATCH of captures, capture i exactly the report -- and, where device_env[i] is given, the envelope -- that the single call of the same flavour gives for it alone (a fresh stream each: the six pairs before its first sample read as silence, never as a neighbour's samples; the rail counters over every code of the capture, its trailing n % 4 too); out: n_captures reports in host memory; device_env and env_cap both NULL (no envelope at all), or per capture the single call's NULL with 0 / ceil(M_i / 28) floats.  Up to 1024 captures share ONE level launch behind at most one unpack (_packed) or conversion (_as fmt 1 | 3, _iq fmt 0) launch into the scratch of adsb_decode_batch_device_packed / _as, one memset and one copy back of their totals (16 KiB a capture: 16 MiB of device and of pinned memory, kept by the handle); larger batches go in such sub-batches.  Returns the sum of the M_i; export rules 5 and 6 hold.  Refused (-1, the message names the capture, nothing launched, written or counted; INTEGRATION.md): what the single call refuses of a capture, n[i] >= 2^32 (IQ, fmt 8 and _power: 2^31), NULL arrays or out, n_captures >= 2^32 - 1.  A capture without power samples (n[i] < 4; IQ and _power: 0) gets a zeroed report, may have NULL pointers and costs nothing.  adsb_level_windows: ONE stream, n_windows consecutive WINDOWS of it in one launch per 1024 -- the buffer holds uint16 samples [first_sample, first_sample + n) as adsb_power_window's does (rules 1 to 3 and 5), edges[0] <= ... <= edges[n_windows] are power samples of the stream, every edge but the last a multiple of 28; out[i] = the report of the floats adsb_power_window writes for [edges[i], edges[i + 1]) (the six older pairs from the buffer where it holds them, else silence) with the rail counters of the codes of their OWN pairs, samples 2 edges[i] .. 2 edges[i + 1]; an empty window: a zeroed report.  The reports add (adsb_level_add: *sum += *part, no device) to the report of [edges[0], edges[n_windows]).  This is where ONE window over a whole capture differs from adsb_level_device: a stream's trailing n % 4 codes belong to no window, so the rails leave them out.  device_env: NULL with 0, or ceil((edges[n_windows] - edges[0]) / 28) floats for ALL windows, env[r] the run at power sample edges[0] + 28 r.  Returns edges[n_windows] - edges[0] (n_windows == 0: 0, nothing launched).  Refused (-1, the message names the window, nothing launched, written or counted): a broken rule, an inner edge off 28, descending edges, 2 edges[0] < first_sample, 2 edges[n_windows] > first_sample + n, NULL edges or out, NULL samples with a non-empty span, the envelope's rules, n_windows >= 2^32 - 1.  _host: through buffers the handle keeps.  No multi-GPU or stream-window form of the batch, _as, _packed, _iq and _power calls (INTEGRATION.md).  adsb_level_percentile: no device; the lower edge of the bin that holds the q-quantile of the sign-clear samples (the first bin at which the running count reaches ceil(q total), and 1); -1 on NULL, an empty histogram or q outside [0, 1].  adsb_bursts_*: THE GATE behind the envelope -- env: n_env floats, the envelope a level call wrote or the caller's own; u[r] = the bits of env[r], 0 where its sign is set; run r is HOT iff u[r] >= bits(threshold) as unsigned integers (NaN and Inf are hot, +0.0 makes every run hot); the hot runs, cut wherever two neighbours differ by more than lead + hang + 1, are the bursts: begin = max(0, first - lead), end = min(n_env, last + hang + 1), hot = the hot runs, peak = the float of the largest u among them; ascending, at least one run apart; in power samples [28 begin, min(28 end, M)).  Returns B, the number of bursts, which may exceed cap: the first min(B, cap) records are written to bursts (HOST memory), complete and in order, nothing at or behind bursts[cap]; NULL with cap 0 only counts; n_env 0: 0, nothing launched.  Waits for its kernels; export rule 5 holds.  Refused (-1, nothing launched or written): NULL env with n_env > 0, a pointer off 4 bytes, n_env >= 2^31, a threshold that is NaN or has its sign set, lead or hang above 2^30, a NULL table with cap > 0.  No batch form, no multi-GPU form.  A stream that comes in slices: a burst with begin == 0 or end == n_env touches the edge, and its record no longer says where its hot runs lay, so the tables of slices cannot be joined; adsb_bursts_slice_* gate a slice with what the slices before it left open.  adsb_bursts_slice_*: THE GATE OF A SLICE OF A STREAM -- the stream's runs count from 0; in: a zeroed carry at the start of a stream, then the carry the call before wrote (runs: the runs covered so far; open: a cluster is open, with its first and last hot run, hot count and peak).  The hot runs of the slice, as stream runs, behind the open cluster's, are cut into clusters wherever two neighbours differ by more than join = lead + hang + 1 (this call's); a cluster with last hot run e is CLOSED iff final or e + join < in->runs + n_env (no run still to come can join it) and is then the record begin = max(0, first - lead), end = min(in->runs + n_env, last + hang + 1), hot, peak in STREAM runs; at most one cluster, the last, stays open and goes to *out, out->runs = in->runs + n_env.  The records of consecutive calls with one threshold, lead and hang, the last one final, are adsb_bursts_* of the whole envelope, however it is cut (slices of 0 runs too).  Returns the bursts closed, which may exceed cap: the first min(B, cap) are written (HOST memory), nothing at or behind bursts[cap]; *out is written in full whatever the cap (after B > cap: the same call again with the same in); in == out is allowed; n_env 0 launches nothing (final: closes the carried cluster).  One set of launches on the handle's stream, waited for; export rule 5 holds.  Refused (-1, nothing launched or written): what adsb_bursts_* refuse, a NULL in or out, in->runs + n_env >= 2^31, an open carry that is not first <= last < runs with hot >= 1. */
 long adsb_power_window(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *device_power, size_t power_cap);
 long adsb_power_window_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, uint64_t m_begin, uint64_t m_end, float *power, size_t power_cap); long adsb_power_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, float *const *power, const size_t *power_cap);
 long adsb_power_device(adsb_decoder *d, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
 long adsb_power_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap);
 long adsb_power_device_packed(adsb_decoder *d, const void *device_packed, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, float *const *device_power, const size_t *power_cap);
 long adsb_power_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, float *device_power, size_t power_cap); long adsb_power_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, float *const *device_power, const size_t *power_cap); typedef struct adsb_level_report { uint64_t samples, negative, rail_lo, rail_hi, over; uint64_t hist[2048]; } adsb_level_report;
-long adsb_level_device(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_packed(adsb_decoder *d, const void *device_packed, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_power(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_host(adsb_decoder *d, const uint16_t *samples, size_t n, adsb_level_report *out, float *env, size_t env_cap); long adsb_level_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, adsb_level_report *out, float *const *env, const size_t *env_cap); long adsb_level_windows(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_windows_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *env, size_t env_cap); void adsb_level_add(adsb_level_report *sum, const adsb_level_report *part); float adsb_level_percentile(const adsb_level_report *r, double q); typedef struct adsb_burst { uint32_t begin, end, hot; float peak; } adsb_burst; /* runs of 28 power samples, [begin, end) */ long adsb_bursts_device(adsb_decoder *d, const float *device_env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); long adsb_bursts_host(adsb_decoder *d, const float *env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); /* adsb_gather_*: KEEP ONLY THE BURSTS -- a capture of m power samples at sample_bytes bytes each (2: int8 IQ; 4: uint16 real, int16 IQ, float32 power; 8: float32 IQ) and an ordered burst table, as adsb_bursts_* returns it; piece i is the power samples [28 begin_i, min(28 end_i, m)), its bytes are capture[s lo_i : s hi_i]; the pieces lie in the output in table order, each from a multiple of 16 bytes on: offsets[0] = 0, offsets[i + 1] = round_up(offsets[i] + s (hi_i - lo_i), 16); pad bytes are zero; the total is offsets[n_bursts].  A piece's start is then a legal adsb_decode_batch_device* pointer (16-byte aligned, at a multiple of 4 samples), and on a flush handle (adsb_set_flush) the piece decodes as its silent twin: report g + 28 begin_i, which is exact, and ts + 28 begin_i, which is the original stream's ts only up to what accepted frames before the piece jumped (demod.c:99,128,134).  adsb_gather_layout: no device; offsets (n_bursts + 1, or NULL) and *total_bytes (or NULL) in host memory; 0, or -1 with adsb_last_error(NULL) naming the record: sample_bytes not 2, 4 or 8, a record with end <= begin or 28 begin >= m, records that do not ascend with a run between neighbours.  adsb_gather_device: device_capture and device_out in device memory, 16-byte aligned; bursts and offsets (n_bursts + 1, or NULL) in host memory; ONE launch on the handle's stream, returned when the bytes are there; returns the total bytes written (n_bursts 0: 0, nothing launched), nothing at or behind device_out + total is written; export rule 5 holds (callable between pushes).  Refused (-1, the message names the burst, nothing launched or written): what the layout refuses, capture_bytes < sample_bytes m, a pointer off 16 bytes or NULL with work to do, out_cap_bytes < total.  _as and _packed captures go through adsb_gather_pack12_* (their pieces are not in the capture's own bytes); no batch form, no joining across the slices of a stream, no multi-GPU form.  adsb_gather_pack12_*: THE SAME FOR A REAL CAPTURE AT 12 BITS -- n uint16 samples x carrying 12-bit codes, m = 2 (n / 4); piece i is the samples x[2 lo_i : 2 hi_i] completed to whole groups of 8 with code 2048 (at most four codes, only where m clips the last piece and m % 4 == 2), taken & 0x0fff and packed as Airspy packed 12-bit samples (ADSB_PACKED12_BYTES): 12 ceil((hi_i - lo_i) / 4) bytes, 84 per run, 3 per power sample where adsb_gather_device writes 4; offsets[i + 1] = round_up(offsets[i] + those, 16), pad bytes zero.  A piece's start is a legal adsb_decode_batch_device_packed pointer with n = 8 ceil((hi_i - lo_i) / 4), and on a flush handle it decodes as the uint16 piece does (the fill is the silence of its twin).  *over (or NULL): the pieces' OWN samples above 4095 -- never the fill, never a sample outside the pieces; their low 12 bits are what is stored.  _layout: no device, the table checked as adsb_gather_layout checks it.  _device: device_samples and device_out 16-byte aligned.  _as (fmt 1 | 3) / _packed (n % 8 == 0, 4-byte aligned): converted or unpacked first, by the launch and into the scratch of adsb_decode_device_as / _packed, then gathered from there; _as adds to adsb_get_format_report.  ONE gather launch on the handle's stream; returns the total bytes (n_bursts 0: 0, nothing launched), nothing at or behind device_out + total is written; export rules 5 and 6 hold.  Refused (-1, the message names the burst, nothing launched, written or counted): what the layout refuses, n >= 2^32, a capture or output pointer off 16 bytes (_packed's capture: 4) or NULL with work to do, out_cap_bytes < total, fmt not 1 or 3, _packed with n % 8 != 0.  Not built: gathering straight from a packed source without the unpack, IQ and power kinds, a batch form, stream slices, a multi-GPU form. */ long adsb_gather_layout(uint64_t m, int sample_bytes, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes); long adsb_gather_device(adsb_decoder *d, const void *device_capture, size_t capture_bytes, int sample_bytes, uint64_t m, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets); long adsb_gather_pack12_layout(uint64_t m, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes); long adsb_gather_pack12_device(adsb_decoder *d, const void *device_samples, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over); long adsb_gather_pack12_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over); long adsb_gather_pack12_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over);
+long adsb_level_device(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_packed(adsb_decoder *d, const void *device_packed, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_iq(adsb_decoder *d, int fmt, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_device_power(adsb_decoder *d, const void *device_samples, size_t n, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_host(adsb_decoder *d, const uint16_t *samples, size_t n, adsb_level_report *out, float *env, size_t env_cap); long adsb_level_batch_device(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_as(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_packed(adsb_decoder *d, size_t n_captures, const void *const *device_packed, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_iq(adsb_decoder *d, int fmt, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_device_power(adsb_decoder *d, size_t n_captures, const void *const *device_samples, const size_t *n, adsb_level_report *out, float *const *device_env, const size_t *env_cap); long adsb_level_batch_host(adsb_decoder *d, size_t n_captures, const uint16_t *const *samples, const size_t *n, adsb_level_report *out, float *const *env, const size_t *env_cap); long adsb_level_windows(adsb_decoder *d, const void *device_samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *device_env, size_t env_cap); long adsb_level_windows_host(adsb_decoder *d, const uint16_t *samples, uint64_t first_sample, size_t n, size_t n_windows, const uint64_t *edges, adsb_level_report *out, float *env, size_t env_cap); void adsb_level_add(adsb_level_report *sum, const adsb_level_report *part); float adsb_level_percentile(const adsb_level_report *r, double q); typedef struct adsb_burst { uint32_t begin, end, hot; float peak; } adsb_burst; /* runs of 28 power samples, [begin, end) */ long adsb_bursts_device(adsb_decoder *d, const float *device_env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); long adsb_bursts_host(adsb_decoder *d, const float *env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, adsb_burst *bursts, size_t cap); typedef struct adsb_burst_carry { uint64_t runs; uint32_t open, first, last, hot; float peak; uint32_t reserved; } adsb_burst_carry; long adsb_bursts_slice_device(adsb_decoder *d, const float *device_env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, const adsb_burst_carry *in, int final, adsb_burst *bursts, size_t cap, adsb_burst_carry *out); long adsb_bursts_slice_host(adsb_decoder *d, const float *env, size_t n_env, float threshold, uint32_t lead, uint32_t hang, const adsb_burst_carry *in, int final, adsb_burst *bursts, size_t cap, adsb_burst_carry *out); /* adsb_gather_*: KEEP ONLY THE BURSTS -- a capture of m power samples at sample_bytes bytes each (2: int8 IQ; 4: uint16 real, int16 IQ, float32 power; 8: float32 IQ) and an ordered burst table, as adsb_bursts_* returns it; piece i is the power samples [28 begin_i, min(28 end_i, m)), its bytes are capture[s lo_i : s hi_i]; the pieces lie in the output in table order, each from a multiple of 16 bytes on: offsets[0] = 0, offsets[i + 1] = round_up(offsets[i] + s (hi_i - lo_i), 16); pad bytes are zero; the total is offsets[n_bursts].  A piece's start is then a legal adsb_decode_batch_device* pointer (16-byte aligned, at a multiple of 4 samples), and on a flush handle (adsb_set_flush) the piece decodes as its silent twin: report g + 28 begin_i, which is exact, and ts + 28 begin_i, which is the original stream's ts only up to what accepted frames before the piece jumped (demod.c:99,128,134).  adsb_gather_layout: no device; offsets (n_bursts + 1, or NULL) and *total_bytes (or NULL) in host memory; 0, or -1 with adsb_last_error(NULL) naming the record: sample_bytes not 2, 4 or 8, a record with end <= begin or 28 begin >= m, records that do not ascend with a run between neighbours.  adsb_gather_device: device_capture and device_out in device memory, 16-byte aligned; bursts and offsets (n_bursts + 1, or NULL) in host memory; ONE launch on the handle's stream, returned when the bytes are there; returns the total bytes written (n_bursts 0: 0, nothing launched), nothing at or behind device_out + total is written; export rule 5 holds (callable between pushes).  Refused (-1, the message names the burst, nothing launched or written): what the layout refuses, capture_bytes < sample_bytes m, a pointer off 16 bytes or NULL with work to do, out_cap_bytes < total.  _as and _packed captures go through adsb_gather_pack12_* (their pieces are not in the capture's own bytes); no batch form, no joining across the slices of a stream, no multi-GPU form.  adsb_gather_pack12_*: THE SAME FOR A REAL CAPTURE AT 12 BITS -- n uint16 samples x carrying 12-bit codes, m = 2 (n / 4); piece i is the samples x[2 lo_i : 2 hi_i] completed to whole groups of 8 with code 2048 (at most four codes, only where m clips the last piece and m % 4 == 2), taken & 0x0fff and packed as Airspy packed 12-bit samples (ADSB_PACKED12_BYTES): 12 ceil((hi_i - lo_i) / 4) bytes, 84 per run, 3 per power sample where adsb_gather_device writes 4; offsets[i + 1] = round_up(offsets[i] + those, 16), pad bytes zero.  A piece's start is a legal adsb_decode_batch_device_packed pointer with n = 8 ceil((hi_i - lo_i) / 4), and on a flush handle it decodes as the uint16 piece does (the fill is the silence of its twin).  *over (or NULL): the pieces' OWN samples above 4095 -- never the fill, never a sample outside the pieces; their low 12 bits are what is stored.  _layout: no device, the table checked as adsb_gather_layout checks it.  _device: device_samples and device_out 16-byte aligned.  _as (fmt 1 | 3) / _packed (n % 8 == 0, 4-byte aligned): converted or unpacked first, by the launch and into the scratch of adsb_decode_device_as / _packed, then gathered from there; _as adds to adsb_get_format_report.  ONE gather launch on the handle's stream; returns the total bytes (n_bursts 0: 0, nothing launched), nothing at or behind device_out + total is written; export rules 5 and 6 hold.  Refused (-1, the message names the burst, nothing launched, written or counted): what the layout refuses, n >= 2^32, a capture or output pointer off 16 bytes (_packed's capture: 4) or NULL with work to do, out_cap_bytes < total, fmt not 1 or 3, _packed with n % 8 != 0.  Not built: gathering straight from a packed source without the unpack, IQ and power kinds, a batch form, stream slices, a multi-GPU form. */ long adsb_gather_layout(uint64_t m, int sample_bytes, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes); long adsb_gather_device(adsb_decoder *d, const void *device_capture, size_t capture_bytes, int sample_bytes, uint64_t m, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets); long adsb_gather_pack12_layout(uint64_t m, const adsb_burst *bursts, size_t n_bursts, uint64_t *offsets, uint64_t *total_bytes); long adsb_gather_pack12_device(adsb_decoder *d, const void *device_samples, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over); long adsb_gather_pack12_device_as(adsb_decoder *d, int fmt, const void *device_samples, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over); long adsb_gather_pack12_device_packed(adsb_decoder *d, const void *device_packed, size_t n, const adsb_burst *bursts, size_t n_bursts, void *device_out, size_t out_cap_bytes, uint64_t *offsets, uint64_t *over);
 /* on = 1: no push refuses for length; the handle follows the reference's uint32_t sample counter (air.c:34) through its wraps, bit for bit.  Only on a
  * fresh or reset handle before the first push (else -1); sticky across adsb_reset.  adsb_get_wraps: wraps so far, and offsets of the seam kernel. adsb_set_flush (off by default; same rule: fresh or reset handle, sticky): decode a capture to its LAST sample instead of keeping the reference's end-of-file horizon (air.c:94-99, demod.c:89: the last ~41 k power samples are never scanned, a capture below 81 960 samples decodes nothing).  adsb_decode_device*, adsb_decode_batch_* and a stream ended by adsb_finish / a _final push then return, record for record and with the same Try/Ok table, what the reference returns for the capture's SILENT TWIN: its whole units (4 floor(n / 4) real samples, 2 floor(n / 2) IQ or power samples) followed by 81 960 power samples of silence (code 2048, (0, 0), +0.0) -- without padding or copying anything (DESIGN.md "Flush").  Every frame the horizon keeps comes back unchanged, in front.  Refuses, and is refused by, adsb_set_long_stream. */
 int adsb_set_long_stream(adsb_decoder *d, int on); int adsb_get_wraps(const adsb_decoder *d, uint64_t *wraps, uint64_t *seam_offsets); int adsb_set_flush(adsb_decoder *d, int on); int adsb_get_flush(const adsb_decoder *d);

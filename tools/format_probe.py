@@ -9,6 +9,7 @@ comparison interleaved.
     python tools/format_probe.py --export-batch [--reps 20] [--out profiles/r20_export_batch.txt] [--ab path/to/parent/libadsbdec_amd.so]   # export_batch_probe()
     python tools/format_probe.py --level [--reps 20] [--out profiles/r23_level.txt] [--variant name=path/to/libadsbdec_amd.so ...]   # level_probe()
     python tools/format_probe.py --level-windows [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/r27_level_windows.txt]   # level_windows_probe()
+    python tools/format_probe.py --burst-stream [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/rNN_burst_stream.txt]   # burst_stream_probe()
     python tools/format_probe.py --bursts [--reps 20] [--ab parent/libadsbdec_amd.so] [--out profiles/rNN_bursts.txt]   # bursts_probe(): NN is the next free round
     python tools/format_probe.py --flush [--reps 10] [--ab parent/libadsbdec_amd.so] [--out profiles/r30_flush.txt]   # flush_probe()
     python tools/format_probe.py --gather [--reps 10] [--ab parent/libadsbdec_amd.so] [--variant name=path/to/libadsbdec_amd.so ...] [--out profiles/r32_gather.txt]   # gather_probe()
@@ -1315,6 +1316,126 @@ def bursts_probe(L, reps, lines, parent):
         lines.append("#     not measured in this run: no --ab parent library given")
 
 
+def burst_stream_probe(L, reps, lines, parent):
+    """The gate of a slice of a stream (burst_slice_kernel.hip, adsb_bursts_slice_device) and the host program's record mode (-S -O), wall
+    time, the sides of a leg interleaved in this one process, the A/A beside every ratio: (a) the envelope of the benchmark's 256 Mi
+    samples as ONE slice beside adsb_bursts_device on it -- the price of the carry; (b) the same envelope in 16 slices beside the one
+    call; (c) adsb_bursts_device beside the library built from the parent commit (--ab); (d) the host program: -S 48,2,4 -O on the
+    256 Mi-sample file beside -L -U 48,2,4 -K on it, each a process of its own, with where the record mode's time went.  Before anything
+    is timed every side's table is levels.bursts's, and the two archives are equal byte for byte."""
+    import subprocess
+    import tempfile
+    import numpy as np
+    from adsbdec_amd import levels
+    t, _ = make_workload(torch, N, seed=1)
+    torch.cuda.synchronize()
+    M = N // 2
+    ke = -(-M // 28)
+    env = torch.zeros(ke, dtype=torch.float32, device="cuda")
+    d = capi.Decoder()
+    h = d._h
+    rep1 = capi.LevelReport()
+    steps = 3
+    assert L.adsb_level_device(h, t.data_ptr(), N, C.byref(rep1), env.data_ptr(), ke) == M
+    median = L.adsb_level_percentile(C.byref(rep1), 0.5)
+    threshold = float(np.float32(capi.Decoder.BURST_FACTOR * median))
+    lead, hang = 2, 4
+    want = levels.bursts(env.cpu().numpy(), threshold, lead, hang)
+    table = np.zeros(want.size + 8, dtype=levels.BURST_DTYPE)
+    carry, zero = levels.burst_carry(), levels.burst_carry()
+
+    def one(B=L, hh=h):
+        b = B.adsb_bursts_device(hh, env.data_ptr(), ke, threshold, lead, hang, table.ctypes.data, table.size)
+        assert b == want.size
+        return table[:b]
+
+    def sliced(k):
+        """k slices of equal length (the last takes the rest), the records one behind the other in the table"""
+        edges = [ke * i // k for i in range(k)] + [ke]
+        carry[:] = zero
+        at = 0
+        for i in range(k):
+            b = L.adsb_bursts_slice_device(h, env.data_ptr() + 4 * edges[i], edges[i + 1] - edges[i], threshold, lead, hang, carry.ctypes.data,
+                                           int(i == k - 1), table.ctypes.data + 16 * at, table.size - at, carry.ctypes.data)
+            assert b >= 0
+            at += b
+        assert at == want.size
+        return table[:at]
+
+    def rotate(sides):
+        names = list(sides)
+        wall = {k_: [] for k_ in names}
+        for r in range(reps):
+            for name in names[r % len(names):] + names[:r % len(names)]:
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    sides[name]()
+                wall[name].append((time.perf_counter() - t0) * 1e3 / steps)
+        return names, wall
+
+    def table_of(names, wall, base):
+        for name in names:
+            q = statistics.quantiles(wall[name], n=4)
+            rr = [a_ / b for a_, b in zip(wall[name], wall[base])]
+            qr = statistics.quantiles(rr, n=4)
+            lines.append(f"    {name:52s} {med(wall[name]):9.4f} ({q[0]:.4f} .. {q[2]:.4f})   {med(rr):.4f} ({qr[0]:.4f} .. {qr[2]:.4f})")
+            print(lines[-1], flush=True)
+
+    for side in (one, lambda: sliced(1), lambda: sliced(16)):
+        assert side().tobytes() == want.tobytes()
+    lines += [f"# (a), (b) an envelope of {ke} runs, threshold {threshold:.9g}, lead {lead} hang {hang}: B = {want.size}; {reps} rounds x {steps} calls per side, the",
+              "#     sides in rotation; every side ends with its table in host memory and gave levels.bursts's table before anything was timed",
+              "#   side                                                    call ms (q1 .. q3)             / adsb_bursts_device (median of rounds, q1 .. q3)"]
+    names, wall = rotate({"adsb_bursts_device": one, "adsb_bursts_device again (the A/A)": one,
+                          "adsb_bursts_slice_device, ONE slice": lambda: sliced(1), "adsb_bursts_slice_device, 16 slices": lambda: sliced(16)})
+    table_of(names, wall, names[0])
+    lines += ["#", "# (c) adsb_bursts_device of this tree beside the library built from the parent commit, loaded into this process"]
+    if parent:
+        B = C.CDLL(parent)
+        for name in ("adsb_create", "adsb_bursts_device"):
+            fn = getattr(B, name)
+            fn.restype, fn.argtypes = capi.SYMBOLS[name]
+        assert not hasattr(B, "adsb_bursts_slice_device"), "the --ab library is not the parent's: it has the slice call"
+        cfg = capi.make_config()
+        hh = B.adsb_create(C.byref(cfg))
+        assert hh, parent
+        assert one(B, hh).tobytes() == want.tobytes(), "the parent's library gives another table"
+        names, wall = rotate({"adsb_bursts_device (tree)": one, "adsb_bursts_device (tree again: the A/A)": one,
+                              "adsb_bursts_device (parent commit)": lambda: one(B, hh)})
+        lines.append("#   side                                                    call ms (q1 .. q3)             / tree (median of rounds, q1 .. q3)")
+        table_of(names, wall, names[0])
+    else:
+        lines.append("#     not measured in this run: no --ab parent library given")
+    # (d) the host program, a process per run
+    lines += ["#", f"# (d) the host program on a file of the {N} samples ({2 * N >> 20} MiB, in the page cache): wall time of the whole process, the two runs in turn;",
+              "#     [record]: the record mode's own account (ADSB_CLI_TIMING=1) of its last run"]
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "capture.bin")
+        t.cpu().numpy().tofile(path)
+        cmds = {"-L -U 48,2,4 -K": [capi.CLI_PATH, "-L", "-U", "48,2,4", "-K", os.path.join(tmp, "k.brs"), "-f", path],
+                "-S 48,2,4 -O (pieces of 299593 runs)": [capi.CLI_PATH, "-S", "48,2,4", "-O", os.path.join(tmp, "s.brs"), "-f", path]}
+        wall = {k_: [] for k_ in cmds}
+        account = ""
+        for r in range(max(3, reps // 4)):
+            for name in list(cmds)[r % 2:] + list(cmds)[:r % 2]:
+                t0 = time.perf_counter()
+                q = subprocess.run(cmds[name], capture_output=True, env=dict(os.environ, ADSB_CLI_TIMING="1"))
+                wall[name].append((time.perf_counter() - t0) * 1e3)
+                assert q.returncode == 0, q.stderr.decode()[-2000:]
+                account = next((ln for ln in q.stderr.decode().splitlines() if ln.startswith("[record]")), account)
+        k_arch, s_arch = (open(os.path.join(tmp, f), "rb").read() for f in ("k.brs", "s.brs"))
+        same = k_arch == s_arch     # (the first piece's median bin is the whole file's on this workload, or the thresholds differ)
+        lines.append(f"#     the two archives: {len(k_arch)} and {len(s_arch)} bytes of {2 * N}, {'equal byte for byte' if same else 'thresholds differ: ' + str(k_arch[36:40] != s_arch[36:40])}")
+        lines.append("#   run                                                     process ms (q1 .. q3)          / -L -U -K")
+        for name in cmds:
+            q = statistics.quantiles(wall[name], n=4)
+            lines.append(f"    {name:52s} {med(wall[name]):9.1f} ({q[0]:.1f} .. {q[2]:.1f})   {med(wall[name]) / med(wall['-L -U 48,2,4 -K']):.3f}")
+            print(lines[-1], flush=True)
+        lines.append("#     " + account)
+        rate = 2.0 * N / (med(wall["-S 48,2,4 -O (pieces of 299593 runs)"]) * 1e-3) / 1e6
+        lines.append(f"#     the record mode takes the file at {rate:.0f} MB/s, the process's start included: {rate / 40.0:.1f} x a live stream's 40 MB/s")
+
+
 def flush_probe(L, reps, lines, parent):
     """Flush (adsb_set_flush), every comparison interleaved in this one process, wall time of the calls, the run's A/A beside every ratio:
     (1) adsb_decode_device on the benchmark capture: the tree without flush beside itself (the A/A), beside the library built from the
@@ -1897,6 +2018,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--bursts", action="store_true", help="the gate behind the envelope (adsb_bursts_device) beside a torch gate and a host gate instead: profiles/rNN_bursts.txt with the next free NN; --ab: the parent commit's library, for (c)")
     ap.add_argument("--flush", action="store_true", help="flush (adsb_set_flush): the decode call across the change, the batch of short captures, the gated pipeline: profiles/r30_flush.txt; --ab: the parent commit's library")
+    ap.add_argument("--burst-stream", action="store_true", help="the gate of a slice of a stream (adsb_bursts_slice_device) as one slice and as 16 beside adsb_bursts_device, and the host program's -S -O beside -L -U -K on a 256 Mi-sample file: profiles/rNN_burst_stream.txt with the next free NN; --ab: the parent commit's library, for (c)")
     ap.add_argument("--gather", action="store_true", help="the burst gather (adsb_gather_device) beside copy loops and a torch gather, its bytes per second, the archive's size, the archive route end to end, odd against even begins (and --variant builds with another load): profiles/r32_gather.txt; --ab: the parent commit's library")
     ap.add_argument("--gather-pack12", action="store_true", help="the 12-bit burst gather (adsb_gather_pack12_*) beside adsb_gather_device, a separate pack in torch, the _packed and _as flavours (and --variant builds with another kernel), the archive's size: profiles/r33_pack12.txt; --ab: the parent commit's library")
     a = ap.parse_args()
@@ -1929,6 +2051,17 @@ def main():
                  f"# {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved, a warm-up round first.",
                  "# Wall time of the C calls through ctypes; every call ends with its frames in host memory.", "#"]
         flush_probe(capi.load(), a.reps, lines, a.ab)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
+    if a.burst_stream:
+        a.out = a.out or next_round("burst_stream")
+        torch.cuda.set_device(0)
+        lines = ["# tools/format_probe.py --burst-stream: the gate of a slice of a stream (burst_slice_kernel.hip, adsb_bursts_slice_device) and the host",
+                 f"# program's record mode, {torch.cuda.get_device_name(0)}; the sides of every comparison interleaved; every side runs once, checked, before",
+                 "# its rounds.  The samples are the benchmark's: tools/gen_signal.py make_workload, 256 Mi samples, seed 1; the envelope is adsb_level_device's.",
+                 "# Wall time of the calls through ctypes; every call waits for its kernels and leaves its table in host memory.", "#"]
+        burst_stream_probe(capi.load(), a.reps, lines, a.ab)
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
         return
